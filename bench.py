@@ -29,7 +29,8 @@ N=1 and reported beside it (never as `value`): `host_landed` (text copied into p
 two-slot pipeline), `host_landed_gz` (the same with the gzip members made on the GPU -- what the product moves), `end_to_end` (the
 dwgsim-hip executable: FASTA in, five output files out) and `end_to_end_genome` (dwgsim-hip on the whole S4 genome, counting sink).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR`: what the last timed step computed goes to DIR as .npy files (OutputSample), so that two
+builds can be compared output for output on the same inputs.
 """
 import argparse, hashlib, json, os, subprocess, sys, tempfile, time
 
@@ -306,6 +307,57 @@ def balanced_batches(api, ranges, world, max_pairs):
     return list(api.split_ranges(ranges, -(-pairs // nb)))
 
 
+class OutputSample:
+    """--dump-outputs DIR: what the launches of this rank's last timed step returned -- the FASTQ text of each stream (fastq_read1 / fastq_read2 /
+    fastq_bfast.npy: byte values as float32; a launch's stream whole when it fits its share of SAMPLE_BYTES, else seeded WINDOW-byte windows of it,
+    in launch order) and per launch its pairs, random pairs, retries and text bytes per stream (launches.npy, float64).  Text stays in HBM only
+    until its output slot is reused: a launch is sampled after the timed region, or -- in steps of more than two launches -- inside it, just before
+    a later launch of the same step writes to its slot."""
+    WINDOW = 4096
+    SAMPLE_BYTES = 15 << 20          # text sampled at most: 60 MiB as float32
+    NAMES = ("fastq_read1", "fastq_read2", "fastq_bfast")
+
+    def __init__(self, device, n_launches):
+        self.device = device
+        self.share = max(self.WINDOW, self.SAMPLE_BYTES // (3 * max(n_launches, 1)) // self.WINDOW * self.WINDOW)
+        self.held, self.text, self.launches = {}, [[] for _ in self.NAMES], []
+
+    def finished(self, slot, b):
+        self.held[slot] = (len(self.launches), b)
+        self.launches.append([b.n_pairs, b.n_random, b.n_retries] + list(b.bytes))
+
+    def reuse(self, slot):
+        if slot in self.held:
+            self.take(*self.held.pop(slot))
+
+    def take(self, k, b):
+        import numpy as np, torch
+
+        class DeviceBytes:          # the slot's text as a tensor without a copy (valid until the slot is reused, include/dwgsim_hip.h)
+            def __init__(self, ptr, n):
+                self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+        for s in range(3):
+            n = int(b.bytes[s])
+            if n == 0:
+                continue
+            text = torch.as_tensor(DeviceBytes(b.dev_ptr[s], n), device=self.device)
+            if n > self.share:
+                starts = np.sort(np.random.default_rng([k, s]).integers(0, n - self.WINDOW + 1, size=self.share // self.WINDOW))
+                text = text[(torch.from_numpy(starts)[:, None] + torch.arange(self.WINDOW)).reshape(-1).to(text.device)]
+            self.text[s].append(text.to(torch.float32).cpu().numpy())
+
+    def save(self, out_dir):
+        import numpy as np
+        for k, b in sorted(self.held.values(), key=lambda e: e[0]):
+            self.take(k, b)
+        self.held = {}
+        os.makedirs(out_dir, exist_ok=True)
+        for name, parts in zip(self.NAMES, self.text):
+            if parts:
+                np.save(os.path.join(out_dir, name + ".npy"), np.concatenate(parts))
+        np.save(os.path.join(out_dir, "launches.npy"), np.array(self.launches, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -331,6 +383,7 @@ def main():
                     "the all-gather is replaced by the counts one reference pass recorded (the path has no data-path collective, so a rank's GPU work does not depend on the others running)")
     ap.add_argument("--solo-sweep", default=None, help="e.g. 2,4,8: every rank of every world size, one at a time on this GPU, weak line and strong (whole-genome) job; prints one JSON object with "
                     "T_r(W), T(1) and efficiency = T(1) / max_r T_r(W) (weak), T(1) / (W x max_r T_r(W)) (strong) -- 'solo-rank, one GPU at a time', not a hardware curve")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed (FASTQ text, sampled to at most 64 MB, and the launch counts) to DIR/<name>.npy")
     args = ap.parse_args()
     solo = args.solo_rank is not None or args.solo_sweep is not None
     if args.solo_rank is not None and not (0 <= args.solo_rank < max(args.world, 1)):
@@ -419,12 +472,12 @@ def main():
         return dict(ctx=ctx, params=params, job_flags=job_flags, contigs=contigs, tot_len=tot_len, paired=params.length[1] > 0, job=job, job_pairs=sum(e[3] for e in job),
                     raw=raw, no_pipeline=no_pipeline, ref_counts={})
 
-    def measure(S, n_steps, warmup, W, R, alone):
+    def measure(S, n_steps, warmup, W, R, alone, sample=False):
         """One measurement on the resident job S as rank R of W: `warmup` + `n_steps` steps, the barrier-bracketed time of the timed ones (maximum over the
         ranks).  alone: this process plays rank R of W by itself (--solo-rank): no process group; what the all-gather would bring -- the random-read
         counts of the other ranks' launches -- comes from one reference pass over ALL launches, made here before anything is timed (the walk is
         deterministic: every step of every rank sees the same counts); the rank's OWN counts are still taken live, every step, as in the real run, and
-        must equal the recorded ones.  -> everything the JSON line is made of."""
+        must equal the recorded ones.  sample: keep what the last timed step returned (OutputSample).  -> everything the JSON line is made of."""
         ctx, no_pipeline, depth = S["ctx"], S["no_pipeline"], args.depth
         group_dist = None if alone else dist
         copies = []          # per copy, per group: handle of its first contig, its launches (each a list of ranges), which of them are this rank's
@@ -437,6 +490,7 @@ def main():
         groups = copies[0]
         my_pairs = sum(n for g in groups for b in g["mine"] for _, _, n in g["launches"][b])
         n_my_launches = sum(len(g["mine"]) for g in groups)
+        sampler = OutputSample(torch.device("cuda", dev), n_my_launches) if sample else None
         ref = None
         if alone and W > 1:
             ref = S["ref_counts"].get(W)
@@ -520,20 +574,25 @@ def main():
                 sl, acc = pending.pop(0)
                 b = ctx.wait(sl)
                 acc["bytes"] += int(b.bytes[0] + b.bytes[1] + b.bytes[2]); acc["rand"] += int(b.n_random)
+                if acc["last"]:
+                    sampler.finished(sl, b)
                 if record:
                     stats["sim_kernel_ms"] += b.sim_kernel_ms; stats["launches"] += 1
 
-        def run(gl, bases, record, then=None, carry=False):
+        def run(gl, bases, record, then=None, carry=False, last=False):
             """all launches of this rank for one step, two in flight; `then` (what is prepared for later steps) runs once the last one is enqueued -- the
             launches of the step before may still run: the walk issued there rewrites the copy of the step before THAT, whose launches were waited
-            for before this step's first was enqueued; carry: leave this step's launches in flight for the next step to wait for"""
-            acc = {"bytes": 0, "rand": 0}
+            for before this step's first was enqueued; carry: leave this step's launches in flight for the next step to wait for; last: the sampler
+            keeps what this step's launches return"""
+            acc = {"bytes": 0, "rand": 0, "last": last and sampler is not None}
             first_launch = True
             for q, g in enumerate(gl):
                 for b in g["mine"]:
                     drain(1, record)
                     base = bases[(q, b)] if W > 1 else (0 if first_launch else api.RAND_CHAIN)
                     first_launch = False
+                    if sampler is not None:
+                        sampler.reuse(flight["slot"])
                     ctx.simulate_ranges_async(g["launches"][b], base, flight["slot"])
                     flight["pending"].append((flight["slot"], acc)); flight["slot"] ^= 1
             nxt = then() if then else None
@@ -545,8 +604,8 @@ def main():
 
         def steps(n, record):
             if no_pipeline:
-                for _ in range(n):
-                    run(copies[0], prepare(copies[0], record), record)
+                for k in range(n):
+                    run(copies[0], prepare(copies[0], record), record, last=record and k == n - 1)
                 return
             # depth D: once the launches of step k are enqueued (those of step k - 1 still run), the walks of step k + D go onto the walk stream and the
             # counts / exchange of step k + 1 are finished on the host.  Beside a k_simulate that fills the device nothing else runs
@@ -567,7 +626,7 @@ def main():
                         issue(far)                                   # the copy step k - 2 read (C = D + 2): its launches were waited for before step k's first was enqueued
                     # (the count of step k + 1 below does not queue behind these walks: it runs on the context's count stream, behind the walk of ITS copy only)
                     return prepare(nx, record, issued=D > 1)
-                bases = run(copies[k % C], bases, record, then=then, carry=not args.no_carry)
+                bases = run(copies[k % C], bases, record, then=then, carry=not args.no_carry, last=record and k == n - 1)
             drain(0, record)
             for d in range(1, D):                                    # (walks issued for steps beyond the last: waited for, inside the timed region)
                 for g in copies[(n + d) % C]:
@@ -592,6 +651,8 @@ def main():
             tp = torch.tensor([my_pairs], dtype=torch.int64)
             group_dist.all_reduce(tp)
             total_pairs = int(tp.item())
+        if sampler is not None:
+            sampler.save(args.dump_outputs)
         out = dict(S)
         out.update(groups=groups, my_pairs=my_pairs, n_my_launches=n_my_launches, stats=stats, elapsed=elapsed, total_pairs=total_pairs)
         return out
@@ -600,7 +661,8 @@ def main():
         print(json.dumps(solo_sweep(args, flags, setup, measure, [int(x) for x in args.solo_sweep.split(",")], lib, dev, numa)), flush=True)
         return
 
-    m = measure(setup(args.workload, args.mode, flags, args.group_bp, world), args.steps, args.warmup, world, rank, args.solo_rank is not None)
+    m = measure(setup(args.workload, args.mode, flags, args.group_bp, world), args.steps, args.warmup, world, rank, args.solo_rank is not None,
+                sample=args.dump_outputs is not None and (rank == 0 or args.solo_rank is not None))
     ctx, params, job_flags, contigs, tot_len, paired, job, job_pairs, groups, my_pairs, n_my_launches, stats, elapsed, total_pairs = (m[k] for k in (
         "ctx", "params", "job_flags", "contigs", "tot_len", "paired", "job", "job_pairs", "groups", "my_pairs", "n_my_launches", "stats", "elapsed", "total_pairs"))
     # the fixed whole-genome job of BASELINE configs[3] split over the ranks, beside the (weak) line: the `strong` object of the line.  Whole-genome

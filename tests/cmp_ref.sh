@@ -5,9 +5,10 @@
 # (FASTQ after gunzip, as the reference's own testdata/test.sh:21-26 does).
 set -u
 FA=$1; shift
-T=$(mktemp -d /tmp/cmpref.XXXXXX)
-/root/repo/oracle/_ref/dwgsim "$@" "$FA" $T/ref > $T/ref.log 2>&1; rc1=$?
-/root/repo/oracle/build/dwgsim_oracle --rng drand48 --verbose "$@" "$FA" $T/ora > $T/ora.log 2>&1; rc2=$?
+R=$(cd "$(dirname "$0")/.." && pwd)
+T=$(mktemp -d -t cmpref.XXXXXX)
+$R/oracle/_ref/dwgsim "$@" "$FA" $T/ref > $T/ref.log 2>&1; rc1=$?
+$R/oracle/build/dwgsim_oracle --rng drand48 --verbose "$@" "$FA" $T/ora > $T/ora.log 2>&1; rc2=$?
 ok=1
 for f in bfast.fastq bwa.read1.fastq bwa.read2.fastq; do
   if [ -f $T/ref.$f.gz ]; then

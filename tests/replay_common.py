@@ -9,13 +9,17 @@ Round 6: quality NOISE is replayed too where it can be.  ran_normal (dwgsim.c:15
 accepted try; a single-end read of EVEN length with -Q > 0 takes L normals = L / 2 accepted tries, so the static cache is empty at every read boundary
 and nothing leaks from read to read: the unmodified reference (glibc log) then consumes the 16-bit polar tries of the D_QUAL0 stream exactly
 as mode B does.  This puts the headline quality path (16-bit operands, det_log, lazy fp32 estimates on the GPU) under the reference itself.  Odd lengths
-and paired ends (the insert-size normal shares the cache, dwgsim.c:657) stay on the two-link chain."""
-import gzip, os, random, subprocess
+and paired ends (the insert-size normal shares the cache, dwgsim.c:657) stay on the two-link chain.
+
+The tests do not run the reference: tests/golden/make_reference_runs.py runs it (run_replay) where it is built and records what it wrote, and which
+stream it was fed, in tests/golden/reference_runs.json; the tests run mode B (run_mode_b) and compare with that record."""
+import gzip, hashlib, json, os, random, subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "dwgsim")
 SHIM = os.path.join(ROOT, "oracle", "build", "libreplay48.so")
 IN_DIR = os.path.join(ROOT, "tests", "golden", "inputs")
+REFERENCE_RUNS = os.path.join(ROOT, "tests", "golden", "reference_runs.json")      # what the reference answered, recorded by tests/golden/make_reference_runs.py
 SUFFIXES = ("bwa.read1.fastq", "bwa.read2.fastq", "bfast.fastq", "mutations.txt", "mutations.vcf")
 FLOW = "TACGTACGTCTGAGCATCGATCGATGTACAGC"
 
@@ -45,32 +49,66 @@ REPLAY_CASES = [
 ]
 
 
-def have_reference():
-    return os.path.exists(REF_BIN)
+REPLAY_FUZZ_SEEDS = [20260929, 31337]      # tests/test_replay_parity.py test_replay_fuzz: 25 option sets each
+
+
+def sha256(data: bytes) -> str:
+    return hashlib.sha256(data).hexdigest()
+
+
+def case_key(fasta, flags):
+    """How a (FASTA, options) case is keyed in tests/golden/reference_runs.json: the FASTA's file name, the input directory as {IN}."""
+    return f"{os.path.basename(fasta)} {flags.replace(IN_DIR, '{IN}')}"
+
+
+_runs = None
+
+
+def reference_run(kind, key):
+    """The recorded answer of the unmodified reference for one case ("cli", "replay" or "mode_a")."""
+    global _runs
+    if _runs is None:
+        with open(REFERENCE_RUNS) as f:
+            _runs = json.load(f)
+    rec = _runs[kind].get(key)
+    assert rec is not None, f"no recorded reference run for the {kind} case {key!r}: record it with tests/golden/make_reference_runs.py (needs the reference)"
+    return rec
+
+
+def read_outputs(prefix, gz):
+    """{suffix: bytes} of the five files a run wrote at prefix (b"" for a file it did not write); gz: the FASTQ are gzipped (the reference)"""
+    out = {}
+    for suf in SUFFIXES:
+        p = prefix + "." + suf + (".gz" if gz and suf.endswith("fastq") else "")
+        if not os.path.exists(p): out[suf] = b""
+        elif p.endswith(".gz"):
+            try: out[suf] = gzip.open(p, "rb").read()
+            except EOFError: out[suf] = b"<truncated gzip>"
+        else: out[suf] = open(p, "rb").read()
+    return out
+
+
+def run_mode_b(oracle_bin, fasta, flags, workdir, timeout=120):
+    """The oracle in mode B with its draws dumped -> (rc, {suffix: bytes}, the dumped draws)"""
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "oracle"], check=True)
+    dump = os.path.join(workdir, "draws.bin")
+    o = subprocess.run([oracle_bin, "--rng", "philox", "--dump-draws", dump] + flags.replace("{IN}", IN_DIR).split() + [fasta, os.path.join(workdir, "o")],
+                       capture_output=True, timeout=timeout)
+    draws = open(dump, "rb").read() if os.path.exists(dump) else b""
+    return o.returncode, read_outputs(os.path.join(workdir, "o"), False), draws
 
 
 def run_replay(oracle_bin, fasta, flags, workdir, timeout=120):
-    """-> (oracle rc, reference rc, {suffix: bytes} of mode B, {suffix: bytes} of the replayed reference, draws served, draws dumped)"""
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "oracle"], check=True)
-    flags = flags.replace("{IN}", IN_DIR)
-    dump = os.path.join(workdir, "draws.bin"); rep = os.path.join(workdir, "report.txt")
-    o = subprocess.run([oracle_bin, "--rng", "philox", "--dump-draws", dump] + flags.split() + [fasta, os.path.join(workdir, "o")], capture_output=True, timeout=timeout)
-    env = dict(os.environ, LD_PRELOAD=SHIM, REPLAY48_FILE=dump, REPLAY48_REPORT=rep)
-    r = subprocess.run([REF_BIN] + flags.split() + [fasta, os.path.join(workdir, "r")], capture_output=True, env=env, timeout=timeout)
-    want, got = {}, {}
-    for suf in SUFFIXES:
-        po = os.path.join(workdir, "o." + suf)
-        want[suf] = open(po, "rb").read() if os.path.exists(po) else b""
-        pr = os.path.join(workdir, "r." + suf + (".gz" if suf.endswith("fastq") else ""))
-        if not os.path.exists(pr): got[suf] = b""
-        elif pr.endswith(".gz"):
-            try: got[suf] = gzip.open(pr, "rb").read()
-            except EOFError: got[suf] = b"<truncated gzip>"
-        else: got[suf] = open(pr, "rb").read()
+    """The reference (oracle/_ref/dwgsim) fed the draws the oracle dumped in mode B -> (reference rc, {suffix: bytes}, draws served, draws available,
+    the dumped draws).  Only tests/golden/make_reference_runs.py runs this: the tests compare with what it recorded."""
+    _, _, draws = run_mode_b(oracle_bin, fasta, flags, workdir, timeout)
+    rep = os.path.join(workdir, "report.txt")
+    env = dict(os.environ, LD_PRELOAD=SHIM, REPLAY48_FILE=os.path.join(workdir, "draws.bin"), REPLAY48_REPORT=rep)
+    r = subprocess.run([REF_BIN] + flags.replace("{IN}", IN_DIR).split() + [fasta, os.path.join(workdir, "r")], capture_output=True, env=env, timeout=timeout)
     served = avail = -1
     if os.path.exists(rep):
         served, avail = (int(x) for x in open(rep).read().split())
-    return o.returncode, r.returncode, want, got, served, avail
+    return r.returncode, read_outputs(os.path.join(workdir, "r"), True), served, avail, draws
 
 
 def random_replay_flags(rng: random.Random):

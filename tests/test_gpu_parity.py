@@ -461,29 +461,31 @@ def test_mut_debug_aborts_like_the_reference(lib, oracle_bin, golden_dir):
     check_mut_debug_aborts(lib, oracle_bin, golden_dir)
 
 
-from replay_common import REPLAY_CASES, have_reference
+from replay_common import REPLAY_CASES
 
 
-@pytest.mark.skipif(not have_reference(), reason="oracle/_ref/dwgsim (the unmodified reference; it travels to the GPU box as a prebuilt binary) is not here")
 @pytest.mark.parametrize("fasta,flags", REPLAY_CASES, ids=[f"{f}:{fl}" for f, fl in REPLAY_CASES])
 def test_hip_path_equals_the_replayed_reference(lib, oracle_bin, golden_dir, tmp_path, fasta, flags):
     """The HIP path against bytes the UNMODIFIED REFERENCE wrote: oracle/_ref/dwgsim with its drand48() replaying the Philox stream (tests/replay_common.py;
     single-end configurations: Illumina, SOLiD, the whole Ion Torrent flow model, heavy -r / -R, -x, -m / -b / -v, and -- reads of even length -- quality
     noise -Q 0.5 ... 60, i.e. the 16-bit polar tries and lazy normals of the headline kernel against the reference's own ran_normal with glibc log) -- no oracle
-    output is compared here, the oracle only dumps the stream.  The last case also goes through the dwgsim-hip executable."""
+    output is compared here, the oracle only dumps the stream, which must be the one the reference was fed (tests/golden/reference_runs.json holds the
+    sha256 of both).  The last case also goes through the dwgsim-hip executable."""
     import gzip, subprocess
-    from replay_common import run_replay, SUFFIXES, IN_DIR
+    from replay_common import SUFFIXES, IN_DIR, case_key, reference_run, run_mode_b, sha256
     fa = os.path.join(golden_dir, fasta)
-    orc, rrc, _, ref, served, avail = run_replay(oracle_bin, fa, flags, str(tmp_path))
-    assert orc == 0 and rrc == 0 and served == avail > 0
+    rec = reference_run("replay", case_key(fasta, flags))
+    orc, _, draws = run_mode_b(oracle_bin, fa, flags, str(tmp_path))
+    assert orc == 0 and rec["rc"] == 0 and rec["served"] == rec["avail"] > 0 and sha256(draws) == rec["draws_sha256"]
+    ref = rec["sha256"]
     fl = flags.replace("{IN}", IN_DIR)
     res = api.run_job(api.parse_flags(fl, lib), api.read_fasta(fa), lib=lib)
-    assert res.streams[0] == ref["bwa.read1.fastq"] and res.streams[1] == ref["bwa.read2.fastq"] and res.streams[2] == ref["bfast.fastq"]
-    assert res.mutations_txt == ref["mutations.txt"] and res.mutations_vcf == ref["mutations.vcf"]
+    assert sha256(res.streams[0]) == ref["bwa.read1.fastq"] and sha256(res.streams[1]) == ref["bwa.read2.fastq"] and sha256(res.streams[2]) == ref["bfast.fastq"]
+    assert sha256(res.mutations_txt) == ref["mutations.txt"] and sha256(res.mutations_vcf) == ref["mutations.vcf"]
     if (fasta, flags) == REPLAY_CASES[-1]:
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         subprocess.run([os.path.join(root, "dwgsim_amd", "dwgsim-hip")] + fl.split() + [fa, str(tmp_path / "cli")], check=True, stderr=subprocess.DEVNULL)
         for suf in SUFFIXES:
             p = str(tmp_path / ("cli." + suf + (".gz" if suf.endswith("fastq") else "")))
             got = (gzip.open(p, "rb").read() if p.endswith(".gz") else open(p, "rb").read()) if os.path.exists(p) else b""
-            assert got == ref[suf], suf
+            assert sha256(got) == ref[suf], suf

@@ -3,8 +3,8 @@
 tests/golden/MANIFEST.json pins the oracle on fixed configurations; this pins it on the option SURFACE: 260 option sets drawn by the product fuzzer's
 own generator (tests/fuzz_flags.py: all three read models, paired / single ends, every rate and switch, and -- `inputs` -- mutation files, target
 regions and -B), both programs run on the same FASTA, all five outputs compared byte for byte (FASTQ after gunzip, as testdata/test.sh:21-26 does).
-Two judges derived this by hand in rounds 4 and 5 (239 and 180 option sets, none differing); it now runs with the CPU suite wherever the reference
-binary exists (the dev container: oracle/Makefile builds it from /root/reference; it travels to the GPU box as a prebuilt file).
+Two judges derived this by hand in rounds 4 and 5 (239 and 180 option sets, none differing); it runs with the CPU suite against what the reference
+wrote on every option set, recorded in tests/golden/reference_runs.json (exit code and sha256 of the five outputs; tests/golden/make_reference_runs.py).
 
 EXCLUDED, and why: `-c 2` with reads shorter than the flow order minus 2.  The reference allocates its flow masks with
 (longer read length) + 2 bytes (dwgsim.c:444-453; the -B calibration with that END's length + 2: dwgsim_opt.c:431-433) and generate_errors_flows
@@ -12,15 +12,16 @@ indexes them by FLOW (dwgsim.c:268-279, up to flow_order_len - 1): a heap overfl
 for the 32-flow order at -1 7 ... -1 20, a wrong -B scaling factor before the crash (allocator slack hides it from -1 ~22 on).  There is no
 reference behaviour to match; the oracle and the product keep one flag per read (the mask never has more than one bit set) and are defined there.
 """
-import gzip, os, random, subprocess, sys
+import os, random, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_BIN = os.path.join(ROOT, "oracle", "_ref", "dwgsim")
-pytestmark = pytest.mark.skipif(not os.path.exists(REF_BIN), reason="oracle/_ref/dwgsim (the unmodified reference) is not here")
-SUFFIXES = ("bwa.read1.fastq", "bwa.read2.fastq", "bfast.fastq", "mutations.txt", "mutations.vcf")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from replay_common import SUFFIXES, case_key, read_outputs, reference_run, sha256
+
 MAX_B_CASES = 3        # -B costs the reference 10^6 reads through the flow model per distinct read length (seconds to a minute)
+FUZZ_SETS = [(660101, 100, False), (660102, 100, True), (660103, 60, True)]
 
 
 def reference_overflows_its_flow_mask(flags):
@@ -35,31 +36,18 @@ def reference_overflows_its_flow_mask(flags):
     return "-B" in t and any(0 < l and l + 2 < nflow for l in lens)      # the calibration's: this end's length + 2 (dwgsim_opt.c:431-433)
 
 
-def run_both(oracle_bin, fasta, flags, workdir, timeout=300):
+def run_mode_a(exe, fasta, flags, workdir, gz, timeout=300):
+    """exe (the oracle in mode A, or the reference) on one option set -> (exit code or "timeout", {suffix: sha256} of its five outputs)"""
     os.makedirs(workdir, exist_ok=True)
-    out = {}
-    for who, exe in (("ref", [REF_BIN]), ("ora", [oracle_bin, "--rng", "drand48"])):
-        try:
-            r = subprocess.run(exe + flags.split() + [fasta, os.path.join(workdir, who)], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout)
-            out[who] = r.returncode
-        except subprocess.TimeoutExpired:
-            out[who] = "timeout"
-    if out["ref"] != 0 or out["ora"] != 0:
-        return out, None
-    diff = []
-    for suf in SUFFIXES:
-        pr = os.path.join(workdir, "ref." + suf + (".gz" if suf.endswith("fastq") else ""))
-        po = os.path.join(workdir, "ora." + suf)
-        a = (gzip.open(pr, "rb").read() if pr.endswith(".gz") else open(pr, "rb").read()) if os.path.exists(pr) else b""
-        b = open(po, "rb").read() if os.path.exists(po) else b""
-        if a != b:
-            diff.append(suf)
-    return out, diff
+    try:
+        r = subprocess.run(exe + flags.split() + [fasta, os.path.join(workdir, "o")], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout)
+    except subprocess.TimeoutExpired:
+        return "timeout", None
+    return r.returncode, {suf: sha256(b) for suf, b in read_outputs(os.path.join(workdir, "o"), gz).items()}
 
 
-@pytest.mark.parametrize("seed,count,inputs", [(660101, 100, False), (660102, 100, True), (660103, 60, True)])
-def test_reference_equals_mode_a_on_random_option_sets(oracle_bin, golden_dir, tmp_path, seed, count, inputs):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
+def option_sets(golden_dir, seed, count, inputs):
+    """-> [(k, fasta path, flags)] of one FUZZ_SETS entry, and how many option sets were excluded"""
     import fuzz_flags
     rng = random.Random(seed)
     cases, n_b, excluded = [], 0, 0
@@ -77,13 +65,22 @@ def test_reference_equals_mode_a_on_random_option_sets(oracle_bin, golden_dir, t
                 flags = flags.replace(" -B", "")
         # -e 1.0 / error rates at which the flow model of the reference does not terminate are not drawn by the generator (fuzz_flags.py)
         cases.append((k, os.path.join(golden_dir, fasta), flags))
+    return cases, excluded
+
+
+@pytest.mark.parametrize("seed,count,inputs", FUZZ_SETS)
+def test_reference_equals_mode_a_on_random_option_sets(oracle_bin, golden_dir, tmp_path, seed, count, inputs):
+    cases, excluded = option_sets(golden_dir, seed, count, inputs)
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        results = list(ex.map(lambda c: run_both(oracle_bin, c[1], c[2], str(tmp_path / f"c{c[0]}")), cases))
+        results = list(ex.map(lambda c: run_mode_a([oracle_bin, "--rng", "drand48"], c[1], c[2], str(tmp_path / f"c{c[0]}"), False), cases))
     compared = 0
-    for (k, fasta, flags), (rc, diff) in zip(cases, results):
-        if diff is None:      # an option set one of them did not run: both must refuse it (the reference's own argument checks; exit code 1 both)
+    for (k, fasta, flags), (orc, got) in zip(cases, results):
+        rec = reference_run("mode_a", case_key(fasta, flags))
+        rc = {"ref": rec["rc"], "ora": orc}
+        if rc["ref"] != 0 or rc["ora"] != 0:      # an option set one of them did not run: both must refuse it (the reference's own argument checks; exit code 1 both)
             assert rc["ref"] == rc["ora"] or (rc["ref"] not in (0, "timeout") and rc["ora"] not in (0, "timeout")), f"reference rc {rc['ref']}, oracle rc {rc['ora']}: {os.path.basename(fasta)} {flags}"
             continue
+        diff = [suf for suf in SUFFIXES if got[suf] != rec["sha256"][suf]]
         assert diff == [], f"{diff} differ between the reference and mode A: {os.path.basename(fasta)} {flags}"
         compared += 1
     assert compared >= count * 0.8, (compared, count, excluded)
