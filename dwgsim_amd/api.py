@@ -79,6 +79,9 @@ EXPORTS = [
     "dwgsim_hip_job_finish", "dwgsim_hip_job_last_error", "dwgsim_hip_job_destroy",
     "dwgsim_hip_set_fail_carry", "dwgsim_hip_failseg_join", "dwgsim_hip_shard_range", "dwgsim_hip_debug_option", "dwgsim_hip_debug_get", "dwgsim_hip_debug_count_byte", "dwgsim_hip_set_gzip", "dwgsim_hip_fetch_gz_async", "dwgsim_hip_debug_gzip",
     "dwgsim_hip_selftest_fp64", "dwgsim_hip_selftest_lazy", "dwgsim_hip_selftest_text",
+    "dwgsim_hip_eval_opts_default", "dwgsim_hip_eval_create", "dwgsim_hip_eval_header", "dwgsim_hip_eval_feed", "dwgsim_hip_eval_finish",
+    "dwgsim_hip_eval_table_text", "dwgsim_hip_eval_incorrect_text", "dwgsim_hip_eval_last_error", "dwgsim_hip_eval_destroy",
+    "dwgsim_hip_eval_debug_time", "dwgsim_hip_eval_debug_device_chunk",
 ]
 
 _lib = None
@@ -165,6 +168,8 @@ def load(path: str | None = None):
     lib.dwgsim_hip_debug_gzip.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, P(C.c_size_t)]
     lib.dwgsim_hip_set_gzip.argtypes = [C.c_void_p, C.c_int]
     lib.dwgsim_hip_fetch_gz_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    if hasattr(lib, "dwgsim_hip_eval_create"):
+        _bind_eval(lib)
     if path is None:
         _lib = lib
     return lib
@@ -708,3 +713,178 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
     res.streams = {k: bytes(v) for k, v in res.streams.items()}
     res.delivered_text_bytes = dict(order["text_n"])
     return res
+
+
+# ---- dwgsim_eval (include/dwgsim_hip.h "dwgsim_eval") ----
+
+class EvalOpts(C.Structure):
+    """dwgsim_hip_eval_opts_t"""
+    _fields_ = [("size", C.c_uint32), ("a", C.c_int32), ("d", C.c_int32), ("e", C.c_int32), ("g", C.c_int32), ("n", C.c_int32),
+                ("q", C.c_int32), ("s", C.c_int32), ("b", C.c_int32), ("c", C.c_int32), ("i", C.c_int32), ("m", C.c_int32),
+                ("p", C.c_int32), ("z", C.c_int32), ("P", C.c_char_p), ("chunk_bytes", C.c_uint64)]
+
+
+class EvalSummary(C.Structure):
+    """dwgsim_hip_eval_summary_t"""
+    _fields_ = [("size", C.c_uint32), ("status", C.c_int32), ("error_code", C.c_int32), ("reserved", C.c_int32),
+                ("error_record", C.c_uint64), ("n", C.c_uint64), ("records", C.c_uint64),
+                ("stderr_text", C.c_void_p), ("stderr_len", C.c_size_t)]
+
+
+EVAL_STOPPED = 1     # DWGSIM_HIP_EVAL_STOPPED
+
+
+def _bind_eval(lib):
+    P = C.POINTER
+    lib.dwgsim_hip_eval_opts_default.argtypes = [P(EvalOpts)]
+    lib.dwgsim_hip_eval_opts_default.restype = None
+    lib.dwgsim_hip_eval_create.restype = C.c_void_p
+    lib.dwgsim_hip_eval_create.argtypes = [P(EvalOpts), C.c_int, P(C.c_int)]
+    lib.dwgsim_hip_eval_header.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.dwgsim_hip_eval_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.dwgsim_hip_eval_finish.argtypes = [C.c_void_p, P(EvalSummary)]
+    lib.dwgsim_hip_eval_table_text.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_size_t)]
+    lib.dwgsim_hip_eval_incorrect_text.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_size_t)]
+    lib.dwgsim_hip_eval_last_error.restype = C.c_char_p
+    lib.dwgsim_hip_eval_last_error.argtypes = [C.c_void_p]
+    lib.dwgsim_hip_eval_destroy.argtypes = [C.c_void_p]
+    lib.dwgsim_hip_eval_destroy.restype = None
+    lib.dwgsim_hip_eval_debug_time.argtypes = [C.c_void_p, P(C.c_double)]
+    lib.dwgsim_hip_eval_debug_device_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, P(C.c_double)]
+
+
+def load_eval(path: str | None = None):
+    """The library for EvalContext: the product's (path None), or another build of the dwgsim_hip_eval_* symbols alone"""
+    if path is None:
+        return load()
+    lib = C.CDLL(path)
+    _bind_eval(lib)
+    return lib
+
+
+@dataclass
+class EvalSummaryResult:
+    status: int              # dwgsim_eval's exit status: 0, or 1 after a fatal record
+    error_code: int          # DWGSIM_HIP_EVAL_E_*, 0
+    error_record: int        # 0-based record line of that error in the run
+    n: int                   # pairs (single-end reads with -z)
+    records: int
+    stderr: bytes            # dwgsim_eval's stderr text
+    incorrect: bytes = b""   # -p: the first header and the incorrectly mapped records
+
+
+class EvalContext:
+    """One dwgsim_eval run on one device: header(file 1), feed(...)..., header(file 2), ..., finish().  Options are dwgsim_eval's
+    (a, b, c, d, e, g, i, m, n, p, q, s, z: ints; P: str) plus chunk_bytes."""
+
+    def __init__(self, device: int = 0, lib=None, chunk_bytes: int = 0, **opts):
+        self.lib = lib or load()
+        o = EvalOpts()
+        self.lib.dwgsim_hip_eval_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k == "P":
+                self._P = None if v is None else (v.encode() if isinstance(v, str) else bytes(v))
+                o.P = self._P
+            elif k in ("a", "b", "c", "d", "e", "g", "i", "m", "n", "p", "q", "s", "z"):
+                setattr(o, k, int(v))
+            else:
+                raise TypeError(f"unknown dwgsim_eval option {k!r}")
+        o.chunk_bytes = chunk_bytes
+        err = C.c_int(0)
+        self.ctx = self.lib.dwgsim_hip_eval_create(C.byref(o), device, C.byref(err))
+        if not self.ctx:
+            raise DwgsimError(f"dwgsim_hip_eval_create failed ({err.value})")
+
+    def _check(self, r: int):
+        if r < 0:
+            raise DwgsimError(self.lib.dwgsim_hip_eval_last_error(self.ctx).decode(errors="replace"))
+        return r
+
+    def header(self, text: bytes):
+        self._check(self.lib.dwgsim_hip_eval_header(self.ctx, text, len(text)))
+
+    def feed(self, buf) -> bool:
+        """record text, split anywhere; False once a fatal record has been found (the rest is not needed)"""
+        n = len(buf)
+        if isinstance(buf, (bytes, bytearray, memoryview)):
+            cbuf = (C.c_char * n).from_buffer_copy(buf) if not isinstance(buf, bytes) else buf
+            r = self.lib.dwgsim_hip_eval_feed(self.ctx, cbuf, n)
+        else:
+            r = self.lib.dwgsim_hip_eval_feed(self.ctx, buf, n)
+        return self._check(r) != EVAL_STOPPED
+
+    def finish(self):
+        """(table text, EvalSummaryResult)"""
+        sm = EvalSummary()
+        sm.size = C.sizeof(EvalSummary)
+        self._check(self.lib.dwgsim_hip_eval_finish(self.ctx, C.byref(sm)))
+        txt, ln = C.c_void_p(), C.c_size_t()
+        self._check(self.lib.dwgsim_hip_eval_table_text(self.ctx, C.byref(txt), C.byref(ln)))
+        table = C.string_at(txt, ln.value) if ln.value else b""
+        self._check(self.lib.dwgsim_hip_eval_incorrect_text(self.ctx, C.byref(txt), C.byref(ln)))
+        inc = C.string_at(txt, ln.value) if ln.value else b""
+        res = EvalSummaryResult(sm.status, sm.error_code, sm.error_record, sm.n, sm.records, C.string_at(sm.stderr_text, sm.stderr_len), inc)
+        return table, res
+
+    def debug_time_ms(self) -> float:
+        t = C.c_double()
+        self._check(self.lib.dwgsim_hip_eval_debug_time(self.ctx, C.byref(t)))
+        return t.value
+
+    def close(self):
+        if self.ctx:
+            self.lib.dwgsim_hip_eval_destroy(self.ctx)
+            self.ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def split_sam_header(data: bytes):
+    """(header, records): the leading lines that start with '@', and the rest"""
+    i = 0
+    while i < len(data) and data[i] == 64:
+        j = data.find(b"\n", i)
+        i = len(data) if j < 0 else j + 1
+    return data[:i], data[i:]
+
+
+def eval_sam(paths, device: int = 0, lib=None, chunk_bytes: int = 0, read_bytes: int = 8 << 20, **opts):
+    """dwgsim_eval -S over SAM files (paths, or file objects opened in binary mode): (table_text, EvalSummaryResult).
+    The table is empty after a fatal record (summary.status == 1; summary.stderr says why)."""
+    if isinstance(paths, (str, bytes, os.PathLike)):
+        paths = [paths]
+    with EvalContext(device, lib, chunk_bytes, **opts) as ctx:
+        for p in paths:
+            f = open(p, "rb") if isinstance(p, (str, bytes, os.PathLike)) else p
+            try:
+                head = b""
+                while True:
+                    blk = f.read(read_bytes)
+                    if not blk:
+                        ctx.header(head)
+                        break
+                    head += blk
+                    h, rest = split_sam_header(head)
+                    if rest:          # a record line has begun: the header is complete
+                        ctx.header(h)
+                        going = ctx.feed(rest)
+                        while going:
+                            blk = f.read(read_bytes)
+                            if not blk:
+                                break
+                            going = ctx.feed(blk)
+                        break
+            finally:
+                if f is not p:
+                    f.close()
+        return ctx.finish()

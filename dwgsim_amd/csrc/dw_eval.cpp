@@ -1,0 +1,622 @@
+// dw_eval.cpp -- host side of dwgsim_eval-hip: the dwgsim_hip_eval_* C-ABI (include/dwgsim_hip.h), chunking of the SAM text, the @SQ tables,
+// and the reference's output text (dwgsim_eval.c dwgsim_eval_counts_print / dwgsim_eval_print_error).
+//
+// Chunks.  Two slots, each a page-locked text buffer and its device buffers on a stream of its own.  The caller's bytes are copied into the
+// filling slot; when it is full, the text up to its last newline is submitted (copy up, four kernels, copy back the per-chunk result) and the
+// other slot becomes the filling one: it starts with the last line of the submitted chunk (the context line that -m compares the next record
+// with) and the partial line that did not fit.  So the copy and the kernels of one chunk overlap with the host filling the next.  Results are
+// read back in submission order: the first chunk with a fatal record ends the run, and its record is the first one in file order.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+#include <array>
+#include <deque>
+#include <map>
+#include <string>
+#include <vector>
+#include "dw_eval_launch.hpp"
+#include "../../include/dwgsim_hip.h"
+
+using namespace dw;
+
+namespace {
+
+constexpr size_t DEFAULT_CHUNK = 32ull << 20, MIN_CHUNK = 4096, MAX_CHUNK = 1ull << 30;
+constexpr int32_t WIN_LO = -EVAL_WIN / 2;
+const char BREAK_LINE[] = "************************************************************\n";
+
+struct Slot {
+    size_t cap = 0;             // text bytes
+    char *h_text = nullptr;     // page-locked
+    EvalRes *h_res = nullptr;   // page-locked
+    uint8_t *d_text = nullptr;
+    uint32_t *d_ends = nullptr, *d_tiles = nullptr;
+    EvalRes *d_res = nullptr;
+    uint64_t *d_spill = nullptr;
+    uint8_t *d_flags = nullptr;
+    hipStream_t st = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    size_t fill = 0, ctx_len = 0, len = 0;
+    uint32_t has_ctx = 0;
+    bool busy = false;
+};
+
+} // namespace
+
+struct dwgsim_hip_eval_ctx {
+    dwgsim_hip_eval_opts_t o;
+    std::string P;
+    int device = 0;
+    std::string err;
+    Slot s[2];
+    int cur = 0;
+    std::deque<int> pending;
+    // targets of the current file: host copies (messages) and device copies (kernels)
+    std::string names;
+    std::vector<uint32_t> off;
+    std::vector<int32_t> hash;
+    char *d_names = nullptr;
+    uint32_t *d_off = nullptr;
+    int32_t *d_hash = nullptr;
+    ev::Targets tg = {};
+    char *d_P = nullptr;
+    unsigned long long *d_hist = nullptr;
+    std::map<int32_t, std::array<uint64_t, 5>> spill;
+    uint64_t n = 0, records = 0;
+    bool failed = false, finished = false, seen_header = false;
+    int code = 0;
+    uint64_t err_rec = 0;
+    std::string err_line;
+    std::string incorrect, table, stderr_text;
+    double kernel_ms = 0;
+    int32_t floor_score = ev::MINAS;
+};
+
+namespace {
+
+#define CK(x)                                                                                         \
+    do {                                                                                              \
+        hipError_t e_ = (x);                                                                          \
+        if (e_ != hipSuccess) {                                                                       \
+            c->err = std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x;                  \
+            return DWGSIM_HIP_ERR_DEVICE;                                                             \
+        }                                                                                             \
+    } while (0)
+
+void slot_free(Slot &S)
+{
+    if (S.h_text) hipHostFree(S.h_text);
+    if (S.h_res) hipHostFree(S.h_res);
+    if (S.d_text) hipFree(S.d_text);
+    if (S.d_ends) hipFree(S.d_ends);
+    if (S.d_tiles) hipFree(S.d_tiles);
+    if (S.d_res) hipFree(S.d_res);
+    if (S.d_spill) hipFree(S.d_spill);
+    if (S.d_flags) hipFree(S.d_flags);
+    S.h_text = nullptr; S.h_res = nullptr; S.d_text = nullptr; S.d_ends = nullptr; S.d_tiles = nullptr;
+    S.d_res = nullptr; S.d_spill = nullptr; S.d_flags = nullptr;
+}
+
+// buffers for `cap` text bytes: a line has at least its newline (ends, flags: cap entries); a record that reaches the histogram has at least
+// 11 bytes (ten tabs and the newline), so the spill list needs fewer than cap / 8 entries
+int slot_alloc(dwgsim_hip_eval_ctx *c, Slot &S, size_t cap)
+{
+    S.cap = cap;
+    CK(hipHostMalloc((void **)&S.h_text, cap, hipHostMallocDefault));
+    CK(hipHostMalloc((void **)&S.h_res, sizeof(EvalRes), hipHostMallocDefault));
+    CK(hipMalloc((void **)&S.d_text, cap + 16));
+    CK(hipMalloc((void **)&S.d_ends, cap * sizeof(uint32_t)));
+    CK(hipMalloc((void **)&S.d_tiles, (cap / EVAL_TILE + 1) * sizeof(uint32_t)));
+    CK(hipMalloc((void **)&S.d_res, sizeof(EvalRes)));
+    CK(hipMalloc((void **)&S.d_spill, (cap / 8 + 1) * sizeof(uint64_t)));
+    CK(hipMalloc((void **)&S.d_flags, cap));
+    return DWGSIM_HIP_OK;
+}
+
+std::string error_block(const char *fn, const char *var, const char *msg, bool fatal)
+{
+    std::string s = BREAK_LINE;
+    s += std::string("\rIn function \"") + fn + "\": " + (fatal ? "Fatal Error" : "Warning") + "[OutOfRange]. ";
+    if (var) s += std::string("Variable/Value: ") + var + ".\n";
+    s += std::string("Message: ") + msg + ".\n";
+    s += fatal ? " ***** Exiting due to errors *****\n" : " ***** Warning *****\n";
+    s += BREAK_LINE;
+    return s;
+}
+
+// the message of the fatal record `line`: the reference prints the read name as it stood when it gave up
+std::string fatal_text(const dwgsim_hip_eval_ctx *c, int code, const std::string &line)
+{
+    std::string var;
+    size_t qlen = line.find('\t');
+    if (qlen == std::string::npos) qlen = line.size();
+    if (code == ev::E_PREFIX || code == ev::E_NAME || code == ev::E_CONTIG) {
+        const ev::NameMask mk = ev::name_mask(line.data(), (int)qlen);
+        for (size_t i = 0; i < qlen; ++i) var += mk.has((int)i) ? ' ' : line[i];
+        if (code != ev::E_PREFIX && c->o.P) {
+            const size_t pl = c->P.size();
+            var = qlen > pl ? var.substr(pl + 1) : std::string();
+        }
+    }
+    switch (code) {
+    case ev::E_MALFORMED: return error_block("process_bam", nullptr, "[dwgsim_eval-hip] malformed SAM record", true);
+    case ev::E_PREFIX: return error_block("process_bam", var.c_str(), "[dwgsim_eval] could not match read name with given read name prefix (-P)", true);
+    case ev::E_NAME: return error_block("process_bam", var.c_str(), "[dwgsim_eval] read was not generated by dwgsim?", true);
+    case ev::E_CONTIG:
+        return error_block("process_bam", var.c_str(), "[dwgsim_eval] the mapped contig does not exist in the SAM header; perhaps you have a read name prefix?", true);
+    case ev::E_RANDOM_CORRECT:
+        return error_block("dwgsim_eval_counts_add", "predicted_value", "predicted value cannot be mapped correctly when the read is unmappable", true);
+    case ev::E_PAIRED: return error_block("run", nullptr, "Found a read that was paired end", true);
+    default: return error_block("run", nullptr, "Found a read that was not paired", true);
+    }
+}
+
+ev::Opts dev_opts(const dwgsim_hip_eval_ctx *c)
+{
+    ev::Opts o;
+    o.a = c->o.a; o.d = c->o.d; o.g = c->o.g; o.q = c->o.q; o.e = c->o.e; o.s = c->o.s; o.i = c->o.i; o.z = c->o.z; o.m = c->o.m;
+    o.P_len = c->o.P ? (int32_t)c->P.size() : -1;
+    o.P = c->d_P;
+    return o;
+}
+
+uint32_t records_grid(size_t len)
+{
+    const size_t g = (len + 256 * 256 - 1) / (256 * 256);       // about 256 bytes of text per lane
+    return (uint32_t)(g < 1 ? 1 : g > 1024 ? 1024 : g);
+}
+
+EvalRecArgs rec_args(dwgsim_hip_eval_ctx *c, const uint8_t *text, uint32_t *ends, EvalRes *res, uint64_t *spill, uint8_t *flags, uint32_t has_ctx)
+{
+    EvalRecArgs A;
+    A.text = text; A.ends = ends; A.res = res; A.hist = c->d_hist; A.spill = spill; A.flags = flags; A.has_ctx = has_ctx;
+    A.win_lo = WIN_LO; A.floor_score = c->floor_score; A.opt = dev_opts(c); A.tg = c->tg;
+    return A;
+}
+
+// the results of the oldest submitted chunk
+int process_oldest(dwgsim_hip_eval_ctx *c)
+{
+    const int k = c->pending.front();
+    c->pending.pop_front();
+    Slot &S = c->s[k];
+    CK(hipStreamSynchronize(S.st));
+    S.busy = false;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, S.e0, S.e1) == hipSuccess) c->kernel_ms += ms;
+    if (c->failed) return DWGSIM_HIP_OK;
+    const EvalRes r = *S.h_res;
+    const uint32_t n_rec = r.n_lines - S.has_ctx;
+    if (r.err != ~0ull) {
+        const uint64_t rec = r.err >> 8;
+        c->failed = true;
+        c->code = (int)(r.err & 0xff);
+        c->err_rec = c->records + rec;
+        const char *p = S.h_text;
+        for (uint64_t i = 0; i < rec + S.has_ctx; ++i) p = (const char *)memchr(p, '\n', S.h_text + S.len - p) + 1;
+        c->err_line.assign(p, (const char *)memchr(p, '\n', S.h_text + S.len - p) - p);
+        return DWGSIM_HIP_OK;
+    }
+    c->n += r.n;
+    c->records += n_rec;
+    if (r.n_spill) {
+        std::vector<uint64_t> sp(r.n_spill);
+        CK(hipMemcpy(sp.data(), S.d_spill, sp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint64_t w : sp) c->spill[(int32_t)(uint32_t)(w >> 32)][(int)(w & 7)]++;
+    }
+    if (c->o.p && n_rec) {
+        std::vector<uint8_t> fl(n_rec);
+        CK(hipMemcpy(fl.data(), S.d_flags, n_rec, hipMemcpyDeviceToHost));
+        const char *p = S.h_text + S.ctx_len, *end = S.h_text + S.len;
+        for (uint32_t i = 0; i < n_rec; ++i) {
+            const char *e = (const char *)memchr(p, '\n', end - p) + 1;
+            if (fl[i]) c->incorrect.append(p, e - p);
+            p = e;
+        }
+    }
+    return DWGSIM_HIP_OK;
+}
+
+int drain(dwgsim_hip_eval_ctx *c)
+{
+    while (!c->pending.empty()) {
+        const int r = process_oldest(c);
+        if (r) return r;
+    }
+    return DWGSIM_HIP_OK;
+}
+
+// submit the filling slot's text up to `cut` (just past a newline); the other slot continues with the context line and the rest
+int submit(dwgsim_hip_eval_ctx *c, size_t cut)
+{
+    Slot &S = c->s[c->cur];
+    S.len = cut;
+    *S.h_res = EvalRes{~0ull, 0, 0, 0};
+    CK(hipEventRecord(S.e0, S.st));
+    CK(hipMemcpyAsync(S.d_text, S.h_text, cut, hipMemcpyHostToDevice, S.st));
+    CK(hipMemcpyAsync(S.d_res, S.h_res, sizeof(EvalRes), hipMemcpyHostToDevice, S.st));
+    const EvalRecArgs A = rec_args(c, S.d_text, S.d_ends, S.d_res, S.d_spill, c->o.p ? S.d_flags : nullptr, S.has_ctx);
+    launch_eval_chunk(S.st, A, cut, S.d_tiles, records_grid(cut));
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(S.h_res, S.d_res, sizeof(EvalRes), hipMemcpyDeviceToHost, S.st));
+    CK(hipEventRecord(S.e1, S.st));
+    S.busy = true;
+    c->pending.push_back(c->cur);
+
+    c->cur ^= 1;
+    Slot &T = c->s[c->cur];
+    if (T.busy) {
+        const int r = process_oldest(c);
+        if (r) return r;
+    }
+    // the last line of the submitted chunk, then what follows it
+    size_t lb = cut - 1;
+    while (lb > 0 && S.h_text[lb - 1] != '\n') --lb;
+    const size_t ctx = cut - lb, rest = S.fill - cut;
+    memcpy(T.h_text, S.h_text + lb, ctx);
+    memcpy(T.h_text + ctx, S.h_text + cut, rest);
+    T.ctx_len = ctx; T.has_ctx = 1; T.fill = ctx + rest;
+    S.fill = 0;
+    return DWGSIM_HIP_OK;
+}
+
+// twice the room in both slots (a line longer than the filling slot's free space after its context line)
+int grow(dwgsim_hip_eval_ctx *c)
+{
+    int r = drain(c);
+    if (r) return r;
+    Slot &F = c->s[c->cur];
+    const size_t cap = F.cap * 2;
+    std::string keep(F.h_text, F.fill);
+    for (Slot &S : c->s) {
+        slot_free(S);
+        if ((r = slot_alloc(c, S, cap))) return r;
+    }
+    memcpy(F.h_text, keep.data(), keep.size());
+    return DWGSIM_HIP_OK;
+}
+
+// the filling slot's complete lines, and a last line without its newline
+int end_file(dwgsim_hip_eval_ctx *c)
+{
+    Slot &F = c->s[c->cur];
+    if (F.fill > F.ctx_len && F.h_text[F.fill - 1] != '\n') {
+        if (F.fill == F.cap) {
+            const int r = grow(c);
+            if (r) return r;
+        }
+        Slot &G = c->s[c->cur];
+        G.h_text[G.fill++] = '\n';
+    }
+    Slot &H = c->s[c->cur];
+    if (H.fill > H.ctx_len && !c->failed) {
+        const int r = submit(c, H.fill);
+        if (r) return r;
+    }
+    return drain(c);
+}
+
+int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
+{
+    c->names.clear();
+    c->off.assign(1, 0);
+    for (size_t p = 0; p < len;) {
+        const char *nl = (const char *)memchr(text + p, '\n', len - p);
+        const size_t e = nl ? (size_t)(nl - text) : len;
+        if (e - p >= 3 && !memcmp(text + p, "@SQ", 3)) {
+            for (size_t f = p; f < e;) {
+                const char *tab = (const char *)memchr(text + f, '\t', e - f);
+                const size_t fe = tab ? (size_t)(tab - text) : e;
+                if (f > p && fe - f >= 3 && !memcmp(text + f, "SN:", 3)) {
+                    c->names.append(text + f + 3, fe - f - 3);
+                    c->off.push_back((uint32_t)c->names.size());
+                    break;
+                }
+                f = fe + 1;
+            }
+        }
+        p = e + 1;
+    }
+    const int32_t nt = (int32_t)c->off.size() - 1;
+    uint32_t hs = 2;
+    while (hs < 2u * (uint32_t)nt) hs <<= 1;
+    c->hash.assign(hs, -1);
+    for (int32_t t = 0; t < nt; ++t) {
+        const uint32_t b = c->off[t], n = c->off[t + 1] - b;
+        uint32_t h = ev::fnv1a(c->names.data() + b, n) & (hs - 1);
+        while (c->hash[h] >= 0) {
+            const int32_t u = c->hash[h];
+            if (c->off[u + 1] - c->off[u] == n && !memcmp(c->names.data() + c->off[u], c->names.data() + b, n)) break;      // a repeated name: the first
+            h = (h + 1) & (hs - 1);
+        }
+        if (c->hash[h] < 0) c->hash[h] = t;
+    }
+    if (c->d_names) hipFree(c->d_names);
+    if (c->d_off) hipFree(c->d_off);
+    if (c->d_hash) hipFree(c->d_hash);
+    c->d_names = nullptr; c->d_off = nullptr; c->d_hash = nullptr;
+    CK(hipMalloc((void **)&c->d_names, c->names.size() + 1));
+    CK(hipMalloc((void **)&c->d_off, c->off.size() * sizeof(uint32_t)));
+    CK(hipMalloc((void **)&c->d_hash, hs * sizeof(int32_t)));
+    CK(hipMemcpy(c->d_names, c->names.data(), c->names.size() + 1, hipMemcpyHostToDevice));
+    CK(hipMemcpy(c->d_off, c->off.data(), c->off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    CK(hipMemcpy(c->d_hash, c->hash.data(), hs * sizeof(int32_t), hipMemcpyHostToDevice));
+    c->tg.names = c->d_names; c->tg.off = c->d_off; c->tg.hash = c->d_hash; c->tg.n = nt; c->tg.hmask = hs - 1;
+    return DWGSIM_HIP_OK;
+}
+
+void format_table(dwgsim_hip_eval_ctx *c, const std::vector<unsigned long long> &h)
+{
+    std::map<int32_t, std::array<uint64_t, 5>> rows = c->spill;
+    for (int k = 0; k <= EVAL_WIN; ++k)
+        for (int cl = 0; cl < 5; ++cl) {
+            const uint64_t v = h[(size_t)cl * (EVAL_WIN + 1) + k];
+            if (v) rows[k < EVAL_WIN ? WIN_LO + k : c->floor_score][cl] += v;
+        }
+    int64_t lo = 0, hi = 0;
+    uint64_t total = 0, m_total = 0, u_total = 0;
+    for (auto &kv : rows) {
+        lo = kv.first < lo ? kv.first : lo;
+        hi = kv.first > hi ? kv.first : hi;
+        const auto &r = kv.second;
+        total += r[0] + r[1] + r[2] + r[3] + r[4];
+        m_total += r[0] + r[1] + r[2];
+        u_total += r[3] + r[4];
+    }
+    const int w = total ? (int)(1 + log10((double)total)) : 1;
+    std::string &t = c->table;
+    t = std::string("# thr | the minimum ") + (c->o.a == 0 ? "mapping quality" : "alignment score") + " threshold\n";
+    t += "# mc | the number of correctly mapped reads that should be mapped at the threshold\n"
+         "# mi | the number of incorrectly mapped reads that should be mapped at the threshold\n"
+         "# mu | the number of unmapped reads that should be mapped at the threshold\n"
+         "# um | the number of mapped reads that should be unmapped at the threshold\n"
+         "# uu | the number of unmapped reads that should be unmapped at the threshold\n"
+         "# mc + mi + mu + um + uu | the total number of reads at the threshold\n"
+         "# mc' | the number of correctly mapped reads that should be mapped at or greater than that threshold\n"
+         "# mi' | the number of incorrectly mapped reads that should be mapped at or greater than that threshold\n"
+         "# mu' | the number of unmapped reads that should be mapped at or greater than that threshold\n"
+         "# um' | the number of mapped reads that should be unmapped at or greater than that threshold\n"
+         "# uu' | the number of unmapped reads that should be unmapped at or greater than that threshold\n"
+         "# mc' + mi' + mu' + um' + uu' | the total number of reads at or greater than the threshold\n"
+         "# (mc / (mc' + mi' + mu')) | sensitivity: the fraction of mappable reads that are mapped correctly at the threshold\n"
+         "# (mc / (mc' + mi')) | positive predictive value: the fraction of mapped mappable reads that are mapped correctly at the threshold\n"
+         "# (um / (um' + uu')) | false discovery rate: the fraction of random reads that are mapped at the threshold\n"
+         "# (mc' / (mc' + mi' + mu')) | sensitivity: the fraction of mappable reads that are mapped correctly at or greater than the threshold\n"
+         "# (mc' / (mc' + mi')) | positive predictive value: the fraction of mapped mappable reads that are mapped correctly at or greater than the threshold\n"
+         "# (um' / (um' + uu')) | false discovery rate: the fraction of random reads that are mapped at or greater than the threshold\n";
+    uint64_t sum[5] = {0, 0, 0, 0, 0}, mm_total = 0;
+    char buf[512];
+    const std::array<uint64_t, 5> zero = {0, 0, 0, 0, 0};
+    auto it = rows.rbegin();
+    for (int64_t sc = hi; sc >= lo; --sc) {
+        while (it != rows.rend() && it->first > sc) ++it;
+        const std::array<uint64_t, 5> &r = (it != rows.rend() && it->first == sc) ? it->second : zero;
+        for (int k = 0; k < 5; ++k) sum[k] += r[k];
+        mm_total += r[0] + r[1];
+        double den = (double)(r[0] + r[1] + r[2]);
+        const double sens_at = den == 0 ? 0. : r[0] / den;
+        const double sens_ge = m_total == 0 ? 0. : sum[0] / (double)m_total;
+        den = (double)(r[0] + r[1]);
+        const double ppv_at = den == 0 ? 0. : r[0] / den;
+        const double ppv_ge = mm_total == 0 ? 0. : sum[0] / (double)mm_total;
+        den = (double)(r[3] + r[4]);
+        const double fdr_at = den == 0 ? 0. : r[3] / den;
+        const double fdr_ge = u_total == 0 ? 0. : sum[3] / (double)u_total;
+        const int32_t thr = (int32_t)((uint32_t)(int32_t)sc * (uint32_t)c->o.d);
+        int k = snprintf(buf, sizeof buf, "%.2d ", thr);
+        const uint64_t v[12] = {r[0], r[1], r[2], r[3], r[4], r[0] + r[1] + r[2] + r[3] + r[4], sum[0], sum[1], sum[2], sum[3], sum[4],
+                                sum[0] + sum[1] + sum[2] + sum[3] + sum[4]};
+        for (int j = 0; j < 12; ++j) k += snprintf(buf + k, sizeof buf - k, "%*llu ", w, (unsigned long long)v[j]);
+        snprintf(buf + k, sizeof buf - k, "%.3e %.3e %.3e %.3e %.3e %.3e\n", sens_at, ppv_at, fdr_at, sens_ge, ppv_ge, fdr_ge);
+        t += buf;
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+void dwgsim_hip_eval_opts_default(dwgsim_hip_eval_opts_t *o)
+{
+    memset(o, 0, sizeof *o);
+    o->size = sizeof *o;
+    o->d = 1; o->e = -1; o->g = 5; o->s = -1;
+}
+
+dwgsim_hip_eval_ctx_t *dwgsim_hip_eval_create(const dwgsim_hip_eval_opts_t *opts, int device, int *err)
+{
+    int dummy;
+    if (!err) err = &dummy;
+    if (!opts || opts->size != sizeof(dwgsim_hip_eval_opts_t) || opts->d == 0 ||
+        (opts->chunk_bytes && (opts->chunk_bytes < MIN_CHUNK || opts->chunk_bytes > MAX_CHUNK))) {
+        *err = DWGSIM_HIP_ERR_ARG;
+        return nullptr;
+    }
+    auto *c = new dwgsim_hip_eval_ctx;
+    c->o = *opts;
+    if (opts->P) c->P = opts->P;
+    c->o.P = opts->P ? c->P.c_str() : nullptr;
+    c->device = device;
+    c->floor_score = ev::cdiv(ev::MINAS, opts->d);
+    if (c->floor_score < ev::MINAS) c->floor_score = ev::MINAS;
+    auto fail = [&](int e) { dwgsim_hip_eval_destroy(c); *err = e; return (dwgsim_hip_eval_ctx_t *)nullptr; };
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd || hipSetDevice(device) != hipSuccess) return fail(DWGSIM_HIP_ERR_DEVICE);
+    const size_t cap = opts->chunk_bytes ? opts->chunk_bytes : DEFAULT_CHUNK;
+    for (Slot &S : c->s) {
+        if (slot_alloc(c, S, cap)) return fail(DWGSIM_HIP_ERR_DEVICE);
+        if (hipStreamCreate(&S.st) != hipSuccess || hipEventCreate(&S.e0) != hipSuccess || hipEventCreate(&S.e1) != hipSuccess)
+            return fail(DWGSIM_HIP_ERR_DEVICE);
+    }
+    const size_t hb = 5 * (EVAL_WIN + 1) * sizeof(unsigned long long);
+    if (hipMalloc((void **)&c->d_hist, hb) != hipSuccess || hipMemset(c->d_hist, 0, hb) != hipSuccess) return fail(DWGSIM_HIP_ERR_DEVICE);
+    if (hipMalloc((void **)&c->d_P, c->P.size() + 1) != hipSuccess || hipMemcpy(c->d_P, c->P.c_str(), c->P.size() + 1, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(DWGSIM_HIP_ERR_DEVICE);
+    if (upload_targets(c, "", 0)) return fail(DWGSIM_HIP_ERR_DEVICE);
+    *err = DWGSIM_HIP_OK;
+    return c;
+}
+
+int dwgsim_hip_eval_header(dwgsim_hip_eval_ctx_t *c, const char *text, size_t len)
+{
+    if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
+    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    int r = end_file(c);
+    if (r) return r;
+    if (!c->seen_header && c->o.p) c->incorrect.assign(text, len);
+    c->seen_header = true;
+    return upload_targets(c, text, len);
+}
+
+int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
+{
+    if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
+    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    c->seen_header = true;      // the first file's header is empty when feed comes first
+    while (len && !c->failed) {
+        Slot &F = c->s[c->cur];
+        if (F.fill == F.cap) {
+            size_t cut = F.fill;
+            while (cut > F.ctx_len && F.h_text[cut - 1] != '\n') --cut;
+            const int r = cut > F.ctx_len ? submit(c, cut) : grow(c);
+            if (r) return r;
+            continue;
+        }
+        const size_t k = len < F.cap - F.fill ? len : F.cap - F.fill;
+        memcpy(F.h_text + F.fill, buf, k);
+        F.fill += k; buf += k; len -= k;
+    }
+    return c->failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *c, dwgsim_hip_eval_summary_t *sm)
+{
+    if (!c || c->finished || !sm || sm->size != sizeof(dwgsim_hip_eval_summary_t)) return c && c->finished ? DWGSIM_HIP_ERR_STATE : DWGSIM_HIP_ERR_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    int r = end_file(c);
+    if (r) return r;
+    c->finished = true;
+    c->stderr_text = "Analyzing...\nCurrently on:\n0";
+    if (c->failed) {
+        c->stderr_text += fatal_text(c, c->code, c->err_line);
+        c->table.clear();
+        c->incorrect.clear();
+    } else {
+        std::vector<unsigned long long> h(5 * (EVAL_WIN + 1));
+        CK(hipMemcpy(h.data(), c->d_hist, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        format_table(c, h);
+        char buf[128];
+        snprintf(buf, sizeof buf, "\r%llu\n", (unsigned long long)c->n);
+        c->stderr_text += buf;
+        if (c->o.n > 0 && c->n != (uint64_t)c->o.n) {
+            snprintf(buf, sizeof buf, "(-n)=%d\tn=%llu\n", c->o.n, (unsigned long long)c->n);
+            c->stderr_text += buf;
+            c->stderr_text += error_block("run", nullptr, "Number of reads found differs from the number specified (-n)", false);
+        }
+        c->stderr_text += "Analysis complete.\n";
+    }
+    const uint32_t size = sm->size;
+    memset(sm, 0, sizeof *sm);
+    sm->size = size;
+    sm->status = c->failed ? 1 : 0;
+    sm->error_code = c->failed ? c->code : 0;
+    sm->error_record = c->failed ? c->err_rec : 0;
+    sm->n = c->n;
+    sm->records = c->records;
+    sm->stderr_text = c->stderr_text.c_str();
+    sm->stderr_len = c->stderr_text.size();
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_table_text(dwgsim_hip_eval_ctx_t *c, const char **txt, size_t *len)
+{
+    if (!c || !c->finished || !txt || !len) return DWGSIM_HIP_ERR_STATE;
+    *txt = c->table.c_str(); *len = c->table.size();
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_incorrect_text(dwgsim_hip_eval_ctx_t *c, const char **txt, size_t *len)
+{
+    if (!c || !c->finished || !txt || !len) return DWGSIM_HIP_ERR_STATE;
+    *txt = c->incorrect.c_str(); *len = c->incorrect.size();
+    return DWGSIM_HIP_OK;
+}
+
+const char *dwgsim_hip_eval_last_error(const dwgsim_hip_eval_ctx_t *c) { return c ? c->err.c_str() : "no context"; }
+
+void dwgsim_hip_eval_destroy(dwgsim_hip_eval_ctx_t *c)
+{
+    if (!c) return;
+    hipSetDevice(c->device);
+    for (Slot &S : c->s) {
+        if (S.st) hipStreamSynchronize(S.st);
+        slot_free(S);
+        if (S.st) hipStreamDestroy(S.st);
+        if (S.e0) hipEventDestroy(S.e0);
+        if (S.e1) hipEventDestroy(S.e1);
+    }
+    if (c->d_names) hipFree(c->d_names);
+    if (c->d_off) hipFree(c->d_off);
+    if (c->d_hash) hipFree(c->d_hash);
+    if (c->d_hist) hipFree(c->d_hist);
+    if (c->d_P) hipFree(c->d_P);
+    delete c;
+}
+
+int dwgsim_hip_eval_debug_time(dwgsim_hip_eval_ctx_t *c, double *kernel_ms)
+{
+    if (!c || !kernel_ms) return DWGSIM_HIP_ERR_ARG;
+    *kernel_ms = c->kernel_ms;
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *c, const void *text, size_t len, int reps, double *ms)
+{
+    if (!c || !text || !len || len > MAX_CHUNK * 4ull || reps < 1 || !ms) return DWGSIM_HIP_ERR_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    uint8_t *dev = nullptr;
+    uint32_t *ends = nullptr, *tiles = nullptr;
+    EvalRes *res = nullptr;
+    uint64_t *spill = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = DWGSIM_HIP_OK;
+    auto cleanup = [&]() {
+        if (dev) hipFree(dev);
+        if (ends) hipFree(ends);
+        if (tiles) hipFree(tiles);
+        if (res) hipFree(res);
+        if (spill) hipFree(spill);
+        if (e0) hipEventDestroy(e0);
+        if (e1) hipEventDestroy(e1);
+    };
+    if (hipMalloc((void **)&dev, len + 16) || hipMalloc((void **)&ends, len * sizeof(uint32_t)) || hipMalloc((void **)&tiles, (len / EVAL_TILE + 1) * sizeof(uint32_t)) ||
+        hipMalloc((void **)&res, sizeof(EvalRes)) || hipMalloc((void **)&spill, (len / 8 + 1) * sizeof(uint64_t)) || hipEventCreate(&e0) ||
+        hipEventCreate(&e1)) {
+        cleanup();
+        c->err = "debug_device_chunk: out of device memory";
+        return DWGSIM_HIP_ERR_NOMEM;
+    }
+    hipStream_t st = c->s[0].st;
+    if (hipMemcpy(dev, text, len, hipMemcpyHostToDevice) != hipSuccess) {
+        cleanup();
+        c->err = "debug_device_chunk: upload failed";
+        return DWGSIM_HIP_ERR_DEVICE;
+    }
+    const EvalRecArgs A = rec_args(c, (const uint8_t *)dev, ends, res, spill, nullptr, 0);
+    hipEventRecord(e0, st);
+    for (int i = 0; i < reps; ++i) {
+        hipMemsetAsync(res, 0xff, 8, st);
+        hipMemsetAsync((char *)res + 8, 0, sizeof(EvalRes) - 8, st);
+        launch_eval_chunk(st, A, len, tiles, records_grid(len));
+    }
+    hipEventRecord(e1, st);
+    if (hipStreamSynchronize(st) != hipSuccess) { c->err = "debug_device_chunk: kernel failed"; rc = DWGSIM_HIP_ERR_DEVICE; }
+    float t = 0;
+    hipEventElapsedTime(&t, e0, e1);
+    *ms = t / reps;
+    cleanup();
+    return rc;
+}
+
+} // extern "C"

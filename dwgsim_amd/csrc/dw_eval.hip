@@ -1,0 +1,159 @@
+// dw_eval.hip -- the kernels of dwgsim_eval-hip: SAM text in, per-score class counts out (host side: dw_eval.cpp; semantics: dw_eval.hpp).
+//
+// A chunk is whole lines of SAM record text (every line ends in '\n'), optionally led by one context line: the last record of the previous chunk,
+// there only so that -m can compare the first record with the one before it.  Per chunk:
+//   k_eval_count    newlines per 4 KiB tile
+//   k_eval_scan     exclusive scan of the tile counts (one block), and the number of lines
+//   k_eval_lines    the position of every newline, in order: line r = (ends[r-1], ends[r]]
+//   k_eval_records  one lane per record: parse, -m / -q / filters / class, first fatal error (atomicMin of record << 8 | code), n, and the
+//                   histogram: an LDS window of EVAL_WIN scores x 5 classes plus one bin for the floor score (the unmapped records of -a 1..3),
+//                   merged into the 64-bit global histogram once per block; a score outside both goes to the spill list, which the host adds.
+// The histogram is fused into k_eval_records: the per-record (class, score) words never go to memory.
+#include <hip/hip_runtime.h>
+#include "dw_eval.hpp"
+#include "dw_eval_launch.hpp"
+
+namespace dw {
+
+constexpr int EV_THREADS = 256;
+constexpr int EV_BYTES = 16;                                 // per lane in the newline kernels
+constexpr uint32_t EV_TILE = EV_THREADS * EV_BYTES;          // 4096
+
+static_assert(EVAL_TILE == EV_TILE, "tile size");
+
+// number of '\n' bytes in a 32-bit word (exact: no carries between bytes)
+__device__ __forceinline__ uint32_t nl_count(uint32_t x)
+{
+    const uint32_t y = x ^ 0x0a0a0a0au;
+    const uint32_t t = ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu);
+    return (uint32_t)__popc(t);
+}
+
+// the 16 bytes of a lane, as four words (past the end: zero bytes, which are no newline)
+__device__ __forceinline__ void load16(const uint8_t *text, uint64_t len, uint64_t at, uint32_t w[4])
+{
+    if (at + EV_BYTES <= len) {
+        const uint4 v = *(const uint4 *)(text + at);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+        for (int k = 0; k < 4; ++k) {
+            uint32_t x = 0;
+            for (int b = 0; b < 4; ++b) {
+                const uint64_t p = at + 4 * k + b;
+                x |= (uint32_t)(p < len ? text[p] : 0) << (8 * b);
+            }
+            w[k] = x;
+        }
+    }
+}
+
+// exclusive scan of one value per lane over the block (256 lanes), and the block total
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *total)
+{
+    __shared__ uint32_t s[EV_THREADS];
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int d = 1; d < EV_THREADS; d <<= 1) {
+        const uint32_t x = t >= d ? s[t - d] : 0;
+        __syncthreads();
+        s[t] += x;
+        __syncthreads();
+    }
+    const uint32_t incl = s[t];
+    *total = s[EV_THREADS - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(EV_THREADS) void k_eval_count(const uint8_t *text, uint64_t len, uint32_t *tile_count)
+{
+    uint32_t w[4];
+    load16(text, len, (uint64_t)blockIdx.x * EV_TILE + threadIdx.x * EV_BYTES, w);
+    const uint32_t c = nl_count(w[0]) + nl_count(w[1]) + nl_count(w[2]) + nl_count(w[3]);
+    uint32_t tot;
+    block_excl_scan(c, &tot);
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(EV_THREADS) void k_eval_scan(uint32_t *tile_count, uint32_t n_tiles, EvalRes *res)
+{
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n_tiles; base += EV_THREADS) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < n_tiles ? tile_count[i] : 0;
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan(v, &tot);
+        if (i < n_tiles) tile_count[i] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) res->n_lines = carry;
+}
+
+__global__ __launch_bounds__(EV_THREADS) void k_eval_lines(const uint8_t *text, uint64_t len, const uint32_t *tile_base, uint32_t *ends)
+{
+    const uint64_t at = (uint64_t)blockIdx.x * EV_TILE + threadIdx.x * EV_BYTES;
+    uint32_t w[4];
+    load16(text, len, at, w);
+    const uint32_t c = nl_count(w[0]) + nl_count(w[1]) + nl_count(w[2]) + nl_count(w[3]);
+    uint32_t tot;
+    uint32_t o = tile_base[blockIdx.x] + block_excl_scan(c, &tot);
+    if (!c) return;
+    for (int k = 0; k < 4; ++k)
+        for (int b = 0; b < 4; ++b)
+            if (((w[k] >> (8 * b)) & 0xff) == '\n') ends[o++] = (uint32_t)(at + 4 * k + b);
+}
+
+__global__ __launch_bounds__(EV_THREADS) void k_eval_records(EvalRecArgs A)
+{
+    __shared__ uint32_t h[5 * (EVAL_WIN + 1)];
+    for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS) h[i] = 0;
+    __syncthreads();
+
+    const uint32_t n_lines = A.res->n_lines;
+    const uint32_t n_rec = n_lines > A.has_ctx ? n_lines - A.has_ctx : 0;
+    const char *text = (const char *)A.text;
+    uint32_t n_local = 0;
+    for (uint32_t r = blockIdx.x * EV_THREADS + threadIdx.x; r < n_rec; r += gridDim.x * EV_THREADS) {
+        const uint32_t li = r + A.has_ctx;
+        const uint32_t b = li ? A.ends[li - 1] + 1 : 0, e = A.ends[li];
+        const char *prev = nullptr;
+        uint32_t pb = 0, pe = 0;
+        if (li) { pb = li >= 2 ? A.ends[li - 2] + 1 : 0; pe = A.ends[li - 1]; prev = text + pb; }
+        const ev::Out o = ev::eval_line(text + b, e - b, prev, pe - pb, A.opt, A.tg);
+        bool incorrect = false;
+        if (o.code) {
+            atomicMin((unsigned long long *)&A.res->err, (unsigned long long)(((uint64_t)r << 8) | (uint32_t)o.code));
+        } else if (!o.skipped) {
+            n_local += (uint32_t)o.n_inc;
+            if (o.cls >= 0) {
+                incorrect = o.cls == ev::MI || o.cls == ev::UM;
+                const int64_t bin = (int64_t)o.score - A.win_lo;
+                if (bin >= 0 && bin < EVAL_WIN) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + (uint32_t)bin], 1u);
+                else if (o.score == A.floor_score) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + EVAL_WIN], 1u);
+                else {
+                    const uint32_t k = atomicAdd(&A.res->n_spill, 1u);
+                    A.spill[k] = ((uint64_t)(uint32_t)o.score << 32) | (uint32_t)o.cls;
+                }
+            }
+        }
+        if (A.flags) A.flags[r] = incorrect ? 1 : 0;
+    }
+    if (n_local) atomicAdd((unsigned long long *)&A.res->n, (unsigned long long)n_local);
+    __syncthreads();
+    for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS)
+        if (h[i]) atomicAdd((unsigned long long *)&A.hist[i], (unsigned long long)h[i]);
+}
+
+void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tile_count, uint32_t grid_records)
+{
+    const uint32_t tiles = (uint32_t)((len + EV_TILE - 1) / EV_TILE);
+    if (tiles) {
+        hipLaunchKernelGGL(k_eval_count, dim3(tiles), dim3(EV_THREADS), 0, st, A.text, len, tile_count);
+        hipLaunchKernelGGL(k_eval_scan, dim3(1), dim3(EV_THREADS), 0, st, tile_count, tiles, A.res);
+        hipLaunchKernelGGL(k_eval_lines, dim3(tiles), dim3(EV_THREADS), 0, st, A.text, len, (const uint32_t *)tile_count, A.ends);
+    }
+    hipLaunchKernelGGL(k_eval_records, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A);
+}
+
+} // namespace dw

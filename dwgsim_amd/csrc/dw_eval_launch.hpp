@@ -1,0 +1,36 @@
+// dw_eval_launch.hpp -- what dw_eval.cpp hands the kernels of dw_eval.hip
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "dw_eval.hpp"
+
+namespace dw {
+
+constexpr uint32_t EVAL_TILE = 4096;      // text bytes per block of the newline kernels
+constexpr int EVAL_WIN = 2048;            // scores held in LDS per class (plus one bin for the floor score)
+
+// per chunk, device-written
+struct EvalRes {
+    unsigned long long err;     // (record << 8) | code of the first fatal record, ~0 when none
+    unsigned long long n;       // the n of the reference (pairs or single-end reads)
+    uint32_t n_lines;           // lines of the chunk, context line included
+    uint32_t n_spill;           // entries of the spill list
+};
+
+struct EvalRecArgs {
+    const uint8_t *text;
+    uint32_t *ends;
+    EvalRes *res;
+    unsigned long long *hist;   // 5 x (EVAL_WIN + 1): class-major; bin EVAL_WIN of a class = floor_score
+    uint64_t *spill;            // (uint32 score << 32) | class
+    uint8_t *flags;             // nullptr, or per record: 1 = mapped incorrectly (-p)
+    uint32_t has_ctx;
+    int32_t win_lo;             // bin k of the window = score win_lo + k
+    int32_t floor_score;
+    ev::Opts opt;
+    ev::Targets tg;
+};
+
+void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tile_count, uint32_t grid_records);
+
+} // namespace dw

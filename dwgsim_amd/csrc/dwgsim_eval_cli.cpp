@@ -1,0 +1,163 @@
+// dwgsim_eval-hip -- the dwgsim_eval command line (reference src/dwgsim_eval.c main / run) over the dwgsim_hip_eval_* C-ABI.  SAM text only.
+#include <errno.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+#include <string>
+#include <vector>
+#include "../../include/dwgsim_hip.h"
+
+#define PACKAGE_VERSION "0.1.17-hip"
+
+static const char *tf(int v) { return v == 1 ? "True" : "False"; }
+
+static int print_usage(const dwgsim_hip_eval_opts_t *a)
+{
+    FILE *f = stderr;
+    fprintf(f, "\n");
+    fprintf(f, "Program: dwgsim_eval-hip (short read simulation evaluator, MI355X hot path of dwgsim_eval)\n");
+    fprintf(f, "Version: %s\n", PACKAGE_VERSION);
+    fprintf(f, "Contact: Nils Homer <dnaa-help@lists.sourceforge.net>\n\n");
+    fprintf(f, "Usage: dwgsim_eval-hip [options] -S <in.sam> [<in2.sam> ...]   (- reads stdin)\n\n");
+    fprintf(f, "Options:\n");
+    fprintf(f, "\t-a\tINT\tsplit by [%d]:\n", a->a);
+    fprintf(f, "\t\t\t\t\t0: by mapping quality\n");
+    fprintf(f, "\t\t\t\t\t1: by alignment score\n");
+    fprintf(f, "\t\t\t\t\t2: by suboptimal alignment score\n");
+    fprintf(f, "\t\t\t\t\t3: by alignment score - suboptimal alignment score\n");
+    fprintf(f, "\t-b\t\talignments are from BWA (for SOLiD data only) [%s]\n", tf(a->b));
+    fprintf(f, "\t-c\t\tcolor space alignments [%s]\n", tf(a->c));
+    fprintf(f, "\t-d\tINT\tdivide quality/alignment score by this factor [%d]\n", a->d);
+    fprintf(f, "\t-g\t\tgap \"wiggle\" [%d]\n", a->g);
+    fprintf(f, "\t-m\t\tconsecutive alignments with the same name (and end for multi-ends) should be treated as multi-mapped reads [%s]\n", tf(a->m));
+    fprintf(f, "\t-n\tINT\tnumber of raw input paired-end reads (otherwise, inferred from all SAM records present) [%d]\n", a->n);
+    fprintf(f, "\t-q\tINT\tconsider only alignments with this mapping quality or greater [%d]\n", a->q);
+    fprintf(f, "\t-z\t\tinput contains only single end reads [%s]\n", tf(a->z));
+    fprintf(f, "\t-S\t\tinput is SAM (required: BAM is not supported) [%s]\n", tf(0));
+    fprintf(f, "\t-p\t\tprint incorrect alignments [%s]\n", tf(a->p));
+    fprintf(f, "\t-s\tINT\tconsider only alignments with the number of specified SNPs [%d]\n", a->s);
+    fprintf(f, "\t-e\tINT\tconsider only alignments with the number of specified errors [%d]\n", a->e);
+    fprintf(f, "\t-i\t\tconsider only alignments with indels [%s]\n", tf(a->i));
+    fprintf(f, "\t-P\tSTRING\ta read prefix that was prepended to each read name [%s]\n", a->P ? a->P : "not using");
+    fprintf(f, "\t-h\t\tprint this help message\n");
+    return 1;
+}
+
+static const char BREAK_LINE[] = "************************************************************\n";
+
+// one file: its '@' lines go to the header call, the rest is fed as it is read
+static int run_file(dwgsim_hip_eval_ctx_t *ctx, FILE *in)
+{
+    std::vector<char> buf(8u << 20);
+    std::string header;
+    bool in_header = true, at_line_start = true;
+    size_t got;
+    while ((got = fread(buf.data(), 1, buf.size(), in)) > 0) {
+        size_t p = 0;
+        if (in_header) {
+            while (p < got && in_header) {
+                if (at_line_start && buf[p] != '@') { in_header = false; break; }
+                const char *nl = (const char *)memchr(buf.data() + p, '\n', got - p);
+                const size_t e = nl ? (size_t)(nl - buf.data()) + 1 : got;
+                header.append(buf.data() + p, e - p);
+                at_line_start = nl != nullptr;
+                p = e;
+            }
+            if (in_header) continue;
+            const int r = dwgsim_hip_eval_header(ctx, header.data(), header.size());
+            if (r) return r;
+        }
+        const int r = dwgsim_hip_eval_feed(ctx, buf.data() + p, got - p);
+        if (r) return r;
+    }
+    if (in_header) return dwgsim_hip_eval_header(ctx, header.data(), header.size());
+    return DWGSIM_HIP_OK;
+}
+
+int main(int argc, char *argv[])
+{
+    dwgsim_hip_eval_opts_t o;
+    dwgsim_hip_eval_opts_default(&o);
+    int S = 0;
+    std::string P;
+    const char *chunk = getenv("DWGSIM_EVAL_CHUNK");      // text bytes per device chunk (tests use small ones)
+    if (chunk) o.chunk_bytes = strtoull(chunk, nullptr, 10);
+    int c;
+    while ((c = getopt(argc, argv, "a:d:e:g:m:n:q:s:bchimpzSP:")) >= 0) {
+        switch (c) {
+        case 'a': o.a = atoi(optarg); break;
+        case 'b': o.b = 1; break;
+        case 'c': o.c = 1; break;
+        case 'd': o.d = atoi(optarg); break;
+        case 'g': o.g = atoi(optarg); break;
+        case 'm': o.m = 1; break;         // "m:" in the reference's option string: -m takes (and ignores) an argument
+        case 'h': return print_usage(&o);
+        case 'n': o.n = atoi(optarg); break;
+        case 'q': o.q = atoi(optarg); break;
+        case 'z': o.z = 1; break;
+        case 'S': S = 1; break;
+        case 'p': o.p = 1; break;
+        case 's': o.s = atoi(optarg); break;
+        case 'e': o.e = atoi(optarg); break;
+        case 'i': o.i = 1; break;
+        case 'P': P = optarg; o.P = P.c_str(); break;
+        default: fprintf(stderr, "Unrecognized option: -%c\n", c); return 1;
+        }
+    }
+    if (argc == optind) return print_usage(&o);
+    if (!S) {
+        fprintf(stderr, "dwgsim_eval-hip: only SAM text is supported: pass -S (samtools view -h in.bam | dwgsim_eval-hip -S -)\n");
+        return 1;
+    }
+    if (o.d == 0) {
+        fprintf(stderr, "dwgsim_eval-hip: -d must not be 0\n");
+        return 1;
+    }
+    int err = 0;
+    dwgsim_hip_eval_ctx_t *ctx = dwgsim_hip_eval_create(&o, 0, &err);
+    if (!ctx) {
+        fprintf(stderr, "dwgsim_eval-hip: cannot start the evaluator on device 0 (error %d)\n", err);
+        return 1;
+    }
+    fputs("Analyzing...\nCurrently on:\n0", stderr);
+    int r = DWGSIM_HIP_OK;
+    for (int i = optind; i < argc && r == DWGSIM_HIP_OK; ++i) {
+        FILE *in = strcmp(argv[i], "-") ? fopen(argv[i], "rb") : stdin;
+        if (!in) {
+            const int e = errno;
+            fprintf(stderr, "%s\rIn function \"run\": Fatal Error[OpenFileError]. Variable/Value: %s.\nMessage: Could not open file for reading.\n", BREAK_LINE, argv[i]);
+            fprintf(stderr, "The file stream error was:: %s\n ***** Exiting due to errors *****\n%s", strerror(e), BREAK_LINE);
+            dwgsim_hip_eval_destroy(ctx);
+            return 1;
+        }
+        r = run_file(ctx, in);
+        if (in != stdin) fclose(in);
+    }
+    if (r != DWGSIM_HIP_OK && r != DWGSIM_HIP_EVAL_STOPPED) {
+        fprintf(stderr, "\ndwgsim_eval-hip: %s\n", dwgsim_hip_eval_last_error(ctx));
+        dwgsim_hip_eval_destroy(ctx);
+        return 1;
+    }
+    dwgsim_hip_eval_summary_t sm;
+    memset(&sm, 0, sizeof sm);
+    sm.size = sizeof sm;
+    if (dwgsim_hip_eval_finish(ctx, &sm) != DWGSIM_HIP_OK) {
+        fprintf(stderr, "\ndwgsim_eval-hip: %s\n", dwgsim_hip_eval_last_error(ctx));
+        dwgsim_hip_eval_destroy(ctx);
+        return 1;
+    }
+    // the reference's stderr, minus the "Analyzing..." lines written above
+    const size_t skip = strlen("Analyzing...\nCurrently on:\n0");
+    if (sm.status == 0) {
+        const char *t;
+        size_t n;
+        if (o.p && dwgsim_hip_eval_incorrect_text(ctx, &t, &n) == DWGSIM_HIP_OK) fwrite(t, 1, n, stdout);
+        if (dwgsim_hip_eval_table_text(ctx, &t, &n) == DWGSIM_HIP_OK) fwrite(t, 1, n, stdout);
+        fflush(stdout);
+    }
+    fwrite(sm.stderr_text + skip, 1, sm.stderr_len - skip, stderr);
+    const int status = sm.status;
+    dwgsim_hip_eval_destroy(ctx);
+    return status;
+}

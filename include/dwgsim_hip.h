@@ -337,6 +337,64 @@ const char *dwgsim_hip_job_last_error(const dwgsim_hip_job_t *job);
 void dwgsim_hip_job_destroy(dwgsim_hip_job_t *job);
 
 /* ====================================================================================================================================
+ * dwgsim_eval: score SAM alignments of simulated reads (reference src/dwgsim_eval.c; DESIGN.md "dwgsim_eval-hip").  SAM text only.
+ * A context evaluates one run: header(file 1), feed(records of file 1)..., header(file 2), feed..., finish, then the texts.  One device.
+ * ==================================================================================================================================== */
+#define DWGSIM_HIP_EVAL_ABI_VERSION 1
+/* fatal record errors (dwgsim_hip_eval_summary_t.error_code): the first record of the run, in file order, that has one decides */
+#define DWGSIM_HIP_EVAL_E_MALFORMED       1   /* not a SAM record (fewer than 11 fields, FLAG / POS / MAPQ out of range, ...) */
+#define DWGSIM_HIP_EVAL_E_PREFIX          2   /* "could not match read name with given read name prefix (-P)" */
+#define DWGSIM_HIP_EVAL_E_NAME            3   /* "read was not generated by dwgsim?" */
+#define DWGSIM_HIP_EVAL_E_CONTIG          4   /* "the mapped contig does not exist in the SAM header" */
+#define DWGSIM_HIP_EVAL_E_RANDOM_CORRECT  5   /* "predicted value cannot be mapped correctly when the read is unmappable" */
+#define DWGSIM_HIP_EVAL_E_PAIRED          6   /* -z: "Found a read that was paired end" */
+#define DWGSIM_HIP_EVAL_E_NOT_PAIRED      7   /* no -z: "Found a read that was not paired" */
+#define DWGSIM_HIP_EVAL_STOPPED           1   /* dwgsim_hip_eval_feed: a fatal record was found, the rest of the input is not needed */
+
+typedef struct dwgsim_hip_eval_ctx dwgsim_hip_eval_ctx_t;
+
+/* the options of dwgsim_eval (getopt "a:d:e:g:m:n:q:s:bchimpzSP:"), defaults from dwgsim_hip_eval_opts_default */
+typedef struct dwgsim_hip_eval_opts {
+    uint32_t size;                  /* sizeof(dwgsim_hip_eval_opts_t) */
+    int32_t a, d, e, g, n, q, s;    /* -a 0, -d 1 (not 0), -e -1, -g 5, -n 0, -q 0, -s -1 */
+    int32_t b, c, i, m, p, z;       /* flags, 0 */
+    const char *P;                  /* -P, NULL: none (copied at create) */
+    uint64_t chunk_bytes;           /* text per device chunk; 0: 32 MiB.  At least 4 KiB */
+} dwgsim_hip_eval_opts_t;
+
+typedef struct dwgsim_hip_eval_summary {
+    uint32_t size;                  /* sizeof(dwgsim_hip_eval_summary_t), set by the caller */
+    int32_t status;                 /* the exit status of dwgsim_eval: 0, or 1 after a fatal record error */
+    int32_t error_code;             /* DWGSIM_HIP_EVAL_E_*, 0 */
+    int32_t reserved;
+    uint64_t error_record;          /* 0-based index of that record among the record lines of the run */
+    uint64_t n;                     /* pairs (single-end reads with -z) */
+    uint64_t records;               /* record lines evaluated */
+    const char *stderr_text;        /* what dwgsim_eval writes to stderr (fatal error, -n warning, "Analysis complete."); valid until destroy */
+    size_t stderr_len;
+} dwgsim_hip_eval_summary_t;
+
+void dwgsim_hip_eval_opts_default(dwgsim_hip_eval_opts_t *opts);
+/* *err: DWGSIM_HIP_OK, DWGSIM_HIP_ERR_ARG (size, -d 0, chunk), DWGSIM_HIP_ERR_DEVICE */
+dwgsim_hip_eval_ctx_t *dwgsim_hip_eval_create(const dwgsim_hip_eval_opts_t *opts, int device, int *err);
+/* starts the next file: its header text (the '@' lines; the @SQ SN: names are its targets) */
+int dwgsim_hip_eval_header(dwgsim_hip_eval_ctx_t *ctx, const char *text, size_t len);
+/* record text of the current file, split anywhere.  DWGSIM_HIP_EVAL_STOPPED once a fatal record has been found */
+int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *ctx, const char *buf, size_t len);
+int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *ctx, dwgsim_hip_eval_summary_t *summary);
+/* after finish without a fatal error: the 19 '#' lines and the rows (stdout of dwgsim_eval after the -p part) */
+int dwgsim_hip_eval_table_text(dwgsim_hip_eval_ctx_t *ctx, const char **txt, size_t *len);
+/* with -p: the first file's header and the incorrectly mapped records, verbatim, in input order */
+int dwgsim_hip_eval_incorrect_text(dwgsim_hip_eval_ctx_t *ctx, const char **txt, size_t *len);
+const char *dwgsim_hip_eval_last_error(const dwgsim_hip_eval_ctx_t *ctx);
+void dwgsim_hip_eval_destroy(dwgsim_hip_eval_ctx_t *ctx);
+/* test hooks: the device time (ms, HIP events) of the chunks so far; and kernel-only throughput: `len` bytes of record lines (host memory)
+ * are uploaded once and then evaluated `reps` times as one chunk from device memory, *ms = time per evaluation.  The run's counts are untouched
+ * except for the histogram, which this adds to. */
+int dwgsim_hip_eval_debug_time(dwgsim_hip_eval_ctx_t *ctx, double *kernel_ms);
+int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *ctx, const void *text, size_t len, int reps, double *ms);
+
+/* ====================================================================================================================================
  * TEST / ANALYSIS HOOKS -- everything below this line is NOT part of the drop-in surface.  A binding of the reference needs none of it; the
  * parity tests and the profiling scripts do.  (All of it is read-only with respect to what the product computes: the options select between
  * code paths that produce the same bytes, the self-tests and counters only report.)

@@ -1,0 +1,73 @@
+"""Throughput of dwgsim_eval-hip (not part of bench.py): GB/s of SAM text and records/s
+  kernel   text already in device memory (uploaded beforehand), the four kernels of one chunk only (dwgsim_hip_eval_debug_device_chunk)
+  e2e      text in page-locked host memory fed through dwgsim_hip_eval_feed: copy into the context's slots, upload, kernels, results
+  model    tests/eval_model.py, the plain-Python model, on one core
+Prints one JSON line.  Usage: python tools/eval_throughput.py [--mib 1024] [--reps 5] [--model-mib 16]"""
+import argparse, ctypes as C, json, os, random, sys, time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from dwgsim_amd import api  # noqa: E402
+import eval_model as M  # noqa: E402
+import eval_sam as S  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mib", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--model-mib", type=int, default=16)
+    ap.add_argument("--a", type=int, default=3)
+    args = ap.parse_args()
+    contigs = [("chr%d" % i, 200_000_000) for i in range(1, 23)]
+    rng = random.Random(5)
+    head = S.header(contigs)
+    block = b"".join(r + b"\n" for r in S.records(rng, S.synth_names(rng, contigs, 40000), contigs))
+    recs_block = block.count(b"\n")
+    k = max(1, (args.mib << 20) // len(block))
+    text = block * k
+    n_bytes, n_recs = len(text), recs_block * k
+    out = {"bytes": n_bytes, "records": n_recs, "a": args.a}
+
+    lib = api.load()
+    with api.EvalContext(a=args.a) as ctx:
+        ctx.header(head)
+        ms = C.c_double()
+        r = lib.dwgsim_hip_eval_debug_device_chunk(ctx.ctx, text, n_bytes, 1, C.byref(ms))      # warm-up
+        r = r or lib.dwgsim_hip_eval_debug_device_chunk(ctx.ctx, text, n_bytes, args.reps, C.byref(ms))
+        if r:
+            raise SystemExit("device chunk failed: %d" % r)
+        out["kernel_ms"] = ms.value
+        out["kernel_GBps"] = n_bytes / ms.value / 1e6
+        out["kernel_Mrec_s"] = n_recs / ms.value / 1e3
+
+    pinned = lib.dwgsim_hip_host_alloc(n_bytes)
+    if not pinned:
+        raise SystemExit("host_alloc failed")
+    C.memmove(pinned, text, n_bytes)
+    best = None
+    for _ in range(args.reps):
+        with api.EvalContext(a=args.a) as ctx:
+            ctx.header(head)
+            t0 = time.perf_counter()
+            lib.dwgsim_hip_eval_feed(ctx.ctx, C.c_void_p(pinned), n_bytes)
+            table, sm = ctx.finish()
+            dt = time.perf_counter() - t0
+        assert sm.status == 0 and sm.records == n_recs
+        best = dt if best is None else min(best, dt)
+    lib.dwgsim_hip_host_free(C.c_void_p(pinned))
+    out["e2e_s"] = best
+    out["e2e_GBps"] = n_bytes / best / 1e9
+    out["e2e_Mrec_s"] = n_recs / best / 1e6
+
+    sub = block * max(1, (args.model_mib << 20) // len(block))
+    t0 = time.perf_counter()
+    M.run([head + sub], M.Opts(a=args.a))
+    dt = time.perf_counter() - t0
+    out["model_GBps"] = len(sub) / dt / 1e9
+    out["model_Mrec_s"] = sub.count(b"\n") / dt / 1e6
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
