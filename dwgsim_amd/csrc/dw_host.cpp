@@ -149,6 +149,7 @@ struct dwgsim_hip_ctx {
     int ion_lds = -1;                      // "ion_lds" (tests): where the Ion Torrent read buffers live (fill_sim_args)
     int n_cu = 0; int flow_slots = 0;      // compute units of the device; "flow_slots": scratch slots per XCD forced by the tests (0: as many as an XCD can hold blocks)
     int64_t walk_cap = -1; bool phases = false; int writer = -1, force_threads = 0; int64_t place_cap = -1; uint64_t place_open = 0; double walk_us = 0, count_us = 0; int split = -1;      // dwgsim_hip_debug_option / _debug_get
+    int64_t sim_form = 0;                  // dwgsim_hip_debug_get("sim_form"): the k_simulate form of the last launch
     hipEvent_t ev_cnt0 = nullptr, ev_cnt1 = nullptr;
     bool gzip_on = false; uint32_t *d_crc_table = nullptr, *d_crc_shift = nullptr;      // dwgsim_hip_set_gzip
     void *h_stage = nullptr; size_t h_stage_cap = 0;   // pinned staging for fetch
@@ -1383,8 +1384,82 @@ static int build_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n,
     return DWGSIM_HIP_OK;
 }
 
-static int fill_sim_args(dwgsim_hip_ctx_t *c, Group &g, SimArgs &a)
+// The k_simulate form of a launch (dw_kernels.hpp SimForm): the one place that decides it, from the options, the base-quality tables, the Ion Torrent
+// capacity multiplier and the debug overrides ("writer", "sim_threads", "split", "ion_lds", "flow_cap").  Sets c->err when the reads cannot be run.
+static int sim_form(dwgsim_hip_ctx_t *c, SimForm &f)
 {
+    const dwgsim_hip_params_t &p = c->prm;
+    const size_t qb = (size_t)c->qb_words;
+    const int lmax = p.length[0] > p.length[1] ? p.length[0] : p.length[1];
+    f = SimForm();
+    f.lpp = p.length[1] > 0 ? 2 : 1;
+    f.out = (p.reads_output_type != 2 ? 1 : 0) | (p.reads_output_type != 1 ? 2 : 0);
+    f.dt = p.data_type;
+    // lanes per k_simulate block: the staged read (lds_words per lane) must fit LDS; long Illumina / SOLiD reads get one-wave blocks
+    f.nthr = SIM_THREADS;
+    f.cap = lmax; f.lds_words = (lmax + 7) / 8;
+    // the FIFO writer unless its LDS costs a resident block per CU (Illumina reads between ~150 and ~240 bases): then 16-byte pieces from registers
+    bool fifo = true;
+    if (p.data_type == 0) {
+        // waves per SIMD the registers allow (k_simulate launch bounds): five, except with both output families (-o 0) through two register writers;
+        // through the FIFO both families leave from one image (dw_read.hpp FifoWriter DUAL) and the kernel needs no more registers than for one
+        const int cap_fifo = 5, cap_reg = (p.reads_output_type == 0) ? 4 : 5;
+        const int b_fifo = sim_blocks_per_cu(sim_lds_bytes((size_t)f.lds_words, SIM_THREADS, qb, true), cap_fifo), b_reg = sim_blocks_per_cu(sim_lds_bytes((size_t)f.lds_words, SIM_THREADS, qb, false), cap_reg);
+        // (-o 0: one assembly for both families outweighs a resident block: 2 x 250 bp 7.72 ms with three blocks per CU against 8.13 ms with four, profiles/r05_o0.txt)
+        if (b_fifo < b_reg && !(p.reads_output_type == 0 && b_fifo >= 3)) fifo = false;
+        if (c->writer >= 0) fifo = c->writer != 0;
+    }
+    const size_t need = sim_lds_bytes((size_t)f.lds_words, SIM_THREADS, qb, fifo);     // staged bases + the two base-quality tables + the text FIFOs
+    // (from where LDS staging leaves room for ONE 256-lane block per CU -- reads of ~650 bases on -- the one-wave blocks are the faster form: 800 / 1 000 /
+    // 2 000 bases 13.1 / 13.0 / 22.7 ms in LDS against 7.8 / 8.0 / 8.6 ms staged in scratch slots, 600 bases 7.4 against 7.9: profiles/r04_long_reads.txt)
+    if (p.data_type != 2 && (need > SIM_LDS_BUDGET || ((sim_blocks_per_cu(need, 8) < 2 || c->force_threads == SIM_THREADS_LONG) && c->force_threads != SIM_THREADS))) {
+        // reads too long to stage in LDS: one-wave blocks whose reads are staged in scratch slots (global memory, dw_simulate.hip GS); what is left in LDS
+        // is the two base-quality tables (2 bytes per base) and the FIFOs, which bounds a read at ~70 000 bases (the reference has no bound, dwgsim.c:75-153)
+        f.nthr = SIM_THREADS_LONG; fifo = true;
+        if (sim_lds_bytes(0, SIM_THREADS_LONG, qb, true) > SIM_LDS_BUDGET) {
+            char b[160]; snprintf(b, sizeof b, "dwgsim-hip: reads longer than %d bases are not supported for -c 0 / -c 1\n", (int)((SIM_LDS_BUDGET - SIM_THREADS_LONG * SIM_FIFO_BYTES) / 2 - 16));
+            c->err = b; return DWGSIM_HIP_ERR_UNSUP;
+        }
+    }
+    if (p.data_type == 2) {        // room for flow-space insertions: ~2.4 empty flows per base, each inserting with probability e, plus cascades
+        const double emax = p.e_start[0] > p.e_start[1] ? p.e_start[0] : p.e_start[1];
+        f.cap = (c->flow_cap_forced > 0 ? std::max(c->flow_cap_forced, lmax) : flow_read_capacity(lmax, emax, c->flow)) * c->flow_cap_mult;      // (the read as extracted must fit: a forced capacity is a test's starting point, never below the read length)
+        // the flow model's one in-place buffer per lane, 2 bits per base (dw_read.hpp flow_errors), and the run stack of its pass 2.  In LDS while at
+        // least two 256-lane blocks -- or else four one-wave blocks -- fit a CU; beyond that (very long reads, error rates at which reads grow
+        // severalfold) in scratch slots of global memory ("ion_lds": 0 slots, 1 / 2 LDS with 256 / 64 lanes, -1 choose)
+        f.lds_words = (f.cap + 15) / 16; f.cap = 16 * f.lds_words;
+        f.stack_words = std::min(FLOW_STACK_WORDS * c->flow_cap_mult, FLOW_STACK_WORDS_MAX);
+        const size_t per_lane = (size_t)(f.lds_words + f.stack_words);
+        const size_t need256 = sim_lds_bytes(per_lane, SIM_THREADS, qb, true), need64 = sim_lds_bytes(per_lane, ION_THREADS_SMALL, qb, true);
+        int mode = c->ion_lds;
+        if (mode < 0) mode = (need256 <= SIM_LDS_BUDGET && sim_blocks_per_cu(need256, 8) >= 2) ? 1 : (need64 <= SIM_LDS_BUDGET && sim_blocks_per_cu(need64, 32) >= 4) ? 2 : 0;
+        if ((mode == 1 && need256 > SIM_LDS_BUDGET) || (mode == 2 && need64 > SIM_LDS_BUDGET)) mode = 0;
+        f.dt = mode != 0 ? 3 : 2; f.nthr = mode == 2 ? ION_THREADS_SMALL : SIM_THREADS;
+    }
+    // Short Illumina reads run as two kernels with the offsets computed in between (dw_simulate.hip SPLIT): no look-backs, and the second half --
+    // no staged bases in LDS -- writes the text in 64-byte bursts.  What does not scale with the read length (placement, the look-backs, the name)
+    // is most of the work there: 2 x 36 / 2 x 50 / 2 x 75 bp and 100 bp single-end run 16 / 17 / 9 / 15 % faster than in the single kernel, 2 x 100
+    // the same, 2 x 150 2-3 % slower (the state crosses HBM, 2.5 GB per chr20-sized launch): profiles/r04_split.txt.  "split" = 0 / 1 forces either.
+    // Round 6, the single kernel with ONE look-back (dw_simulate.hip ONE_LB), re-measured (profiles/r06_bench_lines_final.txt 14): 2 x 36 bp +5.5 % as two kernels, 2 x 50 +0.8 %, 2 x 75
+    // -3 %, 2 x 100 -10 %, 100 bp single-end -9 %, 2 x 150 -12 %: the cut moves from 100 bases to 50.
+    const bool split_wins = lmax <= 50;
+    f.split = (p.data_type == 0 && f.nthr == SIM_THREADS && (c->split < 0 ? split_wins : c->split != 0)) ? 1 : 0;
+    // Ion Torrent with its buffers in LDS: as two kernels as well (the flow model | qualities + text).  The first half holds no text FIFOs, so a fourth
+    // block fits a CU, and no block waits for the record sizes of the blocks in front of it ("split" = 0 forces the single kernel)
+    if (f.dt == 3 && f.nthr == SIM_THREADS && f.cap < 32768 && c->split != 0) f.split = 1;
+    if (f.split && c->writer < 0) fifo = true;      // (its LDS holds no bases: the FIFO writer always fits)
+    // dynamic LDS: the staged bases (Ion Torrent: the read buffers when LDS holds them + the pass-2 run stack; the scratch slots hold the rest, and the
+    // reads of the one-wave blocks) + the base-quality tables + the text FIFOs.  Two kernels: the first half stages the bases only, the second half
+    // (no staged bases) the tables and its FIFOs of 64-byte bursts
+    const size_t stage = f.dt == 3 ? (size_t)(f.lds_words + f.stack_words) : f.dt == 2 ? (size_t)f.stack_words : f.nthr != SIM_THREADS ? 0 : (size_t)f.lds_words;
+    if (f.split) { f.wr = fifo ? 2 : 0; f.lds = sim_lds_bytes(stage, (size_t)f.nthr, 0, false); f.lds_b = sim_lds_bytes(0, (size_t)f.nthr, qb, fifo, SIM_FIFO_BYTES_WIDE); }
+    else { f.wr = fifo ? 1 : 0; f.lds = sim_lds_bytes(stage, (size_t)f.nthr, qb, fifo); }
+    return 0;
+}
+
+static int fill_sim_args(dwgsim_hip_ctx_t *c, Group &g, SimArgs &a, SimForm &f)
+{
+    if (const int rc = sim_form(c, f)) return rc;
     const dwgsim_hip_params_t &p = c->prm;
     memset(&a, 0, sizeof a);
     a.p.std_dev = p.std_dev; a.p.mut_freq = p.mut_freq; a.p.rand_read = p.rand_read; a.p.quality_std = p.quality_std;
@@ -1406,40 +1481,8 @@ static int fill_sim_args(dwgsim_hip_ctx_t *c, Group &g, SimArgs &a)
     a.place_fast = (!c->has_regions && !p.amplicons && p.std_dev * 12.1 + 2.0 < 1e9) ? 1 : 0;
     a.place_k = a.place_fast ? (int32_t)ceil(p.std_dev * 12.1) + 2 : 0;
     a.rand_fixed = c->d_rand_fixed; a.rand_fixed_len = c->rand_fixed_len;
-    // lanes per k_simulate block: the staged read (lds_words per lane) must fit LDS; long Illumina / SOLiD reads get one-wave blocks
-    const int lmax0 = p.length[0] > p.length[1] ? p.length[0] : p.length[1];
-    a.sim_threads = SIM_THREADS;
-    // the FIFO writer unless its LDS costs a resident block per CU (Illumina reads between ~150 and ~240 bases): then 16-byte pieces from registers
-    a.fifo = 1;
-    if (p.data_type == 0) {
-        // waves per SIMD the registers allow (k_simulate launch bounds): five, except with both output families (-o 0) through two register writers;
-        // through the FIFO both families leave from one image (dw_read.hpp FifoWriter DUAL) and the kernel needs no more registers than for one
-        const int cap_fifo = 5, cap_reg = (p.reads_output_type == 0) ? 4 : 5;
-        const size_t w0 = (size_t)((lmax0 + 7) / 8);
-        const int b_fifo = sim_blocks_per_cu(sim_lds_bytes(w0, SIM_THREADS, (size_t)c->qb_words, true), cap_fifo), b_reg = sim_blocks_per_cu(sim_lds_bytes(w0, SIM_THREADS, (size_t)c->qb_words, false), cap_reg);
-        // (-o 0: one assembly for both families outweighs a resident block: 2 x 250 bp 7.72 ms with three blocks per CU against 8.13 ms with four, profiles/r05_o0.txt)
-        if (b_fifo < b_reg && !(p.reads_output_type == 0 && b_fifo >= 3)) a.fifo = 0;
-        if (c->writer >= 0) a.fifo = c->writer ? 1 : 0;
-    }
-    auto lds_need = [&](int lanes) { return sim_lds_bytes((size_t)((lmax0 + 7) / 8), (size_t)lanes, (size_t)c->qb_words, a.fifo != 0); };     // staged bases + the two base-quality tables + the text FIFOs
-    // (from where LDS staging leaves room for ONE 256-lane block per CU -- reads of ~650 bases on -- the one-wave blocks are the faster form: 800 / 1 000 /
-    // 2 000 bases 13.1 / 13.0 / 22.7 ms in LDS against 7.8 / 8.0 / 8.6 ms staged in scratch slots, 600 bases 7.4 against 7.9: profiles/r04_long_reads.txt)
-    if (p.data_type != 2 && (lds_need(SIM_THREADS) > SIM_LDS_BUDGET || ((sim_blocks_per_cu(lds_need(SIM_THREADS), 8) < 2 || c->force_threads == SIM_THREADS_LONG) && c->force_threads != SIM_THREADS))) {
-        // reads too long to stage in LDS: one-wave blocks whose reads are staged in scratch slots (global memory, dw_simulate.hip GS); what is left in LDS
-        // is the two base-quality tables (2 bytes per base) and the FIFOs, which bounds a read at ~70 000 bases (the reference has no bound, dwgsim.c:75-153)
-        a.sim_threads = SIM_THREADS_LONG; a.fifo = 1;
-        if (sim_lds_bytes(0, SIM_THREADS_LONG, (size_t)c->qb_words, true) > SIM_LDS_BUDGET) {
-            char b[160]; snprintf(b, sizeof b, "dwgsim-hip: reads longer than %d bases are not supported for -c 0 / -c 1\n", (int)((SIM_LDS_BUDGET - SIM_THREADS_LONG * SIM_FIFO_BYTES) / 2 - 16));
-            c->err = b; return DWGSIM_HIP_ERR_UNSUP;
-        }
-    }
-    const int lmax = p.length[0] > p.length[1] ? p.length[0] : p.length[1];
-    a.cap = lmax;
-    if (p.data_type == 2) {        // room for flow-space insertions: ~2.4 empty flows per base, each inserting with probability e, plus cascades
-        const double emax = p.e_start[0] > p.e_start[1] ? p.e_start[0] : p.e_start[1];
-        a.cap = (c->flow_cap_forced > 0 ? std::max(c->flow_cap_forced, lmax) : flow_read_capacity(lmax, emax, c->flow)) * c->flow_cap_mult;      // (the read as extracted must fit: a forced capacity is a test's starting point, never below the read length)
-    }
-    a.lds_words = (a.cap + 7) / 8;
+    a.sim_threads = f.nthr; a.fifo = f.wr != 0; a.split = f.split; a.ion_lds = f.dt == 3;
+    a.cap = f.cap; a.lds_words = f.lds_words; a.flow_stack_words = f.stack_words;
     a.flow = c->d_flow; a.flow_len = (int32_t)c->flow.size();
     for (int j = 0; j < 2; ++j) {      // Illumina / SOLiD: the gap chain of a read end's error sites runs at the largest threshold of its ramp (dw_simulate.hip; thresholds as dwgsim_hip_create made them)
         const int n = c->prm.length[j];
@@ -1456,32 +1499,6 @@ static int fill_sim_args(dwgsim_hip_ctx_t *c, Group &g, SimArgs &a)
         const double e0 = c->prm.e_start[j];
         flow_gap_params(!(e0 > 0) ? 0 : e0 >= 1.0 ? 0x100000000ull : (uint64_t)ceil(e0 * 4294967296.0), &a.flow_gap_r[j], &a.flow_gap_s[j]);
     }
-    a.flow_scratch = nullptr; a.flow_free = nullptr; a.flow_slots = 0;
-    if (p.data_type == 2) {
-        // the flow model's one in-place buffer per lane, 2 bits per base (dw_read.hpp flow_errors), and the run stack of its pass 2.  In LDS while at
-        // least two 256-lane blocks -- or else four one-wave blocks -- fit a CU; beyond that (very long reads, error rates at which reads grow
-        // severalfold) in scratch slots of global memory ("ion_lds": 0 slots, 1 / 2 LDS with 256 / 64 lanes, -1 choose)
-        a.lds_words = (a.cap + 15) / 16; a.cap = 16 * a.lds_words;
-        a.flow_stack_words = std::min(FLOW_STACK_WORDS * c->flow_cap_mult, FLOW_STACK_WORDS_MAX);
-        const size_t per_lane = (size_t)(a.lds_words + a.flow_stack_words);
-        const size_t need256 = sim_lds_bytes(per_lane, SIM_THREADS, (size_t)c->qb_words, true), need64 = sim_lds_bytes(per_lane, ION_THREADS_SMALL, (size_t)c->qb_words, true);
-        int mode = c->ion_lds;
-        if (mode < 0) mode = (need256 <= SIM_LDS_BUDGET && sim_blocks_per_cu(need256, 8) >= 2) ? 1 : (need64 <= SIM_LDS_BUDGET && sim_blocks_per_cu(need64, 32) >= 4) ? 2 : 0;
-        if ((mode == 1 && need256 > SIM_LDS_BUDGET) || (mode == 2 && need64 > SIM_LDS_BUDGET)) mode = 0;
-        a.ion_lds = mode != 0; a.sim_threads = mode == 2 ? ION_THREADS_SMALL : SIM_THREADS;
-    }
-    // Short Illumina reads run as two kernels with the offsets computed in between (dw_simulate.hip SPLIT): no look-backs, and the second half --
-    // no staged bases in LDS -- writes the text in 64-byte bursts.  What does not scale with the read length (placement, the look-backs, the name)
-    // is most of the work there: 2 x 36 / 2 x 50 / 2 x 75 bp and 100 bp single-end run 16 / 17 / 9 / 15 % faster than in the single kernel, 2 x 100
-    // the same, 2 x 150 2-3 % slower (the state crosses HBM, 2.5 GB per chr20-sized launch): profiles/r04_split.txt.  "split" = 0 / 1 forces either.
-    // Round 6, the single kernel with ONE look-back (dw_simulate.hip ONE_LB), re-measured (profiles/r06_bench_lines_final.txt 14): 2 x 36 bp +5.5 % as two kernels, 2 x 50 +0.8 %, 2 x 75
-    // -3 %, 2 x 100 -10 %, 100 bp single-end -9 %, 2 x 150 -12 %: the cut moves from 100 bases to 50.
-    const bool split_wins = lmax0 <= 50;
-    a.split = (p.data_type == 0 && a.sim_threads == SIM_THREADS && (c->split < 0 ? split_wins : c->split != 0)) ? 1 : 0;
-    // Ion Torrent with its buffers in LDS: as two kernels as well (the flow model | qualities + text).  The first half holds no text FIFOs, so a fourth
-    // block fits a CU, and no block waits for the record sizes of the blocks in front of it ("split" = 0 forces the single kernel)
-    if (p.data_type == 2 && a.ion_lds && a.sim_threads == SIM_THREADS && a.cap < 32768 && c->split != 0) a.split = 1;
-    if (a.split && c->writer < 0) a.fifo = 1;      // (its LDS holds no bases: the FIFO writer always fits)
     return 0;
 }
 
@@ -1500,8 +1517,8 @@ int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t
     // its group's walk by that walk's event, whatever else has been put on the walk stream since)
     if (g.walk_pending) { if (const int rc = dwgsim_hip_mutate_wait(c, g.first_handle)) return rc; }      // (a walk that exceeded a capacity is run again inside the wait: only then are the summaries final)
     if (g.ev_walk && g.mutated) HIPC(c, hipStreamWaitEvent(st, g.ev_walk, 0));
-    SimArgs a;
-    if (const int rc = fill_sim_args(c, g, a)) return rc;
+    SimArgs a; SimForm f;
+    if (const int rc = fill_sim_args(c, g, a, f)) return rc;
     const size_t ns = segs.size();
     if (ensure(c, c->place_rand, sizeof(uint32_t) * ((size_t)n_blocks + 1))) return DWGSIM_HIP_ERR_DEVICE;
     if (ensure(c, c->place_segs, sizeof(SimSeg) * ns)) return DWGSIM_HIP_ERR_DEVICE;
@@ -1588,14 +1605,14 @@ static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, 
     const dwgsim_hip_params_t &p = c->prm;
     // lanes per block are a property of the options, so the range table can be laid out before the arguments are complete
     Group *gp = nullptr; std::vector<SimSeg> segs; uint64_t n_pairs = 0; uint32_t nblk = 0; int fixed_max = 0;
-    SimArgs a;
+    SimArgs a; SimForm f;
     {
         // (fill_sim_args needs a group: take it from the first range)
         Group *g0 = (r && n >= 1) ? get_group(c, r[0].contig) : nullptr;
         if (!g0) { if (r && n >= 1) return DWGSIM_HIP_ERR_ARG; c->err = "bad range arguments"; return DWGSIM_HIP_ERR_ARG; }
-        if (const int rc = fill_sim_args(c, *g0, a)) return rc;
+        if (const int rc = fill_sim_args(c, *g0, a, f)) return rc;
     }
-    const uint64_t sim_ppb = (uint64_t)(a.sim_threads / (p.length[1] > 0 ? 2 : 1));      // pairs per k_simulate block
+    const uint64_t sim_ppb = (uint64_t)(f.nthr / f.lpp);      // pairs per k_simulate block
     if (const int rc = build_ranges(c, r, n, sim_ppb, &gp, segs, &n_pairs, &nblk, &fixed_max)) return rc;
     Group &g = *gp;
     HIPC(c, hipSetDevice(c->device));
@@ -1603,7 +1620,6 @@ static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, 
     // first round's three look-backs resolved one after the other, 2^17 / 2^18 / 2^19 pairs of 2 x 150 bp -5 / -11.5 / -2 %: profiles/r04_split.txt)
     // (round 6: with one look-back the single kernel is level with the two-kernel form on launches this small too -- 2^17 / 2^18 / 2^19 pairs of 2 x 150 bp +4 / -3 / +9 %, an E. coli-sized
     // contig +2.5 % -- and the rule is gone: profiles/r06_bench_lines_final.txt 14)
-    if (a.split && p.data_type == 2) a.fifo = 1;
     if (c->rand_fixed_len > fixed_max) fixed_max = c->rand_fixed_len;
     // upper bound of one FASTQ record (name tail: 2 positions <= 10 digits, 6 counters, 16 hex digits)
     size_t cap[3] = {0, 0, 0};
@@ -1633,13 +1649,12 @@ static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, 
         if (ensure(c, c->meta, sizeof(uint32_t) * ((size_t)n_pairs + 8))) return DWGSIM_HIP_ERR_DEVICE;      // (+ padding for 16-byte reads)
         const size_t nfb = (size_t)((n_pairs + 256ull * 64 - 1) / (256ull * 64));
         if (ensure(c, c->fail_summ, (nfb * 4 + 2) * sizeof(uint64_t))) return DWGSIM_HIP_ERR_DEVICE;
-        if (p.data_type == 2 ? !a.ion_lds : a.sim_threads != SIM_THREADS) {
+        if (f.dt == 2 || (f.dt < 2 && f.nthr == SIM_THREADS_LONG)) {
             // read buffers (Ion Torrent) / staged reads (one-wave blocks): one slot per block an XCD can hold at a time -- what the LDS admits per CU, at most the eight waves of a SIMD (registers can only
             // lower it; too few slots would make blocks wait, never fail) --, handed from block to block inside the XCD (dw_simulate.hip scratch_slot_take)
             const int cu_per_xcd = (c->n_cu >= 64 && c->n_cu % 8 == 0) ? c->n_cu / 8 : c->n_cu;
             const bool ion = p.data_type == 2;
-            const int per_cu = ion ? sim_blocks_per_cu(sim_lds_bytes((size_t)a.flow_stack_words, SIM_THREADS, (size_t)a.qb_words, a.fifo != 0), 8)
-                                   : sim_blocks_per_cu(sim_lds_bytes(0, SIM_THREADS_LONG, (size_t)a.qb_words, true), 32);       // (one-wave blocks: up to eight per SIMD)
+            const int per_cu = sim_blocks_per_cu(f.lds, ion ? 8 : 32);       // (one-wave blocks: up to eight per SIMD)
             a.flow_slots = c->flow_slots > 0 ? c->flow_slots : cu_per_xcd * per_cu;
             if ((uint64_t)a.flow_slots > (uint64_t)nblk) a.flow_slots = (int32_t)nblk;
             if (ion) {      // reads that have grown far beyond their estimate (capacity re-runs): fewer slots, at most 4 GB of them (blocks wait for a slot, they never fail for want of one)
@@ -1699,7 +1714,8 @@ static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, 
     launch_init(c->stream, sl.d_counters, (uint32_t)N_COUNTERS, a.split ? nullptr : a.status[0], a.split ? 0 : 4 * (uint64_t)nblk, a.flow_free, a.flow_free ? 256 + 8 * (uint64_t)nblk : 0,
                 ch_ptr, rand_base, ch_rand, ch_carry_v, ch_carry);
     HIPC(c, hipEventRecord(sl.ev_k0, c->stream));
-    launch_simulate(c->stream, a);
+    c->sim_form = (int64_t)f.nthr << 20 | f.lpp << 16 | f.out << 12 | f.dt << 8 | f.wr << 4 | f.split;
+    if (!launch_simulate(c->stream, a, f)) { c->err = "simulate: no k_simulate instance for this form"; return DWGSIM_HIP_ERR_FAILED; }
     HIPC(c, hipEventRecord(sl.ev_k1, c->stream));
     sl.cap_mult = c->flow_cap_mult;
     if (!rerun) launch_failrule(c->stream, a.meta, n_pairs, opens, (uint64_t *)c->fail_summ.p, sl.d_counters, c->d_chain);
@@ -2013,6 +2029,8 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *c, const char *key, int64_t value)
 
 // ... and values to read back: "place_open" = pairs the last dwgsim_hip_count_random* call could not settle from the coarse summaries;
 // "walk_us" / "count_us" = accumulated HIP-event time (microseconds) of the walk chains / random-read counts of this context
+// "sim_form" = the k_simulate form of the last simulate launch (0 before the first): NTHR << 20 | LPP << 16 | OUT << 12 | DT << 8 | WR << 4 | SPLIT,
+// where SPLIT = 1 is the two-kernel form and WR the writer of its second half
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
 {
     if (!c || !key || !value) return DWGSIM_HIP_ERR_ARG;
@@ -2020,6 +2038,7 @@ int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
     else if (!strcmp(key, "flow_cap_mult")) *value = (int64_t)c->flow_cap_mult;
     else if (!strcmp(key, "walk_us")) *value = (int64_t)c->walk_us;           // HIP-event time of the walk chains waited for so far (start of the chain to its end, on the walk stream)
     else if (!strcmp(key, "count_us")) *value = (int64_t)c->count_us;         // ... of the random-read counts (k_place .. k_range_counts)
+    else if (!strcmp(key, "sim_form")) *value = c->sim_form;                  // k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> of the last launch, packed
     else { c->err = "unknown debug value"; return DWGSIM_HIP_ERR_ARG; }
     return DWGSIM_HIP_OK;
 }

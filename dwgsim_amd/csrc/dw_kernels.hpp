@@ -29,6 +29,14 @@ inline size_t sim_lds_bytes(size_t words_per_lane, size_t lanes, size_t qb_words
 // blocks of SIM_THREADS lanes a CU holds at this much dynamic LDS (160 KB per CU in granules of 1280 bytes, ~0.6 KB static per block), at most `cap` (the register limit)
 inline int sim_blocks_per_cu(size_t dyn_lds, int cap) { const size_t per = (dyn_lds + 1700 + 1279) / 1280 * 1280;      /* (+ the kernel's static LDS: scan scratch, name lines, the log2 table of the gap draws) */ const int b = (int)(163840 / per); return b < cap ? b : cap; }
 constexpr size_t SIM_LDS_BUDGET = 150 * 1024; // dynamic LDS a block may ask for (160 KB per CU minus the static part)
+// A form of k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> (dw_simulate.hip): what one launch runs, chosen once by the host (dw_host.cpp sim_form).
+// split = 0: k_simulate<lpp, out, dt, nthr, wr, 0> with lds bytes of dynamic LDS.  split = 1, the two-kernel form: the first half
+// k_simulate<lpp, 1, dt, nthr, 1, 1> with lds, k_split_scan, the second half k_simulate<lpp, out, dt, nthr, wr, 2> with lds_b.
+struct SimForm {
+    int lpp, out, dt, nthr, wr, split;
+    size_t lds, lds_b;
+    int cap, lds_words, stack_words;      // the read buffers the LDS is sized for: SimArgs cap, lds_words, flow_stack_words
+};
 constexpr int SCAN_POS_PER_THREAD = 16;  // k_site_scan / k_collect: 16 positions (one 16-B load) per thread
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_POS_PER_BLOCK = SCAN_POS_PER_THREAD * SCAN_THREADS;   // 4096

@@ -26,7 +26,7 @@ void launch_apply_patches(hipStream_t st, const int32_t *pos, const uint16_t *ce
 void launch_collect_mask(hipStream_t st, const uint8_t *h0, const uint8_t *h1, int64_t l, uint16_t *mask, uint32_t *block_count);
 void launch_gather(hipStream_t st, const int32_t *pos, uint32_t n, const uint8_t *ref, const uint8_t *h0, const uint8_t *h1, uint32_t *cells);
 void launch_place(hipStream_t st, const SimArgs &a);
-void launch_simulate(hipStream_t st, const SimArgs &a);
+bool launch_simulate(hipStream_t st, const SimArgs &a, const SimForm &f);      // false: the form has no instance
 void launch_calibrate(hipStream_t st, const CalibArgs &a);
 void launch_failrule(hipStream_t st, const uint32_t *meta, uint64_t n_pairs, uint32_t opens_contig, uint64_t *summ, uint64_t *counters, uint64_t *chain);
 void launch_chain_set(hipStream_t st, uint64_t *chain, uint64_t rand_base, int set_rand, uint64_t carry, int set_carry);

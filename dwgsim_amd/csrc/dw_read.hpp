@@ -749,9 +749,10 @@ struct Writer {               // sequential byte stream of one record -> 16-byte
 // profiles/r04_variants_pmc.txt).  dstb + p is where FIFO position p goes in the BFAST stream; bdone = the first position the BFAST stream has
 // not written yet (it differs from skip only between the suffix and the next drain: the suffix's own two characters are jumped over).
 // bytes [from, upto) of a unit (the ragged first / last unit of a record) from the FIFO at f to dst: rising sizes until the position is aligned (or the
-// next piece would pass upto), then falling sizes.  (DW_DEV_NOINLINE: dw_intrin.hpp)
+// next piece would pass upto), then falling sizes.  (The rare paths of k_simulate -- these, the exact fp64 quality try -- make up a third of its code
+// inlined at every use (94 KB against 57 KB called); the called form measured 1 % slower at 2 x 150 -o 1, 0.5 % faster at -o 0: profiles/r05_bench_lines_final.txt)
 template <uint32_t BURST>
-DW_DEV_NOINLINE void fifo_store_range(const uint8_t *f, uint8_t *dst, uint32_t from, uint32_t upto)
+DW_DEV void fifo_store_range(const uint8_t *f, uint8_t *dst, uint32_t from, uint32_t upto)
 {
     auto ld8 = [&](uint32_t b) { return *reinterpret_cast<const uint64_t *>(f + b); };
     auto st16 = [&](uint32_t b) { *reinterpret_cast<uint4 *>(dst + b) = make_uint4((uint32_t)ld8(b), (uint32_t)(ld8(b) >> 32), (uint32_t)ld8(b + 8), (uint32_t)(ld8(b + 8) >> 32)); };
@@ -769,7 +770,7 @@ DW_DEV_NOINLINE void fifo_store_range(const uint8_t *f, uint8_t *dst, uint32_t f
 }
 // the same for a destination of any alignment (the second stream of FifoWriter DUAL): falling sizes by the bits of the count
 template <uint32_t BURST>
-DW_DEV_NOINLINE void fifo_store_range_unaligned(const uint8_t *f, uint8_t *dstb, uint32_t from, uint32_t upto)
+DW_DEV void fifo_store_range_unaligned(const uint8_t *f, uint8_t *dstb, uint32_t from, uint32_t upto)
 {
     if (from >= upto) return;
     auto ld8u = [&](uint32_t b) { return reinterpret_cast<const Unal8 *>(f + b)->v; };

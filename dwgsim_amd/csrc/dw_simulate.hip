@@ -12,12 +12,8 @@
 // with -ffp-contract=off.
 //
 // The file is compiled in parts so the k_simulate variants build in parallel (csrc/Makefile):
-//   DW_PART 0: k_place, k_place_rest, k_selftest_fp64, host launchers and the k_simulate dispatcher
-//   DW_PART 1..6: k_simulate<LPP, *, DT> for (LPP, DT) = (2,0) (1,0) (2,2) (1,2) (2,1) (1,1); part 4 also holds k_calibrate
-//   DW_PART 7, 8: the one-wave-per-block variants for long Illumina / SOLiD reads
-//   DW_PART 9, 10: the two-kernel form (SPLIT) of the paired / single-end Illumina variants
-//   DW_PART 11, 12, 13: the Ion Torrent variants whose read buffers live in LDS (256-lane blocks paired / single-end, the smaller blocks)
-//   DW_PART 14, 15: ... their two-kernel form, paired / single-end
+//   DW_PART 0: k_place, k_place_rest, the self-tests, the host launchers and the k_simulate dispatcher
+//   DW_PART 1..15: the k_simulate instances of DW_SIM_PART_1 .. DW_SIM_PART_15 (the list at the end of the file); part 4 also holds k_calibrate
 //   DW_PART -1 (default): everything in one translation unit
 #include <algorithm>
 #include "dw_read.hpp"
@@ -31,21 +27,9 @@
 #define DW_SIM_WAVES 5       // minimum waves per SIMD requested for the Illumina variants (one less when both output families are written):
                              // the kernel sits 1-2 VGPRs above these occupancy steps without the hint; measured +4 % at 5 vs 4 waves, 6 spills (so do the SOLiD variants with any hint)
 #endif
-#ifndef DW_PRIO_DROP
-#define DW_PRIO_DROP 1       // where a wave of the single kernel gives up its raised issue priority: 0 = once its block's look-backs are resolved, 1 = after
-                             // the name line that follows them (profiles/r04_split.txt section 5: 5.84 -> 5.75 ms at 2 x 150 bp, Ion Torrent unchanged)
-#endif
 #ifndef DW_SOLID_WAVES
 #define DW_SOLID_WAVES 4     // minimum waves per SIMD requested for the SOLiD variants: without a hint (1) the round-5 kernel takes 152 registers = three waves (126 in
                              // round 4); capped at 128 it spills 20-46 registers and is 11-33 % FASTER (2 x 50 -o 0 / -o 1 / 75 + 35 -o 2: profiles/r05_bench_lines_final.txt section 7)
-#endif
-#ifndef DW_QUAL_FIFO
-#ifndef DW_ONE_LB
-#define DW_ONE_LB 1          // 1: the single Illumina kernel places its records with ONE look-back (k_simulate, "ONE_LB"); 0: the three of rounds 2-5 (analysis builds)
-#endif
-#define DW_QUAL_FIFO 0       // 1: the quality line's pairs of characters placed by two-byte LDS stores (quality_line_fifo); 0: compacted in registers as in rounds
-                             // 2-4.  Measured (profiles/r05_bench_lines_final.txt, one box each): 14.0 k -> 13.2-13.5 k VALU per wave, but four more LDS accesses per
-                             // block (SQ_WAIT_INST_LDS x 4, bank conflicts x 4): 2 x 150 -o 1 1 % SLOWER, E. coli-sized 7 % slower, -o 0 and 2 x 250 equal: not adopted
 #endif
 #ifndef DW_SIM_WAVES_BOTH
 #define DW_SIM_WAVES_BOTH 4  // ... when both output families are written (-o 0) through two register writers (WR = 0; through the FIFO one image serves both)
@@ -283,8 +267,8 @@ DW_DEV void quality_try_exact(uint32_t w, double sigma, bool &ok, int32_t &k0, i
     k0 = (int32_t)(((v2 * fac) * sigma) + 0.5);
     k1 = (int32_t)(((v1 * fac) * sigma) + 0.5);
 }
-// (the same for the read kernels, an accepted try; DW_DEV_NOINLINE: dw_intrin.hpp)
-DW_DEV_NOINLINE uint64_t quality_try_exact_called(uint32_t w, double sigma)
+// (the same for the read kernels, an accepted try; inlined like the other rare paths: dw_read.hpp fifo_store_range)
+DW_DEV uint64_t quality_try_exact_called(uint32_t w, double sigma)
 {
     bool ok; int32_t k0 = 0, k1 = 0;
     quality_try_exact(w, sigma, ok, k0, k1);
@@ -392,48 +376,6 @@ DW_DEV void for_each_quality_block(const SimParams &p, RngKey key, uint32_t dom,
     }
 }
 
-// The same line through the FIFO writer (dw_read.hpp FifoWriter): the pair of characters of each of a block's four tries goes straight to its place
-// in the FIFO -- an unaligned two-byte LDS store `accepted tries so far` x 2 places past the write position, a rejected try's pair overwritten by the
-// next one's --, its two base qualities are picked from the eight loaded in front of the draws by one v_perm_b32 at the same offset: no compaction of the
-// accepted pairs in registers (rounds 2-4: seven 64-bit shifts, selects and masks per block -- the LDS does the byte placement here as it does for every
-// append).  (Loading the base qualities pair by pair at their final offsets, after the draws, exposed four LDS round trips per block: the VALU count
-// fell by 5 % and the time did not, profiles/r05_bench_lines_final.txt.)
-template <class W>
-DW_DEV void quality_line_fifo(W &w, const SimParams &p, RngKey key, uint32_t dom, uint64_t ii, uint32_t att, const uint32_t *qbw, int nq, int n_chars)
-{
-    if (p.fixed_quality >= 0 || !(0 < p.quality_std)) { for_each_quality_block(p, key, dom, ii, att, qbw, nq, n_chars, false, [&](uint64_t blk, uint32_t nb) { w.putn(blk, nb); }); return; }
-    const QualLazy ql{p.q_k, p.q_eps, p.q_lmin, p.q_near1};
-    int pos = 0; uint32_t t = 0;
-    while (pos < n_chars) {
-        // the base qualities of the (up to eight) positions this block can fill: loaded before the draws, whose arithmetic hides the LDS round trip
-        // (positions >= nq reuse the last entry: the table holds eight copies of it behind the nq)
-        const int pc = pos < nq ? pos : nq;
-        const uint32_t q0 = qbw[pc >> 2], q1 = qbw[(pc >> 2) + 1], q2w = qbw[(pc >> 2) + 2];
-        const U4 b = rng_block(key, dom, ii, att, 0, t++);
-        const uint32_t wd[4] = {b.x, b.y, b.z, b.w};
-        int32_t k[8]; uint32_t acc = 0, need = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const uint32_t r = quality_try_lazy(wd[q], ql, k[2 * q], k[2 * q + 1]); acc |= (r & 1u) << q; need |= (r >> 1) << q; }
-        if (need) {                              // rare: the reference's own arithmetic decides (quality_block)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) if ((need >> q) & 1u) { const uint64_t kk = quality_try_exact_called(wd[q], p.quality_std); k[2 * q] = (int32_t)(uint32_t)kk; k[2 * q + 1] = (int32_t)(uint32_t)(kk >> 32); }
-        }
-        const uint32_t qlo = __builtin_amdgcn_alignbyte(q1, q0, (uint32_t)pc & 3u), qhi = __builtin_amdgcn_alignbyte(q2w, q1, (uint32_t)pc & 3u);
-        uint32_t off = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t q2 = lut8(qhi, qlo, off * 0x0101u + 0x0100u);       // bytes off, off + 1 of the eight (one v_perm_b32)
-            int32_t qa = (int8_t)((int32_t)(int8_t)(q2 & 0xffu) + k[2 * q]), qc = (int8_t)((int32_t)(int8_t)((q2 >> 8) & 0xffu) + k[2 * q + 1]);
-            qa = qa < 33 ? 33 : qa > 73 ? 73 : qa; qc = qc < 33 ? 33 : qc > 73 ? 73 : qc;
-            w.poke2(off, (uint32_t)qa | ((uint32_t)qc << 8));
-            off += ((acc >> q) & 1u) ? 2u : 0u;
-        }
-        const int left = n_chars - pos;
-        w.advance((int)off < left ? off : (uint32_t)left);
-        pos += (int)off;
-    }
-}
-
 // sum over i < c of the hexadecimal digits of b + i: what the running index adds to the names of c consecutive random reads (dwgsim.c:1044-1048)
 DW_DEV uint64_t hex_digits_sum(uint64_t b, uint64_t c)
 {
@@ -486,8 +428,18 @@ DW_DEV void scratch_slot_release(uint64_t *ff, uint32_t n_blocks, uint32_t slot)
 // turns the sums into every block's offsets; the SECOND HALF (2) writes the text.  Neither half waits for another block: in the single kernel a
 // block stands still until every block in front of it has published its sizes, and the spread of their arrival times (a few per cent of a
 // block's life, amplified by the maximum over the hundreds of blocks in flight) cost 0.8-0.9 of 5.96 ms (profiles/r04_knockouts.txt).
-template <int LPP, int OUT, int DT, int NTHR = SIM_THREADS, int WR = 1, int SPLIT = 0>
-__global__ void __launch_bounds__(NTHR, (DT == 3 ? (SPLIT == 1 ? DW_IONA_WAVES : SPLIT == 2 ? DW_SIMB_WAVES : DW_IONL_WAVES) : NTHR != SIM_THREADS ? (DT == 1 ? DW_SOLID_WAVES : 1) : DT == 2 ? DW_ION_WAVES : DT == 1 ? DW_SOLID_WAVES : SPLIT == 2 ? DW_SIMB_WAVES : (OUT != 3 || WR != 0) ? DW_SIM_WAVES : DW_SIM_WAVES_BOTH)) k_simulate(SimArgs a)
+// minimum waves per SIMD a variant asks for (the DW_*_WAVES above)
+constexpr int sim_min_waves(int OUT, int DT, int NTHR, int WR, int SPLIT)
+{
+    if (DT == 3) return SPLIT == 1 ? DW_IONA_WAVES : SPLIT == 2 ? DW_SIMB_WAVES : DW_IONL_WAVES;
+    if (NTHR != SIM_THREADS) return DT == 1 ? DW_SOLID_WAVES : 1;
+    if (DT == 2) return DW_ION_WAVES;
+    if (DT == 1) return DW_SOLID_WAVES;
+    if (SPLIT == 2) return DW_SIMB_WAVES;
+    return (OUT != 3 || WR != 0) ? DW_SIM_WAVES : DW_SIM_WAVES_BOTH;
+}
+template <int LPP, int OUT, int DT, int NTHR, int WR, int SPLIT>
+__global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT)) k_simulate(SimArgs a)
 {
     static_assert(SPLIT == 0 || ((DT == 0 || DT == 3) && NTHR == SIM_THREADS), "the two-kernel form exists for the Illumina variants and for Ion Torrent with its buffers in LDS, 256-lane blocks");
     DW_DYN_SHARED(uint32_t, dyn_lds);                                    // [lds_words][blockDim] packed bases
@@ -513,15 +465,13 @@ __global__ void __launch_bounds__(NTHR, (DT == 3 ? (SPLIT == 1 ? DW_IONA_WAVES :
     // carries both sums, and everything else is added by the block itself.  One front, two barriers and two block scans fewer.
     // (SOLiD: the BFAST records' lengths are not a function of the BWA records' -- the name counts differ --: their bytes are a second word, on a chain of its own walked
     // by wave 1 at the same time: still one front)
-    constexpr bool ONE_LB = DW_ONE_LB != 0 && (DT == 0 || DT == 1) && SPLIT == 0;
+    constexpr bool ONE_LB = (DT == 0 || DT == 1) && SPLIT == 0;
     const int LB_SHIFT = a.lb_shift;      // (bits of the byte sum; the host sizes it to the launch and refuses one whose two sums would not fit 62 bits: dw_host.cpp)
     const int tid = (int)threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
     DW_PROBE_INIT();
     if (GS && tid == 0) { s_slot = scratch_slot_take(a.flow_free, (uint32_t)a.flow_slots, a.n_blocks); asm volatile("" ::: "memory"); }      // (before the ticket: see scratch_slot_take)
-#ifndef DW_TICKET_LATE
     if (SPLIT == 0 && tid == 0) s_ticket = (uint32_t)atomicAdd((unsigned long long *)&a.counters[0], 1ull);
-#endif
     if (SPLIT != 1) for (int q = tid; q < 32; q += nthr) s_fixed[1][q] = reinterpret_cast<const uint32_t *>(a.rand_fixed)[q];      // buffers are padded to 256 + 16 bytes
     if (ION && tid < 64) s_ft.flow[tid] = a.flow[tid];
     if (!ION && SPLIT != 2) for (int q = tid; q < FLOW_LG_ENTRIES; q += nthr) s_lg[q] = reinterpret_cast<const uint32_t *>(a.flow + 64)[q];
@@ -531,9 +481,6 @@ __global__ void __launch_bounds__(NTHR, (DT == 3 ? (SPLIT == 1 ? DW_IONA_WAVES :
     if (SPLIT != 1) for (int q = tid; q < 2 * a.qb_words; q += nthr) s_qb[q] = (q < a.qb_words ? a.qbase[0] : a.qbase[1])[q < a.qb_words ? q : q - a.qb_words];
     // this lane's text FIFO (record writer), behind the tables
     uint8_t *const s_fifo = reinterpret_cast<uint8_t *>(dyn_lds + (((stage_words * nthr + 2 * (size_t)a.qb_words) + 3) & ~(size_t)3)) + (size_t)tid * (WR == 2 ? SIM_FIFO_BYTES_WIDE : SIM_FIFO_BYTES);
-#ifdef DW_TICKET_LATE      // (analysis: the ticket taken behind the staging of the tables instead of in front of it: what stands between a block's ticket and its look-back is on every later block's path)
-    if (SPLIT == 0 && tid == 0) s_ticket = (uint32_t)atomicAdd((unsigned long long *)&a.counters[0], 1ull);
-#endif
     if (SPLIT == 0) __syncthreads();
     constexpr int H = SPLIT;      // which half of the path this kernel is: 0 both (the single kernel), 1 first, 2 second
     // logical block.  One kernel: from an atomic ticket, so that a block's predecessors have started when it looks back at them.  Two kernels:
@@ -864,7 +811,7 @@ __global__ void __launch_bounds__(NTHR, (DT == 3 ? (SPLIT == 1 ? DW_IONA_WAVES :
         }
     }
 
-    if (SPLIT == 0 && (DW_PRIO_DROP == 0 || DT == 1)) wave_priority(0);
+    if (SPLIT == 0 && DT == 1) wave_priority(0);
     DW_PROBE_MARK(a, 3);     // name lengths, block scan, look-back
     // ---- SOLiD records (dwgsim.c:934-976, :1056-1094): the two outputs differ in name counts, suffix, alphabet and length ----
     if (DT == 1) {
@@ -908,7 +855,7 @@ __global__ void __launch_bounds__(NTHR, (DT == 3 ? (SPLIT == 1 ? DW_IONA_WAVES :
         else put_pair_tail(o, x0, x1, pd.strand0, pd.strand1, nc, ii);
         }
         o.put_suffix((uint64_t)'/' | ((uint64_t)('1' + j) << 8) | ((uint64_t)'\n' << 16), 3, (uint64_t)'\n', 1);
-        if (SPLIT == 0 && DW_PRIO_DROP == 1) wave_priority(0);      // (the name line still at the raised priority: see DW_PRIO_DROP)
+        if (SPLIT == 0) wave_priority(0);      // (the name line still at the raised priority: 5.84 -> 5.75 ms at 2 x 150 bp against dropping it once the look-backs are resolved, profiles/r04_split.txt section 5)
         DW_PROBE_MARK(a, 4); // header line
         // bases (the second writer of -o 0 starts a new section, so that sixteen bases are one store)
         o.rebase();
@@ -977,13 +924,11 @@ __global__ void __launch_bounds__(NTHR, (DT == 3 ? (SPLIT == 1 ? DW_IONA_WAVES :
         o.put('\n'); o.put('+'); o.put('\n');
         o.rebase();
         }
-        if (SPLIT == 0 && DW_PRIO_DROP == 1) wave_priority(0);      // (a wave none of whose lanes has a record)
+        if (SPLIT == 0) wave_priority(0);      // (a wave none of whose lanes has a record)
         DW_PROBE_MARK(a, 5); // sequence line
         // qualities (dwgsim.c:899-918): up to eight characters per Philox block of the read end's try stream, appended as they come
         if (rec) {
-            if constexpr (WR != 0 && DW_QUAL_FIFO) quality_line_fifo(o.a, a.p, key, D_QUAL0 + (uint32_t)j, ii, att, s_qb + (j ? a.qb_words : 0), s, s_out);
-            else for_each_quality_block(a.p, key, D_QUAL0 + (uint32_t)j, ii, att, s_qb + (j ? a.qb_words : 0), s, s_out, false,
-                                        [&](uint64_t blk, uint32_t nb) { o.putn(blk, nb); });
+            for_each_quality_block(a.p, key, D_QUAL0 + (uint32_t)j, ii, att, s_qb + (j ? a.qb_words : 0), s, s_out, false, [&](uint64_t blk, uint32_t nb) { o.putn(blk, nb); });
         }
         if (rec) { o.put('\n'); o.flush(); }
     }
@@ -1348,143 +1293,14 @@ void launch_place(hipStream_t st, const SimArgs &a)
     launch_scan_excl(st, a.block_rand, a.n_blocks, &a.counters[3]);
     hipLaunchKernelGGL(k_range_counts, dim3(cdiv((uint64_t)a.n_seg, 256)), dim3(256), 0, st, a);
 }
-// one launcher per (LPP, DT) family, each defined in its own part
-void launch_sim_2_0(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_1_0(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_2_2(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_1_2(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_2_1(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_1_1(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_long_2_0(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_long_1_0(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_long_2_1(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_long_1_1(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_2_3(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_1_3(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_long_2_3(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_long_1_3(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out);
-void launch_sim_split_2(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds_a, size_t lds_b, int out);
-void launch_sim_split_1(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds_a, size_t lds_b, int out);
-void launch_sim_split_ion_2(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds_a, size_t lds_b, int out);
-void launch_sim_split_ion_1(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds_a, size_t lds_b, int out);
 void launch_split_scan(hipStream_t st, const SimArgs &a, int lpp)
 {
     hipLaunchKernelGGL(k_split_scan1, dim3(cdiv(a.n_blocks, 1024)), dim3(1024), 0, st, a);
     hipLaunchKernelGGL(k_split_scan2, dim3(1), dim3(64), 0, st, a, lpp);
 }
-void launch_simulate(hipStream_t st, const SimArgs &a)
-{
-    const bool pe = a.p.len[1] > 0, ion = a.p.data_type == 2;
-    const uint32_t nthr = (uint32_t)a.sim_threads;
-    const uint32_t nb = a.n_blocks;                                  // a.segs is laid out for nthr / (pe ? 2 : 1) pairs per block
-    const int out = (a.p.has_bwa ? 1 : 0) | (a.p.has_bfast ? 2 : 0);
-    if (a.split) {      // 256-lane blocks: first half | offsets | second half (k_simulate<.., SPLIT>)
-        const size_t lds_a = sim_lds_bytes((size_t)(a.lds_words + (ion ? a.flow_stack_words : 0)), nthr, 0, false), lds_b = sim_lds_bytes(0, nthr, (size_t)a.qb_words, a.fifo != 0, SIM_FIFO_BYTES_WIDE);      // (the second half stages no bases)
-        if (ion) { if (pe) launch_sim_split_ion_2(st, a, nb, lds_a, lds_b, out); else launch_sim_split_ion_1(st, a, nb, lds_a, lds_b, out); }
-        else if (pe) launch_sim_split_2(st, a, nb, lds_a, lds_b, out); else launch_sim_split_1(st, a, nb, lds_a, lds_b, out);
-        return;
-    }
-    // staged bases (Ion Torrent: the read buffers when LDS holds them + the pass-2 run stack; otherwise they are, like the long reads of the one-wave blocks, in a.flow_scratch)
-    // + the base-quality tables + the text FIFOs
-    const size_t lds = sim_lds_bytes((size_t)(ion ? (a.ion_lds ? a.lds_words : 0) + a.flow_stack_words : nthr != (uint32_t)SIM_THREADS ? 0 : a.lds_words), nthr, (size_t)a.qb_words, a.fifo != 0);
-    const bool solid = a.p.data_type == 1;
-    if (ion && a.ion_lds) {                                          // Ion Torrent, read buffers in LDS: 256-lane blocks, or one-wave blocks
-        if (nthr != (uint32_t)SIM_THREADS) { if (pe) launch_sim_long_2_3(st, a, nb, lds, out); else launch_sim_long_1_3(st, a, nb, lds, out); }
-        else { if (pe) launch_sim_2_3(st, a, nb, lds, out); else launch_sim_1_3(st, a, nb, lds, out); }
-        return;
-    }
-    if (nthr != (uint32_t)SIM_THREADS) {                             // long Illumina / SOLiD reads: one-wave blocks
-        if (pe) { if (solid) launch_sim_long_2_1(st, a, nb, lds, out); else launch_sim_long_2_0(st, a, nb, lds, out); }
-        else { if (solid) launch_sim_long_1_1(st, a, nb, lds, out); else launch_sim_long_1_0(st, a, nb, lds, out); }
-        return;
-    }
-    if (pe) { if (ion) launch_sim_2_2(st, a, nb, lds, out); else if (solid) launch_sim_2_1(st, a, nb, lds, out); else launch_sim_2_0(st, a, nb, lds, out); }
-    else { if (ion) launch_sim_1_2(st, a, nb, lds, out); else if (solid) launch_sim_1_1(st, a, nb, lds, out); else launch_sim_1_0(st, a, nb, lds, out); }
-}
-#endif // DW_HAS(0): launchers
+#endif // DW_HAS(0)
 
-#define DW_SIM_FAMILY(LPP, DT)                                                                                   \
-    void launch_sim_##LPP##_##DT(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out)             \
-    {                                                                                                            \
-        const uint32_t nthr = SIM_THREADS;                                                                       \
-        if (DT == 0 && !a.fifo) {                                                                                \
-            if (out == 1) hipLaunchKernelGGL((k_simulate<LPP, 1, DT == 0 ? 0 : DT, SIM_THREADS, DT == 0 ? 0 : 1>), dim3(nb), dim3(nthr), lds, st, a);      \
-            else if (out == 2) hipLaunchKernelGGL((k_simulate<LPP, 2, DT == 0 ? 0 : DT, SIM_THREADS, DT == 0 ? 0 : 1>), dim3(nb), dim3(nthr), lds, st, a); \
-            else hipLaunchKernelGGL((k_simulate<LPP, 3, DT == 0 ? 0 : DT, SIM_THREADS, DT == 0 ? 0 : 1>), dim3(nb), dim3(nthr), lds, st, a);               \
-            return;                                                                                              \
-        }                                                                                                        \
-        if (out == 1) hipLaunchKernelGGL((k_simulate<LPP, 1, DT>), dim3(nb), dim3(nthr), lds, st, a);            \
-        else if (out == 2) hipLaunchKernelGGL((k_simulate<LPP, 2, DT>), dim3(nb), dim3(nthr), lds, st, a);       \
-        else hipLaunchKernelGGL((k_simulate<LPP, 3, DT>), dim3(nb), dim3(nthr), lds, st, a);                     \
-    }
-#define DW_SIM_FAMILY_LONG(LPP, DT)                                                                                             \
-    void launch_sim_long_##LPP##_##DT(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out)                          \
-    {                                                                                                                               \
-        const uint32_t nthr = SIM_THREADS_LONG;                                                                                     \
-        if (out == 1) hipLaunchKernelGGL((k_simulate<LPP, 1, DT, SIM_THREADS_LONG>), dim3(nb), dim3(nthr), lds, st, a);             \
-        else if (out == 2) hipLaunchKernelGGL((k_simulate<LPP, 2, DT, SIM_THREADS_LONG>), dim3(nb), dim3(nthr), lds, st, a);        \
-        else hipLaunchKernelGGL((k_simulate<LPP, 3, DT, SIM_THREADS_LONG>), dim3(nb), dim3(nthr), lds, st, a);                      \
-    }
-// the two-kernel form (Illumina, 256-lane blocks): first half, k_split_scan, second half
-void launch_split_scan(hipStream_t st, const SimArgs &a, int lpp);
-#define DW_SIM_SPLIT(LPP)                                                                                                                  \
-    void launch_sim_split_##LPP(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds_a, size_t lds_b, int out)                        \
-    {                                                                                                                                      \
-        hipLaunchKernelGGL((k_simulate<LPP, 1, 0, SIM_THREADS, 1, 1>), dim3(nb), dim3(SIM_THREADS), lds_a, st, a);                         \
-        launch_split_scan(st, a, LPP);                                                                                                     \
-        if (a.fifo) {                                                                                                                      \
-            if (out == 1) hipLaunchKernelGGL((k_simulate<LPP, 1, 0, SIM_THREADS, 2, 2>), dim3(nb), dim3(SIM_THREADS), lds_b, st, a);       \
-            else if (out == 2) hipLaunchKernelGGL((k_simulate<LPP, 2, 0, SIM_THREADS, 2, 2>), dim3(nb), dim3(SIM_THREADS), lds_b, st, a);  \
-            else hipLaunchKernelGGL((k_simulate<LPP, 3, 0, SIM_THREADS, 2, 2>), dim3(nb), dim3(SIM_THREADS), lds_b, st, a);                \
-        } else {                                                                                                                           \
-            if (out == 1) hipLaunchKernelGGL((k_simulate<LPP, 1, 0, SIM_THREADS, 0, 2>), dim3(nb), dim3(SIM_THREADS), lds_b, st, a);       \
-            else if (out == 2) hipLaunchKernelGGL((k_simulate<LPP, 2, 0, SIM_THREADS, 0, 2>), dim3(nb), dim3(SIM_THREADS), lds_b, st, a);  \
-            else hipLaunchKernelGGL((k_simulate<LPP, 3, 0, SIM_THREADS, 0, 2>), dim3(nb), dim3(SIM_THREADS), lds_b, st, a);                \
-        }                                                                                                                                  \
-    }
-// ... of Ion Torrent with its buffers in LDS: the first half is the flow model (no text FIFOs: a block more per CU, and no block waits for the record
-// sizes of the blocks in front of it), the second half qualities and text from the finished reads in HBM
-#define DW_SIM_SPLIT_ION(LPP)                                                                                                              \
-    void launch_sim_split_ion_##LPP(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds_a, size_t lds_b, int out)                    \
-    {                                                                                                                                      \
-        hipLaunchKernelGGL((k_simulate<LPP, 1, 3, SIM_THREADS, 1, 1>), dim3(nb), dim3(SIM_THREADS), lds_a, st, a);                         \
-        launch_split_scan(st, a, LPP);                                                                                                     \
-        if (out == 1) hipLaunchKernelGGL((k_simulate<LPP, 1, 3, SIM_THREADS, 2, 2>), dim3(nb), dim3(SIM_THREADS), lds_b, st, a);           \
-        else if (out == 2) hipLaunchKernelGGL((k_simulate<LPP, 2, 3, SIM_THREADS, 2, 2>), dim3(nb), dim3(SIM_THREADS), lds_b, st, a);      \
-        else hipLaunchKernelGGL((k_simulate<LPP, 3, 3, SIM_THREADS, 2, 2>), dim3(nb), dim3(SIM_THREADS), lds_b, st, a);                    \
-    }
-#if DW_HAS(14)
-DW_SIM_SPLIT_ION(2)
-#endif
-#if DW_HAS(15)
-DW_SIM_SPLIT_ION(1)
-#endif
-#if DW_HAS(1)
-DW_SIM_FAMILY(2, 0)
-#endif
-#if DW_HAS(9)
-DW_SIM_SPLIT(2)
-#endif
-#if DW_HAS(10)
-DW_SIM_SPLIT(1)
-#endif
-#if DW_HAS(7)
-DW_SIM_FAMILY_LONG(2, 0)
-DW_SIM_FAMILY_LONG(1, 0)
-#endif
-#if DW_HAS(8)
-DW_SIM_FAMILY_LONG(2, 1)
-DW_SIM_FAMILY_LONG(1, 1)
-#endif
-#if DW_HAS(2)
-DW_SIM_FAMILY(1, 0)
-#endif
-#if DW_HAS(3)
-DW_SIM_FAMILY(2, 2)
-#endif
-#if DW_HAS(4)
-DW_SIM_FAMILY(1, 2)
-
+#if DW_HAS(4)      // (k_calibrate stays beside the single-end Ion Torrent instances it has always been compiled with: in another part its code and theirs come out different)
 // -B (dwgsim_opt.c:415-457): lane = one random read of read end a.end pushed through the flow model on the forward strand; the block
 // adds its error and length sums to counters[8], [9].  Draws: bases = narrow words of (D_CALIB + end, read, attempt 0), flow model =
 // the streams of (D_CALIB + end, read, attempt 1).  The read buffers (dw_read.hpp flow_errors: a.lds_words words per lane) are in a.scratch.
@@ -1529,29 +1345,69 @@ void launch_calibrate(hipStream_t st, const CalibArgs &a)
     hipLaunchKernelGGL(k_calibrate, dim3(cdiv(std::min(a.chunk_reads, a.n_reads - a.first_read), (uint64_t)PAIRS_PER_BLOCK)), dim3(PAIRS_PER_BLOCK), (size_t)a.stack_words * PAIRS_PER_BLOCK * 4, st, a);
 }
 #endif
-#if DW_HAS(11)
-DW_SIM_FAMILY(2, 3)
+
+// ---- the k_simulate instances that exist: (LPP, OUT, DT, NTHR, WR, SPLIT), by part ----
+#define DW_SIM_OUTS(X, LPP, DT, NTHR, WR, SPLIT) X(LPP, 1, DT, NTHR, WR, SPLIT) X(LPP, 2, DT, NTHR, WR, SPLIT) X(LPP, 3, DT, NTHR, WR, SPLIT)
+#define DW_SIM_PART_1(X)  DW_SIM_OUTS(X, 2, 0, 256, 0, 0) DW_SIM_OUTS(X, 2, 0, 256, 1, 0)      // Illumina, 256-lane blocks: the register / FIFO writer
+#define DW_SIM_PART_2(X)  DW_SIM_OUTS(X, 1, 0, 256, 0, 0) DW_SIM_OUTS(X, 1, 0, 256, 1, 0)
+#define DW_SIM_PART_3(X)  DW_SIM_OUTS(X, 2, 2, 256, 1, 0)                                      // Ion Torrent, read buffers in scratch slots
+#define DW_SIM_PART_4(X)  DW_SIM_OUTS(X, 1, 2, 256, 1, 0)
+#define DW_SIM_PART_5(X)  DW_SIM_OUTS(X, 2, 1, 256, 1, 0)                                      // SOLiD
+#define DW_SIM_PART_6(X)  DW_SIM_OUTS(X, 1, 1, 256, 1, 0)
+#define DW_SIM_PART_7(X)  DW_SIM_OUTS(X, 2, 0, 64, 1, 0) DW_SIM_OUTS(X, 1, 0, 64, 1, 0)        // one-wave blocks for long Illumina / SOLiD reads
+#define DW_SIM_PART_8(X)  DW_SIM_OUTS(X, 2, 1, 64, 1, 0) DW_SIM_OUTS(X, 1, 1, 64, 1, 0)
+#define DW_SIM_PART_9(X)  X(2, 1, 0, 256, 1, 1) DW_SIM_OUTS(X, 2, 0, 256, 2, 2) DW_SIM_OUTS(X, 2, 0, 256, 0, 2)      // Illumina, two kernels
+#define DW_SIM_PART_10(X) X(1, 1, 0, 256, 1, 1) DW_SIM_OUTS(X, 1, 0, 256, 2, 2) DW_SIM_OUTS(X, 1, 0, 256, 0, 2)
+#define DW_SIM_PART_11(X) DW_SIM_OUTS(X, 2, 3, 256, 1, 0)                                      // Ion Torrent, read buffers in LDS
+#define DW_SIM_PART_12(X) DW_SIM_OUTS(X, 1, 3, 256, 1, 0)
+#define DW_SIM_PART_13(X) DW_SIM_OUTS(X, 2, 3, ION_THREADS_SMALL, 1, 0) DW_SIM_OUTS(X, 1, 3, ION_THREADS_SMALL, 1, 0)      // ... the smaller blocks
+#define DW_SIM_PART_14(X) X(2, 1, 3, 256, 1, 1) DW_SIM_OUTS(X, 2, 3, 256, 2, 2)               // ... two kernels
+#define DW_SIM_PART_15(X) X(1, 1, 3, 256, 1, 1) DW_SIM_OUTS(X, 1, 3, 256, 2, 2)
+#define DW_SIM_ALL(X) DW_SIM_PART_1(X) DW_SIM_PART_2(X) DW_SIM_PART_3(X) DW_SIM_PART_4(X) DW_SIM_PART_5(X) DW_SIM_PART_6(X) DW_SIM_PART_7(X) DW_SIM_PART_8(X) \
+                      DW_SIM_PART_9(X) DW_SIM_PART_10(X) DW_SIM_PART_11(X) DW_SIM_PART_12(X) DW_SIM_PART_13(X) DW_SIM_PART_14(X) DW_SIM_PART_15(X)
+
+template <int LPP, int OUT, int DT, int NTHR, int WR, int SPLIT>
+void launch_sim(hipStream_t st, const SimArgs &a, size_t lds)
+{
+    hipLaunchKernelGGL((k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT>), dim3(a.n_blocks), dim3(NTHR), lds, st, a);
+}
+// each part instantiates its share of the list; part 0 only refers to them
+#define DW_SIM_INSTANCE(LPP, OUT, DT, NTHR, WR, SPLIT) template void launch_sim<LPP, OUT, DT, NTHR, WR, SPLIT>(hipStream_t, const SimArgs &, size_t);
+#define DW_SIM_EXTERN(LPP, OUT, DT, NTHR, WR, SPLIT) extern template void launch_sim<LPP, OUT, DT, NTHR, WR, SPLIT>(hipStream_t, const SimArgs &, size_t);
+#define DW_CAT(a, b) DW_CAT_(a, b)
+#define DW_CAT_(a, b) a##b
+#if DW_PART == -1
+DW_SIM_ALL(DW_SIM_INSTANCE)
+#elif DW_PART == 0
+DW_SIM_ALL(DW_SIM_EXTERN)
+#else
+DW_CAT(DW_SIM_PART_, DW_PART)(DW_SIM_INSTANCE)
 #endif
-#if DW_HAS(12)
-DW_SIM_FAMILY(1, 3)
-#endif
-#if DW_HAS(13)
-#define DW_SIM_FAMILY_ION_SMALL(LPP)                                                                                               \
-    void launch_sim_long_##LPP##_3(hipStream_t st, const SimArgs &a, uint32_t nb, size_t lds, int out)                              \
-    {                                                                                                                               \
-        const uint32_t nthr = ION_THREADS_SMALL;                                                                                    \
-        if (out == 1) hipLaunchKernelGGL((k_simulate<LPP, 1, 3, ION_THREADS_SMALL>), dim3(nb), dim3(nthr), lds, st, a);             \
-        else if (out == 2) hipLaunchKernelGGL((k_simulate<LPP, 2, 3, ION_THREADS_SMALL>), dim3(nb), dim3(nthr), lds, st, a);        \
-        else hipLaunchKernelGGL((k_simulate<LPP, 3, 3, ION_THREADS_SMALL>), dim3(nb), dim3(nthr), lds, st, a);                      \
+
+#if DW_HAS(0)
+// the form the host chose (dw_host.cpp sim_form): its entry in the list, or both halves and k_split_scan between them
+bool launch_simulate(hipStream_t st, const SimArgs &a, const SimForm &f)
+{
+    using Launch = void (*)(hipStream_t, const SimArgs &, size_t);
+    struct Entry { int lpp, out, dt, nthr, wr, split; Launch launch; };
+#define DW_SIM_ENTRY(LPP, OUT, DT, NTHR, WR, SPLIT) {LPP, OUT, DT, NTHR, WR, SPLIT, &launch_sim<LPP, OUT, DT, NTHR, WR, SPLIT>},
+    static const Entry list[] = {DW_SIM_ALL(DW_SIM_ENTRY)};
+    auto find = [&](int out, int wr, int split) -> Launch {
+        for (const Entry &e : list) if (e.lpp == f.lpp && e.out == out && e.dt == f.dt && e.nthr == f.nthr && e.wr == wr && e.split == split) return e.launch;
+        return nullptr;
+    };
+    if (!f.split) {
+        const Launch k = find(f.out, f.wr, 0);
+        if (k) k(st, a, f.lds);
+        return k != nullptr;
     }
-DW_SIM_FAMILY_ION_SMALL(2)
-DW_SIM_FAMILY_ION_SMALL(1)
-#endif
-#if DW_HAS(5)
-DW_SIM_FAMILY(2, 1)
-#endif
-#if DW_HAS(6)
-DW_SIM_FAMILY(1, 1)
+    const Launch k1 = find(1, 1, 1), k2 = find(f.out, f.wr, 2);
+    if (!k1 || !k2) return false;
+    k1(st, a, f.lds);
+    launch_split_scan(st, a, f.lpp);
+    k2(st, a, f.lds_b);
+    return true;
+}
 #endif
 
 } // namespace dw

@@ -410,7 +410,9 @@ int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *ctx, const void *t
 int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *ctx, const char *key, int64_t value);
 /* "place_open": pairs the last dwgsim_hip_count_random* call could not settle from the coarse haplotype summaries; "flow_cap_mult": how often (as a
  * power of two) the Ion Torrent read capacity has been doubled so far; "walk_us" / "count_us":
- * HIP-event time (microseconds, accumulated) of the context's walk chains / random-read counts on the walk stream */
+ * HIP-event time (microseconds, accumulated) of the context's walk chains / random-read counts on the walk stream; "sim_form": the
+ * k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> form of the context's last simulate launch (0 before the first), packed as
+ * NTHR << 20 | LPP << 16 | OUT << 12 | DT << 8 | WR << 4 | SPLIT (SPLIT 1: the two-kernel form, WR: the writer of its second half) */
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *ctx, const char *key, int64_t *value);
 /* the gzip kernel on arbitrary host bytes (the product only ever feeds it FASTQ text) */
 int dwgsim_hip_debug_gzip(dwgsim_hip_ctx_t *ctx, const void *text, size_t n, void *out, size_t cap, size_t *out_n);

@@ -571,3 +571,58 @@ def test_a_call_whose_look_back_word_would_overflow_is_refused_on_cpu_emulation(
             ctx.simulate_ranges([(h0, 0, 1 << 34)], 0, 0)
         b = ctx.simulate_ranges([(h0, 0, 100)], 0, 0)      # (and the context is still good)
         assert b.n_pairs == 100
+
+
+FLOW_ORDER = "-c 2 -f TACGTACGTCTGAGCATCGATCGATGTACAGC"
+SIM_FORMS = [      # (flags, debug options, k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> the launch must run)
+    ("-1 50 -2 50", {}, (2, 3, 0, 256, 2, 1)),              # short reads: the two-kernel form
+    ("-1 51 -2 51", {}, (2, 3, 0, 256, 1, 0)),
+    ("-1 150 -2 150 -o 1", {}, (2, 1, 0, 256, 1, 0)),
+    ("-1 150 -2 150 -o 0", {}, (2, 3, 0, 256, 1, 0)),
+    ("-1 200 -2 200 -o 1", {}, (2, 1, 0, 256, 0, 0)),       # the FIFO would cost a resident block: the register writer
+    ("-1 200 -2 200 -o 1", {"writer": 1}, (2, 1, 0, 256, 1, 0)),
+    ("-1 150 -2 150 -o 1", {"writer": 0}, (2, 1, 0, 256, 0, 0)),
+    ("-1 50 -2 50", {"writer": 0}, (2, 3, 0, 256, 0, 1)),
+    ("-1 50 -2 50", {"writer": 1}, (2, 3, 0, 256, 2, 1)),
+    ("-1 150 -2 150", {"split": 1}, (2, 3, 0, 256, 2, 1)),
+    ("-1 150 -2 150", {"split": 1, "writer": 0}, (2, 3, 0, 256, 0, 1)),
+    ("-1 50 -2 50", {"split": 0}, (2, 3, 0, 256, 1, 0)),
+    ("-1 100 -2 0", {}, (1, 3, 0, 256, 1, 0)),
+    ("-1 40 -2 0", {}, (1, 3, 0, 256, 2, 1)),
+    ("-1 800 -2 800 -d 2000", {}, (2, 3, 0, 64, 1, 0)),    # long reads: one-wave blocks
+    ("-1 800 -2 800 -d 2000", {"sim_threads": 256}, (2, 3, 0, 256, 1, 0)),
+    ("-1 100 -2 100", {"sim_threads": 64}, (2, 3, 0, 64, 1, 0)),
+    ("-c 1 -1 50 -2 50", {}, (2, 3, 1, 256, 1, 0)),
+    ("-c 1 -1 50 -2 0", {}, (1, 3, 1, 256, 1, 0)),
+    (FLOW_ORDER + " -1 100 -2 100", {}, (2, 3, 3, 256, 2, 1)),
+    (FLOW_ORDER + " -1 100 -2 100", {"ion_lds": 0}, (2, 3, 2, 256, 1, 0)),
+    (FLOW_ORDER + " -1 100 -2 100", {"ion_lds": 1}, (2, 3, 3, 256, 2, 1)),
+    (FLOW_ORDER + " -1 100 -2 100", {"ion_lds": 2}, (2, 3, 3, 128, 1, 0)),
+    (FLOW_ORDER + " -1 100 -2 100", {"ion_lds": 1, "split": 0}, (2, 3, 3, 256, 1, 0)),
+    (FLOW_ORDER + " -1 100 -2 100", {"flow_cap": 32768}, (2, 3, 2, 256, 1, 0)),      # a capacity of 32768 bases: not split
+    ("-1 100 -2 100 -o 2", {}, (2, 2, 0, 256, 1, 0)),
+]
+
+
+@pytest.mark.parametrize("flags,opts,form", SIM_FORMS, ids=[f"{fl}:{o}" for fl, o, _ in SIM_FORMS])
+def test_k_simulate_form_chosen_by_the_host_on_cpu_emulation(emu_lib, golden_dir, flags, opts, form):
+    """Which k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> a launch runs (dw_host.cpp), read back through dwgsim_hip_debug_get("sim_form")."""
+    lpp, out, dt, nthr, wr, split = form
+    params = api.parse_flags("-z 3 " + flags, emu_lib)
+    with api.Context(params, 0, emu_lib) as ctx:
+        for k, v in opts.items():
+            ctx.debug_option(k, v)
+        h0 = ctx.add_contigs(api.read_fasta(os.path.join(golden_dir, "tiny.fa"))[:1], indices=[0])
+        ctx.mutate(h0)
+        assert ctx.simulate_ranges([(h0, 0, 8)], 0, 0).n_pairs == 8
+        assert ctx.debug_get("sim_form") == nthr << 20 | lpp << 16 | out << 12 | dt << 8 | wr << 4 | split
+
+
+def test_reads_too_long_for_the_quality_tables_are_refused_on_cpu_emulation(emu_lib, golden_dir):
+    """Illumina / SOLiD reads whose two base-quality tables and text FIFOs do not fit the LDS of a one-wave block."""
+    params = api.parse_flags("-z 3 -1 76000 -2 0", emu_lib)
+    with api.Context(params, 0, emu_lib) as ctx:
+        h0 = ctx.add_contigs(api.read_fasta(os.path.join(golden_dir, "tiny.fa"))[:1], indices=[0])
+        ctx.mutate(h0)
+        with pytest.raises(api.DwgsimError, match="reads longer than 75504 bases are not supported for -c 0 / -c 1"):
+            ctx.simulate_ranges([(h0, 0, 8)], 0, 0)
