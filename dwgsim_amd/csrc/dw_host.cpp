@@ -599,6 +599,32 @@ extern "C" int dwgsim_hip_selftest_text(int device, uint64_t first, uint64_t n, 
     return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
 }
 
+// Not part of the drop-in ABI either: the gap draw geom_gap at threshold thr (0 < thr < 2^32) on the words [first, first + n), with the R, s and log2 table
+// of the product's own host functions (dw_kernels.hpp flow_gap_params, flow_log2_table) -- dw_simulate.hip k_selftest_gap.  chg (g_cnt words, host
+// memory): chg[k] = the first word w in (first, first + n) whose G is below g_lo + k, 0 where no word of the range is (the whole range: #{w : G(w) >= g}).
+// out[0] = words where G increases with w, out[1] = words at the clip 0x3FFFFFFF, out[2] = words evaluated, out[3] = G of the last word.
+extern "C" int dwgsim_hip_selftest_gap(int device, uint64_t thr, uint32_t first, uint64_t n, uint32_t g_lo, uint32_t g_cnt, uint32_t *chg, uint64_t *out)
+{
+    if (!out || (g_cnt && !chg) || thr == 0 || thr >= 0x100000000ull || n == 0 || (uint64_t)first + n > 0x100000000ull) return DWGSIM_HIP_ERR_ARG;
+    if (hipSetDevice(device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    uint32_t lg[FLOW_LG_ENTRIES];
+    flow_log2_table(lg);
+    uint64_t R; int32_t sR;
+    flow_gap_params(thr, &R, &sR);
+    uint64_t *d = nullptr; uint32_t *d_lg = nullptr, *d_chg = nullptr;
+    const size_t chg_bytes = (size_t)g_cnt * sizeof(uint32_t);
+    if (hipMalloc((void **)&d, 4 * sizeof(uint64_t)) != hipSuccess || hipMalloc((void **)&d_lg, sizeof lg) != hipSuccess ||
+        hipMalloc((void **)&d_chg, chg_bytes ? chg_bytes : 4) != hipSuccess) { hipFree(d); hipFree(d_lg); return DWGSIM_HIP_ERR_NOMEM; }
+    hipMemset(d, 0, 4 * sizeof(uint64_t));
+    hipMemset(d_chg, 0, chg_bytes ? chg_bytes : 4);
+    hipMemcpy(d_lg, lg, sizeof lg, hipMemcpyHostToDevice);
+    launch_selftest_gap(nullptr, d_lg, R, sR, first, n, g_lo, g_cnt, d_chg, d);
+    hipError_t e = hipMemcpy(out, d, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && chg_bytes) e = hipMemcpy(chg, d_chg, chg_bytes, hipMemcpyDeviceToHost);
+    hipFree(d); hipFree(d_lg); hipFree(d_chg);
+    return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
+}
+
 // Not part of the drop-in ABI either: self-test of the lazy quality normals (dw_simulate.hip k_selftest_lazy).  out[0..4] = counters of the
 // comparison with the exact form on the n tries w = first, first + 1, ... (n = 2^32: EVERY try) at quality_std = sigma, out[5] = max
 // |estimate - exact| / eps, out[6..8] = worst error of v_log_f32 / v_rcp_f32 / v_sqrt_f32 over EVERY float of their operand ranges, in units of

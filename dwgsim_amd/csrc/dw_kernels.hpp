@@ -138,7 +138,10 @@ inline void flow_gap_params(uint64_t thr, uint64_t *R, int32_t *s)
     const uint64_t Lq = (32ull << 56) - flow_ilog2_fixed(0x100000000ull - thr, 56);
     const int sh = __builtin_clzll(Lq);
     const unsigned __int128 q = ((unsigned __int128)1 << 127) / (Lq << sh);
-    *R = (uint64_t)(q >> 64) ? ~0ull : (uint64_t)q; *s = 63 - sh;
+    // q = 2^64 where -log2(1 - e') is a power of two (thr = 2^31, 3 2^30, ..., 2^32 - 1): G = Lu / Lq = Lu >> (s + 1) exactly, as R = 2^63 and one shift less
+    // (R = 2^64 - 1 gave (Lu - 1) >> s: one too few wherever Lu is a multiple of 2^s -- 128 words per gap value at e' = 1/2)
+    if ((uint64_t)(q >> 64)) { *R = 1ull << 63; *s = 62 - sh; }
+    else { *R = (uint64_t)q; *s = 63 - sh; }
 }
 
 struct CalibArgs {

@@ -7,6 +7,7 @@
 //     k_place, k_place_rest  dwgsim_hip_count_random (sharding): random reads in a read-index range without producing them
 //     k_calibrate     -B: per-base calibration of the Ion Torrent flow error (dwgsim_opt.c:415-457)
 //     k_selftest_fp64 device self-test of the range-restricted fp64 forms (dw_common.hpp)
+//     k_selftest_gap  device self-test of the gap draw geom_gap (dw_common.hpp) on every word of a range
 //
 // Byte/integer work plus fp64 for the normals: no MFMA.  fp64 expressions mirror the reference's evaluation order; compile
 // with -ffp-contract=off.
@@ -481,7 +482,9 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
     if (SPLIT != 1) for (int q = tid; q < 2 * a.qb_words; q += nthr) s_qb[q] = (q < a.qb_words ? a.qbase[0] : a.qbase[1])[q < a.qb_words ? q : q - a.qb_words];
     // this lane's text FIFO (record writer), behind the tables
     uint8_t *const s_fifo = reinterpret_cast<uint8_t *>(dyn_lds + (((stage_words * nthr + 2 * (size_t)a.qb_words) + 3) & ~(size_t)3)) + (size_t)tid * (WR == 2 ? SIM_FIFO_BYTES_WIDE : SIM_FIFO_BYTES);
-    if (SPLIT == 0) __syncthreads();
+    // (the first half of the two-kernel form, Illumina: s_lg, which the error sites below read at arbitrary entries, needs a barrier of its own -- Ion Torrent
+    // has the one in front of fill_flow_tables)
+    if (SPLIT == 0 || (SPLIT == 1 && !ION)) __syncthreads();
     constexpr int H = SPLIT;      // which half of the path this kernel is: 0 both (the single kernel), 1 first, 2 second
     // logical block.  One kernel: from an atomic ticket, so that a block's predecessors have started when it looks back at them.  Two kernels:
     // no block waits for another, the block index will do
@@ -1089,6 +1092,49 @@ void launch_selftest_text(hipStream_t st, uint64_t first, uint64_t n, uint64_t s
 {
     const uint64_t nb = cdiv(n, 256);
     hipLaunchKernelGGL(k_selftest_text, dim3((uint32_t)(nb < (1u << 16) ? (nb ? nb : 1) : (1u << 16))), dim3(256), 0, st, first, n, stride, out);
+}
+// Self-test of the gap draw geom_gap (dw_common.hpp) on the words [first, first + n): the log2 table lg staged in LDS behind a barrier, as k_simulate
+// stages it; a lane takes GAP_RUN consecutive words and the G of the word in front of them.  out[0] += words w > first with G(w) > G(w - 1) (0: G is
+// non-increasing in w), out[1] += words with G = 0x3FFFFFFF (the clip), out[2] += words evaluated, out[3] = G of the last word; chg[g - g_lo] = w for every
+// g in [g_lo, g_lo + g_cnt) with G(w - 1) >= g > G(w), first < w < first + n: the first word whose G is below g, #{w : G(w) >= g} over the whole range.  Monotonicity and these
+// change points are the whole function (tests/test_gpu_gap_law.py).
+constexpr uint32_t GAP_RUN = 256;
+__global__ void __launch_bounds__(256) k_selftest_gap(const uint32_t *lg, uint64_t R, int sR, uint32_t first, uint64_t n, uint32_t g_lo, uint32_t g_cnt, uint32_t *chg, uint64_t *out)
+{
+    __shared__ uint32_t s_lg[FLOW_LG_ENTRIES];
+    for (int q = threadIdx.x; q < FLOW_LG_ENTRIES; q += 256) s_lg[q] = lg[q];
+    __syncthreads();
+    uint32_t up = 0, clip = 0, done = 0;
+    const uint64_t g_end = (uint64_t)g_lo + g_cnt;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r * GAP_RUN < n; r += (uint64_t)gridDim.x * 256) {
+        const uint64_t i0 = r * GAP_RUN, i1 = i0 + GAP_RUN < n ? i0 + GAP_RUN : n;
+        uint32_t prev = i0 ? geom_gap(first + (uint32_t)i0 - 1u, s_lg, R, sR) : 0u;
+        for (uint64_t i = i0; i < i1; ++i) {
+            const uint32_t G = geom_gap(first + (uint32_t)i, s_lg, R, sR);
+            clip += G == 0x3FFFFFFFu;
+            if (i + 1 == n) out[3] = G;
+            if (i) {
+                up += G > prev;
+                if (G < prev && (uint64_t)G + 1 < g_end && (uint64_t)prev >= g_lo) {
+                    const uint64_t a = (uint64_t)G + 1 > g_lo ? (uint64_t)G + 1 : g_lo, b = (uint64_t)prev < g_end ? (uint64_t)prev + 1 : g_end;
+                    for (uint64_t g = a; g < b; ++g) chg[g - g_lo] = first + (uint32_t)i;
+                }
+            }
+            prev = G;
+        }
+        done += (uint32_t)(i1 - i0);
+    }
+    const uint32_t s0 = wave_sum_u32(up), s1 = wave_sum_u32(clip), s2 = wave_sum_u32(done);
+    if ((threadIdx.x & 63) == 0) {
+        if (s0) atomicAdd((unsigned long long *)&out[0], (unsigned long long)s0);
+        if (s1) atomicAdd((unsigned long long *)&out[1], (unsigned long long)s1);
+        atomicAdd((unsigned long long *)&out[2], (unsigned long long)s2);
+    }
+}
+void launch_selftest_gap(hipStream_t st, const uint32_t *lg, uint64_t R, int sR, uint32_t first, uint64_t n, uint32_t g_lo, uint32_t g_cnt, uint32_t *chg, uint64_t *out)
+{
+    const uint64_t nb = cdiv(cdiv(n, GAP_RUN), 256);
+    hipLaunchKernelGGL(k_selftest_gap, dim3((uint32_t)(nb < (1u << 16) ? (nb ? nb : 1) : (1u << 16))), dim3(256), 0, st, lg, R, sR, first, n, g_lo, g_cnt, chg, out);
 }
 void launch_selftest_fp64(hipStream_t st, uint32_t seed, uint64_t n, uint64_t *mism)
 {

@@ -426,6 +426,10 @@ int dwgsim_hip_selftest_lazy(int device, uint32_t first, uint64_t n, double sigm
 /* the number formatters of the name line (decimal positions and counts, the hexadecimal read index: dw_read.hpp put_dec / put_hex) against one
  * division per digit on the values first + i * stride, i < n.  out[0] / out[1]: decimal / hexadecimal texts that differ, out[2]: values compared. */
 int dwgsim_hip_selftest_text(int device, uint64_t first, uint64_t n, uint64_t stride, uint64_t *out);
+/* the gap draw of the error sites, walk sites and flow first draws (dw_common.hpp geom_gap) at threshold thr (0 < thr < 2^32), with the product's own
+ * table and reciprocal, on the words [first, first + n).  chg[k] (g_cnt words): the first word of the range whose gap is below g_lo + k (0: none);
+ * out[0]: words where the gap increases with the word, out[1]: words at the clip 0x3FFFFFFF, out[2]: words evaluated, out[3]: the gap of the last word. */
+int dwgsim_hip_selftest_gap(int device, uint64_t thr, uint32_t first, uint64_t n, uint32_t g_lo, uint32_t g_cnt, uint32_t *chg, uint64_t *out);
 
 #ifdef __cplusplus
 }

@@ -214,7 +214,8 @@ static gap_par_t flow_gap_params(uint64_t thr)       /* -log2(1 - e') in Q8.56, 
     const uint64_t Lq = (32ull << 56) - ilog2_fixed(0x100000000ull - thr, 56);
     const int sh = __builtin_clzll(Lq);
     const unsigned __int128 q = ((unsigned __int128)1 << 127) / (Lq << sh);
-    g.R = q >> 64 ? ~0ull : (uint64_t)q; g.s = 63 - sh;
+    if (q >> 64) { g.R = 1ull << 63; g.s = 62 - sh; }      /* q = 2^64: -log2(1 - e') a power of two, G = Lu >> (s + 1) exactly (dw_kernels.hpp) */
+    else { g.R = (uint64_t)q; g.s = 63 - sh; }
     return g;
 }
 #define FLOW_NEVER 0xFFFFFFFFu
@@ -229,6 +230,36 @@ static uint32_t flow_gap(uint32_t w, const gap_par_t *g)      /* quiet first dra
     const uint64_t Lu = ((uint64_t)(33 - p) << 56) - ((uint64_t)f << 24);
     const uint64_t G = (uint64_t)(((unsigned __int128)Lu * g->R) >> 64) >> g->s;
     return G > 0x3FFFFFFFull ? 0x3FFFFFFFu : (uint32_t)G;
+}
+
+/* ---- exports for the tests of the gap law (tests/test_gap_law.py, tests/test_gpu_gap_law.py); nothing in the simulation calls them ---- */
+void oracle_flow_gap_params(uint64_t thr, uint64_t *R, int32_t *s) { const gap_par_t g = flow_gap_params(thr); *R = g.R; *s = g.s; }
+uint32_t oracle_flow_gap(uint64_t thr, uint32_t w) { const gap_par_t g = flow_gap_params(thr); return flow_gap(w, &g); }
+/* out[k] = #{w : G(w) >= g_lo + k} for k < g_cnt, G = flow_gap at thr (0 < thr < 2^32): G is non-increasing in w, so this is the first word whose G is
+ * below g.  Found from the previous boundary scaled by (1 - e') -- the law says the boundaries are about that far apart -- by galloping and bisection. */
+void oracle_gap_bounds(uint64_t thr, uint32_t g_lo, uint64_t g_cnt, uint64_t *out)
+{
+    const gap_par_t par = flow_gap_params(thr);
+    const double q = 1.0 - (double)thr * 0x1p-32;
+    uint64_t prev = 0;
+    for (uint64_t k = 0; k < g_cnt; ++k) {
+        const uint64_t g = (uint64_t)g_lo + k;
+        uint64_t lo, hi;      /* G(lo - 1) >= g (or lo = 0), G(hi) < g (or hi = 2^32): the boundary is in [lo, hi] */
+        if (g == 0) { out[k] = 0x100000000ull; prev = out[k]; continue; }
+        double guess = k ? (double)prev * q : 4294967296.0 * pow(q, (double)g);
+        uint64_t c = guess < 1.0 ? 0 : guess >= 4294967296.0 ? 0xFFFFFFFFull : (uint64_t)guess;
+        if (k && c > prev) c = prev;
+        uint64_t step = 1;
+        if (c < 0x100000000ull && flow_gap((uint32_t)c, &par) >= g) {      /* the boundary is above c */
+            lo = c + 1; hi = c + 1;
+            while (hi < 0x100000000ull && flow_gap((uint32_t)hi, &par) >= g) { lo = hi + 1; hi = c + (step <<= 1); if (hi > 0x100000000ull) hi = 0x100000000ull; }
+        } else {                                                             /* ... at or below c */
+            hi = c; lo = c;
+            while (lo > 0 && flow_gap((uint32_t)(lo - 1), &par) < g) { hi = lo - 1; lo = c > (step <<= 1) ? c - step : 0; }
+        }
+        while (lo < hi) { const uint64_t m = lo + (hi - lo) / 2; if (flow_gap((uint32_t)m, &par) >= g) lo = m + 1; else hi = m; }
+        out[k] = prev = lo;
+    }
 }
 
 /* mut.c:618 `c < 4 && drand48() < opt->mut_rate`, once per ACGT position outside a live deletion run: by far the most frequent draw of the walk -- and one

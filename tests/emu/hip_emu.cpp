@@ -5,6 +5,7 @@
 // pthread barriers, the first form of this file, spent nearly all of its time in futex calls: a ballot cost a hundred microseconds.)
 // Blocks run one after the other, in order (static __shared__ storage; look-backs find their predecessors finished).  A wave operation
 // inside divergent control flow, which hangs the GPU, is reported here: the scheduler sees that no fiber can move.
+// HIPEMU_WAVES_APART (launch below) runs the waves of a block one at a time between barriers and poisons LDS at every block start.
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 #include <mutex>
@@ -47,7 +48,7 @@ thread_local Idx t_threadIdx, t_blockIdx, t_blockDim, t_gridDim;
 
 namespace {
 constexpr size_t STACK = (size_t)512 << 10, GUARD = 4096;
-struct Fiber { void *sp; bool done; };
+struct Fiber { void *sp; bool done, at_block; unsigned bar_gen; };      // at_block: arrived at the __syncthreads() of generation bar_gen
 struct Barrier { unsigned arrived = 0, gen = 0; };
 struct Run {
     Fiber fib[1024]; unsigned nt = 0, cur = 0; void *sched_sp = nullptr;
@@ -93,9 +94,33 @@ void wait_at(Barrier &b, unsigned count)
     if (++b.arrived == count) { b.arrived = 0; ++b.gen; g.progress = true; return; }
     while (b.gen == gen) to_scheduler();
 }
+bool waits_at_block(unsigned t) { return g.fib[t].at_block && g.fib[t].bar_gen == g.block_bar.gen; }
+
+void run_fiber(unsigned t)
+{
+    g.cur = t; t_threadIdx = Idx{t, 0, 0};
+#if EMU_ASAN
+    void *fake = nullptr;
+    __sanitizer_start_switch_fiber(&fake, stack_of(t), STACK);
+#endif
+    emu_switch(&g.sched_sp, g.fib[t].sp);
+#if EMU_ASAN
+    __sanitizer_finish_switch_fiber(fake, nullptr, nullptr);
+#endif
+}
 } // namespace
 
-void sync_block() { wait_at(g.block_bar, g.nt); }
+// the static __shared__ storage of the kernels: tests/emu/lds.ld collects it between these two symbols (build.sh checks that it holds all of it;
+// a library linked without the script has neither, and refuses HIPEMU_WAVES_APART)
+extern "C" __attribute__((weak)) unsigned char hipemu_lds_begin[], hipemu_lds_end[];
+
+void sync_block()
+{
+    Fiber &f = g.fib[g.cur];
+    f.at_block = true; f.bar_gen = g.block_bar.gen;
+    wait_at(g.block_bar, g.nt);
+    f.at_block = false;
+}
 void sync_wave() { wait_at(g.wave_bar[t_threadIdx.x >> 6], 64); }
 void yield() { to_scheduler(); }
 uint64_t *wave_buf() { return g.wave_buf[t_threadIdx.x >> 6]; }
@@ -114,6 +139,7 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()> &fn
         for (unsigned t = 0; t < 1024; ++t) mprotect(g.stacks + (size_t)t * (STACK + GUARD), GUARD, PROT_NONE);
     }
     g.dyn.assign(shmem + 64, 0);
+    constexpr unsigned char LDS_POISON = 0xA5;
     g.nt = nt; g.fn = &fn;
     // HIPEMU_REVERSE=<kernel name>[,<kernel name>...]: the blocks of those kernels run from the last to the first, and so do the lanes of a
     // block.  Threads that are meant to be independent (one cluster of the left-justification each) must not care; run in index order only,
@@ -132,6 +158,14 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()> &fn
     };
     const bool reverse_blocks = named_in("HIPEMU_REVERSE");
     const bool reverse_lanes = reverse_blocks || named_in("HIPEMU_REVERSE_LANES");
+    // HIPEMU_WAVES_APART=<kernel names>|all: the waves of a block run one at a time -- a wave alone, its lanes round-robin, until every one of them has
+    // finished or waits at __syncthreads(), then the next wave: the last wave first, or in an order shuffled per block by HIPEMU_WAVES_SEED=<n>.  Waves
+    // are unordered between barriers on the GPU, so this is a legal schedule; under it the wave that runs first sees none of the other waves' stores
+    // since the last barrier, and a missing barrier between a table's fill and its use shows every time.  LDS (static __shared__ and dynamic) is filled with the byte
+    // LDS_POISON at every block start, as undefined as on the GPU.
+    const bool apart = named_in("HIPEMU_WAVES_APART");
+    const char *seed_env = getenv("HIPEMU_WAVES_SEED");
+    if (apart && !hipemu_lds_begin) { fprintf(stderr, "hipemu: HIPEMU_WAVES_APART needs a library linked with tests/emu/lds.ld\n"); abort(); }
     const unsigned gy = grid.y ? grid.y : 1;
     const Idx saved[4] = {t_threadIdx, t_blockIdx, t_blockDim, t_gridDim};
     t_blockDim = Idx{nt, 1, 1}; t_gridDim = Idx{grid.x, gy, 1};
@@ -145,28 +179,58 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()> &fn
                 void **top = (void **)(stack_of(t) + STACK);
                 top[-2] = (void *)&fiber_main;            // return address of the first switch; the stack pointer is 8 mod 16 behind it, as after a call
                 for (int k = 3; k <= 8; ++k) top[-k] = nullptr;
-                g.fib[t].sp = (void *)(top - 8); g.fib[t].done = false;
+                g.fib[t].sp = (void *)(top - 8); g.fib[t].done = false; g.fib[t].at_block = false;
+            }
+            if (apart) {      // LDS is undefined at the start of a block
+                memset(hipemu_lds_begin, LDS_POISON, (size_t)(hipemu_lds_end - hipemu_lds_begin));
+                memset(g.dyn.data(), LDS_POISON, g.dyn.size());
+            }
+            const unsigned nw = nt / 64;
+            unsigned wave_order[16];
+            for (unsigned k = 0; k < nw; ++k) wave_order[k] = nw - 1 - k;            // the last wave first
+            if (apart && seed_env) {
+                uint64_t x = strtoull(seed_env, nullptr, 0) * 0x9E3779B97F4A7C15ull + ((uint64_t)y << 32 | b);
+                for (unsigned k = nw; k > 1; --k) {                                   // Fisher-Yates with splitmix64
+                    x += 0x9E3779B97F4A7C15ull;
+                    uint64_t z = x; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
+                    const unsigned r = (unsigned)(z % k); const unsigned tmp = wave_order[k - 1]; wave_order[k - 1] = wave_order[r]; wave_order[r] = tmp;
+                }
             }
             unsigned left = nt, idle_rounds = 0;
             while (left) {
-                g.progress = false;
-                for (unsigned tt = 0; tt < nt; ++tt) {
-                    const unsigned t = reverse_lanes ? nt - 1 - tt : tt;
-                    if (g.fib[t].done) continue;
-                    g.cur = t; t_threadIdx = Idx{t, 0, 0};
-#if EMU_ASAN
-                    void *fake = nullptr;
-                    __sanitizer_start_switch_fiber(&fake, stack_of(t), STACK);
-#endif
-                    emu_switch(&g.sched_sp, g.fib[t].sp);
-#if EMU_ASAN
-                    __sanitizer_finish_switch_fiber(fake, nullptr, nullptr);
-#endif
-                    if (g.fib[t].done) --left;
+                bool moved = false;
+                if (apart) {
+                    // one wave at a time, until each of its lanes has finished or waits at __syncthreads(); a wave whose lanes only poll (yield without
+                    // a barrier completed or a lane finished) passes its turn
+                    for (unsigned k = 0; k < nw; ++k) {
+                        const unsigned w = wave_order[k];
+                        for (;;) {
+                            g.progress = false;
+                            bool ran = false;
+                            for (unsigned l = 0; l < 64; ++l) {
+                                const unsigned t = w * 64 + (reverse_lanes ? 63 - l : l);
+                                if (g.fib[t].done || waits_at_block(t)) continue;
+                                ran = true;
+                                run_fiber(t);
+                                if (g.fib[t].done) --left;
+                            }
+                            if (!ran || !g.progress) break;
+                            moved = true;
+                        }
+                    }
+                } else {
+                    g.progress = false;
+                    for (unsigned tt = 0; tt < nt; ++tt) {
+                        const unsigned t = reverse_lanes ? nt - 1 - tt : tt;
+                        if (g.fib[t].done) continue;
+                        run_fiber(t);
+                        if (g.fib[t].done) --left;
+                    }
+                    moved = g.progress;
                 }
                 // no barrier completed, no lane finished: either lanes poll memory for one another (s_sleep loops), or some lanes wait at a wave
                 // operation the others will never reach
-                idle_rounds = g.progress ? 0 : idle_rounds + 1;
+                idle_rounds = moved ? 0 : idle_rounds + 1;
                 if (idle_rounds > 100000) { fprintf(stderr, "hipemu: block %u: no lane can move -- a wave operation (ballot, shuffle, barrier) inside divergent control flow?\n", b); abort(); }
             }
         }
