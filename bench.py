@@ -24,10 +24,13 @@ random-read count, exchange: walk stream and host -- runs beside the kernels of 
   --mode weak   (default) per-GPU work is fixed: the job's coverage is N times the workload's (-C 30 N), i.e. N times the pairs
   --mode strong one fixed job (e.g. --workload grch38: the 325 M-pair S4 genome) split over the ranks
 
-`value` = pairs of all ranks / max-over-ranks wall time of the timed steps, text left in HBM (the contract).  More legs are measured at
-N=1 and reported beside it (never as `value`): `host_landed` (text copied into page-locked host memory through the asynchronous
-two-slot pipeline), `host_landed_gz` (the same with the gzip members made on the GPU -- what the product moves), `end_to_end` (the
-dwgsim-hip executable: FASTA in, five output files out) and `end_to_end_genome` (dwgsim-hip on the whole S4 genome, counting sink).
+`value` = pairs of all ranks / max-over-ranks wall time of the timed steps, text left in HBM (the contract).  A plain run does only what
+that needs: it makes the job resident, runs the warm-up and timed steps, writes --dump-outputs and prints the line.  `--full` also
+measures, after the timed steps and reported beside `value` (never as it): at N=1 `host_landed` (text copied into page-locked host
+memory through the asynchronous two-slot pipeline), `host_landed_gz` (the same with the gzip members made on the GPU -- what the product
+moves), `end_to_end` (the dwgsim-hip executable: FASTA in, five output files out), `cpu_baseline` (the reference on the host cores) and
+`end_to_end_genome` (dwgsim-hip on the whole S4 genome, counting sink); at every N the `strong` object (the whole-genome job split over
+the ranks).  --no-legs, --no-cpu-baseline, --no-genome-leg and --no-strong-leg leave parts of that out.
 
 Prints ONE JSON line on rank 0.  `--dump-outputs DIR`: what the last timed step computed goes to DIR as .npy files (OutputSample), so that two
 builds can be compared output for output on the same inputs.
@@ -367,16 +370,18 @@ def main():
     ap.add_argument("--mode", default="weak", choices=["weak", "strong"])
     ap.add_argument("--group-bp", type=int, default=32 << 20, help="contigs are resident together (one walk chain, launches across contigs) up to this many bases")
     ap.add_argument("--ion", action="store_true", help="BASELINE configs[4] flags (Ion Torrent flow model, 400 bp SE, 50x) instead of 2x150 Illumina")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the host_landed / end_to_end legs")
-    ap.add_argument("--no-genome-leg", action="store_true", help="skip the end_to_end_genome leg (dwgsim-hip on the whole S4 genome: about a minute, most of it making the synthetic FASTA)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the host_landed / end_to_end legs, the CPU baseline, the end_to_end_genome leg "
+                    "and the strong whole-genome line (a plain run only times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the host_landed / end_to_end legs")
+    ap.add_argument("--no-genome-leg", action="store_true", help="with --full: skip the end_to_end_genome leg (dwgsim-hip on the whole S4 genome: about a minute, most of it making the synthetic FASTA)")
     ap.add_argument("--flags", default=None, help="analysis only: override the dwgsim flags of the workload (the default is the BASELINE configuration)")
     ap.add_argument("--phases", action="store_true", help="analysis only: print the phase split of the -DDW_PHASE_TIMING build (DWGSIM_HIP_LIB=dwgsim_amd/libdwgsim_hip_phases.so)")
     ap.add_argument("--depth", type=int, default=3, help="how many steps ahead the walks run (contigs resident depth + 2 times)")
     ap.add_argument("--no-carry", action="store_true", help="every step waits for its own launches before the next step's first launch is enqueued (the form of rounds 3-4)")
     ap.add_argument("--no-pipeline", action="store_true", help="every step prepares itself (walk, random-read count, exchange) before its first launch, on one resident copy of the contigs")
     ap.add_argument("--share-gpu", action="store_true", help="analysis only: several ranks on one GPU (1-GPU box)")
-    ap.add_argument("--strong-leg", action="store_true", help="also measure the fixed whole-genome job (BASELINE configs[3]) split over the ranks: the `strong` object of the line (default with --gpus > 1, and at N = 1 unless --no-legs)")
+    ap.add_argument("--strong-leg", action="store_true", help="also measure the fixed whole-genome job (BASELINE configs[3]) split over the ranks: the `strong` object of the line (default with --full: at --gpus > 1, and at N = 1 unless --no-legs)")
     ap.add_argument("--no-strong-leg", action="store_true")
     ap.add_argument("--world", type=int, default=0, help="with --solo-rank: the world size W of the run this process plays one rank of")
     ap.add_argument("--solo-rank", type=int, default=None, help="run ALONE, on this one GPU, exactly what rank r of a --world W run does on its GPU: its walks, its random-read counts, its batches; "
@@ -388,7 +393,8 @@ def main():
     solo = args.solo_rank is not None or args.solo_sweep is not None
     if args.solo_rank is not None and not (0 <= args.solo_rank < max(args.world, 1)):
         raise SystemExit("bench.py: --solo-rank r needs --world W with 0 <= r < W")
-    args.strong_leg = (args.strong_leg or args.gpus > 1 or not args.no_legs) and not args.no_strong_leg      # (N = 1 carries it too: the curve's efficiency is taken against that line)
+    legs = args.full and not args.no_legs
+    args.strong_leg = (args.strong_leg or (args.full and (args.gpus > 1 or not args.no_legs))) and not args.no_strong_leg      # (N = 1 carries it too: the curve's efficiency is taken against that line)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks (one process per GPU) ourselves
@@ -671,7 +677,7 @@ def main():
     landed = {}
     printer = rank == 0 or args.solo_rank is not None
     n_gpus = 1 if args.solo_rank is not None else world
-    if world == 1 and not args.no_legs:      # (the legs that need the resident contig: before the context makes room for the whole-genome job)
+    if world == 1 and legs:      # (the legs that need the resident contig: before the context makes room for the whole-genome job)
         g0 = max(groups, key=lambda g: g["pairs"])
         cid0, n0 = max(g0["members"], key=lambda mm: mm[1])          # the contig with the most pairs
         ctx.mutate(cid0)
@@ -757,15 +763,15 @@ def main():
         if ctx is not None:
             ctx.close(); ctx = None
         small = [(name, arr) for name, arr, _, _ in job]
-        if world == 1 and not args.no_legs and args.workload in ("ecoli", "chr20", "ecoli_like", "chr20_like"):
+        if world == 1 and legs and args.workload in ("ecoli", "chr20", "ecoli_like", "chr20_like"):
             out["end_to_end"] = end_to_end_leg(small, flags, job_pairs)
             cpu_gz = end_to_end_leg(small, flags, job_pairs, "cpu")
             if cpu_gz and "seconds" in cpu_gz:
                 out["end_to_end"]["with_zlib_on_host"] = {k: cpu_gz[k] for k in ("seconds", "value", "gz_bytes", "gzip")}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             base_contigs = small[:1] if len(small) == 1 else [c for c in small if c[0] == "chr20"] or small[:1]      # (whole-genome jobs: the chr20-sized contig)
             out["cpu_baseline"] = cpu_baseline(base_contigs, flags)
-        if world == 1 and not args.no_legs and not args.no_genome_leg and not args.ion and args.flags is None:
+        if world == 1 and legs and not args.no_genome_leg and not args.ion and args.flags is None:
             # steady state of the product: dwgsim-hip on the whole S4 genome (BASELINE configs[3] on one GPU), FASTA streamed through its .fai,
             # 325 M pairs, 232 GB of text -> 115 GB of gzip members landed in host memory and counted (they would not fit a tmpfs)
             g38 = small if args.workload == "grch38" else synth.workload_contigs("grch38")
