@@ -85,6 +85,8 @@ struct DevBuf {                     // grow-only device buffer
     void *p = nullptr; size_t cap = 0;
 };
 
+struct HostBuf { void *p = nullptr; size_t cap = 0; };      // grow-only page-locked host buffer (ensure_host)
+
 constexpr int N_COUNTERS = 32;      // u64 words of a counter block (SimArgs::counters)
 
 struct Slot {                       // one of the two batches a context can have in flight
@@ -94,7 +96,7 @@ struct Slot {                       // one of the two batches a context can have
     int group = -1;                 // the group the batch in flight reads
     uint64_t n_pairs = 0, out_bytes[3] = {0, 0, 0}, gz_bytes[3] = {0, 0, 0};
     DevBuf gz_out[3], gz_status, segs;        // GPU gzip: the members of each stream, look-back words; the range table of the launch
-    SimSeg *h_segs = nullptr; size_t h_segs_cap = 0;      // ... and its page-locked source
+    HostBuf h_segs;                           // ... and its page-locked source
     std::vector<dwgsim_hip_range_t> ranges;      // what the batch in flight covers (it is enqueued again, with larger read buffers, when an Ion Torrent read outgrew them)
     uint64_t *d_rerun_chain = nullptr;           // [2]: the chain words such a second run starts from
     int cap_mult = 1;                            // the context's flow_cap_mult this batch was enqueued with
@@ -129,9 +131,8 @@ struct dwgsim_hip_ctx {
     DevBuf w_slots, w_slot_aux;      // the site scan's per-block slots (dw_walk.hip k_site_scan_slots) and their counts / bases
     int site_slots = -1; int64_t site_slot_cap = -1;      // "site_slots": -1 choose, 0 the look-back form, 1 the slot form; "site_slot_cap": a slot size to start from (tests: the overflow re-run)
     DevBuf scratch_mask, scratch_cnt, scratch_status, w_cand, w_ev, w_flags, w_lo, w_sufmin, w_bound, w_ppos, w_pcells, up_ascii, l_pos, l_cells, place_segs, place_rand, place_list, place_aux;
-    uint8_t *h_up = nullptr; size_t h_up_cap = 0; hipEvent_t ev_up = nullptr; bool up_in_flight = false;      // page-locked staging of a group's sequence
-    SimSeg *h_place_segs = nullptr; size_t h_place_segs_cap = 0;
-    uint64_t *h_range_rand = nullptr; size_t h_range_rand_cap = 0;      // page-locked: count_random's result per range
+    HostBuf h_up; hipEvent_t ev_up = nullptr; bool up_in_flight = false;      // page-locked staging of a group's sequence
+    HostBuf h_place_segs, h_range_rand;      // page-locked: count_random's range table and its result per range
     std::vector<int32_t> h_ppos; std::vector<uint16_t> h_pcells; std::vector<Event> h_pev;      // file-driven mutations of the group being walked
     bool seq_justify = false, dense_view = false;      // "justify_seq", "dense_view": the cross-check forms of the walk (one thread justifies a whole group; the views are made from every cell)
     MutInput mutin; bool has_mutin = false;                             // -m / -b / -v
@@ -152,7 +153,7 @@ struct dwgsim_hip_ctx {
     int64_t sim_form = 0;                  // dwgsim_hip_debug_get("sim_form"): the k_simulate form of the last launch
     hipEvent_t ev_cnt0 = nullptr, ev_cnt1 = nullptr;
     bool gzip_on = false; uint32_t *d_crc_table = nullptr, *d_crc_shift = nullptr;      // dwgsim_hip_set_gzip
-    void *h_stage = nullptr; size_t h_stage_cap = 0;   // pinned staging for fetch
+    HostBuf h_stage;                       // pinned staging for fetch
     std::string txt, vcf;
 };
 
@@ -185,6 +186,19 @@ int ensure(dwgsim_hip_ctx *c, DevBuf &b, size_t bytes)
     b.cap = want;
     return 0;
 }
+
+// page-locked: room for `bytes`, else a new buffer of `want` (each site has its growth rule and first waits for what may read the old one)
+int ensure_host(dwgsim_hip_ctx *c, HostBuf &b, size_t bytes, size_t want)
+{
+    if (bytes <= b.cap) return 0;
+    if (b.p) HIPC(c, hipHostFree(b.p));
+    b.p = nullptr; b.cap = 0;
+    HIPC(c, hipHostMalloc(&b.p, want, hipHostMallocDefault));
+    b.cap = want;
+    return 0;
+}
+
+void free_host(HostBuf &b) { if (b.p) hipHostFree(b.p); b = HostBuf(); }
 
 uint8_t nt4(int ch)      // dwgsim.c:56-73
 {
@@ -402,8 +416,7 @@ int64_t dwgsim_hip_group_layout(const int64_t *lens, int n, int64_t *starts)
 // flow of a given base (about 2.5 for the usual 32-flow orders, 1.5 for TACG, but 15 for an order that keeps three bases away for 37 flows).  The
 // mean growth is g = m e / (1 - e) per base, with the cascade 1 / (1 - g); two and a half times that (m is taken as at least 3, twice what the
 // usual orders have) plus slack keeps overflow out of reach for realistic error rates -- and what does overflow is run again with twice the room
-// (dwgsim_hip_wait), never written out of bounds.  The room is LDS (dw_read.hpp flow_errors: one in-place buffer of cap / 4 bytes per lane), so it is
-// not handed out as generously as rounds 1-4 did with global scratch (len + 64 + 4 len g).
+// (dwgsim_hip_wait), never written out of bounds.  The room is LDS (dw_read.hpp flow_errors: one in-place buffer of cap / 4 bytes per lane), spent sparingly.
 static int flow_read_capacity(int len, double e, const std::vector<uint8_t> &flow)
 {
     const double ec = !(e > 0) ? 0 : e > 0.9 ? 0.9 : e;       // (NaN, e.g. -B with -e 0: no flow errors at all)
@@ -418,6 +431,14 @@ static int flow_read_capacity(int len, double e, const std::vector<uint8_t> &flo
     double g = m * ec / (1.0 - ec);
     g = g / (1.0 - (g < 0.75 ? g : 0.75));
     return len + 32 + (int)(len * 2.5 * g);
+}
+
+// Ion Torrent: the read capacity of a job before flow_cap_mult -- "flow_cap" (tests), or flow_read_capacity of the longer read end at the larger error rate
+static int flow_base_capacity(const dwgsim_hip_ctx *c)
+{
+    const int lmax = c->prm.length[0] > c->prm.length[1] ? c->prm.length[0] : c->prm.length[1];
+    const double emax = c->prm.e_start[0] > c->prm.e_start[1] ? c->prm.e_start[0] : c->prm.e_start[1];
+    return c->flow_cap_forced > 0 ? c->flow_cap_forced : flow_read_capacity(lmax, emax, c->flow);
 }
 
 static int set_err(int *err, int v) { if (err) *err = v; return v; }
@@ -665,10 +686,7 @@ void dwgsim_hip_destroy(dwgsim_hip_ctx_t *c)
     hipFree(c->d_rand_fixed); hipFree(c->d_counters); hipFree(c->d_wcounters); hipFree(c->d_pcounters); hipFree(c->d_flow); hipFree(c->d_chain); hipFree(c->d_crc_table); hipFree(c->d_crc_shift);
     if (c->h_counters) hipHostFree(c->h_counters);
     if (c->h_pcounters) hipHostFree(c->h_pcounters);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    if (c->h_up) hipHostFree(c->h_up);
-    if (c->h_place_segs) hipHostFree(c->h_place_segs);
-    if (c->h_range_rand) hipHostFree(c->h_range_rand);
+    for (HostBuf *b : {&c->h_stage, &c->h_up, &c->h_place_segs, &c->h_range_rand}) free_host(*b);
     if (c->ev_up) hipEventDestroy(c->ev_up);
     if (c->ev_cnt0) hipEventDestroy(c->ev_cnt0);
     if (c->ev_cnt1) hipEventDestroy(c->ev_cnt1);
@@ -676,7 +694,7 @@ void dwgsim_hip_destroy(dwgsim_hip_ctx_t *c)
         hipFree(sl.d_counters); hipFree(sl.d_rerun_chain); hipFree(sl.gz_status.p); hipFree(sl.segs.p);
         for (int t = 0; t < 3; ++t) hipFree(sl.gz_out[t].p);
         if (sl.h_counters) hipHostFree(sl.h_counters);
-        if (sl.h_segs) hipHostFree(sl.h_segs);
+        free_host(sl.h_segs);
         for (hipEvent_t e : {sl.ev_k0, sl.ev_k1, sl.ev_end, sl.ev_done, sl.ev_fetched}) if (e) hipEventDestroy(e);
     }
     if (c->copy_stream) hipStreamDestroy(c->copy_stream);
@@ -769,19 +787,14 @@ int dwgsim_hip_add_contigs(dwgsim_hip_ctx_t *c, int n, const char *const *names,
             for (int k = 0; k < n; ++k) if (lens[k] > 0) HIPC(c, hipMemcpyAsync(d_ascii + starts[(size_t)k], ascii[k], (size_t)lens[k], hipMemcpyHostToDevice, c->walk_stream));
         } else {
             if (c->up_in_flight) { HIPC(c, hipEventSynchronize(c->ev_up)); c->up_in_flight = false; }
-            if ((size_t)total > c->h_up_cap) {
-                if (c->h_up) HIPC(c, hipHostFree(c->h_up));
-                c->h_up = nullptr; c->h_up_cap = 0;
-                const size_t want = (size_t)total + (size_t)total / 4 + 4096;
-                HIPC(c, hipHostMalloc((void **)&c->h_up, want, hipHostMallocDefault));
-                c->h_up_cap = want;
-            }
+            if (const int rc = ensure_host(c, c->h_up, (size_t)total, (size_t)total + (size_t)total / 4 + 4096)) return rc;
+            uint8_t *h_up = (uint8_t *)c->h_up.p;
             for (int k = 0; k < n; ++k) {
                 const int64_t end = starts[(size_t)k] + lens[k], next = k + 1 < n ? starts[(size_t)k + 1] : total;
-                if (lens[k] > 0) memcpy(c->h_up + starts[(size_t)k], ascii[k], (size_t)lens[k]);
-                memset(c->h_up + end, 0, (size_t)(next - end));
+                if (lens[k] > 0) memcpy(h_up + starts[(size_t)k], ascii[k], (size_t)lens[k]);
+                memset(h_up + end, 0, (size_t)(next - end));
             }
-            HIPC(c, hipMemcpyAsync(d_ascii, c->h_up, (size_t)total, hipMemcpyHostToDevice, c->walk_stream));
+            HIPC(c, hipMemcpyAsync(d_ascii, h_up, (size_t)total, hipMemcpyHostToDevice, c->walk_stream));
             HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream));
             HIPC(c, hipEventRecord(c->ev_up, c->walk_stream)); c->up_in_flight = true;
         }
@@ -936,6 +949,21 @@ static int mut_debug_verdict(dwgsim_hip_ctx_t *c, const Group &g, uint64_t pre, 
     return DWGSIM_HIP_ERR_FAILED;
 }
 
+// The insertion tables of haplotype h of a group: room for `entries` entries (+ 25 % + 64) and `bases` inserted bases (+ 25 % + 256)
+static int ensure_ins(dwgsim_hip_ctx_t *c, Group &g, int h, size_t entries, size_t bases)
+{
+    if (entries > g.cap_ins[h]) {
+        hipFree(g.d_ins_pos[h]); hipFree(g.d_ins_len[h]); hipFree(g.d_ins_off[h]);
+        g.d_ins_pos[h] = nullptr; g.d_ins_len[h] = g.d_ins_off[h] = nullptr;
+        g.cap_ins[h] = entries + entries / 4 + 64;
+        HIPC(c, hipMalloc((void **)&g.d_ins_pos[h], sizeof(int32_t) * g.cap_ins[h]));
+        HIPC(c, hipMalloc((void **)&g.d_ins_len[h], sizeof(uint32_t) * g.cap_ins[h]));
+        HIPC(c, hipMalloc((void **)&g.d_ins_off[h], sizeof(uint32_t) * g.cap_ins[h]));
+    }
+    if (bases > g.cap_bases[h]) { hipFree(g.d_ins_bases[h]); g.d_ins_bases[h] = nullptr; g.cap_bases[h] = bases + bases / 4 + 256; HIPC(c, hipMalloc((void **)&g.d_ins_bases[h], g.cap_bases[h] + 16)); }
+    return DWGSIM_HIP_OK;
+}
+
 // One attempt of the walk of a whole group, enqueued on the walk stream without any host read-back in between: buffers are sized for a
 // capacity (candidate sites are a Binomial(l, mut_rate) draw: mean + 8 sigma), the kernels take their element counts from device memory, and
 // the read-back at the end (dwgsim_hip_mutate_wait) also tells whether a capacity was exceeded -- then the walk is simply run again with
@@ -999,21 +1027,8 @@ static int enqueue_walk(dwgsim_hip_ctx_t *c, Group &g)
         ensure(c, c->w_flags, sizeof(uint4) * (ncap + 64)) ||      // (+ 64 rows / entries: the segment totals of k_scan4, the segment minima of k_sufmin)
         ensure(c, c->w_lo, sizeof(int32_t) * ncap) || ensure(c, c->w_sufmin, sizeof(int32_t) * (ncap + 64)) ||
         ensure(c, c->w_bound, ncap)) return DWGSIM_HIP_ERR_DEVICE;
-    for (int h = 0; h < 2; ++h) {      // insertion tables: at most one entry per candidate; the base pools are checked on the device
-        if (ncap > g.cap_ins[h]) {
-            hipFree(g.d_ins_pos[h]); hipFree(g.d_ins_len[h]); hipFree(g.d_ins_off[h]);
-            g.d_ins_pos[h] = nullptr; g.d_ins_len[h] = g.d_ins_off[h] = nullptr;
-            g.cap_ins[h] = ncap + ncap / 4 + 64;
-            HIPC(c, hipMalloc((void **)&g.d_ins_pos[h], sizeof(int32_t) * g.cap_ins[h]));
-            HIPC(c, hipMalloc((void **)&g.d_ins_len[h], sizeof(uint32_t) * g.cap_ins[h]));
-            HIPC(c, hipMalloc((void **)&g.d_ins_off[h], sizeof(uint32_t) * g.cap_ins[h]));
-        }
-        if (cap_bases > g.cap_bases[h]) {
-            hipFree(g.d_ins_bases[h]); g.d_ins_bases[h] = nullptr;
-            g.cap_bases[h] = cap_bases + cap_bases / 4 + 256;
-            HIPC(c, hipMalloc((void **)&g.d_ins_bases[h], g.cap_bases[h] + 16));
-        }
-    }
+    // insertion tables: at most one entry per candidate; the base pools are checked on the device
+    for (int h = 0; h < 2; ++h) if (const int rc = ensure_ins(c, g, h, ncap, cap_bases)) return rc;
     int32_t *d_cand = (int32_t *)c->w_cand.p; Event *d_ev = (Event *)c->w_ev.p; uint4 *d_flags = (uint4 *)c->w_flags.p;
     uint32_t *d_small = reinterpret_cast<uint32_t *>(&c->d_wcounters[8]);   // [0] max_del, [1..4] tot4: eight words in counters[8..11], so that one copy brings counters[7..11] back
     const Count nc{&c->d_wcounters[7], cap};
@@ -1100,16 +1115,7 @@ int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
         for (int h = 0; h < 2; ++h) {
             const size_t n = hi[h].pos.size(), nb = hi[h].bases.size();
             g.n_ins[h] = (uint32_t)n; g.n_ins_bases[h] = (uint32_t)nb;
-            const size_t nn = n ? n : 1, nbb = nb ? nb : 1;
-            if (nn > g.cap_ins[h]) {
-                hipFree(g.d_ins_pos[h]); hipFree(g.d_ins_len[h]); hipFree(g.d_ins_off[h]);
-                g.d_ins_pos[h] = nullptr; g.d_ins_len[h] = g.d_ins_off[h] = nullptr;
-                g.cap_ins[h] = nn + nn / 4 + 64;
-                HIPC(c, hipMalloc((void **)&g.d_ins_pos[h], sizeof(int32_t) * g.cap_ins[h]));
-                HIPC(c, hipMalloc((void **)&g.d_ins_len[h], sizeof(uint32_t) * g.cap_ins[h]));
-                HIPC(c, hipMalloc((void **)&g.d_ins_off[h], sizeof(uint32_t) * g.cap_ins[h]));
-            }
-            if (nbb > g.cap_bases[h]) { hipFree(g.d_ins_bases[h]); g.d_ins_bases[h] = nullptr; g.cap_bases[h] = nbb + nbb / 4 + 256; HIPC(c, hipMalloc((void **)&g.d_ins_bases[h], g.cap_bases[h] + 16)); }
+            if (const int rc = ensure_ins(c, g, h, n ? n : 1, nb ? nb : 1)) return rc;
             if (n) {
                 HIPC(c, hipMemcpy(g.d_ins_pos[h], hi[h].pos.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
                 HIPC(c, hipMemcpy(g.d_ins_len[h], hi[h].len.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
@@ -1379,12 +1385,27 @@ int dwgsim_hip_mutlist_text(dwgsim_hip_mutlist_t *L, int k, const char **txt, si
 void dwgsim_hip_mutlist_free(dwgsim_hip_mutlist_t *L) { delete L; }
 
 // ---- read simulation ----
+namespace {
+// One launch over a list of ranges (sim_resolve): form, group, range table with its pairs, blocks and longest "[prefix_]name", arguments
+struct Launch { SimForm f; SimArgs a; Group *g = nullptr; std::vector<SimSeg> segs; uint64_t n_pairs = 0; uint32_t nblk = 0; int fixed_max = 0; };
+// The sizes of one k_simulate launch besides its arguments (sim_plan), in bytes -- 0: the launch does not use that buffer -- and what follows from them
+struct SimPlan {
+    size_t cap[3];                        // record capacity of each stream (0: not written); its text buffer holds 64 bytes more
+    int32_t lb_shift; bool too_many;      // SimArgs::lb_shift; the launch's sums would not fit the look-back word of the single Illumina / SOLiD kernel
+    size_t block_rand, status, meta, fail_summ, split_state, split_hand, split_agg, split_pre, split_chunk;      // (split_*: what the first half of the two-kernel form hands to the second)
+    bool scratch; int32_t flow_slots; size_t flow_scratch, flow_free;      // scratch slots: in use, per XCD, the slots, their free lists
+    size_t segs, gz_chunks[3], gz_cap[3], gz_status;      // the range table; GPU gzip: chunks and member capacity of each stream, the look-back words of all
+};
+struct ChainSet { uint64_t *words; int set_rand, set_carry; uint64_t carry; };      // where a launch's running values come from (launch_init / launch_chain_set)
+}
+
 // The ranges of one launch: all of one walked group, in file order.  ppb = pairs per block of the kernel that will run.
-static int build_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t ppb, Group **gout, std::vector<SimSeg> &segs, uint64_t *n_pairs, uint32_t *n_blocks, int *fixed_max)
+static int build_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t ppb, Launch &L)
 {
     if (!r || n < 1) { c->err = "bad range arguments"; return DWGSIM_HIP_ERR_ARG; }
     Group *g = nullptr;
     uint64_t pairs = 0, blocks = 0; int fmax = 0;
+    std::vector<SimSeg> &segs = L.segs;
     segs.clear();
     for (int q = 0; q < n; ++q) {
         int k = 0;
@@ -1406,7 +1427,7 @@ static int build_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n,
         if (blocks > 0x7fffffffull) { c->err = "too many pairs in one call"; return DWGSIM_HIP_ERR_ARG; }
     }
     if (!g->mutated || g->walk_pending) { c->err = "mutate_contig must run first"; return DWGSIM_HIP_ERR_STATE; }
-    *gout = g; *n_pairs = pairs; *n_blocks = (uint32_t)blocks; *fixed_max = fmax;
+    L.g = g; L.n_pairs = pairs; L.nblk = (uint32_t)blocks; L.fixed_max = fmax;
     return DWGSIM_HIP_OK;
 }
 
@@ -1448,8 +1469,7 @@ static int sim_form(dwgsim_hip_ctx_t *c, SimForm &f)
         }
     }
     if (p.data_type == 2) {        // room for flow-space insertions: ~2.4 empty flows per base, each inserting with probability e, plus cascades
-        const double emax = p.e_start[0] > p.e_start[1] ? p.e_start[0] : p.e_start[1];
-        f.cap = (c->flow_cap_forced > 0 ? std::max(c->flow_cap_forced, lmax) : flow_read_capacity(lmax, emax, c->flow)) * c->flow_cap_mult;      // (the read as extracted must fit: a forced capacity is a test's starting point, never below the read length)
+        f.cap = std::max(flow_base_capacity(c), lmax) * c->flow_cap_mult;      // (the read as extracted must fit: a forced capacity is a test's starting point, never below the read length)
         // the flow model's one in-place buffer per lane, 2 bits per base (dw_read.hpp flow_errors), and the run stack of its pass 2.  In LDS while at
         // least two 256-lane blocks -- or else four one-wave blocks -- fit a CU; beyond that (very long reads, error rates at which reads grow
         // severalfold) in scratch slots of global memory ("ion_lds": 0 slots, 1 / 2 LDS with 256 / 64 lanes, -1 choose)
@@ -1463,11 +1483,10 @@ static int sim_form(dwgsim_hip_ctx_t *c, SimForm &f)
         f.dt = mode != 0 ? 3 : 2; f.nthr = mode == 2 ? ION_THREADS_SMALL : SIM_THREADS;
     }
     // Short Illumina reads run as two kernels with the offsets computed in between (dw_simulate.hip SPLIT): no look-backs, and the second half --
-    // no staged bases in LDS -- writes the text in 64-byte bursts.  What does not scale with the read length (placement, the look-backs, the name)
-    // is most of the work there: 2 x 36 / 2 x 50 / 2 x 75 bp and 100 bp single-end run 16 / 17 / 9 / 15 % faster than in the single kernel, 2 x 100
-    // the same, 2 x 150 2-3 % slower (the state crosses HBM, 2.5 GB per chr20-sized launch): profiles/r04_split.txt.  "split" = 0 / 1 forces either.
-    // Round 6, the single kernel with ONE look-back (dw_simulate.hip ONE_LB), re-measured (profiles/r06_bench_lines_final.txt 14): 2 x 36 bp +5.5 % as two kernels, 2 x 50 +0.8 %, 2 x 75
-    // -3 %, 2 x 100 -10 %, 100 bp single-end -9 %, 2 x 150 -12 %: the cut moves from 100 bases to 50.
+    // no staged bases in LDS -- writes the text in 64-byte bursts: what does not scale with the read length (placement, the look-backs, the name) is most of the
+    // work of short reads.  Against the single kernel with ONE look-back (dw_simulate.hip ONE_LB; profiles/r06_bench_lines_final.txt 14): 2 x 36 bp +5.5 % as
+    // two kernels, 2 x 50 +0.8 %, 2 x 75 -3 %, 2 x 100 -10 %, 100 bp single-end -9 %, 2 x 150 -12 %.  "split" = 0 / 1 forces either.
+    // (The cut at 100 bases of rounds 4-5 and their rule for small launches: DESIGN.md §4, k_simulate.)
     const bool split_wins = lmax <= 50;
     f.split = (p.data_type == 0 && f.nthr == SIM_THREADS && (c->split < 0 ? split_wins : c->split != 0)) ? 1 : 0;
     // Ion Torrent with its buffers in LDS: as two kernels as well (the flow model | qualities + text).  The first half holds no text FIFOs, so a fourth
@@ -1483,9 +1502,9 @@ static int sim_form(dwgsim_hip_ctx_t *c, SimForm &f)
     return 0;
 }
 
-static int fill_sim_args(dwgsim_hip_ctx_t *c, Group &g, SimArgs &a, SimForm &f)
+// The arguments of a launch of form f over group g that do not depend on its ranges (sim_plan and the enqueue step add those)
+static void fill_sim_args(const dwgsim_hip_ctx_t *c, const Group &g, const SimForm &f, SimArgs &a)
 {
-    if (const int rc = sim_form(c, f)) return rc;
     const dwgsim_hip_params_t &p = c->prm;
     memset(&a, 0, sizeof a);
     a.p.std_dev = p.std_dev; a.p.mut_freq = p.mut_freq; a.p.rand_read = p.rand_read; a.p.quality_std = p.quality_std;
@@ -1525,7 +1544,18 @@ static int fill_sim_args(dwgsim_hip_ctx_t *c, Group &g, SimArgs &a, SimForm &f)
         const double e0 = c->prm.e_start[j];
         flow_gap_params(!(e0 > 0) ? 0 : e0 >= 1.0 ? 0x100000000ull : (uint64_t)ceil(e0 * 4294967296.0), &a.flow_gap_r[j], &a.flow_gap_s[j]);
     }
-    return 0;
+}
+
+// The resolve step of a k_simulate launch, in a fixed order: the group of r[0] is known, the form, the range table laid out for the form's pairs per
+// block, the arguments for the table's group (r[0]'s: build_ranges refuses ranges of two groups).
+static int sim_resolve(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, Launch &L)
+{
+    if (!r || n < 1) { c->err = "bad range arguments"; return DWGSIM_HIP_ERR_ARG; }
+    if (!get_group(c, r[0].contig)) return DWGSIM_HIP_ERR_ARG;
+    if (const int rc = sim_form(c, L.f)) return rc;
+    if (const int rc = build_ranges(c, r, n, (uint64_t)(L.f.nthr / L.f.lpp), L)) return rc;
+    fill_sim_args(c, *L.g, L.f, L.a);
+    return DWGSIM_HIP_OK;
 }
 
 int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t *n_random, uint64_t *per_range)
@@ -1533,33 +1563,29 @@ int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t
     if (!c) return DWGSIM_HIP_ERR_ARG;
     if (n_random) *n_random = 0;
     if (per_range) for (int q = 0; q < n; ++q) per_range[q] = 0;
-    Group *gp = nullptr; std::vector<SimSeg> segs; uint64_t n_pairs = 0; uint32_t n_blocks = 0; int fixed_max = 0;
-    if (const int rc = build_ranges(c, r, n, PLACE_PAIRS, &gp, segs, &n_pairs, &n_blocks, &fixed_max)) return rc;
+    // the resolve step of sim_resolve in the count's order: k_place's range table does not depend on the form, so bad ranges are reported first, a
+    // count without pairs is no error, and the form is taken behind the group's walk
+    Launch L;
+    if (const int rc = build_ranges(c, r, n, PLACE_PAIRS, L)) return rc;
+    const uint64_t n_pairs = L.n_pairs; const uint32_t n_blocks = L.nblk;
     if (n_pairs == 0) return DWGSIM_HIP_OK;
-    Group &g = *gp;
+    Group &g = *L.g;
     HIPC(c, hipSetDevice(c->device));
     hipStream_t st = c->count_stream;     // (the count of one group can run while batches of another -- or of this one -- are being simulated)
     // (the haplotype summaries k_place reads -- per 64 and per 1024 cells -- were written with the read views at the end of the walk: the count follows
     // its group's walk by that walk's event, whatever else has been put on the walk stream since)
     if (g.walk_pending) { if (const int rc = dwgsim_hip_mutate_wait(c, g.first_handle)) return rc; }      // (a walk that exceeded a capacity is run again inside the wait: only then are the summaries final)
     if (g.ev_walk && g.mutated) HIPC(c, hipStreamWaitEvent(st, g.ev_walk, 0));
-    SimArgs a; SimForm f;
-    if (const int rc = fill_sim_args(c, g, a, f)) return rc;
-    const size_t ns = segs.size();
-    if (ensure(c, c->place_rand, sizeof(uint32_t) * ((size_t)n_blocks + 1))) return DWGSIM_HIP_ERR_DEVICE;
-    if (ensure(c, c->place_segs, sizeof(SimSeg) * ns)) return DWGSIM_HIP_ERR_DEVICE;
-    if (ensure(c, c->place_aux, PLACE_LISTS * 16 * sizeof(uint32_t) + sizeof(uint64_t) * ns)) return DWGSIM_HIP_ERR_DEVICE;
-    if (ns > c->h_place_segs_cap || ns > c->h_range_rand_cap) {
-        HIPC(c, hipStreamSynchronize(st));
-        if (c->h_place_segs) HIPC(c, hipHostFree(c->h_place_segs));
-        if (c->h_range_rand) HIPC(c, hipHostFree(c->h_range_rand));
-        c->h_place_segs = nullptr; c->h_range_rand = nullptr; c->h_place_segs_cap = c->h_range_rand_cap = 0;
-        HIPC(c, hipHostMalloc((void **)&c->h_place_segs, sizeof(SimSeg) * (ns + 64), hipHostMallocDefault));
-        HIPC(c, hipHostMalloc((void **)&c->h_range_rand, sizeof(uint64_t) * (ns + 64), hipHostMallocDefault));
-        c->h_place_segs_cap = c->h_range_rand_cap = ns + 64;
-    }
-    memcpy(c->h_place_segs, segs.data(), sizeof(SimSeg) * ns);
-    HIPC(c, hipMemcpyAsync(c->place_segs.p, c->h_place_segs, sizeof(SimSeg) * ns, hipMemcpyHostToDevice, st));
+    if (const int rc = sim_form(c, L.f)) return rc;
+    SimArgs &a = L.a; fill_sim_args(c, g, L.f, a);
+    const size_t ns = L.segs.size();
+    if (ensure(c, c->place_rand, sizeof(uint32_t) * ((size_t)n_blocks + 1)) || ensure(c, c->place_segs, sizeof(SimSeg) * ns) ||
+        ensure(c, c->place_aux, PLACE_LISTS * 16 * sizeof(uint32_t) + sizeof(uint64_t) * ns)) return DWGSIM_HIP_ERR_DEVICE;
+    if (sizeof(SimSeg) * ns > c->h_place_segs.cap || sizeof(uint64_t) * ns > c->h_range_rand.cap) HIPC(c, hipStreamSynchronize(st));      // (before the page-locked pair is replaced)
+    if (ensure_host(c, c->h_place_segs, sizeof(SimSeg) * ns, sizeof(SimSeg) * (ns + 64)) || ensure_host(c, c->h_range_rand, sizeof(uint64_t) * ns, sizeof(uint64_t) * (ns + 64))) return DWGSIM_HIP_ERR_DEVICE;
+    const uint64_t *h_range_rand = (const uint64_t *)c->h_range_rand.p;
+    memcpy(c->h_place_segs.p, L.segs.data(), sizeof(SimSeg) * ns);
+    HIPC(c, hipMemcpyAsync(c->place_segs.p, c->h_place_segs.p, sizeof(SimSeg) * ns, hipMemcpyHostToDevice, st));
     a.segs = (const SimSeg *)c->place_segs.p; a.n_seg = (int32_t)ns; a.n_blocks = n_blocks; a.n_pairs = n_pairs;
     a.block_rand = (uint32_t *)c->place_rand.p; a.counters = c->d_pcounters;
     // the lists of pairs k_place leaves open: room for an eighth of the pairs (the usual share is a per cent); if that does not do -- contigs
@@ -1579,7 +1605,7 @@ int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t
         HIPC(c, hipEventRecord(c->ev_cnt1, st));
         HIPC(c, hipGetLastError());
         HIPC(c, hipMemcpyAsync(c->h_pcounters, c->d_pcounters, N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIPC(c, hipMemcpyAsync(c->h_range_rand, a.range_rand, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
+        HIPC(c, hipMemcpyAsync(c->h_range_rand.p, a.range_rand, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
         HIPC(c, hipStreamSynchronize(st));
         { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_cnt0, c->ev_cnt1) == hipSuccess) c->count_us += 1e3 * ms; else (void)hipGetLastError(); }
         if (!(c->h_pcounters[2] & 16) || attempt > 0) break;
@@ -1588,13 +1614,8 @@ int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t
     if (c->h_pcounters[2] & 16) { c->err = "count_random: the list of undecided pairs overflowed twice"; return DWGSIM_HIP_ERR_FAILED; }
     if (c->h_pcounters[2]) { char b[128]; snprintf(b, sizeof b, "\r[dwgsim_core] failed to generate a read after %d trials\n", MAX_ATTEMPTS + 1); c->err = b; return DWGSIM_HIP_ERR_FAILED; }
     c->place_open = c->h_pcounters[5];
-    uint64_t total = 0; size_t si = 0;
-    for (int q = 0; q < n; ++q) {
-        if (r[q].n_pairs == 0) continue;
-        total += c->h_range_rand[si];
-        if (per_range) per_range[q] = c->h_range_rand[si];
-        ++si;
-    }
+    uint64_t total = 0;
+    for (int q = 0, si = 0; q < n; ++q) if (r[q].n_pairs) { total += h_range_rand[si]; if (per_range) per_range[q] = h_range_rand[si]; ++si; }
     if (n_random) *n_random = total;
     return DWGSIM_HIP_OK;
 }
@@ -1612,133 +1633,105 @@ int dwgsim_hip_set_fail_carry(dwgsim_hip_ctx_t *c, uint64_t carry)
     return DWGSIM_HIP_OK;
 }
 
-// Enqueue one batch on the compute stream: [chain set] -> memsets -> k_simulate -> abort-rule epilogue -> [k_gzip] -> counters to the slot's
-// pinned mirror -> event.  Every buffer the batch needs is in place before anything is enqueued or the chain state moves, so a failing call
-// leaves the context as it found it.
-// rerun: the batch of this slot once more with larger Ion Torrent read buffers (dwgsim_hip_wait).  Nothing of the chain moves: the random reads and
-// the failed attempts of a batch do not depend on the flow model, so the first run's epilogue stands; the kernels start from the chain words the
-// first run started from (rand_base = its counters[22]).
-static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t rand_base, int slot, bool rerun);
-int dwgsim_hip_simulate_ranges_async(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t rand_base, int slot)
+// The plan step: every size the launch needs, from its form, arguments and ranges.  No side effects.
+static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
 {
-    return sim_enqueue(c, r, n, rand_base, slot, false);
-}
-static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t rand_base, int slot, bool rerun)
-{
-    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS) { if (c) c->err = "bad simulate arguments"; return DWGSIM_HIP_ERR_ARG; }
-    Slot &sl = c->slot[slot];
-    if (sl.pending) { c->err = "simulate: the slot still holds a batch that was not waited for"; return DWGSIM_HIP_ERR_STATE; }
-    const dwgsim_hip_params_t &p = c->prm;
-    // lanes per block are a property of the options, so the range table can be laid out before the arguments are complete
-    Group *gp = nullptr; std::vector<SimSeg> segs; uint64_t n_pairs = 0; uint32_t nblk = 0; int fixed_max = 0;
-    SimArgs a; SimForm f;
-    {
-        // (fill_sim_args needs a group: take it from the first range)
-        Group *g0 = (r && n >= 1) ? get_group(c, r[0].contig) : nullptr;
-        if (!g0) { if (r && n >= 1) return DWGSIM_HIP_ERR_ARG; c->err = "bad range arguments"; return DWGSIM_HIP_ERR_ARG; }
-        if (const int rc = fill_sim_args(c, *g0, a, f)) return rc;
-    }
-    const uint64_t sim_ppb = (uint64_t)(f.nthr / f.lpp);      // pairs per k_simulate block
-    if (const int rc = build_ranges(c, r, n, sim_ppb, &gp, segs, &n_pairs, &nblk, &fixed_max)) return rc;
-    Group &g = *gp;
-    HIPC(c, hipSetDevice(c->device));
-    // (rounds 4-5: a SMALL launch -- up to ~3 rounds of resident blocks: the product's 2^18-pair batches, an E. coli-sized contig -- also ran as two kernels: the
-    // first round's three look-backs resolved one after the other, 2^17 / 2^18 / 2^19 pairs of 2 x 150 bp -5 / -11.5 / -2 %: profiles/r04_split.txt)
-    // (round 6: with one look-back the single kernel is level with the two-kernel form on launches this small too -- 2^17 / 2^18 / 2^19 pairs of 2 x 150 bp +4 / -3 / +9 %, an E. coli-sized
-    // contig +2.5 % -- and the rule is gone: profiles/r06_bench_lines_final.txt 14)
-    if (c->rand_fixed_len > fixed_max) fixed_max = c->rand_fixed_len;
+    const dwgsim_hip_params_t &p = c->prm; const SimForm &f = L.f;
+    const uint64_t n_pairs = L.n_pairs; const size_t nblk = L.nblk;
+    SimPlan P{};
     // upper bound of one FASTQ record (name tail: 2 positions <= 10 digits, 6 counters, 16 hex digits)
-    size_t cap[3] = {0, 0, 0};
-    for (int j = 0; j < 2; ++j) if (p.length[j] > 0) cap[j] = (size_t)n_pairs * (size_t)(1 + fixed_max + 120 + 3 + 2 * (p.data_type == 2 ? a.cap : p.length[j]) + 4);
-    {   // the one look-back word of the single Illumina kernel: 62 bits for the random reads and the bytes of stream 1 in front of a block
-        const uint64_t bytes0 = (uint64_t)cap[0] | 1ull;
-        int bw_bytes = 0, bw_pairs = 0;
-        while (bw_bytes < 63 && (bytes0 >> bw_bytes)) ++bw_bytes;
-        while (bw_pairs < 63 && ((uint64_t)n_pairs >> bw_pairs)) ++bw_pairs;
-        a.lb_shift = bw_bytes;
-        if (p.data_type != 2 && bw_bytes + bw_pairs > 62) { c->err = "too many pairs in one call"; return DWGSIM_HIP_ERR_ARG; }      // (Illumina and SOLiD; at 2 x 150 bp: more than 2^26 pairs)
+    const int fixed_max = std::max(L.fixed_max, c->rand_fixed_len);
+    for (int j = 0; j < 2; ++j) if (p.length[j] > 0) P.cap[j] = (size_t)n_pairs * (size_t)(1 + fixed_max + 120 + 3 + 2 * (p.data_type == 2 ? f.cap : p.length[j]) + 4);
+    // the one look-back word of the single Illumina kernel: 62 bits for the random reads and the bytes of stream 1 in front of a block
+    int bw_bytes = 0, bw_pairs = 0;
+    while (bw_bytes < 63 && (((uint64_t)P.cap[0] | 1ull) >> bw_bytes)) ++bw_bytes;
+    while (bw_pairs < 63 && (n_pairs >> bw_pairs)) ++bw_pairs;
+    P.lb_shift = bw_bytes; P.too_many = p.data_type != 2 && bw_bytes + bw_pairs > 62;      // (Illumina and SOLiD; at 2 x 150 bp: more than 2^26 pairs)
+    P.cap[2] = P.cap[0] + P.cap[1];
+    if (!L.a.p.has_bwa) P.cap[0] = P.cap[1] = 0;
+    if (!L.a.p.has_bfast) P.cap[2] = 0;
+    P.block_rand = sizeof(uint32_t) * nblk;
+    if (!f.split) P.status = 4 * sizeof(uint64_t) * nblk;      // the four look-back arrays, contiguous: one memset per batch
+    else { P.split_state = sizeof(uint32_t) * (size_t)f.lds_words * SIM_THREADS * nblk; P.split_hand = 16 * (size_t)SIM_THREADS * nblk; P.split_agg = 16 * nblk; P.split_pre = 32 * nblk; P.split_chunk = 32 * (nblk / 1024 + 1); }
+    P.meta = sizeof(uint32_t) * ((size_t)n_pairs + 8);      // (+ padding for 16-byte reads)
+    P.fail_summ = ((size_t)((n_pairs + 256ull * 64 - 1) / (256ull * 64)) * 4 + 2) * sizeof(uint64_t);
+    P.scratch = f.dt == 2 || (f.dt < 2 && f.nthr == SIM_THREADS_LONG);
+    if (P.scratch) {
+        // read buffers (Ion Torrent) / staged reads (one-wave blocks): one slot per block an XCD can hold at a time -- what the LDS admits per CU, at most the eight waves of a SIMD (registers can only
+        // lower it; too few slots would make blocks wait, never fail) --, handed from block to block inside the XCD (dw_simulate.hip scratch_slot_take)
+        const int cu_per_xcd = (c->n_cu >= 64 && c->n_cu % 8 == 0) ? c->n_cu / 8 : c->n_cu;
+        const bool ion = p.data_type == 2;
+        const int per_cu = sim_blocks_per_cu(f.lds, ion ? 8 : 32);       // (one-wave blocks: up to eight per SIMD)
+        P.flow_slots = c->flow_slots > 0 ? c->flow_slots : cu_per_xcd * per_cu;
+        if ((uint64_t)P.flow_slots > (uint64_t)nblk) P.flow_slots = (int32_t)nblk;
+        if (ion) {      // reads that have grown far beyond their estimate (capacity re-runs): fewer slots, at most 4 GB of them (blocks wait for a slot, they never fail for want of one)
+            const size_t slot_bytes = (size_t)flow_words_per_lane(f.lds_words) * (size_t)SIM_THREADS * sizeof(uint32_t);
+            const size_t fit = std::max<size_t>(1, ((size_t)4 << 30) / (slot_bytes * 8));
+            if ((size_t)P.flow_slots > fit) P.flow_slots = (int32_t)fit;
+        }
+        const size_t words = (ion ? (size_t)flow_words_per_lane(f.lds_words) * (size_t)SIM_THREADS : (size_t)f.lds_words * (size_t)SIM_THREADS_LONG) * (size_t)P.flow_slots * 8;
+        P.flow_scratch = words * sizeof(uint32_t); P.flow_free = sizeof(uint64_t) * (256 + 8 * nblk);
     }
-    cap[2] = cap[0] + cap[1];
-    if (!a.p.has_bwa) cap[0] = cap[1] = 0;
-    if (!a.p.has_bfast) cap[2] = 0;
-    if (n_pairs) {
-        // the slot's text may still be on its way to the host: wait for that before a buffer could be replaced
-        if (sl.fetch_in_flight) { HIPC(c, hipStreamWaitEvent(c->stream, sl.ev_fetched, 0)); bool grows = false; for (int t = 0; t < 3; ++t) if (cap[t] + 64 > c->out[slot][t].cap) grows = true; if (grows) HIPC(c, hipEventSynchronize(sl.ev_fetched)); sl.fetch_in_flight = false; }
-        for (int t = 0; t < 3; ++t) { if (ensure(c, c->out[slot][t], cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE; a.out[t] = (uint8_t *)c->out[slot][t].p; }
-        if (ensure(c, c->block_rand, sizeof(uint32_t) * (size_t)nblk)) return DWGSIM_HIP_ERR_DEVICE;
-        if (!a.split && ensure(c, c->status_all, 4 * sizeof(uint64_t) * (size_t)nblk)) return DWGSIM_HIP_ERR_DEVICE;      // the four look-back arrays, contiguous: one memset per batch
-        if (a.split) {      // what the first half hands to the second
-            if (ensure(c, c->split_state, sizeof(uint32_t) * (size_t)a.lds_words * SIM_THREADS * (size_t)nblk) || ensure(c, c->split_hand, 16 * (size_t)SIM_THREADS * (size_t)nblk) ||
-                ensure(c, c->split_agg, 16 * (size_t)nblk) || ensure(c, c->split_pre, 32 * (size_t)nblk) || ensure(c, c->split_chunk, 32 * ((size_t)nblk / 1024 + 1))) return DWGSIM_HIP_ERR_DEVICE;
-            a.split_state = (uint32_t *)c->split_state.p; a.split_hand = (uint32_t *)c->split_hand.p; a.split_agg = (uint32_t *)c->split_agg.p; a.split_pre = (uint64_t *)c->split_pre.p; a.split_chunk = (uint64_t *)c->split_chunk.p;
-        }
-        if (ensure(c, c->meta, sizeof(uint32_t) * ((size_t)n_pairs + 8))) return DWGSIM_HIP_ERR_DEVICE;      // (+ padding for 16-byte reads)
-        const size_t nfb = (size_t)((n_pairs + 256ull * 64 - 1) / (256ull * 64));
-        if (ensure(c, c->fail_summ, (nfb * 4 + 2) * sizeof(uint64_t))) return DWGSIM_HIP_ERR_DEVICE;
-        if (f.dt == 2 || (f.dt < 2 && f.nthr == SIM_THREADS_LONG)) {
-            // read buffers (Ion Torrent) / staged reads (one-wave blocks): one slot per block an XCD can hold at a time -- what the LDS admits per CU, at most the eight waves of a SIMD (registers can only
-            // lower it; too few slots would make blocks wait, never fail) --, handed from block to block inside the XCD (dw_simulate.hip scratch_slot_take)
-            const int cu_per_xcd = (c->n_cu >= 64 && c->n_cu % 8 == 0) ? c->n_cu / 8 : c->n_cu;
-            const bool ion = p.data_type == 2;
-            const int per_cu = sim_blocks_per_cu(f.lds, ion ? 8 : 32);       // (one-wave blocks: up to eight per SIMD)
-            a.flow_slots = c->flow_slots > 0 ? c->flow_slots : cu_per_xcd * per_cu;
-            if ((uint64_t)a.flow_slots > (uint64_t)nblk) a.flow_slots = (int32_t)nblk;
-            if (ion) {      // reads that have grown far beyond their estimate (capacity re-runs): fewer slots, at most 4 GB of them (blocks wait for a slot, they never fail for want of one)
-                const size_t slot_bytes = (size_t)flow_words_per_lane(a.lds_words) * (size_t)SIM_THREADS * sizeof(uint32_t);
-                const size_t fit = std::max<size_t>(1, ((size_t)4 << 30) / (slot_bytes * 8));
-                if ((size_t)a.flow_slots > fit) a.flow_slots = (int32_t)fit;
-            }
-            const size_t words = (ion ? (size_t)flow_words_per_lane(a.lds_words) * (size_t)SIM_THREADS : (size_t)a.lds_words * (size_t)SIM_THREADS_LONG) * (size_t)a.flow_slots * 8;
-            if (ensure(c, c->flow_scratch, words * sizeof(uint32_t)) || ensure(c, c->flow_free, sizeof(uint64_t) * (256 + 8 * (size_t)nblk))) return DWGSIM_HIP_ERR_DEVICE;
-            a.flow_scratch = (uint32_t *)c->flow_scratch.p; a.flow_free = (uint64_t *)c->flow_free.p;
-        }
-        if (ensure(c, sl.segs, sizeof(SimSeg) * segs.size())) return DWGSIM_HIP_ERR_DEVICE;
-        if (segs.size() > sl.h_segs_cap) {
-            if (sl.h_segs) HIPC(c, hipHostFree(sl.h_segs));
-            sl.h_segs = nullptr; sl.h_segs_cap = 0;
-            HIPC(c, hipHostMalloc((void **)&sl.h_segs, sizeof(SimSeg) * (segs.size() + 64), hipHostMallocDefault));
-            sl.h_segs_cap = segs.size() + 64;
-        }
-        if (c->gzip_on) {
-            size_t off = 0;
-            for (int t = 0; t < 3; ++t) { off += (size_t)gz_chunks(cap[t]); if (cap[t] && ensure(c, sl.gz_out[t], (size_t)gz_capacity(cap[t]) + 64)) return DWGSIM_HIP_ERR_DEVICE; }
-            if (ensure(c, sl.gz_status, sizeof(uint64_t) * (off ? off : 1))) return DWGSIM_HIP_ERR_DEVICE;
-        }
+    P.segs = sizeof(SimSeg) * L.segs.size();
+    if (c->gzip_on) {
+        size_t chunks = 0;
+        for (int t = 0; t < 3; ++t) { P.gz_chunks[t] = (size_t)gz_chunks(P.cap[t]); chunks += P.gz_chunks[t]; if (P.cap[t]) P.gz_cap[t] = (size_t)gz_capacity(P.cap[t]); }
+        P.gz_status = sizeof(uint64_t) * (chunks ? chunks : 1);
     }
-    // ---- nothing below fails for want of memory ----
-    for (int t = 0; t < 3; ++t) sl.out_bytes[t] = sl.gz_bytes[t] = 0;
-    sl.n_pairs = n_pairs; sl.empty = n_pairs == 0;
+    return P;
+}
+
+// The reserve step: every buffer grown to its plan (ensure of 0 bytes: nothing), after the wait for a copy of the slot's text still in flight
+static int sim_reserve(dwgsim_hip_ctx_t *c, int slot, const SimPlan &P)
+{
+    Slot &sl = c->slot[slot]; DevBuf *out = c->out[slot];
+    if (sl.fetch_in_flight) { HIPC(c, hipStreamWaitEvent(c->stream, sl.ev_fetched, 0)); bool grows = false; for (int t = 0; t < 3; ++t) if (P.cap[t] + 64 > out[t].cap) grows = true; if (grows) HIPC(c, hipEventSynchronize(sl.ev_fetched)); sl.fetch_in_flight = false; }
+    for (int t = 0; t < 3; ++t) if (ensure(c, out[t], P.cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE;
+    if (ensure(c, c->block_rand, P.block_rand) || ensure(c, c->status_all, P.status) ||
+        ensure(c, c->split_state, P.split_state) || ensure(c, c->split_hand, P.split_hand) || ensure(c, c->split_agg, P.split_agg) || ensure(c, c->split_pre, P.split_pre) || ensure(c, c->split_chunk, P.split_chunk) ||
+        ensure(c, c->meta, P.meta) || ensure(c, c->fail_summ, P.fail_summ) || ensure(c, c->flow_scratch, P.flow_scratch) || ensure(c, c->flow_free, P.flow_free) || ensure(c, sl.segs, P.segs) ||
+        ensure_host(c, sl.h_segs, P.segs, P.segs + 64 * sizeof(SimSeg))) return DWGSIM_HIP_ERR_DEVICE;      // (+ 64 entries; the slot is not pending: no copy reads the old one)
+    for (int t = 0; t < 3; ++t) if (P.gz_cap[t] && ensure(c, sl.gz_out[t], P.gz_cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE;
+    return ensure(c, sl.gz_status, P.gz_status);
+}
+
+// The chain step: the running values the batch starts from; the context's chain moves on to its end (a re-run moves nothing)
+static ChainSet sim_chain(dwgsim_hip_ctx_t *c, Slot &sl, const dwgsim_hip_range_t *r, int n, bool set_rand, bool rerun)
+{
+    if (rerun) return ChainSet{sl.d_rerun_chain, 1, 1, 0};
     // the reference's failure counter (dwgsim.c:635) runs over the pairs of ONE contig in index order: it is carried from the previous
     // batch only when this one continues it; any other range starts from zero unless the caller supplied the carry (sharded jobs)
     const dwgsim_hip_range_t *r_first = nullptr, *r_last = nullptr;
     for (int q = 0; q < n; ++q) if (r[q].n_pairs) { if (!r_first) r_first = &r[q]; r_last = &r[q]; }
     if (!r_first) { r_first = &r[0]; r_last = &r[n - 1]; }
-    uint64_t *ch_ptr = c->d_chain; int ch_rand = 0, ch_carry = 0; uint64_t ch_carry_v = 0;      // the running values the launch starts from: set by launch_init with the rest
-    if (!rerun) {
     const bool continues = c->chain_contig == r_first->contig && c->chain_next_ii == r_first->first_ii && r_first->first_ii != 0;
-    const bool set_carry = c->has_carry_override || !continues;
-    const uint64_t carry = c->has_carry_override ? c->carry_override : 0;
-    c->has_carry_override = false;
-    const bool set_rand = rand_base != DWGSIM_HIP_RAND_CHAIN;
-    ch_ptr = c->d_chain; ch_rand = set_rand ? 1 : 0; ch_carry_v = carry; ch_carry = set_carry ? 1 : 0;
-    c->chain_contig = r_last->contig; c->chain_next_ii = r_last->first_ii + r_last->n_pairs;
+    const ChainSet ch{c->d_chain, set_rand ? 1 : 0, (c->has_carry_override || !continues) ? 1 : 0, c->has_carry_override ? c->carry_override : 0};
+    c->has_carry_override = false; c->chain_contig = r_last->contig; c->chain_next_ii = r_last->first_ii + r_last->n_pairs;
     if (sl.ranges.data() != r) sl.ranges.assign(r, r + n);
-    } else {
-        ch_ptr = sl.d_rerun_chain; ch_rand = 1; ch_carry_v = 0; ch_carry = 1;
-        a.chain = sl.d_rerun_chain;
-    }
-    if (n_pairs == 0) { if (ch_rand || ch_carry) launch_chain_set(c->stream, ch_ptr, rand_base, ch_rand, ch_carry_v, ch_carry); return DWGSIM_HIP_OK; }
-    uint32_t opens = 0;
-    for (const SimSeg &s : segs) opens |= s.contig_start;
-    memcpy(sl.h_segs, segs.data(), sizeof(SimSeg) * segs.size());
-    HIPC(c, hipMemcpyAsync(sl.segs.p, sl.h_segs, sizeof(SimSeg) * segs.size(), hipMemcpyHostToDevice, c->stream));
-    a.segs = (const SimSeg *)sl.segs.p; a.n_seg = (int32_t)segs.size(); a.n_blocks = nblk; a.n_pairs = n_pairs;
+    return ch;
+}
+
+// The enqueue step: [chain set] -> launch_init -> k_simulate -> abort-rule epilogue -> [k_gzip] -> counters to the slot's pinned mirror -> event
+static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P, const ChainSet &ch, uint64_t rand_base, bool rerun)
+{
+    Slot &sl = c->slot[slot]; SimArgs &a = L.a; const SimForm &f = L.f;
+    const uint64_t n_pairs = L.n_pairs; const uint32_t nblk = L.nblk;
+    for (int t = 0; t < 3; ++t) sl.out_bytes[t] = sl.gz_bytes[t] = 0;
+    sl.n_pairs = n_pairs; sl.empty = n_pairs == 0;
+    if (n_pairs == 0) { if (ch.set_rand || ch.set_carry) launch_chain_set(c->stream, ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry); return DWGSIM_HIP_OK; }
+    uint32_t opens = 0; for (const SimSeg &s : L.segs) opens |= s.contig_start;      // (ranges that begin their contig)
+    memcpy(sl.h_segs.p, L.segs.data(), P.segs);
+    HIPC(c, hipMemcpyAsync(sl.segs.p, sl.h_segs.p, P.segs, hipMemcpyHostToDevice, c->stream));
+    a.segs = (const SimSeg *)sl.segs.p; a.n_seg = (int32_t)L.segs.size(); a.n_blocks = nblk; a.n_pairs = n_pairs; a.chain = ch.words; a.lb_shift = P.lb_shift;
     a.meta = (uint32_t *)c->meta.p; a.block_rand = (uint32_t *)c->block_rand.p; a.counters = sl.d_counters;
-    for (int j = 0; j < 4; ++j) a.status[j] = a.split ? nullptr : (uint64_t *)c->status_all.p + (size_t)j * (size_t)nblk;
-    sl.group = c->handles[(size_t)g.first_handle].group;
+    for (int t = 0; t < 3; ++t) a.out[t] = (uint8_t *)c->out[slot][t].p;
+    for (int j = 0; j < 4; ++j) a.status[j] = f.split ? nullptr : (uint64_t *)c->status_all.p + (size_t)j * (size_t)nblk;
+    if (f.split) { a.split_state = (uint32_t *)c->split_state.p; a.split_hand = (uint32_t *)c->split_hand.p; a.split_agg = (uint32_t *)c->split_agg.p; a.split_pre = (uint64_t *)c->split_pre.p; a.split_chunk = (uint64_t *)c->split_chunk.p; }
+    if (P.scratch) { a.flow_scratch = (uint32_t *)c->flow_scratch.p; a.flow_free = (uint64_t *)c->flow_free.p; a.flow_slots = P.flow_slots; }
+    sl.group = c->handles[(size_t)L.g->first_handle].group;
     // one operation in front of the kernel: counters, look-back words (the four arrays are contiguous), the scratch slots' free lists, the running values
-    launch_init(c->stream, sl.d_counters, (uint32_t)N_COUNTERS, a.split ? nullptr : a.status[0], a.split ? 0 : 4 * (uint64_t)nblk, a.flow_free, a.flow_free ? 256 + 8 * (uint64_t)nblk : 0,
-                ch_ptr, rand_base, ch_rand, ch_carry_v, ch_carry);
+    launch_init(c->stream, sl.d_counters, (uint32_t)N_COUNTERS, a.status[0], f.split ? 0 : 4 * (uint64_t)nblk, a.flow_free, a.flow_free ? 256 + 8 * (uint64_t)nblk : 0,
+                ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry);
     HIPC(c, hipEventRecord(sl.ev_k0, c->stream));
     c->sim_form = (int64_t)f.nthr << 20 | f.lpp << 16 | f.out << 12 | f.dt << 8 | f.wr << 4 | f.split;
     if (!launch_simulate(c->stream, a, f)) { c->err = "simulate: no k_simulate instance for this form"; return DWGSIM_HIP_ERR_FAILED; }
@@ -1746,15 +1739,13 @@ static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, 
     sl.cap_mult = c->flow_cap_mult;
     if (!rerun) launch_failrule(c->stream, a.meta, n_pairs, opens, (uint64_t *)c->fail_summ.p, sl.d_counters, c->d_chain);
     if (c->gzip_on) {      // the .gz form of every stream, enqueued behind the text (lengths are read on the device: counters[4 + t])
-        size_t nch[3], off = 0;
-        for (int t = 0; t < 3; ++t) { nch[t] = (size_t)gz_chunks(cap[t]); off += nch[t]; }
-        HIPC(c, hipMemsetAsync(sl.gz_status.p, 0, sizeof(uint64_t) * (off ? off : 1), c->stream));
-        off = 0;
+        HIPC(c, hipMemsetAsync(sl.gz_status.p, 0, P.gz_status, c->stream));
+        size_t off = 0;
         for (int t = 0; t < 3; ++t) {
-            if (cap[t] == 0) continue;
-            launch_gzip(c->stream, a.out[t], &sl.d_counters[4 + t], cap[t], (uint8_t *)sl.gz_out[t].p, (size_t)gz_capacity(cap[t]), (uint64_t *)sl.gz_status.p + off, &sl.d_counters[28 + t], &sl.d_counters[24 + t], &sl.d_counters[2],
+            if (P.cap[t] == 0) continue;
+            launch_gzip(c->stream, a.out[t], &sl.d_counters[4 + t], P.cap[t], (uint8_t *)sl.gz_out[t].p, P.gz_cap[t], (uint64_t *)sl.gz_status.p + off, &sl.d_counters[28 + t], &sl.d_counters[24 + t], &sl.d_counters[2],
                         c->d_crc_table, c->d_crc_shift);
-            off += nch[t];
+            off += P.gz_chunks[t];
         }
     }
     HIPC(c, hipEventRecord(sl.ev_end, c->stream));
@@ -1764,6 +1755,27 @@ static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, 
     sl.pending = true;
     return DWGSIM_HIP_OK;
 }
+
+// Enqueue one batch on the compute stream: resolve -> plan -> reserve -> chain -> enqueue.  Every buffer the batch needs is in place before anything
+// is enqueued or the chain state moves, so a failing call leaves the context as it found it.
+// rerun: the batch of this slot once more with larger Ion Torrent read buffers (dwgsim_hip_wait).  Nothing of the chain moves: the random reads and
+// the failed attempts of a batch do not depend on the flow model, so the first run's epilogue stands; the kernels start from the chain words the
+// first run started from (rand_base = its counters[22]).
+static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t rand_base, int slot, bool rerun)
+{
+    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS) { if (c) c->err = "bad simulate arguments"; return DWGSIM_HIP_ERR_ARG; }
+    if (c->slot[slot].pending) { c->err = "simulate: the slot still holds a batch that was not waited for"; return DWGSIM_HIP_ERR_STATE; }
+    Launch L;
+    if (const int rc = sim_resolve(c, r, n, L)) return rc;
+    HIPC(c, hipSetDevice(c->device));
+    const SimPlan P = sim_plan(c, L);
+    if (P.too_many) { c->err = "too many pairs in one call"; return DWGSIM_HIP_ERR_ARG; }
+    if (L.n_pairs) { if (const int rc = sim_reserve(c, slot, P)) return rc; }
+    // ---- nothing below fails for want of memory ----
+    return sim_launch(c, slot, L, P, sim_chain(c, c->slot[slot], r, n, rand_base != DWGSIM_HIP_RAND_CHAIN, rerun), rand_base, rerun);
+}
+
+int dwgsim_hip_simulate_ranges_async(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t rand_base, int slot) { return sim_enqueue(c, r, n, rand_base, slot, false); }
 
 int dwgsim_hip_simulate_async(dwgsim_hip_ctx_t *c, int contig, uint64_t first_ii, uint64_t n_pairs, uint64_t rand_base, int slot)
 {
@@ -1791,11 +1803,8 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
         while (h[2] & 2) {
             if (sl.cap_mult >= c->flow_cap_mult) {      // (another batch may have doubled it already)
                 // the reference doubles without end (dwgsim.c:296-311); here up to FLOW_CAP_MAX bases per read -- two thousand times a 400-base read, in
-                // scratch slots whose number shrinks as they grow (sim_enqueue).  (Rounds 3-4 stopped at 16 x the estimate: 3 of 300 random flow orders)
-                const int lmx = c->prm.length[0] > c->prm.length[1] ? c->prm.length[0] : c->prm.length[1];
-                const double emx = c->prm.e_start[0] > c->prm.e_start[1] ? c->prm.e_start[0] : c->prm.e_start[1];
-                const int64_t base_cap = c->flow_cap_forced > 0 ? c->flow_cap_forced : flow_read_capacity(lmx, emx, c->flow);
-                if (base_cap * (int64_t)c->flow_cap_mult * 2 > (int64_t)FLOW_CAP_MAX) break;
+                // scratch slots whose number shrinks as they grow (sim_plan; the retired 16 x limit: DESIGN.md §4, Ion Torrent)
+                if ((int64_t)flow_base_capacity(c) * (int64_t)c->flow_cap_mult * 2 > (int64_t)FLOW_CAP_MAX) break;
                 c->flow_cap_mult *= 2;
             }
             if (const int rc = sim_enqueue(c, sl.ranges.data(), (int)sl.ranges.size(), base, slot, true)) return rc;
@@ -1889,21 +1898,23 @@ void dwgsim_hip_host_free(void *p)
     munmap(r.base, r.len);
 }
 
-// Copies on the context's second stream: a batch that is being copied out of one slot overlaps with the kernels filling the other.
-int dwgsim_hip_fetch_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap)
+// Copies on the context's second stream: a batch that is being copied out of one slot overlaps with the kernels filling the other.  gz: the
+// stream's gzip members instead of its text.
+static int fetch_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap, bool gz)
 {
     if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream > 2 || (!host_dst && cap)) { if (c) c->err = "bad fetch arguments"; return DWGSIM_HIP_ERR_ARG; }
     Slot &sl = c->slot[slot];
     if (sl.pending) { c->err = "fetch: wait for the batch first (its sizes are not known yet)"; return DWGSIM_HIP_ERR_STATE; }
     HIPC(c, hipSetDevice(c->device));
-    const size_t n = (size_t)sl.out_bytes[stream];
+    const size_t n = (size_t)(gz ? sl.gz_bytes[stream] : sl.out_bytes[stream]);
     if (n > cap) { c->err = "fetch: destination too small"; return DWGSIM_HIP_ERR_ARG; }
     if (n == 0) return DWGSIM_HIP_OK;
-    HIPC(c, hipMemcpyAsync(host_dst, c->out[slot][stream].p, n, hipMemcpyDeviceToHost, c->copy_stream));
+    HIPC(c, hipMemcpyAsync(host_dst, gz ? sl.gz_out[stream].p : c->out[slot][stream].p, n, hipMemcpyDeviceToHost, c->copy_stream));
     HIPC(c, hipEventRecord(sl.ev_fetched, c->copy_stream));
     sl.fetch_in_flight = true;
     return DWGSIM_HIP_OK;
 }
+int dwgsim_hip_fetch_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap) { return fetch_async(c, slot, stream, host_dst, cap, false); }
 
 int dwgsim_hip_set_gzip(dwgsim_hip_ctx_t *c, int on)
 {
@@ -1920,20 +1931,7 @@ int dwgsim_hip_set_gzip(dwgsim_hip_ctx_t *c, int on)
     return DWGSIM_HIP_OK;
 }
 
-int dwgsim_hip_fetch_gz_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap)
-{
-    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream > 2 || (!host_dst && cap)) { if (c) c->err = "bad fetch arguments"; return DWGSIM_HIP_ERR_ARG; }
-    Slot &sl = c->slot[slot];
-    if (sl.pending) { c->err = "fetch: wait for the batch first (its sizes are not known yet)"; return DWGSIM_HIP_ERR_STATE; }
-    HIPC(c, hipSetDevice(c->device));
-    const size_t n = (size_t)sl.gz_bytes[stream];
-    if (n > cap) { c->err = "fetch: destination too small"; return DWGSIM_HIP_ERR_ARG; }
-    if (n == 0) return DWGSIM_HIP_OK;
-    HIPC(c, hipMemcpyAsync(host_dst, sl.gz_out[stream].p, n, hipMemcpyDeviceToHost, c->copy_stream));
-    HIPC(c, hipEventRecord(sl.ev_fetched, c->copy_stream));
-    sl.fetch_in_flight = true;
-    return DWGSIM_HIP_OK;
-}
+int dwgsim_hip_fetch_gz_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap) { return fetch_async(c, slot, stream, host_dst, cap, true); }
 
 int dwgsim_hip_fetch_wait(dwgsim_hip_ctx_t *c, int slot)
 {
@@ -1962,9 +1960,9 @@ int dwgsim_hip_fetch(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, 
     }
     // double-buffered pinned staging: D2H of chunk k+1 overlaps the host copy of chunk k
     const size_t CH = (size_t)16 << 20;
-    if (!c->h_stage) { HIPC(c, hipHostMalloc(&c->h_stage, 2 * CH, hipHostMallocDefault)); c->h_stage_cap = 2 * CH; }
+    if (const int rc = ensure_host(c, c->h_stage, 2 * CH, 2 * CH)) return rc;
     const uint8_t *src = (const uint8_t *)c->out[slot][stream].p;
-    uint8_t *stage[2] = {(uint8_t *)c->h_stage, (uint8_t *)c->h_stage + CH};
+    uint8_t *stage[2] = {(uint8_t *)c->h_stage.p, (uint8_t *)c->h_stage.p + CH};
     size_t done = 0; int b = 0;
     size_t cur = n < CH ? n : CH;
     HIPC(c, hipMemcpyAsync(stage[0], src, cur, hipMemcpyDeviceToHost, c->copy_stream));
