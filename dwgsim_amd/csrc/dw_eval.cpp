@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 #include "dw_eval_launch.hpp"
+#include "dw_mem.hpp"
 #include "../../include/dwgsim_hip.h"
 
 using namespace dw;
@@ -27,14 +28,8 @@ constexpr int32_t WIN_LO = -EVAL_WIN / 2;
 const char BREAK_LINE[] = "************************************************************\n";
 
 struct Slot {
-    size_t cap = 0;             // text bytes
-    char *h_text = nullptr;     // page-locked
-    EvalRes *h_res = nullptr;   // page-locked
-    uint8_t *d_text = nullptr;
-    uint32_t *d_ends = nullptr, *d_tiles = nullptr;
-    EvalRes *d_res = nullptr;
-    uint64_t *d_spill = nullptr;
-    uint8_t *d_flags = nullptr;
+    HostMem h_text, h_res;      // page-locked: the text (its capacity is the slot's), an EvalRes
+    DevMem d_text, d_ends, d_tiles, d_res, d_spill, d_flags;      // text, u32, u32, EvalRes, u64, u8
     hipStream_t st = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     size_t fill = 0, ctx_len = 0, len = 0;
@@ -56,12 +51,9 @@ struct dwgsim_hip_eval_ctx {
     std::string names;
     std::vector<uint32_t> off;
     std::vector<int32_t> hash;
-    char *d_names = nullptr;
-    uint32_t *d_off = nullptr;
-    int32_t *d_hash = nullptr;
+    DevMem d_names, d_off, d_hash;      // char, u32, i32
     ev::Targets tg = {};
-    char *d_P = nullptr;
-    unsigned long long *d_hist = nullptr;
+    DevMem d_P, d_hist;                 // char, unsigned long long
     std::map<int32_t, std::array<uint64_t, 5>> spill;
     uint64_t n = 0, records = 0;
     bool failed = false, finished = false, seen_header = false;
@@ -84,33 +76,29 @@ namespace {
         }                                                                                             \
     } while (0)
 
-void slot_free(Slot &S)
-{
-    if (S.h_text) hipHostFree(S.h_text);
-    if (S.h_res) hipHostFree(S.h_res);
-    if (S.d_text) hipFree(S.d_text);
-    if (S.d_ends) hipFree(S.d_ends);
-    if (S.d_tiles) hipFree(S.d_tiles);
-    if (S.d_res) hipFree(S.d_res);
-    if (S.d_spill) hipFree(S.d_spill);
-    if (S.d_flags) hipFree(S.d_flags);
-    S.h_text = nullptr; S.h_res = nullptr; S.d_text = nullptr; S.d_ends = nullptr; S.d_tiles = nullptr;
-    S.d_res = nullptr; S.d_spill = nullptr; S.d_flags = nullptr;
-}
-
 // buffers for `cap` text bytes: a line has at least its newline (ends, flags: cap entries); a record that reaches the histogram has at least
-// 11 bytes (ten tabs and the newline), so the spill list needs fewer than cap / 8 entries
+// 11 bytes (ten tabs and the newline), so the spill list needs fewer than cap / 8 entries.  Each buffer of a smaller slot is freed before its
+// successor is made; the text buffer comes last, so that its capacity -- the slot's -- is the new one only once all the others were made.
 int slot_alloc(dwgsim_hip_eval_ctx *c, Slot &S, size_t cap)
 {
-    S.cap = cap;
-    CK(hipHostMalloc((void **)&S.h_text, cap, hipHostMallocDefault));
-    CK(hipHostMalloc((void **)&S.h_res, sizeof(EvalRes), hipHostMallocDefault));
-    CK(hipMalloc((void **)&S.d_text, cap + 16));
-    CK(hipMalloc((void **)&S.d_ends, cap * sizeof(uint32_t)));
-    CK(hipMalloc((void **)&S.d_tiles, (cap / EVAL_TILE + 1) * sizeof(uint32_t)));
-    CK(hipMalloc((void **)&S.d_res, sizeof(EvalRes)));
-    CK(hipMalloc((void **)&S.d_spill, (cap / 8 + 1) * sizeof(uint64_t)));
-    CK(hipMalloc((void **)&S.d_flags, cap));
+    auto exact = [](auto &b, size_t n) { return b.reserve(n, n); };
+    CK(exact(S.h_res, sizeof(EvalRes)));
+    CK(exact(S.d_text, cap + 16));
+    CK(exact(S.d_ends, cap * sizeof(uint32_t)));
+    CK(exact(S.d_tiles, (cap / EVAL_TILE + 1) * sizeof(uint32_t)));
+    CK(exact(S.d_res, sizeof(EvalRes)));
+    CK(exact(S.d_spill, (cap / 8 + 1) * sizeof(uint64_t)));
+    CK(exact(S.d_flags, cap));
+    CK(exact(S.h_text, cap));
+    return DWGSIM_HIP_OK;
+}
+
+// a device copy of n host bytes, in a buffer of exactly n bytes (the one it replaces is freed first)
+int upload(dwgsim_hip_eval_ctx *c, DevMem &b, const void *src, size_t n)
+{
+    b.reset();
+    CK(b.reserve(n, n));
+    CK(hipMemcpy(b.get(), src, n, hipMemcpyHostToDevice));
     return DWGSIM_HIP_OK;
 }
 
@@ -157,7 +145,7 @@ ev::Opts dev_opts(const dwgsim_hip_eval_ctx *c)
     ev::Opts o;
     o.a = c->o.a; o.d = c->o.d; o.g = c->o.g; o.q = c->o.q; o.e = c->o.e; o.s = c->o.s; o.i = c->o.i; o.z = c->o.z; o.m = c->o.m;
     o.P_len = c->o.P ? (int32_t)c->P.size() : -1;
-    o.P = c->d_P;
+    o.P = c->d_P.get<char>();
     return o;
 }
 
@@ -170,7 +158,7 @@ uint32_t records_grid(size_t len)
 EvalRecArgs rec_args(dwgsim_hip_eval_ctx *c, const uint8_t *text, uint32_t *ends, EvalRes *res, uint64_t *spill, uint8_t *flags, uint32_t has_ctx)
 {
     EvalRecArgs A;
-    A.text = text; A.ends = ends; A.res = res; A.hist = c->d_hist; A.spill = spill; A.flags = flags; A.has_ctx = has_ctx;
+    A.text = text; A.ends = ends; A.res = res; A.hist = c->d_hist.get<unsigned long long>(); A.spill = spill; A.flags = flags; A.has_ctx = has_ctx;
     A.win_lo = WIN_LO; A.floor_score = c->floor_score; A.opt = dev_opts(c); A.tg = c->tg;
     return A;
 }
@@ -186,29 +174,29 @@ int process_oldest(dwgsim_hip_eval_ctx *c)
     float ms = 0;
     if (hipEventElapsedTime(&ms, S.e0, S.e1) == hipSuccess) c->kernel_ms += ms;
     if (c->failed) return DWGSIM_HIP_OK;
-    const EvalRes r = *S.h_res;
+    const EvalRes r = *S.h_res.get<EvalRes>();
     const uint32_t n_rec = r.n_lines - S.has_ctx;
     if (r.err != ~0ull) {
         const uint64_t rec = r.err >> 8;
         c->failed = true;
         c->code = (int)(r.err & 0xff);
         c->err_rec = c->records + rec;
-        const char *p = S.h_text;
-        for (uint64_t i = 0; i < rec + S.has_ctx; ++i) p = (const char *)memchr(p, '\n', S.h_text + S.len - p) + 1;
-        c->err_line.assign(p, (const char *)memchr(p, '\n', S.h_text + S.len - p) - p);
+        const char *p = S.h_text.get<char>();
+        for (uint64_t i = 0; i < rec + S.has_ctx; ++i) p = (const char *)memchr(p, '\n', S.h_text.get<char>() + S.len - p) + 1;
+        c->err_line.assign(p, (const char *)memchr(p, '\n', S.h_text.get<char>() + S.len - p) - p);
         return DWGSIM_HIP_OK;
     }
     c->n += r.n;
     c->records += n_rec;
     if (r.n_spill) {
         std::vector<uint64_t> sp(r.n_spill);
-        CK(hipMemcpy(sp.data(), S.d_spill, sp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        CK(hipMemcpy(sp.data(), S.d_spill.get<uint64_t>(), sp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
         for (uint64_t w : sp) c->spill[(int32_t)(uint32_t)(w >> 32)][(int)(w & 7)]++;
     }
     if (c->o.p && n_rec) {
         std::vector<uint8_t> fl(n_rec);
-        CK(hipMemcpy(fl.data(), S.d_flags, n_rec, hipMemcpyDeviceToHost));
-        const char *p = S.h_text + S.ctx_len, *end = S.h_text + S.len;
+        CK(hipMemcpy(fl.data(), S.d_flags.get(), n_rec, hipMemcpyDeviceToHost));
+        const char *p = S.h_text.get<char>() + S.ctx_len, *end = S.h_text.get<char>() + S.len;
         for (uint32_t i = 0; i < n_rec; ++i) {
             const char *e = (const char *)memchr(p, '\n', end - p) + 1;
             if (fl[i]) c->incorrect.append(p, e - p);
@@ -232,14 +220,14 @@ int submit(dwgsim_hip_eval_ctx *c, size_t cut)
 {
     Slot &S = c->s[c->cur];
     S.len = cut;
-    *S.h_res = EvalRes{~0ull, 0, 0, 0};
+    *S.h_res.get<EvalRes>() = EvalRes{~0ull, 0, 0, 0};
     CK(hipEventRecord(S.e0, S.st));
-    CK(hipMemcpyAsync(S.d_text, S.h_text, cut, hipMemcpyHostToDevice, S.st));
-    CK(hipMemcpyAsync(S.d_res, S.h_res, sizeof(EvalRes), hipMemcpyHostToDevice, S.st));
-    const EvalRecArgs A = rec_args(c, S.d_text, S.d_ends, S.d_res, S.d_spill, c->o.p ? S.d_flags : nullptr, S.has_ctx);
-    launch_eval_chunk(S.st, A, cut, S.d_tiles, records_grid(cut));
+    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, S.st));
+    CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st));
+    const EvalRecArgs A = rec_args(c, S.d_text.get(), S.d_ends.get<uint32_t>(), S.d_res.get<EvalRes>(), S.d_spill.get<uint64_t>(), c->o.p ? S.d_flags.get() : nullptr, S.has_ctx);
+    launch_eval_chunk(S.st, A, cut, S.d_tiles.get<uint32_t>(), records_grid(cut));
     CK(hipGetLastError());
-    CK(hipMemcpyAsync(S.h_res, S.d_res, sizeof(EvalRes), hipMemcpyDeviceToHost, S.st));
+    CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st));
     CK(hipEventRecord(S.e1, S.st));
     S.busy = true;
     c->pending.push_back(c->cur);
@@ -252,10 +240,10 @@ int submit(dwgsim_hip_eval_ctx *c, size_t cut)
     }
     // the last line of the submitted chunk, then what follows it
     size_t lb = cut - 1;
-    while (lb > 0 && S.h_text[lb - 1] != '\n') --lb;
+    while (lb > 0 && S.h_text.get<char>()[lb - 1] != '\n') --lb;
     const size_t ctx = cut - lb, rest = S.fill - cut;
-    memcpy(T.h_text, S.h_text + lb, ctx);
-    memcpy(T.h_text + ctx, S.h_text + cut, rest);
+    memcpy(T.h_text.get<char>(), S.h_text.get<char>() + lb, ctx);
+    memcpy(T.h_text.get<char>() + ctx, S.h_text.get<char>() + cut, rest);
     T.ctx_len = ctx; T.has_ctx = 1; T.fill = ctx + rest;
     S.fill = 0;
     return DWGSIM_HIP_OK;
@@ -267,13 +255,10 @@ int grow(dwgsim_hip_eval_ctx *c)
     int r = drain(c);
     if (r) return r;
     Slot &F = c->s[c->cur];
-    const size_t cap = F.cap * 2;
-    std::string keep(F.h_text, F.fill);
-    for (Slot &S : c->s) {
-        slot_free(S);
-        if ((r = slot_alloc(c, S, cap))) return r;
-    }
-    memcpy(F.h_text, keep.data(), keep.size());
+    const size_t cap = F.h_text.cap() * 2;
+    std::string keep(F.h_text.get<char>(), F.fill);
+    for (Slot &S : c->s) if ((r = slot_alloc(c, S, cap))) return r;
+    memcpy(F.h_text.get<char>(), keep.data(), keep.size());
     return DWGSIM_HIP_OK;
 }
 
@@ -281,13 +266,13 @@ int grow(dwgsim_hip_eval_ctx *c)
 int end_file(dwgsim_hip_eval_ctx *c)
 {
     Slot &F = c->s[c->cur];
-    if (F.fill > F.ctx_len && F.h_text[F.fill - 1] != '\n') {
-        if (F.fill == F.cap) {
+    if (F.fill > F.ctx_len && F.h_text.get<char>()[F.fill - 1] != '\n') {
+        if (F.fill == F.h_text.cap()) {
             const int r = grow(c);
             if (r) return r;
         }
         Slot &G = c->s[c->cur];
-        G.h_text[G.fill++] = '\n';
+        G.h_text.get<char>()[G.fill++] = '\n';
     }
     Slot &H = c->s[c->cur];
     if (H.fill > H.ctx_len && !c->failed) {
@@ -332,17 +317,10 @@ int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
         }
         if (c->hash[h] < 0) c->hash[h] = t;
     }
-    if (c->d_names) hipFree(c->d_names);
-    if (c->d_off) hipFree(c->d_off);
-    if (c->d_hash) hipFree(c->d_hash);
-    c->d_names = nullptr; c->d_off = nullptr; c->d_hash = nullptr;
-    CK(hipMalloc((void **)&c->d_names, c->names.size() + 1));
-    CK(hipMalloc((void **)&c->d_off, c->off.size() * sizeof(uint32_t)));
-    CK(hipMalloc((void **)&c->d_hash, hs * sizeof(int32_t)));
-    CK(hipMemcpy(c->d_names, c->names.data(), c->names.size() + 1, hipMemcpyHostToDevice));
-    CK(hipMemcpy(c->d_off, c->off.data(), c->off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    CK(hipMemcpy(c->d_hash, c->hash.data(), hs * sizeof(int32_t), hipMemcpyHostToDevice));
-    c->tg.names = c->d_names; c->tg.off = c->d_off; c->tg.hash = c->d_hash; c->tg.n = nt; c->tg.hmask = hs - 1;
+    if (const int r = upload(c, c->d_names, c->names.data(), c->names.size() + 1)) return r;
+    if (const int r = upload(c, c->d_off, c->off.data(), c->off.size() * sizeof(uint32_t))) return r;
+    if (const int r = upload(c, c->d_hash, c->hash.data(), hs * sizeof(int32_t))) return r;
+    c->tg.names = c->d_names.get<char>(); c->tg.off = c->d_off.get<uint32_t>(); c->tg.hash = c->d_hash.get<int32_t>(); c->tg.n = nt; c->tg.hmask = hs - 1;
     return DWGSIM_HIP_OK;
 }
 
@@ -450,9 +428,8 @@ dwgsim_hip_eval_ctx_t *dwgsim_hip_eval_create(const dwgsim_hip_eval_opts_t *opts
             return fail(DWGSIM_HIP_ERR_DEVICE);
     }
     const size_t hb = 5 * (EVAL_WIN + 1) * sizeof(unsigned long long);
-    if (hipMalloc((void **)&c->d_hist, hb) != hipSuccess || hipMemset(c->d_hist, 0, hb) != hipSuccess) return fail(DWGSIM_HIP_ERR_DEVICE);
-    if (hipMalloc((void **)&c->d_P, c->P.size() + 1) != hipSuccess || hipMemcpy(c->d_P, c->P.c_str(), c->P.size() + 1, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(DWGSIM_HIP_ERR_DEVICE);
+    if (c->d_hist.reserve(hb, hb) != hipSuccess || hipMemset(c->d_hist.get(), 0, hb) != hipSuccess) return fail(DWGSIM_HIP_ERR_DEVICE);
+    if (upload(c, c->d_P, c->P.c_str(), c->P.size() + 1)) return fail(DWGSIM_HIP_ERR_DEVICE);
     if (upload_targets(c, "", 0)) return fail(DWGSIM_HIP_ERR_DEVICE);
     *err = DWGSIM_HIP_OK;
     return c;
@@ -476,15 +453,15 @@ int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
     c->seen_header = true;      // the first file's header is empty when feed comes first
     while (len && !c->failed) {
         Slot &F = c->s[c->cur];
-        if (F.fill == F.cap) {
+        if (F.fill == F.h_text.cap()) {
             size_t cut = F.fill;
-            while (cut > F.ctx_len && F.h_text[cut - 1] != '\n') --cut;
+            while (cut > F.ctx_len && F.h_text.get<char>()[cut - 1] != '\n') --cut;
             const int r = cut > F.ctx_len ? submit(c, cut) : grow(c);
             if (r) return r;
             continue;
         }
-        const size_t k = len < F.cap - F.fill ? len : F.cap - F.fill;
-        memcpy(F.h_text + F.fill, buf, k);
+        const size_t k = len < F.h_text.cap() - F.fill ? len : F.h_text.cap() - F.fill;
+        memcpy(F.h_text.get<char>() + F.fill, buf, k);
         F.fill += k; buf += k; len -= k;
     }
     return c->failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
@@ -504,7 +481,7 @@ int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *c, dwgsim_hip_eval_summary_t *
         c->incorrect.clear();
     } else {
         std::vector<unsigned long long> h(5 * (EVAL_WIN + 1));
-        CK(hipMemcpy(h.data(), c->d_hist, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        CK(hipMemcpy(h.data(), c->d_hist.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         format_table(c, h);
         char buf[128];
         snprintf(buf, sizeof buf, "\r%llu\n", (unsigned long long)c->n);
@@ -551,16 +528,10 @@ void dwgsim_hip_eval_destroy(dwgsim_hip_eval_ctx_t *c)
     hipSetDevice(c->device);
     for (Slot &S : c->s) {
         if (S.st) hipStreamSynchronize(S.st);
-        slot_free(S);
         if (S.st) hipStreamDestroy(S.st);
         if (S.e0) hipEventDestroy(S.e0);
         if (S.e1) hipEventDestroy(S.e1);
     }
-    if (c->d_names) hipFree(c->d_names);
-    if (c->d_off) hipFree(c->d_off);
-    if (c->d_hash) hipFree(c->d_hash);
-    if (c->d_hist) hipFree(c->d_hist);
-    if (c->d_P) hipFree(c->d_P);
     delete c;
 }
 
@@ -575,47 +546,32 @@ int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *c, const void *tex
 {
     if (!c || !text || !len || len > MAX_CHUNK * 4ull || reps < 1 || !ms) return DWGSIM_HIP_ERR_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    uint8_t *dev = nullptr;
-    uint32_t *ends = nullptr, *tiles = nullptr;
-    EvalRes *res = nullptr;
-    uint64_t *spill = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = DWGSIM_HIP_OK;
-    auto cleanup = [&]() {
-        if (dev) hipFree(dev);
-        if (ends) hipFree(ends);
-        if (tiles) hipFree(tiles);
-        if (res) hipFree(res);
-        if (spill) hipFree(spill);
-        if (e0) hipEventDestroy(e0);
-        if (e1) hipEventDestroy(e1);
-    };
-    if (hipMalloc((void **)&dev, len + 16) || hipMalloc((void **)&ends, len * sizeof(uint32_t)) || hipMalloc((void **)&tiles, (len / EVAL_TILE + 1) * sizeof(uint32_t)) ||
-        hipMalloc((void **)&res, sizeof(EvalRes)) || hipMalloc((void **)&spill, (len / 8 + 1) * sizeof(uint64_t)) || hipEventCreate(&e0) ||
-        hipEventCreate(&e1)) {
-        cleanup();
+    DevMem dev, ends, tiles, res, spill;
+    DevEvent e0, e1;
+    auto exact = [](DevMem &b, size_t n) { return b.reserve(n, n) != hipSuccess; };
+    if (exact(dev, len + 16) || exact(ends, len * sizeof(uint32_t)) || exact(tiles, (len / EVAL_TILE + 1) * sizeof(uint32_t)) || exact(res, sizeof(EvalRes)) ||
+        exact(spill, (len / 8 + 1) * sizeof(uint64_t)) || e0.create() || e1.create()) {
         c->err = "debug_device_chunk: out of device memory";
         return DWGSIM_HIP_ERR_NOMEM;
     }
     hipStream_t st = c->s[0].st;
-    if (hipMemcpy(dev, text, len, hipMemcpyHostToDevice) != hipSuccess) {
-        cleanup();
+    if (hipMemcpy(dev.get(), text, len, hipMemcpyHostToDevice) != hipSuccess) {
         c->err = "debug_device_chunk: upload failed";
         return DWGSIM_HIP_ERR_DEVICE;
     }
-    const EvalRecArgs A = rec_args(c, (const uint8_t *)dev, ends, res, spill, nullptr, 0);
-    hipEventRecord(e0, st);
+    int rc = DWGSIM_HIP_OK;
+    const EvalRecArgs A = rec_args(c, dev.get(), ends.get<uint32_t>(), res.get<EvalRes>(), spill.get<uint64_t>(), nullptr, 0);
+    hipEventRecord(e0.get(), st);
     for (int i = 0; i < reps; ++i) {
-        hipMemsetAsync(res, 0xff, 8, st);
-        hipMemsetAsync((char *)res + 8, 0, sizeof(EvalRes) - 8, st);
-        launch_eval_chunk(st, A, len, tiles, records_grid(len));
+        hipMemsetAsync(res.get(), 0xff, 8, st);
+        hipMemsetAsync(res.get() + 8, 0, sizeof(EvalRes) - 8, st);
+        launch_eval_chunk(st, A, len, tiles.get<uint32_t>(), records_grid(len));
     }
-    hipEventRecord(e1, st);
+    hipEventRecord(e1.get(), st);
     if (hipStreamSynchronize(st) != hipSuccess) { c->err = "debug_device_chunk: kernel failed"; rc = DWGSIM_HIP_ERR_DEVICE; }
     float t = 0;
-    hipEventElapsedTime(&t, e0, e1);
+    hipEventElapsedTime(&t, e0.get(), e1.get());
     *ms = t / reps;
-    cleanup();
     return rc;
 }
 

@@ -31,6 +31,7 @@
 #include "dw_kernels.hpp"
 #include "dw_launch.hpp"
 #include "dw_mutin.hpp"
+#include "dw_mem.hpp"
 
 using namespace dw;
 
@@ -48,57 +49,58 @@ struct Member {                      // one contig of a group
     ResolvedContig rc;               // -m / -b / -v: the file's entries for this contig, resolved when the contig was added
 };
 
+// What a dropped group leaves for the next one (dwgsim_hip_ctx::pool): its device memory, the events and page-locked counters of its walk, and the
+// host sources of its uploads.  The buffers of cells are sized for d_ref.cap() padded cells.
+struct GroupMem {
+    DevMem d_ref, d_cells[2], d_view[2];      // reference codes, byte cells, 4-bit read views
+    DevMem d_ins_pos[2], d_ins_len[2], d_ins_off[2], d_ins_bases[2];      // insertion tables (int32 / uint32 entries; inserted bases + 16 bytes)
+    DevMem d_names, d_reg, d_seg;            // name pool, region pool, segment table (start[n + 1] | len[n] | cindex[n])
+    std::vector<uint8_t> h_names; std::vector<int32_t> h_reg, h_seg;      // their host sources (alive while asynchronous copies may read them)
+    DevMem d_summ[2], d_summ2[2];            // haplotype summaries (uint16, per 64 and per 1024 cells) for count_random: kept in step with the read views
+    // the walk as sparse work (dw_walk.hip k_mark_dirty / k_dirty_chunks): the view and the summaries of the UNMUTATED group, made once at upload, and
+    // the bitmap (uint32) of 64-cell chunks the last walk may have written
+    DevMem d_refview, d_refsumm, d_refsumm2, d_dirty;
+    DevEvent ev_walk, ev_walk0;      // end / start of the walk chain on the walk stream
+    HostMem h_wc;                    // page-locked mirror (16 x u64) of the walk's counters (the context's d_wcounters) at the end of THIS group's walk: several groups' walks can be in flight
+};
+
 struct Group {
     bool alive = false, mutated = false, walk_pending = false;
     int first_handle = -1;
     std::vector<Member> m;
     int64_t total = 0;               // cells of the coordinate space (a multiple of 16; allocations add CELL_PAD = 64: a whole 64-cell chunk past the last cell stays inside)
-    uint8_t *d_ref = nullptr, *d_cells[2] = {nullptr, nullptr}, *d_view[2] = {nullptr, nullptr};      // reference codes, byte cells, 4-bit read views
-    int32_t *d_ins_pos[2] = {nullptr, nullptr};
-    uint32_t *d_ins_len[2] = {nullptr, nullptr}, *d_ins_off[2] = {nullptr, nullptr};
-    uint8_t *d_ins_bases[2] = {nullptr, nullptr};
+    GroupMem mem;
     uint32_t n_ins[2] = {0, 0}, n_ins_bases[2] = {0, 0};
-    size_t cap_ins[2] = {0, 0}, cap_bases[2] = {0, 0};
-    uint8_t *d_names = nullptr; int32_t *d_reg = nullptr; int32_t *d_seg = nullptr;      // name pool, region pool, segment table (start[n + 1] | len[n] | cindex[n])
-    std::vector<uint8_t> h_names; std::vector<int32_t> h_reg, h_seg;                     // their host sources (alive while asynchronous copies may read them)
     int fixed_max = 0;               // longest "[prefix_]name"
     uint32_t n_cand = 0;
-    uint16_t *d_summ[2] = {nullptr, nullptr}, *d_summ2[2] = {nullptr, nullptr};      // haplotype summaries (per 64 and per 1024 cells) for count_random: kept in step with the read views
-    // the walk as sparse work (dw_walk.hip k_mark_dirty / k_dirty_chunks): the view and the summaries of the UNMUTATED group, made once at upload, and
-    // the bitmap of 64-cell chunks the last walk may have written (dirty_any) -- or "everything" after a walk that kept no bitmap (dirty_all)
-    uint8_t *d_refview = nullptr; uint16_t *d_refsumm = nullptr, *d_refsumm2 = nullptr; uint32_t *d_dirty = nullptr; uint32_t n_dirty_words = 0;
-    bool dirty_any = false, dirty_all = false;
-    // what the allocations above were made for (a dropped group's memory is kept for the next one: dwgsim_hip_ctx::pool)
-    size_t cap_cells = 0, cap_names = 0, cap_reg = 0, cap_seg = 0;
+    uint32_t n_dirty_words = 0; bool dirty_any = false, dirty_all = false;      // mem.d_dirty: words, any chunk written -- or "everything" after a walk that kept no bitmap (dirty_all)
     // a walk that was enqueued and not yet waited for
     int walk_attempt = 0; uint32_t walk_cap = 0; size_t walk_cap_bases = 0; bool walk_reset = false;
     uint32_t n_patch = 0, n_patch_ev = 0;       // file-driven mutations: patched cells / indel events
-    hipEvent_t ev_walk = nullptr, ev_walk0 = nullptr;      // end / start of the walk chain on the walk stream
-    uint64_t *h_wc = nullptr;        // page-locked mirror of the walk's counters (the context's d_wcounters) at the end of THIS group's walk: several groups' walks can be in flight
     // the mutated cells of the finished walk, fetched once for mutations_text
     bool list_valid = false; std::vector<int32_t> pos; std::vector<uint32_t> cells; HostIns ins[2];
 };
 
 struct HandleRef { int group = -1, k = 0; };
 
-struct DevBuf {                     // grow-only device buffer
-    void *p = nullptr; size_t cap = 0;
-};
-
-struct HostBuf { void *p = nullptr; size_t cap = 0; };      // grow-only page-locked host buffer (ensure_host)
-
 constexpr int N_COUNTERS = 32;      // u64 words of a counter block (SimArgs::counters)
 
+struct Counters {                   // a device counter block and its page-locked mirror
+    DevMem d; HostMem h;
+    uint64_t *dev() const { return d.get<uint64_t>(); }
+    uint64_t *host() const { return h.get<uint64_t>(); }
+};
+
 struct Slot {                       // one of the two batches a context can have in flight
-    uint64_t *d_counters = nullptr, *h_counters = nullptr;      // device block + pinned mirror
+    Counters counters;
     hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_end = nullptr, ev_done = nullptr, ev_fetched = nullptr;
     bool pending = false, empty = true, fetch_in_flight = false;
     int group = -1;                 // the group the batch in flight reads
     uint64_t n_pairs = 0, out_bytes[3] = {0, 0, 0}, gz_bytes[3] = {0, 0, 0};
-    DevBuf gz_out[3], gz_status, segs;        // GPU gzip: the members of each stream, look-back words; the range table of the launch
-    HostBuf h_segs;                           // ... and its page-locked source
+    DevMem gz_out[3], gz_status, segs;        // GPU gzip: the members of each stream, look-back words; the range table of the launch
+    HostMem h_segs;                           // ... and its page-locked source
     std::vector<dwgsim_hip_range_t> ranges;      // what the batch in flight covers (it is enqueued again, with larger read buffers, when an Ion Torrent read outgrew them)
-    uint64_t *d_rerun_chain = nullptr;           // [2]: the chain words such a second run starts from
+    DevMem d_rerun_chain;                        // [2]: the chain words such a second run starts from
     int cap_mult = 1;                            // the context's flow_cap_mult this batch was enqueued with
 };
 
@@ -108,7 +110,7 @@ struct dwgsim_hip_ctx {
     dwgsim_hip_params_t prm;
     std::string read_prefix;
     std::vector<uint8_t> flow;            // Ion Torrent flow order as base codes
-    uint8_t *d_flow = nullptr;
+    DevMem d_flow;
     int device = 0;
     hipStream_t stream = nullptr;            // simulate: kernels of the batches
     hipStream_t copy_stream = nullptr;       // device -> host copies of finished text
@@ -117,32 +119,32 @@ struct dwgsim_hip_ctx {
                                              // on the walk stream the count of step k+1 waited for the walks of steps k+2, k+3 (round 6: profiles/r06_solo_rank_entry.txt)
     std::string err;
     double e_by[2] = {0, 0};
-    uint64_t *d_thr[2] = {nullptr, nullptr};
-    uint32_t *d_thr32[2] = {nullptr, nullptr}; int e_full = 0;
-    uint32_t *d_qbase[2] = {nullptr, nullptr}; int32_t qb_words = 1;
-    uint8_t *d_rand_fixed = nullptr; int32_t rand_fixed_len = 0;
+    DevMem d_thr[2];                         // u64
+    DevMem d_thr32[2]; int e_full = 0;       // u32
+    DevMem d_qbase[2]; int32_t qb_words = 1;      // u32
+    DevMem d_rand_fixed; int32_t rand_fixed_len = 0;
     std::vector<Group> groups;
-    std::vector<Group> pool;                 // the device memory, events and page-locked mirrors of dropped groups, handed to the next add_contigs whose cells fit: a
+    std::vector<GroupMem> pool;              // the device memory, events and page-locked mirrors of dropped groups, handed to the next add_contigs whose cells fit: a
                                              // job of many groups pays its hipMalloc / hipFree (each a device-wide synchronisation) once, not at every group end
     std::vector<HandleRef> handles;          // contig handle -> (group, member); handles are never reused
     // simulate() working set
-    DevBuf meta, fail_summ, block_rand, status_all, out[DWGSIM_HIP_SLOTS][3], split_state, split_hand, split_agg, split_pre, split_chunk;
+    DevMem meta, fail_summ, block_rand, status_all, out[DWGSIM_HIP_SLOTS][3], split_state, split_hand, split_agg, split_pre, split_chunk;
     // walk-stream working set (grow-only)
-    DevBuf w_slots, w_slot_aux;      // the site scan's per-block slots (dw_walk.hip k_site_scan_slots) and their counts / bases
+    DevMem w_slots, w_slot_aux;      // the site scan's per-block slots (dw_walk.hip k_site_scan_slots) and their counts / bases
     int site_slots = -1; int64_t site_slot_cap = -1;      // "site_slots": -1 choose, 0 the look-back form, 1 the slot form; "site_slot_cap": a slot size to start from (tests: the overflow re-run)
-    DevBuf scratch_mask, scratch_cnt, scratch_status, w_cand, w_ev, w_flags, w_lo, w_sufmin, w_bound, w_ppos, w_pcells, up_ascii, l_pos, l_cells, place_segs, place_rand, place_list, place_aux;
-    HostBuf h_up; hipEvent_t ev_up = nullptr; bool up_in_flight = false;      // page-locked staging of a group's sequence
-    HostBuf h_place_segs, h_range_rand;      // page-locked: count_random's range table and its result per range
+    DevMem scratch_mask, scratch_cnt, scratch_status, w_cand, w_ev, w_flags, w_lo, w_sufmin, w_bound, w_ppos, w_pcells, up_ascii, l_pos, l_cells, place_segs, place_rand, place_list, place_aux;
+    HostMem h_up; hipEvent_t ev_up = nullptr; bool up_in_flight = false;      // page-locked staging of a group's sequence
+    HostMem h_place_segs, h_range_rand;      // page-locked: count_random's range table and its result per range
     std::vector<int32_t> h_ppos; std::vector<uint16_t> h_pcells; std::vector<Event> h_pev;      // file-driven mutations of the group being walked
     bool seq_justify = false, dense_view = false;      // "justify_seq", "dense_view": the cross-check forms of the walk (one thread justifies a whole group; the views are made from every cell)
     MutInput mutin; bool has_mutin = false;                             // -m / -b / -v
     Regions regions; bool has_regions = false;                           // -x
-    DevBuf flow_scratch, flow_free;
-    uint64_t *d_counters = nullptr, *h_counters = nullptr;          // N_COUNTERS x u64 + pinned mirror: calibrate / count_random / debug hooks (compute stream)
-    uint64_t *d_wcounters = nullptr;                                // 16 x u64 (mirrored per group: Group::h_wc): the walk ([7] candidates, [8..11] eight words, [12], [13] mut_debug, [14] listed cells)
-    uint64_t *d_pcounters = nullptr, *h_pcounters = nullptr;        // N_COUNTERS x u64 + pinned mirror: count_random (walk stream)
+    DevMem flow_scratch, flow_free;
+    Counters counters;                       // calibrate / count_random / debug hooks (compute stream)
+    DevMem d_wcounters;                      // 16 x u64 (mirrored per group: Group::h_wc): the walk ([7] candidates, [8..11] eight words, [12], [13] mut_debug, [14] listed cells)
+    Counters pcounters;                      // count_random (walk stream)
     Slot slot[DWGSIM_HIP_SLOTS];             // simulate(): up to three batches in flight (kernels | copy-out issued | copy-out landing: dw_job.cpp)
-    uint64_t *d_chain = nullptr;             // [0] random reads emitted before the next batch, [1] the abort rule's carry: handed from batch to batch on the device
+    DevMem d_chain;                          // [0] random reads emitted before the next batch, [1] the abort rule's carry: handed from batch to batch on the device
     int chain_contig = -1; uint64_t chain_next_ii = 0;      // which (contig, read index) the carry continues
     bool has_carry_override = false; uint64_t carry_override = 0;
     int flow_cap_forced = 0;               // "flow_cap" (tests): the capacity a job starts from, instead of flow_read_capacity()
@@ -152,8 +154,8 @@ struct dwgsim_hip_ctx {
     int64_t walk_cap = -1; bool phases = false; int writer = -1, force_threads = 0; int64_t place_cap = -1; uint64_t place_open = 0; double walk_us = 0, count_us = 0; int split = -1;      // dwgsim_hip_debug_option / _debug_get
     int64_t sim_form = 0;                  // dwgsim_hip_debug_get("sim_form"): the k_simulate form of the last launch
     hipEvent_t ev_cnt0 = nullptr, ev_cnt1 = nullptr;
-    bool gzip_on = false; uint32_t *d_crc_table = nullptr, *d_crc_shift = nullptr;      // dwgsim_hip_set_gzip
-    HostBuf h_stage;                       // pinned staging for fetch
+    bool gzip_on = false; DevMem d_crc_table, d_crc_shift;      // dwgsim_hip_set_gzip (u32; d_crc_shift is uploaded last)
+    HostMem h_stage;                       // pinned staging for fetch
     std::string txt, vcf;
 };
 
@@ -161,44 +163,40 @@ namespace {
 
 #define HIPC(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { char b_[512]; snprintf(b_, sizeof b_, "HIP error %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #call); (ctx)->err = b_; return DWGSIM_HIP_ERR_DEVICE; } } while (0)
 
-void free_group(struct Group &g);
-
-// hipMalloc; when the device is out of memory the sets of dropped groups the context keeps for reuse (dwgsim_hip_ctx::pool) are given back and the
+// hipMalloc (DevKind); when the device is out of memory the sets of dropped groups the context keeps for reuse (dwgsim_hip_ctx::pool) are given back and the
 // allocation is tried once more -- a job that fitted when groups were freed at drop (rounds 1-4) must not fail with gigabytes idle in the pool
 hipError_t dev_malloc(dwgsim_hip_ctx *c, void **p, size_t bytes)
 {
-    hipError_t e = hipMalloc(p, bytes);
+    hipError_t e = DevKind::alloc(p, bytes);
     if (e == hipSuccess || c->pool.empty()) return e;
     (void)hipGetLastError();
     hipStreamSynchronize(c->walk_stream);
-    for (auto &g : c->pool) free_group(g);
     c->pool.clear();
-    return hipMalloc(p, bytes);
+    return DevKind::alloc(p, bytes);
 }
 
-int ensure(dwgsim_hip_ctx *c, DevBuf &b, size_t bytes)
+// every device allocation of a context goes through dev_malloc: room for `need` bytes in b, else a new buffer of `want` bytes
+hipError_t reserve(dwgsim_hip_ctx *c, DevMem &b, size_t need, size_t want)
 {
-    if (bytes <= b.cap) return 0;
-    if (b.p) HIPC(c, hipFree(b.p));
-    b.p = nullptr; b.cap = 0;
-    size_t want = bytes + bytes / 8 + 4096;
-    HIPC(c, dev_malloc(c, &b.p, want));
-    b.cap = want;
+    return b.reserve(need, want, [c](void **p, size_t n) { return dev_malloc(c, p, n); });
+}
+
+// the growth rule of the context's working sets
+int ensure(dwgsim_hip_ctx *c, DevMem &b, size_t bytes)
+{
+    HIPC(c, reserve(c, b, bytes, bytes + bytes / 8 + 4096));
     return 0;
 }
 
-// page-locked: room for `bytes`, else a new buffer of `want` (each site has its growth rule and first waits for what may read the old one)
-int ensure_host(dwgsim_hip_ctx *c, HostBuf &b, size_t bytes, size_t want)
+// a table of n bytes made once: allocated and copied up (b stays empty when the copy fails, so that the table is made again)
+int upload(dwgsim_hip_ctx *c, DevMem &b, const void *src, size_t n)
 {
-    if (bytes <= b.cap) return 0;
-    if (b.p) HIPC(c, hipHostFree(b.p));
-    b.p = nullptr; b.cap = 0;
-    HIPC(c, hipHostMalloc(&b.p, want, hipHostMallocDefault));
-    b.cap = want;
+    HIPC(c, reserve(c, b, n, n));
+    const hipError_t e = hipMemcpy(b.get(), src, n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) b.reset();
+    HIPC(c, e);
     return 0;
 }
-
-void free_host(HostBuf &b) { if (b.p) hipHostFree(b.p); b = HostBuf(); }
 
 uint8_t nt4(int ch)      // dwgsim.c:56-73
 {
@@ -227,7 +225,7 @@ WalkParams walk_params(const dwgsim_hip_ctx *c)
     w.indel_min = c->prm.indel_min; w.is_hap = c->prm.is_hap; w.seed = (uint32_t)c->prm.seed;
     w.mut_thr = !(c->prm.mut_rate > 0) ? 0 : c->prm.mut_rate >= 1.0 ? 0x100000000ull : (uint64_t)ceil(c->prm.mut_rate * 4294967296.0);   // exact scaling by 2^32
     flow_gap_params(w.mut_thr, &w.gap_r, &w.gap_s);
-    w.lg = reinterpret_cast<const uint32_t *>(c->d_flow + 64);      // (behind the flow order: made in dwgsim_hip_create for every context)
+    w.lg = reinterpret_cast<const uint32_t *>(c->d_flow.get() + 64);      // (behind the flow order: made in dwgsim_hip_create for every context)
     return w;
 }
 
@@ -236,15 +234,17 @@ size_t padded_cells(const Group &g) { return (size_t)g.total + CELL_PAD; }
 SegTab seg_tab(const Group &g)
 {
     const int n = (int)g.m.size();
-    SegTab t; t.start = g.d_seg; t.len = g.d_seg + (n + 1); t.cindex = reinterpret_cast<const uint32_t *>(g.d_seg + (2 * n + 1)); t.n = n;
+    const int32_t *seg = g.mem.d_seg.get<int32_t>();
+    SegTab t; t.start = seg; t.len = seg + (n + 1); t.cindex = reinterpret_cast<const uint32_t *>(seg + (2 * n + 1)); t.n = n;
     return t;
 }
 
 void fill_haps(const Group &g, HapDev (&hap)[2])
 {
+    const GroupMem &M = g.mem;
     for (int h = 0; h < 2; ++h) {
-        hap[h].cells = g.d_cells[h]; hap[h].view = g.d_view[h]; hap[h].ins_pos = g.d_ins_pos[h]; hap[h].ins_len = g.d_ins_len[h];
-        hap[h].ins_off = g.d_ins_off[h]; hap[h].ins_bases = g.d_ins_bases[h]; hap[h].n_ins = g.n_ins[h]; hap[h].pos_off = 0;
+        hap[h].cells = M.d_cells[h].get(); hap[h].view = M.d_view[h].get(); hap[h].ins_pos = M.d_ins_pos[h].get<int32_t>(); hap[h].ins_len = M.d_ins_len[h].get<uint32_t>();
+        hap[h].ins_off = M.d_ins_off[h].get<uint32_t>(); hap[h].ins_bases = M.d_ins_bases[h].get(); hap[h].n_ins = g.n_ins[h]; hap[h].pos_off = 0;
     }
 }
 
@@ -252,22 +252,13 @@ ContigDev group_dev(const Group &g)
 {
     ContigDev d;
     fill_haps(g, d.hap);
-    d.ref = g.d_ref; d.l = g.total; d.seg = seg_tab(g);
+    d.ref = g.mem.d_ref.get(); d.l = g.total; d.seg = seg_tab(g);
     d.tot4 = nullptr; d.cap_bases[0] = d.cap_bases[1] = 0;
     return d;
 }
 
-void free_group(Group &g)
-{
-    hipFree(g.d_ref);
-    for (int h = 0; h < 2; ++h) { hipFree(g.d_cells[h]); hipFree(g.d_view[h]); hipFree(g.d_ins_pos[h]); hipFree(g.d_ins_len[h]); hipFree(g.d_ins_off[h]); hipFree(g.d_ins_bases[h]); hipFree(g.d_summ[h]); hipFree(g.d_summ2[h]); }
-    hipFree(g.d_refview); hipFree(g.d_refsumm); hipFree(g.d_refsumm2); hipFree(g.d_dirty);
-    hipFree(g.d_names); hipFree(g.d_reg); hipFree(g.d_seg);
-    if (g.ev_walk) hipEventDestroy(g.ev_walk);
-    if (g.ev_walk0) hipEventDestroy(g.ev_walk0);
-    if (g.h_wc) hipHostFree(g.h_wc);
-    g = Group();
-}
+// the inserted-base pool of haplotype h (its allocation holds 16 bytes more: ensure_ins)
+size_t ins_bases_cap(const Group &g, int h) { const size_t cap = g.mem.d_ins_bases[h].cap(); return cap ? cap - 16 : 0; }
 
 // contig handle -> its group and member (nullptr + error text for a handle that is unknown or was dropped)
 Group *get_group(dwgsim_hip_ctx_t *c, int contig, int *k = nullptr)
@@ -481,23 +472,22 @@ dwgsim_hip_ctx_t *dwgsim_hip_create(const dwgsim_hip_params_t *p, int device, in
         HIPC(c, hipStreamCreateWithPriority(&c->walk_stream, hipStreamDefault, prio_walk));
         HIPC(c, hipStreamCreateWithPriority(&c->count_stream, hipStreamDefault, prio_walk));
         HIPC(c, hipEventCreate(&c->ev_up)); HIPC(c, hipEventCreate(&c->ev_cnt0)); HIPC(c, hipEventCreate(&c->ev_cnt1));
-        HIPC(c, hipMalloc((void **)&c->d_counters, N_COUNTERS * sizeof(uint64_t)));
-        HIPC(c, hipHostMalloc((void **)&c->h_counters, N_COUNTERS * sizeof(uint64_t), hipHostMallocDefault));
-        HIPC(c, hipMalloc((void **)&c->d_wcounters, 16 * sizeof(uint64_t)));
-        HIPC(c, hipMalloc((void **)&c->d_pcounters, N_COUNTERS * sizeof(uint64_t)));
-        HIPC(c, hipHostMalloc((void **)&c->h_pcounters, N_COUNTERS * sizeof(uint64_t), hipHostMallocDefault));
-        HIPC(c, hipMalloc((void **)&c->d_chain, 4 * sizeof(uint64_t)));
-        HIPC(c, hipMemset(c->d_chain, 0, 4 * sizeof(uint64_t)));
+        const size_t cnt_bytes = N_COUNTERS * sizeof(uint64_t);
+        auto counters = [&](Counters &k) -> int { HIPC(c, reserve(c, k.d, cnt_bytes, cnt_bytes)); HIPC(c, k.h.reserve(cnt_bytes, cnt_bytes)); return 0; };
+        if (counters(c->counters)) return -1;
+        HIPC(c, reserve(c, c->d_wcounters, 16 * sizeof(uint64_t), 16 * sizeof(uint64_t)));
+        if (counters(c->pcounters)) return -1;
+        HIPC(c, reserve(c, c->d_chain, 4 * sizeof(uint64_t), 4 * sizeof(uint64_t)));
+        HIPC(c, hipMemset(c->d_chain.get(), 0, 4 * sizeof(uint64_t)));
         for (Slot &sl : c->slot) {
-            HIPC(c, hipMalloc((void **)&sl.d_counters, N_COUNTERS * sizeof(uint64_t)));
-            HIPC(c, hipHostMalloc((void **)&sl.h_counters, N_COUNTERS * sizeof(uint64_t), hipHostMallocDefault));
-            HIPC(c, hipMalloc((void **)&sl.d_rerun_chain, 2 * sizeof(uint64_t)));
+            if (counters(sl.counters)) return -1;
+            HIPC(c, reserve(c, sl.d_rerun_chain, 2 * sizeof(uint64_t), 2 * sizeof(uint64_t)));
             HIPC(c, hipEventCreate(&sl.ev_k0)); HIPC(c, hipEventCreate(&sl.ev_k1)); HIPC(c, hipEventCreate(&sl.ev_end)); HIPC(c, hipEventCreate(&sl.ev_done)); HIPC(c, hipEventCreate(&sl.ev_fetched));
         }
         {   // the flow order (64 bytes) and, behind it, the log2 table the flow model's gap draws interpolate in (dw_kernels.hpp flow_log2_table)
             std::vector<uint8_t> fl(64 + sizeof(uint32_t) * FLOW_LG_ENTRIES, 4); for (size_t i = 0; i < c->flow.size() && i < 64; ++i) fl[i] = c->flow[i];
             flow_log2_table(reinterpret_cast<uint32_t *>(fl.data() + 64));
-            HIPC(c, hipMalloc((void **)&c->d_flow, fl.size())); HIPC(c, hipMemcpy(c->d_flow, fl.data(), fl.size(), hipMemcpyHostToDevice));
+            if (upload(c, c->d_flow, fl.data(), fl.size())) return -1;
         }
         // -B (dwgsim_opt.c:415-457): rescale the flow error so that the per-base error rate of 10^6 random reads matches -e
         if (c->prm.data_type == 2 && c->prm.use_base_error) {
@@ -516,7 +506,7 @@ dwgsim_hip_ctx_t *dwgsim_hip_create(const dwgsim_hip_params_t *p, int device, in
                 ca.seed = (uint32_t)c->prm.seed; ca.end = i; ca.len = len; ca.n_reads = 1000000;       // ERROR_RATE_NUM_RANDOM_READS, dwgsim_opt.h:5
                 ca.thr = !(e > 0) ? 0 : e >= 1.0 ? 0x100000000ull : (uint64_t)ceil(e * 4294967296.0);
                 flow_gap_params(ca.thr, &ca.gap_r, &ca.gap_s);
-                ca.flow = c->d_flow; ca.flow_len = (int32_t)c->flow.size();
+                ca.flow = c->d_flow.get(); ca.flow_len = (int32_t)c->flow.size();
                 // a read that outgrows its buffers: once more with twice the room (the reference doubles its buffers, dwgsim.c:296-311) -- by the rule of
                 // dwgsim_hip_wait: up to FLOW_CAP_MAX bases per read.  The scratch holds a CHUNK of the 10^6 reads (at most ~2 GiB), so the room a read
                 // may take does not depend on how many reads there are (round 5 stopped at 16 x: -B then refused flow orders the simulate path handles)
@@ -530,17 +520,17 @@ dwgsim_hip_ctx_t *dwgsim_hip_create(const dwgsim_hip_params_t *p, int device, in
                     const size_t nblk = std::max<size_t>(1, std::min(nblk_all, ((size_t)2 << 30) / per_block));
                     ca.chunk_reads = (uint64_t)nblk * PAIRS_PER_BLOCK;
                     if (ensure(c, c->flow_scratch, per_block * nblk)) return -1;
-                    ca.scratch = (uint32_t *)c->flow_scratch.p; ca.counters = c->d_counters;
-                    HIPC(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(uint64_t), c->stream));
+                    ca.scratch = c->flow_scratch.get<uint32_t>(); ca.counters = c->counters.dev();
+                    HIPC(c, hipMemsetAsync(c->counters.dev(), 0, N_COUNTERS * sizeof(uint64_t), c->stream));
                     for (ca.first_read = 0; ca.first_read < ca.n_reads; ca.first_read += ca.chunk_reads) launch_calibrate(c->stream, ca);
-                    HIPC(c, hipMemcpyAsync(c->h_counters, c->d_counters, N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+                    HIPC(c, hipMemcpyAsync(c->counters.host(), c->counters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
                     HIPC(c, hipStreamSynchronize(c->stream));
-                    if (!c->h_counters[2] || base_cap * (int64_t)mult * 2 > (int64_t)FLOW_CAP_MAX) break;
+                    if (!c->counters.host()[2] || base_cap * (int64_t)mult * 2 > (int64_t)FLOW_CAP_MAX) break;
                 }
                 // the job's reads will need the room the calibration's needed: start there instead of running the first overflowing batch twice
                 if (mult > c->flow_cap_mult) c->flow_cap_mult = mult;
-                if (c->h_counters[2]) { c->err = "-B calibration: a read outgrew its flow-space buffer (the flow model's growth at this error rate and flow order: INTEGRATION.md)"; fail_code = DWGSIM_HIP_ERR_FAILED; return -1; }
-                const int32_t n_err = (int32_t)c->h_counters[8], counts = (int32_t)c->h_counters[9];       // int32 accumulators as in the reference
+                if (c->counters.host()[2]) { c->err = "-B calibration: a read outgrew its flow-space buffer (the flow model's growth at this error rate and flow order: INTEGRATION.md)"; fail_code = DWGSIM_HIP_ERR_FAILED; return -1; }
+                const int32_t n_err = (int32_t)c->counters.host()[8], counts = (int32_t)c->counters.host()[9];       // int32 accumulators as in the reference
                 sf = e / (n_err / (1.0 * counts));
                 c->prm.e_end[i] *= sf; c->prm.e_start[i] = c->prm.e_end[i];
                 fprintf(stderr, "[dwgsim_core] Updated with scaling factor %.5lf!\n", sf);
@@ -559,31 +549,27 @@ dwgsim_hip_ctx_t *dwgsim_hip_create(const dwgsim_hip_params_t *p, int device, in
                 if (ei > 0) q = (char)((int)(-10.0 * log(ei) / log(10.0) + 0.499) + '!'); else q = 40 + '!';
                 qb[(size_t)i] = (int8_t)q;
             }
-            HIPC(c, hipMalloc((void **)&c->d_thr[j], sizeof(uint64_t) * (size_t)n));
+            if (upload(c, c->d_thr[j], thr.data(), sizeof(uint64_t) * (size_t)n)) return -1;
             {   // packed table: n entries, then the last one repeated (>= 8 copies), the same word count for both read ends
                 const int lmax = c->prm.length[0] > c->prm.length[1] ? c->prm.length[0] : c->prm.length[1];
                 c->qb_words = (lmax + 4 + 3) / 4 + 2;      // (a block of the quality stream looks at eight positions: three words from any position <= lmax)
                 std::vector<int8_t> padded((size_t)c->qb_words * 4, qb[(size_t)n - 1]);
                 memcpy(padded.data(), qb.data(), (size_t)n);
-                HIPC(c, hipMalloc((void **)&c->d_qbase[j], padded.size()));
-                HIPC(c, hipMemcpy(c->d_qbase[j], padded.data(), padded.size(), hipMemcpyHostToDevice));
+                if (upload(c, c->d_qbase[j], padded.data(), padded.size())) return -1;
             }
-            HIPC(c, hipMemcpy(c->d_thr[j], thr.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
             std::vector<uint32_t> t32(((size_t)n + 7) / 8 * 8, 0u);
             for (int i = 0; i < n; ++i) {
                 if (thr[(size_t)i] >= 0x100000000ull) { t32[(size_t)i] = 0xFFFFFFFFu; c->e_full = 1; }
                 else t32[(size_t)i] = (uint32_t)thr[(size_t)i];
             }
             if (c->e_full) for (int i = 0; i < n; ++i) if (thr[(size_t)i] == 0xFFFFFFFFull) { c->err = "an error rate within 2^-32 of (but not equal to) 1 next to one equal to 1 is not representable"; return -1; }
-            HIPC(c, hipMalloc((void **)&c->d_thr32[j], sizeof(uint32_t) * t32.size()));
-            HIPC(c, hipMemcpy(c->d_thr32[j], t32.data(), sizeof(uint32_t) * t32.size(), hipMemcpyHostToDevice));
+            if (upload(c, c->d_thr32[j], t32.data(), sizeof(uint32_t) * t32.size())) return -1;
         }
         // device copy: '@' + "[prefix_]rand", zero padded to >= 256 + 16 bytes (the kernel stages 128 bytes in LDS)
         std::string rf = c->read_prefix.empty() ? std::string("rand") : c->read_prefix + "_rand";
         c->rand_fixed_len = (int32_t)rf.size();
         std::string rbuf = "@" + rf; rbuf.resize(rbuf.size() < 256 ? 272 : rbuf.size() + 16, '\0');
-        HIPC(c, hipMalloc((void **)&c->d_rand_fixed, rbuf.size()));
-        HIPC(c, hipMemcpy(c->d_rand_fixed, rbuf.data(), rbuf.size(), hipMemcpyHostToDevice));
+        if (upload(c, c->d_rand_fixed, rbuf.data(), rbuf.size())) return -1;
         return 0;
     };
     if (init() != 0) return fail("context initialisation failed");
@@ -597,12 +583,11 @@ dwgsim_hip_ctx_t *dwgsim_hip_create(const dwgsim_hip_params_t *p, int device, in
 extern "C" int dwgsim_hip_selftest_fp64(int device, uint32_t seed, uint64_t n, uint64_t *out)
 {
     if (!out || hipSetDevice(device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    uint64_t *d = nullptr;
-    if (hipMalloc((void **)&d, 4 * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
-    hipMemset(d, 0, 4 * sizeof(uint64_t));
-    launch_selftest_fp64(nullptr, seed, n, d);
-    const hipError_t e = hipMemcpy(out, d, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    hipFree(d);
+    DevMem d;
+    if (d.reserve(4 * sizeof(uint64_t), 4 * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
+    hipMemset(d.get(), 0, 4 * sizeof(uint64_t));
+    launch_selftest_fp64(nullptr, seed, n, d.get<uint64_t>());
+    const hipError_t e = hipMemcpy(out, d.get(), 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
     return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
 }
 
@@ -611,12 +596,11 @@ extern "C" int dwgsim_hip_selftest_fp64(int device, uint32_t seed, uint64_t n, u
 extern "C" int dwgsim_hip_selftest_text(int device, uint64_t first, uint64_t n, uint64_t stride, uint64_t *out)
 {
     if (!out || hipSetDevice(device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    uint64_t *d = nullptr;
-    if (hipMalloc((void **)&d, 4 * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
-    hipMemset(d, 0, 4 * sizeof(uint64_t));
-    launch_selftest_text(nullptr, first, n, stride, d);
-    const hipError_t e = hipMemcpy(out, d, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    hipFree(d);
+    DevMem d;
+    if (d.reserve(4 * sizeof(uint64_t), 4 * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
+    hipMemset(d.get(), 0, 4 * sizeof(uint64_t));
+    launch_selftest_text(nullptr, first, n, stride, d.get<uint64_t>());
+    const hipError_t e = hipMemcpy(out, d.get(), 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
     return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
 }
 
@@ -632,17 +616,16 @@ extern "C" int dwgsim_hip_selftest_gap(int device, uint64_t thr, uint32_t first,
     flow_log2_table(lg);
     uint64_t R; int32_t sR;
     flow_gap_params(thr, &R, &sR);
-    uint64_t *d = nullptr; uint32_t *d_lg = nullptr, *d_chg = nullptr;
-    const size_t chg_bytes = (size_t)g_cnt * sizeof(uint32_t);
-    if (hipMalloc((void **)&d, 4 * sizeof(uint64_t)) != hipSuccess || hipMalloc((void **)&d_lg, sizeof lg) != hipSuccess ||
-        hipMalloc((void **)&d_chg, chg_bytes ? chg_bytes : 4) != hipSuccess) { hipFree(d); hipFree(d_lg); return DWGSIM_HIP_ERR_NOMEM; }
-    hipMemset(d, 0, 4 * sizeof(uint64_t));
-    hipMemset(d_chg, 0, chg_bytes ? chg_bytes : 4);
-    hipMemcpy(d_lg, lg, sizeof lg, hipMemcpyHostToDevice);
-    launch_selftest_gap(nullptr, d_lg, R, sR, first, n, g_lo, g_cnt, d_chg, d);
-    hipError_t e = hipMemcpy(out, d, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && chg_bytes) e = hipMemcpy(chg, d_chg, chg_bytes, hipMemcpyDeviceToHost);
-    hipFree(d); hipFree(d_lg); hipFree(d_chg);
+    DevMem d, d_lg, d_chg;
+    const size_t chg_bytes = (size_t)g_cnt * sizeof(uint32_t), chg_alloc = chg_bytes ? chg_bytes : 4;
+    if (d.reserve(4 * sizeof(uint64_t), 4 * sizeof(uint64_t)) != hipSuccess || d_lg.reserve(sizeof lg, sizeof lg) != hipSuccess ||
+        d_chg.reserve(chg_alloc, chg_alloc) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
+    hipMemset(d.get(), 0, 4 * sizeof(uint64_t));
+    hipMemset(d_chg.get(), 0, chg_alloc);
+    hipMemcpy(d_lg.get(), lg, sizeof lg, hipMemcpyHostToDevice);
+    launch_selftest_gap(nullptr, d_lg.get<uint32_t>(), R, sR, first, n, g_lo, g_cnt, d_chg.get<uint32_t>(), d.get<uint64_t>());
+    hipError_t e = hipMemcpy(out, d.get(), 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && chg_bytes) e = hipMemcpy(chg, d_chg.get(), chg_bytes, hipMemcpyDeviceToHost);
     return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
 }
 
@@ -653,8 +636,9 @@ extern "C" int dwgsim_hip_selftest_gap(int device, uint64_t thr, uint32_t first,
 extern "C" int dwgsim_hip_selftest_lazy(int device, uint32_t first, uint64_t n, double sigma, int exhaustive, uint64_t *out)
 {
     if (!out || hipSetDevice(device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    uint64_t *d = nullptr;
-    if (hipMalloc((void **)&d, 12 * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
+    DevMem dm;
+    if (dm.reserve(12 * sizeof(uint64_t), 12 * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
+    uint64_t *d = dm.get<uint64_t>();
     hipMemset(d, 0, 12 * sizeof(uint64_t));
     float qk, qeps, qlmin; int32_t qnear1;
     lazy_quality_params(sigma, &qk, &qeps, &qlmin, &qnear1);
@@ -665,7 +649,6 @@ extern "C" int dwgsim_hip_selftest_lazy(int device, uint32_t first, uint64_t n, 
         launch_selftest_lazy(nullptr, 3, 0, 0x42000000u - 0x2B000000u, 0, 0, 0, 0, 0, d);           // [2^-41, 2^5)
     }
     const hipError_t e = hipMemcpy(out, d, 12 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    hipFree(d);
     return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
 }
 
@@ -677,26 +660,10 @@ void dwgsim_hip_destroy(dwgsim_hip_ctx_t *c)
     if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
     if (c->walk_stream) hipStreamSynchronize(c->walk_stream);
     if (c->count_stream) hipStreamSynchronize(c->count_stream);
-    for (auto &g : c->groups) if (g.alive) free_group(g);
-    for (auto &g : c->pool) free_group(g);
-    for (int j = 0; j < 2; ++j) { hipFree(c->d_thr[j]); hipFree(c->d_thr32[j]); hipFree(c->d_qbase[j]); }
-    for (DevBuf *b : {&c->meta, &c->fail_summ, &c->block_rand, &c->status_all, &c->split_state, &c->split_hand, &c->split_agg, &c->split_pre, &c->split_chunk, &c->place_segs, &c->place_rand, &c->place_list, &c->place_aux, &c->scratch_mask, &c->scratch_cnt, &c->scratch_status, &c->w_cand, &c->w_ev, &c->w_flags, &c->w_lo, &c->w_sufmin,
-                      &c->w_bound, &c->w_ppos, &c->w_pcells, &c->up_ascii, &c->l_pos, &c->l_cells, &c->flow_scratch, &c->flow_free, &c->w_slots, &c->w_slot_aux}) hipFree(b->p);
-    for (int s = 0; s < DWGSIM_HIP_SLOTS; ++s) for (int t = 0; t < 3; ++t) hipFree(c->out[s][t].p);
-    hipFree(c->d_rand_fixed); hipFree(c->d_counters); hipFree(c->d_wcounters); hipFree(c->d_pcounters); hipFree(c->d_flow); hipFree(c->d_chain); hipFree(c->d_crc_table); hipFree(c->d_crc_shift);
-    if (c->h_counters) hipHostFree(c->h_counters);
-    if (c->h_pcounters) hipHostFree(c->h_pcounters);
-    for (HostBuf *b : {&c->h_stage, &c->h_up, &c->h_place_segs, &c->h_range_rand}) free_host(*b);
     if (c->ev_up) hipEventDestroy(c->ev_up);
     if (c->ev_cnt0) hipEventDestroy(c->ev_cnt0);
     if (c->ev_cnt1) hipEventDestroy(c->ev_cnt1);
-    for (Slot &sl : c->slot) {
-        hipFree(sl.d_counters); hipFree(sl.d_rerun_chain); hipFree(sl.gz_status.p); hipFree(sl.segs.p);
-        for (int t = 0; t < 3; ++t) hipFree(sl.gz_out[t].p);
-        if (sl.h_counters) hipHostFree(sl.h_counters);
-        free_host(sl.h_segs);
-        for (hipEvent_t e : {sl.ev_k0, sl.ev_k1, sl.ev_end, sl.ev_done, sl.ev_fetched}) if (e) hipEventDestroy(e);
-    }
+    for (Slot &sl : c->slot) for (hipEvent_t e : {sl.ev_k0, sl.ev_k1, sl.ev_end, sl.ev_done, sl.ev_fetched}) if (e) hipEventDestroy(e);
     if (c->copy_stream) hipStreamDestroy(c->copy_stream);
     if (c->walk_stream) hipStreamDestroy(c->walk_stream);
     if (c->count_stream) hipStreamDestroy(c->count_stream);
@@ -739,39 +706,31 @@ int dwgsim_hip_add_contigs(dwgsim_hip_ctx_t *c, int n, const char *const *names,
     {   // memory of a dropped group, if one is large enough (the smallest such; none more than four times too large)
         const size_t want = (size_t)total + CELL_PAD;
         int best = -1;
-        for (size_t i = 0; i < c->pool.size(); ++i) if (c->pool[i].cap_cells >= want && c->pool[i].cap_cells <= 4 * want + (1u << 20) && (best < 0 || c->pool[i].cap_cells < c->pool[(size_t)best].cap_cells)) best = (int)i;
-        if (best >= 0) { g = c->pool[(size_t)best]; c->pool.erase(c->pool.begin() + best); }
-        // what describes the group that was dropped goes; the allocations and their capacities stay
-        g.mutated = g.walk_pending = false; g.m.clear(); g.h_names.clear(); g.h_reg.clear(); g.h_seg.clear(); g.fixed_max = 0; g.n_cand = 0;
-        g.n_ins[0] = g.n_ins[1] = g.n_ins_bases[0] = g.n_ins_bases[1] = 0; g.walk_attempt = 0; g.walk_cap = 0; g.walk_cap_bases = 0; g.walk_reset = false; g.n_patch = g.n_patch_ev = 0;
-        g.list_valid = false; g.pos.clear(); g.cells.clear(); g.ins[0] = HostIns(); g.ins[1] = HostIns(); g.dirty_any = g.dirty_all = false;
+        for (size_t i = 0; i < c->pool.size(); ++i) {
+            const size_t cap = c->pool[i].d_ref.cap();
+            if (cap >= want && cap <= 4 * want + (1u << 20) && (best < 0 || cap < c->pool[(size_t)best].d_ref.cap())) best = (int)i;
+        }
+        if (best >= 0) { g.mem = std::move(c->pool[(size_t)best]); c->pool.erase(c->pool.begin() + best); }
     }
+    GroupMem &M = g.mem;
     g.alive = true; g.total = total; g.first_handle = (int)c->handles.size();
     g.m.resize((size_t)n);
     for (int k = 0; k < n; ++k) { Member &m = g.m[(size_t)k]; m.name = names[k]; m.l = m.l_place = lens[k]; m.contig_index = contig_index[k]; m.start = (int32_t)starts[(size_t)k]; }
     const size_t padded = padded_cells(g);
     bool synced = true;
     auto fill = [&]() -> int {
-        if (!g.ev_walk) HIPC(c, hipEventCreate(&g.ev_walk));
-        if (!g.ev_walk0) HIPC(c, hipEventCreate(&g.ev_walk0));
-        if (!g.h_wc) HIPC(c, hipHostMalloc((void **)&g.h_wc, 16 * sizeof(uint64_t), hipHostMallocDefault));
-        if (g.cap_cells < padded) {
-            hipFree(g.d_ref); hipFree(g.d_refview); hipFree(g.d_refsumm); hipFree(g.d_refsumm2); hipFree(g.d_dirty);
-            g.d_ref = g.d_refview = nullptr; g.d_refsumm = g.d_refsumm2 = nullptr; g.d_dirty = nullptr;
-            for (int h = 0; h < 2; ++h) { hipFree(g.d_cells[h]); hipFree(g.d_view[h]); hipFree(g.d_summ[h]); hipFree(g.d_summ2[h]); g.d_cells[h] = g.d_view[h] = nullptr; g.d_summ[h] = g.d_summ2[h] = nullptr; }
-            g.cap_cells = 0;
-            HIPC(c, dev_malloc(c, (void **)&g.d_ref, padded));
-            for (int h = 0; h < 2; ++h) {
-                HIPC(c, dev_malloc(c, (void **)&g.d_cells[h], padded)); HIPC(c, dev_malloc(c, (void **)&g.d_view[h], padded / 2 + 32));
-                HIPC(c, dev_malloc(c, (void **)&g.d_summ[h], sizeof(uint16_t) * (padded / SUMM_CELLS + 16))); HIPC(c, dev_malloc(c, (void **)&g.d_summ2[h], sizeof(uint16_t) * (padded / SUMM2_CELLS + 16)));
-            }
-            HIPC(c, dev_malloc(c, (void **)&g.d_refview, padded / 2 + 32)); HIPC(c, dev_malloc(c, (void **)&g.d_refsumm, sizeof(uint16_t) * (padded / SUMM_CELLS + 16))); HIPC(c, dev_malloc(c, (void **)&g.d_refsumm2, sizeof(uint16_t) * (padded / SUMM2_CELLS + 16)));
-            HIPC(c, dev_malloc(c, (void **)&g.d_dirty, sizeof(uint32_t) * ((padded + 32 * SUMM_CELLS - 1) / (32 * SUMM_CELLS) + 2)));
-            g.cap_cells = padded;
+        HIPC(c, M.ev_walk.create()); HIPC(c, M.ev_walk0.create());
+        HIPC(c, M.h_wc.reserve(16 * sizeof(uint64_t), 16 * sizeof(uint64_t)));
+        if (M.d_ref.cap() < padded) {      // the buffers of cells go and come together (d_ref's capacity stands for all of them)
+            DevMem *cellbufs[] = {&M.d_ref, &M.d_cells[0], &M.d_view[0], &M.d_summ[0], &M.d_summ2[0], &M.d_cells[1], &M.d_view[1], &M.d_summ[1], &M.d_summ2[1], &M.d_refview, &M.d_refsumm, &M.d_refsumm2, &M.d_dirty};
+            for (DevMem *b : cellbufs) b->reset();
+            const size_t view = padded / 2 + 32, summ = sizeof(uint16_t) * (padded / SUMM_CELLS + 16), summ2 = sizeof(uint16_t) * (padded / SUMM2_CELLS + 16);
+            const size_t sizes[] = {padded, padded, view, summ, summ2, padded, view, summ, summ2, view, summ, summ2, sizeof(uint32_t) * ((padded + 32 * SUMM_CELLS - 1) / (32 * SUMM_CELLS) + 2)};
+            for (size_t i = 0; i < sizeof sizes / sizeof sizes[0]; ++i) HIPC(c, reserve(c, *cellbufs[i], sizes[i], sizes[i]));
         }
         g.n_dirty_words = (uint32_t)((padded + 32 * SUMM_CELLS - 1) / (32 * SUMM_CELLS));
         if (ensure(c, c->up_ascii, padded)) return DWGSIM_HIP_ERR_DEVICE;
-        uint8_t *d_ascii = (uint8_t *)c->up_ascii.p;
+        uint8_t *d_ascii = c->up_ascii.get();
         // The sequence goes up on the walk stream.  One copy when the caller's buffers already are the group layout inside ONE page-locked
         // allocation (ascii[k] = ascii[0] + start[k], zero bytes between the contigs): nothing is staged and the call does not wait -- the
         // buffers must then stay as they are until dwgsim_hip_mutate_wait returned.  A few contigs: one copy each into a zeroed device buffer.
@@ -787,8 +746,8 @@ int dwgsim_hip_add_contigs(dwgsim_hip_ctx_t *c, int n, const char *const *names,
             for (int k = 0; k < n; ++k) if (lens[k] > 0) HIPC(c, hipMemcpyAsync(d_ascii + starts[(size_t)k], ascii[k], (size_t)lens[k], hipMemcpyHostToDevice, c->walk_stream));
         } else {
             if (c->up_in_flight) { HIPC(c, hipEventSynchronize(c->ev_up)); c->up_in_flight = false; }
-            if (const int rc = ensure_host(c, c->h_up, (size_t)total, (size_t)total + (size_t)total / 4 + 4096)) return rc;
-            uint8_t *h_up = (uint8_t *)c->h_up.p;
+            HIPC(c, c->h_up.reserve((size_t)total, (size_t)total + (size_t)total / 4 + 4096));
+            uint8_t *h_up = c->h_up.get();
             for (int k = 0; k < n; ++k) {
                 const int64_t end = starts[(size_t)k] + lens[k], next = k + 1 < n ? starts[(size_t)k + 1] : total;
                 if (lens[k] > 0) memcpy(h_up + starts[(size_t)k], ascii[k], (size_t)lens[k]);
@@ -798,43 +757,48 @@ int dwgsim_hip_add_contigs(dwgsim_hip_ctx_t *c, int n, const char *const *names,
             HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream));
             HIPC(c, hipEventRecord(c->ev_up, c->walk_stream)); c->up_in_flight = true;
         }
-        launch_pack(c->walk_stream, d_ascii, g.d_ref, g.d_cells[0], g.d_cells[1], (int64_t)padded & ~(int64_t)15);
+        uint8_t *ref = M.d_ref.get(), *refview = M.d_refview.get();
+        uint16_t *refsumm = M.d_refsumm.get<uint16_t>(), *refsumm2 = M.d_refsumm2.get<uint16_t>();
+        launch_pack(c->walk_stream, d_ascii, ref, M.d_cells[0].get(), M.d_cells[1].get(), (int64_t)padded & ~(int64_t)15);
         // the read views and summaries of the unmutated group, once: the pristine copies, and what both haplotypes start from (a walk then rewrites
         // only the chunks it touches)
-        launch_make_view(c->walk_stream, g.d_ref, g.d_ref, (int64_t)padded & ~(int64_t)15, g.total, g.d_refview, g.d_view[0], g.d_refsumm, g.d_summ[0], g.d_refsumm2, g.d_summ2[0]);
-        HIPC(c, hipMemcpyAsync(g.d_view[1], g.d_refview, padded / 2, hipMemcpyDeviceToDevice, c->walk_stream));
-        HIPC(c, hipMemcpyAsync(g.d_summ[1], g.d_refsumm, sizeof(uint16_t) * (padded / SUMM_CELLS), hipMemcpyDeviceToDevice, c->walk_stream));
-        HIPC(c, hipMemcpyAsync(g.d_summ2[1], g.d_refsumm2, sizeof(uint16_t) * (padded / SUMM2_CELLS), hipMemcpyDeviceToDevice, c->walk_stream));
-        HIPC(c, hipMemsetAsync(g.d_dirty, 0, sizeof(uint32_t) * ((size_t)g.n_dirty_words + 2), c->walk_stream));
+        launch_make_view(c->walk_stream, ref, ref, (int64_t)padded & ~(int64_t)15, g.total, refview, M.d_view[0].get(), refsumm, M.d_summ[0].get<uint16_t>(), refsumm2, M.d_summ2[0].get<uint16_t>());
+        HIPC(c, hipMemcpyAsync(M.d_view[1].get(), refview, padded / 2, hipMemcpyDeviceToDevice, c->walk_stream));
+        HIPC(c, hipMemcpyAsync(M.d_summ[1].get(), refsumm, sizeof(uint16_t) * (padded / SUMM_CELLS), hipMemcpyDeviceToDevice, c->walk_stream));
+        HIPC(c, hipMemcpyAsync(M.d_summ2[1].get(), refsumm2, sizeof(uint16_t) * (padded / SUMM2_CELLS), hipMemcpyDeviceToDevice, c->walk_stream));
+        HIPC(c, hipMemsetAsync(M.d_dirty.get(), 0, sizeof(uint32_t) * ((size_t)g.n_dirty_words + 2), c->walk_stream));
         HIPC(c, hipGetLastError());
         // segment table, name pool, target regions
-        g.h_seg.resize((size_t)(3 * n + 1));
-        for (int k = 0; k < n; ++k) { g.h_seg[(size_t)k] = g.m[(size_t)k].start; g.h_seg[(size_t)(n + 1 + k)] = (int32_t)g.m[(size_t)k].l; g.h_seg[(size_t)(2 * n + 1 + k)] = (int32_t)g.m[(size_t)k].contig_index; }
-        g.h_seg[(size_t)n] = (int32_t)total;
-        if (g.cap_seg < g.h_seg.size()) { hipFree(g.d_seg); g.d_seg = nullptr; g.cap_seg = 0; HIPC(c, hipMalloc((void **)&g.d_seg, sizeof(int32_t) * (g.h_seg.size() + 64))); g.cap_seg = g.h_seg.size() + 64; }
-        HIPC(c, hipMemcpyAsync(g.d_seg, g.h_seg.data(), sizeof(int32_t) * g.h_seg.size(), hipMemcpyHostToDevice, c->walk_stream));
+        std::vector<int32_t> &h_seg = M.h_seg, &h_reg = M.h_reg; std::vector<uint8_t> &h_names = M.h_names;
+        h_seg.assign((size_t)(3 * n + 1), 0);
+        for (int k = 0; k < n; ++k) { h_seg[(size_t)k] = g.m[(size_t)k].start; h_seg[(size_t)(n + 1 + k)] = (int32_t)g.m[(size_t)k].l; h_seg[(size_t)(2 * n + 1 + k)] = (int32_t)g.m[(size_t)k].contig_index; }
+        h_seg[(size_t)n] = (int32_t)total;
+        HIPC(c, reserve(c, M.d_seg, sizeof(int32_t) * h_seg.size(), sizeof(int32_t) * (h_seg.size() + 64)));
+        HIPC(c, hipMemcpyAsync(M.d_seg.get(), h_seg.data(), sizeof(int32_t) * h_seg.size(), hipMemcpyHostToDevice, c->walk_stream));
+        h_names.clear();
         for (int k = 0; k < n; ++k) {      // '@' + "[prefix_]name", zero padded to >= 256 + 16 bytes (the kernel stages 128 bytes in LDS), entries 16-byte aligned
             Member &m = g.m[(size_t)k];
             const std::string nf = c->read_prefix.empty() ? m.name : c->read_prefix + "_" + m.name;
-            m.name_fixed_len = (int32_t)nf.size(); m.name_off = (uint32_t)g.h_names.size();
+            m.name_fixed_len = (int32_t)nf.size(); m.name_off = (uint32_t)h_names.size();
             if (m.name_fixed_len > g.fixed_max) g.fixed_max = m.name_fixed_len;
             const size_t room = ((nf.size() + 1 < 256 ? 272 : nf.size() + 1 + 16) + 15) & ~(size_t)15;
-            g.h_names.resize(g.h_names.size() + room, 0);
-            g.h_names[m.name_off] = '@'; memcpy(&g.h_names[m.name_off + 1], nf.data(), nf.size());
+            h_names.resize(h_names.size() + room, 0);
+            h_names[m.name_off] = '@'; memcpy(&h_names[m.name_off + 1], nf.data(), nf.size());
         }
-        if (g.cap_names < g.h_names.size()) { hipFree(g.d_names); g.d_names = nullptr; g.cap_names = 0; HIPC(c, hipMalloc((void **)&g.d_names, g.h_names.size() + 4096)); g.cap_names = g.h_names.size() + 4096; }
-        HIPC(c, hipMemcpyAsync(g.d_names, g.h_names.data(), g.h_names.size(), hipMemcpyHostToDevice, c->walk_stream));
+        HIPC(c, reserve(c, M.d_names, h_names.size(), h_names.size() + 4096));
+        HIPC(c, hipMemcpyAsync(M.d_names.get(), h_names.data(), h_names.size(), hipMemcpyHostToDevice, c->walk_stream));
+        h_reg.clear();
         if (c->has_regions) {
             for (int k = 0; k < n; ++k) {
                 Member &m = g.m[(size_t)k];
                 std::vector<int32_t> st, en; int64_t tot = 0;
                 for (size_t q = 0; q < c->regions.contig.size(); ++q) if (c->regions.contig[q] == m.contig_index) { st.push_back((int32_t)c->regions.start[q]); en.push_back((int32_t)c->regions.end[q]); tot += c->regions.end[q] - c->regions.start[q]; }
-                m.reg_off = (int32_t)g.h_reg.size(); m.n_reg = (int32_t)st.size(); m.l_place = tot;
-                g.h_reg.insert(g.h_reg.end(), st.begin(), st.end()); g.h_reg.insert(g.h_reg.end(), en.begin(), en.end());
+                m.reg_off = (int32_t)h_reg.size(); m.n_reg = (int32_t)st.size(); m.l_place = tot;
+                h_reg.insert(h_reg.end(), st.begin(), st.end()); h_reg.insert(h_reg.end(), en.begin(), en.end());
             }
-            g.h_reg.push_back(0);
-            if (g.cap_reg < g.h_reg.size()) { hipFree(g.d_reg); g.d_reg = nullptr; g.cap_reg = 0; HIPC(c, hipMalloc((void **)&g.d_reg, sizeof(int32_t) * (g.h_reg.size() + 64))); g.cap_reg = g.h_reg.size() + 64; }
-            HIPC(c, hipMemcpyAsync(g.d_reg, g.h_reg.data(), sizeof(int32_t) * g.h_reg.size(), hipMemcpyHostToDevice, c->walk_stream));
+            h_reg.push_back(0);
+            HIPC(c, reserve(c, M.d_reg, sizeof(int32_t) * h_reg.size(), sizeof(int32_t) * (h_reg.size() + 64)));
+            HIPC(c, hipMemcpyAsync(M.d_reg.get(), h_reg.data(), sizeof(int32_t) * h_reg.size(), hipMemcpyHostToDevice, c->walk_stream));
         }
         // -m / -b / -v: the file's entries for these contigs are resolved now, while the sequence is at hand (mut.c:644-745)
         if (c->has_mutin) for (int k = 0; k < n; ++k) resolve_mutation_input(c->mutin, g.m[(size_t)k].contig_index, ascii[k], lens[k], (uint32_t)c->prm.seed, c->prm.is_hap != 0, g.m[(size_t)k].rc);
@@ -842,7 +806,7 @@ int dwgsim_hip_add_contigs(dwgsim_hip_ctx_t *c, int n, const char *const *names,
         return 0;
     };
     const int rc = fill();
-    if (rc != 0) { (void)hipStreamSynchronize(c->walk_stream); free_group(g); return rc; }      // no half-built group stays behind a failed call
+    if (rc != 0) { (void)hipStreamSynchronize(c->walk_stream); g = Group(); return rc; }      // no half-built group stays behind a failed call
     for (int k = 0; k < n; ++k) c->handles.push_back(HandleRef{gid, k});
     return g.first_handle;
 }
@@ -864,16 +828,15 @@ int dwgsim_hip_drop_contig(dwgsim_hip_ctx_t *c, int contig)
     // a batch of the group that was enqueued and not yet waited for: its wait may have to run it AGAIN (an Ion Torrent read that outgrew its buffers,
     // dwgsim_hip_wait), which needs the group -- wait first, then drop (include/dwgsim_hip.h)
     for (int s = 0; s < DWGSIM_HIP_SLOTS; ++s) if (c->slot[s].pending && !c->slot[s].empty && c->slot[s].group == gid) { c->err = "drop_contig: a batch that reads this group has not been waited for (dwgsim_hip_wait first)"; return DWGSIM_HIP_ERR_STATE; }
-    if (g->walk_pending) hipEventSynchronize(g->ev_walk);
+    if (g->walk_pending) hipEventSynchronize(g->mem.ev_walk.get());
     for (size_t k = 0; k < g->m.size(); ++k) { if (c->chain_contig == g->first_handle + (int)k) c->chain_contig = -1; c->handles[(size_t)g->first_handle + k].group = -1; }
     // the group's memory waits for the next group (at most three sets are kept: the one that has waited longest goes -- a set that no later
     // group can use, e.g. one more than four times too large, does not stay for the life of the context; round 5 dropped the smallest)
-    g->alive = false;
-    c->pool.push_back(*g);
+    c->pool.push_back(std::move(g->mem));
     *g = Group();
     if (c->pool.size() > 3) {
         hipStreamSynchronize(c->walk_stream);
-        free_group(c->pool[0]); c->pool.erase(c->pool.begin());
+        c->pool.erase(c->pool.begin());
     }
     return DWGSIM_HIP_OK;
 }
@@ -949,18 +912,14 @@ static int mut_debug_verdict(dwgsim_hip_ctx_t *c, const Group &g, uint64_t pre, 
     return DWGSIM_HIP_ERR_FAILED;
 }
 
-// The insertion tables of haplotype h of a group: room for `entries` entries (+ 25 % + 64) and `bases` inserted bases (+ 25 % + 256)
+// The insertion tables of haplotype h of a group: room for `entries` entries (+ 25 % + 64) and `bases` inserted bases (+ 25 % + 256; the
+// allocation holds 16 bytes more: ins_bases_cap)
 static int ensure_ins(dwgsim_hip_ctx_t *c, Group &g, int h, size_t entries, size_t bases)
 {
-    if (entries > g.cap_ins[h]) {
-        hipFree(g.d_ins_pos[h]); hipFree(g.d_ins_len[h]); hipFree(g.d_ins_off[h]);
-        g.d_ins_pos[h] = nullptr; g.d_ins_len[h] = g.d_ins_off[h] = nullptr;
-        g.cap_ins[h] = entries + entries / 4 + 64;
-        HIPC(c, hipMalloc((void **)&g.d_ins_pos[h], sizeof(int32_t) * g.cap_ins[h]));
-        HIPC(c, hipMalloc((void **)&g.d_ins_len[h], sizeof(uint32_t) * g.cap_ins[h]));
-        HIPC(c, hipMalloc((void **)&g.d_ins_off[h], sizeof(uint32_t) * g.cap_ins[h]));
-    }
-    if (bases > g.cap_bases[h]) { hipFree(g.d_ins_bases[h]); g.d_ins_bases[h] = nullptr; g.cap_bases[h] = bases + bases / 4 + 256; HIPC(c, hipMalloc((void **)&g.d_ins_bases[h], g.cap_bases[h] + 16)); }
+    GroupMem &M = g.mem;
+    const size_t want = sizeof(int32_t) * (entries + entries / 4 + 64);      // (int32 / uint32 entries alike)
+    for (DevMem *b : {&M.d_ins_pos[h], &M.d_ins_len[h], &M.d_ins_off[h]}) HIPC(c, reserve(c, *b, sizeof(int32_t) * entries, want));
+    HIPC(c, reserve(c, M.d_ins_bases[h], bases + 16, bases + bases / 4 + 256 + 16));
     return DWGSIM_HIP_OK;
 }
 
@@ -968,6 +927,22 @@ static int ensure_ins(dwgsim_hip_ctx_t *c, Group &g, int h, size_t entries, size
 // capacity (candidate sites are a Binomial(l, mut_rate) draw: mean + 8 sigma), the kernels take their element counts from device memory, and
 // the read-back at the end (dwgsim_hip_mutate_wait) also tells whether a capacity was exceeded -- then the walk is simply run again with
 // exact sizes.
+// the read views and summaries of both haplotypes, made from every cell
+static void make_views(hipStream_t st, const Group &g)
+{
+    const GroupMem &M = g.mem;
+    launch_make_view(st, M.d_cells[0].get(), M.d_cells[1].get(), (int64_t)padded_cells(g) & ~(int64_t)15, g.total, M.d_view[0].get(), M.d_view[1].get(),
+                     M.d_summ[0].get<uint16_t>(), M.d_summ[1].get<uint16_t>(), M.d_summ2[0].get<uint16_t>(), M.d_summ2[1].get<uint16_t>());
+}
+
+// dw_walk.hip k_dirty_chunks over the group's bitmap: restore = the chunks go back to the pristine copies, else their views and summaries are made again
+static void dirty_chunks(hipStream_t st, bool restore, const Group &g)
+{
+    const GroupMem &M = g.mem;
+    launch_dirty_chunks(st, restore, M.d_dirty.get<uint32_t>(), g.n_dirty_words, g.total, M.d_ref.get(), M.d_refview.get(), M.d_refsumm.get<uint16_t>(), M.d_refsumm2.get<uint16_t>(),
+                        M.d_cells[0].get(), M.d_cells[1].get(), M.d_view[0].get(), M.d_view[1].get(), M.d_summ[0].get<uint16_t>(), M.d_summ[1].get<uint16_t>(), M.d_summ2[0].get<uint16_t>(), M.d_summ2[1].get<uint16_t>());
+}
+
 static int enqueue_walk(dwgsim_hip_ctx_t *c, Group &g)
 {
     const WalkParams wp = walk_params(c);
@@ -975,50 +950,52 @@ static int enqueue_walk(dwgsim_hip_ctx_t *c, Group &g)
     const size_t padded = padded_cells(g);
     hipStream_t st = c->walk_stream;
     const SegTab seg = seg_tab(g);
-    HIPC(c, hipEventRecord(g.ev_walk0, st));
+    const GroupMem &M = g.mem;
+    uint64_t *wcnt = c->d_wcounters.get<uint64_t>(), *wc = M.h_wc.get<uint64_t>();      // the walk's counters and the group's mirror of them
+    HIPC(c, hipEventRecord(M.ev_walk0.get(), st));
     if (c->has_mutin) {      // file-driven mutations (mut.c:644-745): the host resolved the entries, the GPU scatters and left-justifies
         const uint32_t np = g.n_patch, nev = g.n_patch_ev;
-        if (g.walk_reset) for (int h = 0; h < 2; ++h) HIPC(c, hipMemcpyAsync(g.d_cells[h], g.d_ref, padded, hipMemcpyDeviceToDevice, st));
-        HIPC(c, hipMemsetAsync(&c->d_wcounters[12], 0xff, 2 * sizeof(uint64_t), st));
+        if (g.walk_reset) for (int h = 0; h < 2; ++h) HIPC(c, hipMemcpyAsync(M.d_cells[h].get(), M.d_ref.get(), padded, hipMemcpyDeviceToDevice, st));
+        HIPC(c, hipMemsetAsync(&wcnt[12], 0xff, 2 * sizeof(uint64_t), st));
         if (np) {
             if (ensure(c, c->w_ppos, sizeof(int32_t) * np) || ensure(c, c->w_pcells, sizeof(uint16_t) * np) || ensure(c, c->w_ev, sizeof(Event) * (nev ? nev : 1)) ||
                 ensure(c, c->w_lo, sizeof(int32_t) * (nev ? nev : 1)) || ensure(c, c->w_sufmin, sizeof(int32_t) * ((nev ? nev : 1) + 64)) || ensure(c, c->w_bound, nev ? nev : 1)) return DWGSIM_HIP_ERR_DEVICE;      // (+ 64: segment minima of k_sufmin)
-            HIPC(c, hipMemcpyAsync(c->w_ppos.p, c->h_ppos.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
-            HIPC(c, hipMemcpyAsync(c->w_pcells.p, c->h_pcells.data(), sizeof(uint16_t) * np, hipMemcpyHostToDevice, st));
-            if (nev) HIPC(c, hipMemcpyAsync(c->w_ev.p, c->h_pev.data(), sizeof(Event) * nev, hipMemcpyHostToDevice, st));
-            launch_apply_patches(st, (const int32_t *)c->w_ppos.p, (const uint16_t *)c->w_pcells.p, np, g.d_cells[0], g.d_cells[1]);
+            HIPC(c, hipMemcpyAsync(c->w_ppos.get(), c->h_ppos.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
+            HIPC(c, hipMemcpyAsync(c->w_pcells.get(), c->h_pcells.data(), sizeof(uint16_t) * np, hipMemcpyHostToDevice, st));
+            if (nev) HIPC(c, hipMemcpyAsync(c->w_ev.get(), c->h_pev.data(), sizeof(Event) * nev, hipMemcpyHostToDevice, st));
+            launch_apply_patches(st, c->w_ppos.get<int32_t>(), c->w_pcells.get<uint16_t>(), np, M.d_cells[0].get(), M.d_cells[1].get());
             const ContigDev cd = group_dev(g);
-            launch_mut_debug(st, g.d_ref, g.d_cells[0], g.d_cells[1], total, &c->d_wcounters[12]);      // mut.c:753
+            launch_mut_debug(st, M.d_ref.get(), M.d_cells[0].get(), M.d_cells[1].get(), total, &wcnt[12]);      // mut.c:753
             if (nev) {
-                if (c->seq_justify) launch_justify_seq(st, (const Event *)c->w_ev.p, Count{nullptr, nev}, cd);
-                else launch_justify(st, (const Event *)c->w_ev.p, Count{nullptr, nev}, cd, (int32_t *)c->w_lo.p, (int32_t *)c->w_sufmin.p, (uint8_t *)c->w_bound.p);
+                if (c->seq_justify) launch_justify_seq(st, c->w_ev.get<Event>(), Count{nullptr, nev}, cd);
+                else launch_justify(st, c->w_ev.get<Event>(), Count{nullptr, nev}, cd, c->w_lo.get<int32_t>(), c->w_sufmin.get<int32_t>(), c->w_bound.get<uint8_t>());
             }
-            launch_mut_debug(st, g.d_ref, g.d_cells[0], g.d_cells[1], total, &c->d_wcounters[13]);      // mut.c:757
+            launch_mut_debug(st, M.d_ref.get(), M.d_cells[0].get(), M.d_cells[1].get(), total, &wcnt[13]);      // mut.c:757
         }
-        launch_make_view(st, g.d_cells[0], g.d_cells[1], (int64_t)padded & ~(int64_t)15, g.total, g.d_view[0], g.d_view[1], g.d_summ[0], g.d_summ[1], g.d_summ2[0], g.d_summ2[1]);
+        make_views(st, g);
         g.dirty_all = true;
         HIPC(c, hipGetLastError());
-        HIPC(c, hipMemcpyAsync(&g.h_wc[12], &c->d_wcounters[12], 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIPC(c, hipEventRecord(g.ev_walk, st));
+        HIPC(c, hipMemcpyAsync(&wc[12], &wcnt[12], 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPC(c, hipEventRecord(M.ev_walk.get(), st));
         return DWGSIM_HIP_OK;
     }
     const uint32_t nblk = (uint32_t)((total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
     if (ensure(c, c->scratch_status, ((size_t)nblk + 2) * sizeof(uint64_t))) return DWGSIM_HIP_ERR_DEVICE;      // look-back words of k_site_scan_list + its ticket
-    uint64_t *d_status = (uint64_t *)c->scratch_status.p, *d_ticket = d_status + nblk;
+    uint64_t *d_status = c->scratch_status.get<uint64_t>(), *d_ticket = d_status + nblk;
     // where the group stands: fresh from the upload, or with the chunks the previous walk wrote -- those go back to the pristine copies --, or (a
     // capacity re-run, a walk that kept no bitmap) all of it
     if (g.walk_attempt > 0 || g.dirty_all) {
         for (int h = 0; h < 2; ++h) {
-            HIPC(c, hipMemcpyAsync(g.d_cells[h], g.d_ref, padded, hipMemcpyDeviceToDevice, st));
-            HIPC(c, hipMemcpyAsync(g.d_view[h], g.d_refview, padded / 2, hipMemcpyDeviceToDevice, st));
-            HIPC(c, hipMemcpyAsync(g.d_summ[h], g.d_refsumm, sizeof(uint16_t) * (padded / SUMM_CELLS), hipMemcpyDeviceToDevice, st));
-            HIPC(c, hipMemcpyAsync(g.d_summ2[h], g.d_refsumm2, sizeof(uint16_t) * (padded / SUMM2_CELLS), hipMemcpyDeviceToDevice, st));
+            HIPC(c, hipMemcpyAsync(M.d_cells[h].get(), M.d_ref.get(), padded, hipMemcpyDeviceToDevice, st));
+            HIPC(c, hipMemcpyAsync(M.d_view[h].get(), M.d_refview.get(), padded / 2, hipMemcpyDeviceToDevice, st));
+            HIPC(c, hipMemcpyAsync(M.d_summ[h].get(), M.d_refsumm.get(), sizeof(uint16_t) * (padded / SUMM_CELLS), hipMemcpyDeviceToDevice, st));
+            HIPC(c, hipMemcpyAsync(M.d_summ2[h].get(), M.d_refsumm2.get(), sizeof(uint16_t) * (padded / SUMM2_CELLS), hipMemcpyDeviceToDevice, st));
         }
-        HIPC(c, hipMemsetAsync(g.d_dirty, 0, sizeof(uint32_t) * ((size_t)g.n_dirty_words + 2), st));
+        HIPC(c, hipMemsetAsync(M.d_dirty.get(), 0, sizeof(uint32_t) * ((size_t)g.n_dirty_words + 2), st));
         g.dirty_all = false; g.dirty_any = false;
     } else if (g.dirty_any) {
-        launch_dirty_chunks(st, true, g.d_dirty, g.n_dirty_words, g.total, g.d_ref, g.d_refview, g.d_refsumm, g.d_refsumm2, g.d_cells[0], g.d_cells[1], g.d_view[0], g.d_view[1], g.d_summ[0], g.d_summ[1], g.d_summ2[0], g.d_summ2[1]);
-        HIPC(c, hipMemsetAsync(g.d_dirty, 0, sizeof(uint32_t) * ((size_t)g.n_dirty_words + 2), st));
+        dirty_chunks(st, true, g);
+        HIPC(c, hipMemsetAsync(M.d_dirty.get(), 0, sizeof(uint32_t) * ((size_t)g.n_dirty_words + 2), st));
         g.dirty_any = false;
     }
     const uint32_t cap = g.walk_cap; const size_t cap_bases = g.walk_cap_bases;
@@ -1029,10 +1006,10 @@ static int enqueue_walk(dwgsim_hip_ctx_t *c, Group &g)
         ensure(c, c->w_bound, ncap)) return DWGSIM_HIP_ERR_DEVICE;
     // insertion tables: at most one entry per candidate; the base pools are checked on the device
     for (int h = 0; h < 2; ++h) if (const int rc = ensure_ins(c, g, h, ncap, cap_bases)) return rc;
-    int32_t *d_cand = (int32_t *)c->w_cand.p; Event *d_ev = (Event *)c->w_ev.p; uint4 *d_flags = (uint4 *)c->w_flags.p;
-    uint32_t *d_small = reinterpret_cast<uint32_t *>(&c->d_wcounters[8]);   // [0] max_del, [1..4] tot4: eight words in counters[8..11], so that one copy brings counters[7..11] back
-    const Count nc{&c->d_wcounters[7], cap};
-    HIPC(c, hipMemsetAsync(&c->d_wcounters[7], 0, 5 * sizeof(uint64_t), st));
+    int32_t *d_cand = c->w_cand.get<int32_t>(); Event *d_ev = c->w_ev.get<Event>(); uint4 *d_flags = c->w_flags.get<uint4>();
+    uint32_t *d_small = reinterpret_cast<uint32_t *>(&wcnt[8]);   // [0] max_del, [1..4] tot4: eight words in counters[8..11], so that one copy brings counters[7..11] back
+    const Count nc{&wcnt[7], cap};
+    HIPC(c, hipMemsetAsync(&wcnt[7], 0, 5 * sizeof(uint64_t), st));
     // K1: candidate sites -> ordered list, from the pristine 4-bit view.  First attempt: every block into a slot of its own, no block waits for another
     // (dw_walk.hip k_site_scan_slots: mean + 8 sigma + 32 entries per block of 65 536 positions); a re-run, a mutation rate at which the slots would
     // be as large as the list itself, or "site_slots" = 0: one kernel with a decoupled look-back
@@ -1045,37 +1022,37 @@ static int enqueue_walk(dwgsim_hip_ctx_t *c, Group &g)
         const bool use_slots = g.walk_attempt == 0 && c->site_slots != 0 && nbs > 0 && (c->site_slots > 0 || slot_bytes <= std::max<size_t>((size_t)64 << 20, (size_t)ncap * 16));
         if (use_slots) {
             if (ensure(c, c->w_slots, slot_bytes) || ensure(c, c->w_slot_aux, 2 * (size_t)nbs * sizeof(uint32_t))) return DWGSIM_HIP_ERR_DEVICE;
-            launch_site_scan_slots(st, g.d_refview, total, seg, wp, (int32_t *)c->w_slots.p, slot_cap, (uint32_t *)c->w_slot_aux.p, d_cand, cap, &c->d_wcounters[7], &d_small[6]);
+            launch_site_scan_slots(st, M.d_refview.get(), total, seg, wp, c->w_slots.get<int32_t>(), slot_cap, c->w_slot_aux.get<uint32_t>(), d_cand, cap, &wcnt[7], &d_small[6]);
         } else {
             HIPC(c, hipMemsetAsync(d_status, 0, ((size_t)nblk + 2) * sizeof(uint64_t), st));
-            launch_site_scan_list(st, g.d_refview, total, seg, wp, d_status, d_ticket, d_cand, cap, &c->d_wcounters[7]);
+            launch_site_scan_list(st, M.d_refview.get(), total, seg, wp, d_status, d_ticket, d_cand, cap, &wcnt[7]);
         }
     }
     // K2: events, liveness, insertion-table allocation
-    launch_events(st, d_cand, nc, g.d_ref, seg, wp, d_ev, &d_small[0]);
+    launch_events(st, d_cand, nc, M.d_ref.get(), seg, wp, d_ev, &d_small[0]);
     launch_resolve(st, d_ev, nc, &d_small[0], d_flags, &d_small[1]);
     // K3 + K4
     ContigDev cd = group_dev(g);
-    cd.tot4 = &d_small[1]; cd.cap_bases[0] = (uint32_t)std::min<size_t>(g.cap_bases[0], 0xFFFFFFFFu); cd.cap_bases[1] = (uint32_t)std::min<size_t>(g.cap_bases[1], 0xFFFFFFFFu);
+    cd.tot4 = &d_small[1]; cd.cap_bases[0] = (uint32_t)std::min<size_t>(ins_bases_cap(g, 0), 0xFFFFFFFFu); cd.cap_bases[1] = (uint32_t)std::min<size_t>(ins_bases_cap(g, 1), 0xFFFFFFFFu);
     launch_apply(st, d_ev, nc, d_flags, cd, wp);
     // mut_debug (mut.c:753, :757) cannot fire on randomly drawn mutations and is not run here: a substitution always changes the base
     // ((c + 1..3) & 3, mut.c:621), a homozygous one writes the same cell to both haplotypes and a heterozygous one leaves the other
     // haplotype's cell as it was -- the reference base, also under a deletion or an insertion, before and after left-justification
     // (which only moves an indel over bases equal to its own).  File-driven mutations (-m / -b / -v, above) can violate all three.
     if (c->seq_justify || c->dense_view) {      // (the cross-check forms: one thread justifies the whole group / the views are made from every cell as rounds 1-4 did)
-        if (c->seq_justify) launch_justify_seq(st, d_ev, nc, cd); else launch_justify(st, d_ev, nc, cd, (int32_t *)c->w_lo.p, (int32_t *)c->w_sufmin.p, (uint8_t *)c->w_bound.p);
-        launch_make_view(st, g.d_cells[0], g.d_cells[1], (int64_t)padded & ~(int64_t)15, g.total, g.d_view[0], g.d_view[1], g.d_summ[0], g.d_summ[1], g.d_summ2[0], g.d_summ2[1]);
+        if (c->seq_justify) launch_justify_seq(st, d_ev, nc, cd); else launch_justify(st, d_ev, nc, cd, c->w_lo.get<int32_t>(), c->w_sufmin.get<int32_t>(), c->w_bound.get<uint8_t>());
+        make_views(st, g);
         g.dirty_all = true;
     } else {
-        launch_justify(st, d_ev, nc, cd, (int32_t *)c->w_lo.p, (int32_t *)c->w_sufmin.p, (uint8_t *)c->w_bound.p);
+        launch_justify(st, d_ev, nc, cd, c->w_lo.get<int32_t>(), c->w_sufmin.get<int32_t>(), c->w_bound.get<uint8_t>());
         // the chunks the walk may have written (every live event from the lower end of its justification scan to its last cell): their views and summaries
-        launch_mark_dirty(st, d_ev, nc, (const int32_t *)c->w_lo.p, g.d_dirty);
-        launch_dirty_chunks(st, false, g.d_dirty, g.n_dirty_words, g.total, g.d_ref, g.d_refview, g.d_refsumm, g.d_refsumm2, g.d_cells[0], g.d_cells[1], g.d_view[0], g.d_view[1], g.d_summ[0], g.d_summ[1], g.d_summ2[0], g.d_summ2[1]);
+        launch_mark_dirty(st, d_ev, nc, c->w_lo.get<int32_t>(), M.d_dirty.get<uint32_t>());
+        dirty_chunks(st, false, g);
         g.dirty_any = true;
     }
     HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(&g.h_wc[7], &c->d_wcounters[7], 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));      // [7] candidates, [8..11] the eight words
-    HIPC(c, hipEventRecord(g.ev_walk, st));
+    HIPC(c, hipMemcpyAsync(&wc[7], &wcnt[7], 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));      // [7] candidates, [8..11] the eight words
+    HIPC(c, hipEventRecord(M.ev_walk.get(), st));
     return DWGSIM_HIP_OK;
 }
 
@@ -1086,7 +1063,7 @@ int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
     Group &g = *gp;
     if (g.walk_pending) { c->err = "mutate: the group's previous walk was not waited for"; return DWGSIM_HIP_ERR_STATE; }
     // (walks of several groups may be in flight: they run one after the other on the walk stream and share its device scratch in stream order;
-    // what the host reads back afterwards -- counts, mut_debug verdicts -- lands in the group's own page-locked mirror g.h_wc)
+    // what the host reads back afterwards -- counts, mut_debug verdicts -- lands in the group's own page-locked mirror g.mem.h_wc)
     for (const Slot &sl : c->slot) if (sl.pending && sl.group == c->handles[(size_t)contig].group) { c->err = "mutate: a batch that reads this group is still in flight (wait for it first)"; return DWGSIM_HIP_ERR_STATE; }
     HIPC(c, hipSetDevice(c->device));
     g.walk_reset = g.mutated;      // walked before: the cells start again from the resident packed reference
@@ -1117,10 +1094,10 @@ int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
             g.n_ins[h] = (uint32_t)n; g.n_ins_bases[h] = (uint32_t)nb;
             if (const int rc = ensure_ins(c, g, h, n ? n : 1, nb ? nb : 1)) return rc;
             if (n) {
-                HIPC(c, hipMemcpy(g.d_ins_pos[h], hi[h].pos.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-                HIPC(c, hipMemcpy(g.d_ins_len[h], hi[h].len.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-                HIPC(c, hipMemcpy(g.d_ins_off[h], hi[h].off.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-                HIPC(c, hipMemcpy(g.d_ins_bases[h], hi[h].bases.data(), nb, hipMemcpyHostToDevice));
+                HIPC(c, hipMemcpy(g.mem.d_ins_pos[h].get<int32_t>(), hi[h].pos.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
+                HIPC(c, hipMemcpy(g.mem.d_ins_len[h].get<uint32_t>(), hi[h].len.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+                HIPC(c, hipMemcpy(g.mem.d_ins_off[h].get<uint32_t>(), hi[h].off.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+                HIPC(c, hipMemcpy(g.mem.d_ins_bases[h].get(), hi[h].bases.data(), nb, hipMemcpyHostToDevice));
             }
         }
     } else {
@@ -1143,16 +1120,16 @@ int dwgsim_hip_mutate_wait(dwgsim_hip_ctx_t *c, int contig)
     if (!g.walk_pending) return g.mutated ? DWGSIM_HIP_OK : (c->err = "mutate_wait: no walk was enqueued for this group", DWGSIM_HIP_ERR_STATE);
     HIPC(c, hipSetDevice(c->device));
     for (;;) {
-        HIPC(c, hipEventSynchronize(g.ev_walk));
-        { float ms = 0; if (hipEventElapsedTime(&ms, g.ev_walk0, g.ev_walk) == hipSuccess) c->walk_us += 1e3 * ms; else (void)hipGetLastError(); }      // (analysis: dwgsim_hip_debug_get "walk_us")
+        HIPC(c, hipEventSynchronize(g.mem.ev_walk.get()));
+        { float ms = 0; if (hipEventElapsedTime(&ms, g.mem.ev_walk0.get(), g.mem.ev_walk.get()) == hipSuccess) c->walk_us += 1e3 * ms; else (void)hipGetLastError(); }      // (analysis: dwgsim_hip_debug_get "walk_us")
         if (c->has_mutin) {
             g.walk_pending = false;
-            return g.n_patch ? mut_debug_verdict(c, g, g.h_wc[12], g.h_wc[13]) : DWGSIM_HIP_OK;
+            return g.n_patch ? mut_debug_verdict(c, g, g.mem.h_wc.get<uint64_t>()[12], g.mem.h_wc.get<uint64_t>()[13]) : DWGSIM_HIP_OK;
         }
-        const uint64_t n_cand = g.h_wc[7];
-        const uint32_t *h_small = reinterpret_cast<const uint32_t *>(&g.h_wc[8]);
+        const uint64_t n_cand = g.mem.h_wc.get<uint64_t>()[7];
+        const uint32_t *h_small = reinterpret_cast<const uint32_t *>(&g.mem.h_wc.get<uint64_t>()[8]);
         const bool slot_over = h_small[6] != 0;      // a block of the site scan outgrew its slot (nothing behind it ran: the candidate count was set to 0; h_small[7] = the real one)
-        const bool fits = !slot_over && n_cand <= g.walk_cap && h_small[2] <= g.cap_bases[0] && h_small[4] <= g.cap_bases[1];
+        const bool fits = !slot_over && n_cand <= g.walk_cap && h_small[2] <= ins_bases_cap(g, 0) && h_small[4] <= ins_bases_cap(g, 1);
         if (fits || g.walk_attempt >= 2) {
             g.walk_pending = false;
             if (!fits) { c->err = "mutation walk: capacities still exceeded after an exact re-run"; return DWGSIM_HIP_ERR_FAILED; }
@@ -1174,7 +1151,7 @@ int dwgsim_hip_mutate_poll(dwgsim_hip_ctx_t *c, int contig)
     if (!gp) return DWGSIM_HIP_ERR_ARG;
     if (!gp->walk_pending) return 1;
     HIPC(c, hipSetDevice(c->device));
-    const hipError_t e = hipEventQuery(gp->ev_walk);
+    const hipError_t e = hipEventQuery(gp->mem.ev_walk.get());
     if (e == hipSuccess) return 1;
     (void)hipGetLastError();
     return e == hipErrorNotReady ? 0 : (c->err = "mutate_poll: device error", DWGSIM_HIP_ERR_DEVICE);
@@ -1295,26 +1272,26 @@ int fetch_mutated_list(dwgsim_hip_ctx_t *c, Group &g)
         const uint32_t nblk = (uint32_t)((g.total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
         if (ensure(c, c->scratch_mask, (size_t)nblk * SCAN_THREADS * sizeof(uint16_t))) return DWGSIM_HIP_ERR_DEVICE;
         if (ensure(c, c->scratch_cnt, (size_t)nblk * sizeof(uint32_t))) return DWGSIM_HIP_ERR_DEVICE;
-        uint16_t *d_mask = (uint16_t *)c->scratch_mask.p; uint32_t *d_cnt = (uint32_t *)c->scratch_cnt.p;
-        launch_collect_mask(st, g.d_cells[0], g.d_cells[1], g.total, d_mask, d_cnt);
-        launch_scan_excl(st, d_cnt, nblk, &c->d_wcounters[14]);
-        HIPC(c, hipMemcpyAsync(&g.h_wc[14], &c->d_wcounters[14], sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        uint16_t *d_mask = c->scratch_mask.get<uint16_t>(); uint32_t *d_cnt = c->scratch_cnt.get<uint32_t>();
+        launch_collect_mask(st, g.mem.d_cells[0].get(), g.mem.d_cells[1].get(), g.total, d_mask, d_cnt);
+        launch_scan_excl(st, d_cnt, nblk, &c->d_wcounters.get<uint64_t>()[14]);
+        HIPC(c, hipMemcpyAsync(&g.mem.h_wc.get<uint64_t>()[14], &c->d_wcounters.get<uint64_t>()[14], sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIPC(c, hipStreamSynchronize(st));
-        const uint32_t n = (uint32_t)g.h_wc[14];
+        const uint32_t n = (uint32_t)g.mem.h_wc.get<uint64_t>()[14];
         if (n) {
             if (ensure(c, c->l_pos, sizeof(int32_t) * (size_t)n) || ensure(c, c->l_cells, sizeof(uint32_t) * (size_t)n)) return DWGSIM_HIP_ERR_DEVICE;
-            launch_compact(st, d_mask, d_cnt, (int32_t *)c->l_pos.p, g.total, n);
-            launch_gather(st, (const int32_t *)c->l_pos.p, n, g.d_ref, g.d_cells[0], g.d_cells[1], (uint32_t *)c->l_cells.p);
+            launch_compact(st, d_mask, d_cnt, c->l_pos.get<int32_t>(), g.total, n);
+            launch_gather(st, c->l_pos.get<int32_t>(), n, g.mem.d_ref.get(), g.mem.d_cells[0].get(), g.mem.d_cells[1].get(), c->l_cells.get<uint32_t>());
             g.pos.resize(n); g.cells.resize(n);
-            HIPC(c, hipMemcpyAsync(g.pos.data(), c->l_pos.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPC(c, hipMemcpyAsync(g.cells.data(), c->l_cells.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIPC(c, hipMemcpyAsync(g.pos.data(), c->l_pos.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIPC(c, hipMemcpyAsync(g.cells.data(), c->l_cells.get(), sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
         }
         for (int h = 0; h < 2; ++h) if (g.n_ins[h]) {
             g.ins[h].pos.resize(g.n_ins[h]); g.ins[h].len.resize(g.n_ins[h]); g.ins[h].off.resize(g.n_ins[h]); g.ins[h].bases.resize(g.n_ins_bases[h]);
-            HIPC(c, hipMemcpyAsync(g.ins[h].pos.data(), g.d_ins_pos[h], sizeof(int32_t) * g.n_ins[h], hipMemcpyDeviceToHost, st));
-            HIPC(c, hipMemcpyAsync(g.ins[h].len.data(), g.d_ins_len[h], sizeof(uint32_t) * g.n_ins[h], hipMemcpyDeviceToHost, st));
-            HIPC(c, hipMemcpyAsync(g.ins[h].off.data(), g.d_ins_off[h], sizeof(uint32_t) * g.n_ins[h], hipMemcpyDeviceToHost, st));
-            HIPC(c, hipMemcpyAsync(g.ins[h].bases.data(), g.d_ins_bases[h], g.n_ins_bases[h], hipMemcpyDeviceToHost, st));
+            HIPC(c, hipMemcpyAsync(g.ins[h].pos.data(), g.mem.d_ins_pos[h].get<int32_t>(), sizeof(int32_t) * g.n_ins[h], hipMemcpyDeviceToHost, st));
+            HIPC(c, hipMemcpyAsync(g.ins[h].len.data(), g.mem.d_ins_len[h].get<uint32_t>(), sizeof(uint32_t) * g.n_ins[h], hipMemcpyDeviceToHost, st));
+            HIPC(c, hipMemcpyAsync(g.ins[h].off.data(), g.mem.d_ins_off[h].get<uint32_t>(), sizeof(uint32_t) * g.n_ins[h], hipMemcpyDeviceToHost, st));
+            HIPC(c, hipMemcpyAsync(g.ins[h].bases.data(), g.mem.d_ins_bases[h].get(), g.n_ins_bases[h], hipMemcpyDeviceToHost, st));
         }
         HIPC(c, hipStreamSynchronize(st));
     }
@@ -1515,20 +1492,20 @@ static void fill_sim_args(const dwgsim_hip_ctx_t *c, const Group &g, const SimFo
     a.p.seed = (uint32_t)p.seed;
     lazy_quality_params(p.quality_std, &a.p.q_k, &a.p.q_eps, &a.p.q_lmin, &a.p.q_near1);
     fill_haps(g, a.hap);
-    a.chain = c->d_chain;
-    a.have_regions = c->has_regions ? 1 : 0; a.reg = g.d_reg;
-    for (int j = 0; j < 2; ++j) { a.e_thr[j] = c->d_thr[j]; a.e_thr32[j] = c->d_thr32[j]; a.qbase[j] = c->d_qbase[j] ? c->d_qbase[j] : c->d_qbase[0]; }
+    a.chain = c->d_chain.get<uint64_t>();
+    a.have_regions = c->has_regions ? 1 : 0; a.reg = g.mem.d_reg.get<int32_t>();
+    for (int j = 0; j < 2; ++j) { a.e_thr[j] = c->d_thr[j].get<uint64_t>(); a.e_thr32[j] = c->d_thr32[j].get<uint32_t>(); a.qbase[j] = c->d_qbase[j].get<uint32_t>() ? c->d_qbase[j].get<uint32_t>() : c->d_qbase[0].get<uint32_t>(); }
     a.qb_words = c->qb_words;
     a.e_full = c->e_full;
-    a.names = g.d_names;
-    a.summ[0] = g.d_summ[0]; a.summ[1] = g.d_summ[1]; a.summ2[0] = g.d_summ2[0]; a.summ2[1] = g.d_summ2[1];
+    a.names = g.mem.d_names.get();
+    a.summ[0] = g.mem.d_summ[0].get<uint16_t>(); a.summ[1] = g.mem.d_summ[1].get<uint16_t>(); a.summ2[0] = g.mem.d_summ2[0].get<uint16_t>(); a.summ2[1] = g.mem.d_summ2[1].get<uint16_t>();
     // k_place decides most pairs without their insert size: |normal| <= sqrt(-2 ln 2^-104) < 12.01 for the polar method on 53-bit uniforms (dw_simulate.hip pair_surely_accepted)
     a.place_fast = (!c->has_regions && !p.amplicons && p.std_dev * 12.1 + 2.0 < 1e9) ? 1 : 0;
     a.place_k = a.place_fast ? (int32_t)ceil(p.std_dev * 12.1) + 2 : 0;
-    a.rand_fixed = c->d_rand_fixed; a.rand_fixed_len = c->rand_fixed_len;
+    a.rand_fixed = c->d_rand_fixed.get(); a.rand_fixed_len = c->rand_fixed_len;
     a.sim_threads = f.nthr; a.fifo = f.wr != 0; a.split = f.split; a.ion_lds = f.dt == 3;
     a.cap = f.cap; a.lds_words = f.lds_words; a.flow_stack_words = f.stack_words;
-    a.flow = c->d_flow; a.flow_len = (int32_t)c->flow.size();
+    a.flow = c->d_flow.get(); a.flow_len = (int32_t)c->flow.size();
     for (int j = 0; j < 2; ++j) {      // Illumina / SOLiD: the gap chain of a read end's error sites runs at the largest threshold of its ramp (dw_simulate.hip; thresholds as dwgsim_hip_create made them)
         const int n = c->prm.length[j];
         uint64_t tmax = 0, tmin = ~0ull;
@@ -1575,19 +1552,19 @@ int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t
     // (the haplotype summaries k_place reads -- per 64 and per 1024 cells -- were written with the read views at the end of the walk: the count follows
     // its group's walk by that walk's event, whatever else has been put on the walk stream since)
     if (g.walk_pending) { if (const int rc = dwgsim_hip_mutate_wait(c, g.first_handle)) return rc; }      // (a walk that exceeded a capacity is run again inside the wait: only then are the summaries final)
-    if (g.ev_walk && g.mutated) HIPC(c, hipStreamWaitEvent(st, g.ev_walk, 0));
+    if (g.mem.ev_walk.get() && g.mutated) HIPC(c, hipStreamWaitEvent(st, g.mem.ev_walk.get(), 0));
     if (const int rc = sim_form(c, L.f)) return rc;
     SimArgs &a = L.a; fill_sim_args(c, g, L.f, a);
     const size_t ns = L.segs.size();
     if (ensure(c, c->place_rand, sizeof(uint32_t) * ((size_t)n_blocks + 1)) || ensure(c, c->place_segs, sizeof(SimSeg) * ns) ||
         ensure(c, c->place_aux, PLACE_LISTS * 16 * sizeof(uint32_t) + sizeof(uint64_t) * ns)) return DWGSIM_HIP_ERR_DEVICE;
-    if (sizeof(SimSeg) * ns > c->h_place_segs.cap || sizeof(uint64_t) * ns > c->h_range_rand.cap) HIPC(c, hipStreamSynchronize(st));      // (before the page-locked pair is replaced)
-    if (ensure_host(c, c->h_place_segs, sizeof(SimSeg) * ns, sizeof(SimSeg) * (ns + 64)) || ensure_host(c, c->h_range_rand, sizeof(uint64_t) * ns, sizeof(uint64_t) * (ns + 64))) return DWGSIM_HIP_ERR_DEVICE;
-    const uint64_t *h_range_rand = (const uint64_t *)c->h_range_rand.p;
-    memcpy(c->h_place_segs.p, L.segs.data(), sizeof(SimSeg) * ns);
-    HIPC(c, hipMemcpyAsync(c->place_segs.p, c->h_place_segs.p, sizeof(SimSeg) * ns, hipMemcpyHostToDevice, st));
-    a.segs = (const SimSeg *)c->place_segs.p; a.n_seg = (int32_t)ns; a.n_blocks = n_blocks; a.n_pairs = n_pairs;
-    a.block_rand = (uint32_t *)c->place_rand.p; a.counters = c->d_pcounters;
+    if (sizeof(SimSeg) * ns > c->h_place_segs.cap() || sizeof(uint64_t) * ns > c->h_range_rand.cap()) HIPC(c, hipStreamSynchronize(st));      // (before the page-locked pair is replaced)
+    HIPC(c, c->h_place_segs.reserve(sizeof(SimSeg) * ns, sizeof(SimSeg) * (ns + 64))); HIPC(c, c->h_range_rand.reserve(sizeof(uint64_t) * ns, sizeof(uint64_t) * (ns + 64)));
+    const uint64_t *h_range_rand = c->h_range_rand.get<uint64_t>();
+    memcpy(c->h_place_segs.get(), L.segs.data(), sizeof(SimSeg) * ns);
+    HIPC(c, hipMemcpyAsync(c->place_segs.get(), c->h_place_segs.get(), sizeof(SimSeg) * ns, hipMemcpyHostToDevice, st));
+    a.segs = c->place_segs.get<SimSeg>(); a.n_seg = (int32_t)ns; a.n_blocks = n_blocks; a.n_pairs = n_pairs;
+    a.block_rand = c->place_rand.get<uint32_t>(); a.counters = c->pcounters.dev();
     // the lists of pairs k_place leaves open: room for an eighth of the pairs (the usual share is a per cent); if that does not do -- contigs
     // made of N runs, a read length close to the contig's -- the count is run once more with room for every pair
     const uint64_t waves = (uint64_t)n_blocks * (PLACE_PAIRS / 64);
@@ -1596,24 +1573,24 @@ int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t
     if (c->place_cap >= 0 && (uint64_t)c->place_cap < cap) cap = (uint32_t)c->place_cap;      // dwgsim_hip_debug_option("place_cap"): start too small, exercise the second run
     for (int attempt = 0;; ++attempt) {
         if (ensure(c, c->place_list, sizeof(uint32_t) * (size_t)cap * PLACE_LISTS)) return DWGSIM_HIP_ERR_DEVICE;
-        a.place_list = (uint32_t *)c->place_list.p; a.place_list_cap = cap;
-        a.place_list_n = (uint32_t *)c->place_aux.p; a.range_rand = reinterpret_cast<uint64_t *>((uint8_t *)c->place_aux.p + PLACE_LISTS * 16 * sizeof(uint32_t));
-        HIPC(c, hipMemsetAsync(c->d_pcounters, 0, N_COUNTERS * sizeof(uint64_t), st));
-        HIPC(c, hipMemsetAsync(c->place_aux.p, 0, PLACE_LISTS * 16 * sizeof(uint32_t) + sizeof(uint64_t) * ns, st));
+        a.place_list = c->place_list.get<uint32_t>(); a.place_list_cap = cap;
+        a.place_list_n = c->place_aux.get<uint32_t>(); a.range_rand = reinterpret_cast<uint64_t *>(c->place_aux.get<uint8_t>() + PLACE_LISTS * 16 * sizeof(uint32_t));
+        HIPC(c, hipMemsetAsync(c->pcounters.dev(), 0, N_COUNTERS * sizeof(uint64_t), st));
+        HIPC(c, hipMemsetAsync(c->place_aux.get(), 0, PLACE_LISTS * 16 * sizeof(uint32_t) + sizeof(uint64_t) * ns, st));
         HIPC(c, hipEventRecord(c->ev_cnt0, st));
         launch_place(st, a);
         HIPC(c, hipEventRecord(c->ev_cnt1, st));
         HIPC(c, hipGetLastError());
-        HIPC(c, hipMemcpyAsync(c->h_pcounters, c->d_pcounters, N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIPC(c, hipMemcpyAsync(c->h_range_rand.p, a.range_rand, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
+        HIPC(c, hipMemcpyAsync(c->pcounters.host(), c->pcounters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPC(c, hipMemcpyAsync(c->h_range_rand.get(), a.range_rand, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
         HIPC(c, hipStreamSynchronize(st));
         { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_cnt0, c->ev_cnt1) == hipSuccess) c->count_us += 1e3 * ms; else (void)hipGetLastError(); }
-        if (!(c->h_pcounters[2] & 16) || attempt > 0) break;
+        if (!(c->pcounters.host()[2] & 16) || attempt > 0) break;
         cap = cap_full;
     }
-    if (c->h_pcounters[2] & 16) { c->err = "count_random: the list of undecided pairs overflowed twice"; return DWGSIM_HIP_ERR_FAILED; }
-    if (c->h_pcounters[2]) { char b[128]; snprintf(b, sizeof b, "\r[dwgsim_core] failed to generate a read after %d trials\n", MAX_ATTEMPTS + 1); c->err = b; return DWGSIM_HIP_ERR_FAILED; }
-    c->place_open = c->h_pcounters[5];
+    if (c->pcounters.host()[2] & 16) { c->err = "count_random: the list of undecided pairs overflowed twice"; return DWGSIM_HIP_ERR_FAILED; }
+    if (c->pcounters.host()[2]) { char b[128]; snprintf(b, sizeof b, "\r[dwgsim_core] failed to generate a read after %d trials\n", MAX_ATTEMPTS + 1); c->err = b; return DWGSIM_HIP_ERR_FAILED; }
+    c->place_open = c->pcounters.host()[5];
     uint64_t total = 0;
     for (int q = 0, si = 0; q < n; ++q) if (r[q].n_pairs) { total += h_range_rand[si]; if (per_range) per_range[q] = h_range_rand[si]; ++si; }
     if (n_random) *n_random = total;
@@ -1684,13 +1661,13 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
 // The reserve step: every buffer grown to its plan (ensure of 0 bytes: nothing), after the wait for a copy of the slot's text still in flight
 static int sim_reserve(dwgsim_hip_ctx_t *c, int slot, const SimPlan &P)
 {
-    Slot &sl = c->slot[slot]; DevBuf *out = c->out[slot];
-    if (sl.fetch_in_flight) { HIPC(c, hipStreamWaitEvent(c->stream, sl.ev_fetched, 0)); bool grows = false; for (int t = 0; t < 3; ++t) if (P.cap[t] + 64 > out[t].cap) grows = true; if (grows) HIPC(c, hipEventSynchronize(sl.ev_fetched)); sl.fetch_in_flight = false; }
+    Slot &sl = c->slot[slot]; DevMem *out = c->out[slot];
+    if (sl.fetch_in_flight) { HIPC(c, hipStreamWaitEvent(c->stream, sl.ev_fetched, 0)); bool grows = false; for (int t = 0; t < 3; ++t) if (P.cap[t] + 64 > out[t].cap()) grows = true; if (grows) HIPC(c, hipEventSynchronize(sl.ev_fetched)); sl.fetch_in_flight = false; }
     for (int t = 0; t < 3; ++t) if (ensure(c, out[t], P.cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE;
     if (ensure(c, c->block_rand, P.block_rand) || ensure(c, c->status_all, P.status) ||
         ensure(c, c->split_state, P.split_state) || ensure(c, c->split_hand, P.split_hand) || ensure(c, c->split_agg, P.split_agg) || ensure(c, c->split_pre, P.split_pre) || ensure(c, c->split_chunk, P.split_chunk) ||
-        ensure(c, c->meta, P.meta) || ensure(c, c->fail_summ, P.fail_summ) || ensure(c, c->flow_scratch, P.flow_scratch) || ensure(c, c->flow_free, P.flow_free) || ensure(c, sl.segs, P.segs) ||
-        ensure_host(c, sl.h_segs, P.segs, P.segs + 64 * sizeof(SimSeg))) return DWGSIM_HIP_ERR_DEVICE;      // (+ 64 entries; the slot is not pending: no copy reads the old one)
+        ensure(c, c->meta, P.meta) || ensure(c, c->fail_summ, P.fail_summ) || ensure(c, c->flow_scratch, P.flow_scratch) || ensure(c, c->flow_free, P.flow_free) || ensure(c, sl.segs, P.segs)) return DWGSIM_HIP_ERR_DEVICE;
+    HIPC(c, sl.h_segs.reserve(P.segs, P.segs + 64 * sizeof(SimSeg)));      // (+ 64 entries; the slot is not pending: no copy reads the old one)
     for (int t = 0; t < 3; ++t) if (P.gz_cap[t] && ensure(c, sl.gz_out[t], P.gz_cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE;
     return ensure(c, sl.gz_status, P.gz_status);
 }
@@ -1698,14 +1675,14 @@ static int sim_reserve(dwgsim_hip_ctx_t *c, int slot, const SimPlan &P)
 // The chain step: the running values the batch starts from; the context's chain moves on to its end (a re-run moves nothing)
 static ChainSet sim_chain(dwgsim_hip_ctx_t *c, Slot &sl, const dwgsim_hip_range_t *r, int n, bool set_rand, bool rerun)
 {
-    if (rerun) return ChainSet{sl.d_rerun_chain, 1, 1, 0};
+    if (rerun) return ChainSet{sl.d_rerun_chain.get<uint64_t>(), 1, 1, 0};
     // the reference's failure counter (dwgsim.c:635) runs over the pairs of ONE contig in index order: it is carried from the previous
     // batch only when this one continues it; any other range starts from zero unless the caller supplied the carry (sharded jobs)
     const dwgsim_hip_range_t *r_first = nullptr, *r_last = nullptr;
     for (int q = 0; q < n; ++q) if (r[q].n_pairs) { if (!r_first) r_first = &r[q]; r_last = &r[q]; }
     if (!r_first) { r_first = &r[0]; r_last = &r[n - 1]; }
     const bool continues = c->chain_contig == r_first->contig && c->chain_next_ii == r_first->first_ii && r_first->first_ii != 0;
-    const ChainSet ch{c->d_chain, set_rand ? 1 : 0, (c->has_carry_override || !continues) ? 1 : 0, c->has_carry_override ? c->carry_override : 0};
+    const ChainSet ch{c->d_chain.get<uint64_t>(), set_rand ? 1 : 0, (c->has_carry_override || !continues) ? 1 : 0, c->has_carry_override ? c->carry_override : 0};
     c->has_carry_override = false; c->chain_contig = r_last->contig; c->chain_next_ii = r_last->first_ii + r_last->n_pairs;
     if (sl.ranges.data() != r) sl.ranges.assign(r, r + n);
     return ch;
@@ -1720,37 +1697,37 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
     sl.n_pairs = n_pairs; sl.empty = n_pairs == 0;
     if (n_pairs == 0) { if (ch.set_rand || ch.set_carry) launch_chain_set(c->stream, ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry); return DWGSIM_HIP_OK; }
     uint32_t opens = 0; for (const SimSeg &s : L.segs) opens |= s.contig_start;      // (ranges that begin their contig)
-    memcpy(sl.h_segs.p, L.segs.data(), P.segs);
-    HIPC(c, hipMemcpyAsync(sl.segs.p, sl.h_segs.p, P.segs, hipMemcpyHostToDevice, c->stream));
-    a.segs = (const SimSeg *)sl.segs.p; a.n_seg = (int32_t)L.segs.size(); a.n_blocks = nblk; a.n_pairs = n_pairs; a.chain = ch.words; a.lb_shift = P.lb_shift;
-    a.meta = (uint32_t *)c->meta.p; a.block_rand = (uint32_t *)c->block_rand.p; a.counters = sl.d_counters;
-    for (int t = 0; t < 3; ++t) a.out[t] = (uint8_t *)c->out[slot][t].p;
-    for (int j = 0; j < 4; ++j) a.status[j] = f.split ? nullptr : (uint64_t *)c->status_all.p + (size_t)j * (size_t)nblk;
-    if (f.split) { a.split_state = (uint32_t *)c->split_state.p; a.split_hand = (uint32_t *)c->split_hand.p; a.split_agg = (uint32_t *)c->split_agg.p; a.split_pre = (uint64_t *)c->split_pre.p; a.split_chunk = (uint64_t *)c->split_chunk.p; }
-    if (P.scratch) { a.flow_scratch = (uint32_t *)c->flow_scratch.p; a.flow_free = (uint64_t *)c->flow_free.p; a.flow_slots = P.flow_slots; }
+    memcpy(sl.h_segs.get(), L.segs.data(), P.segs);
+    HIPC(c, hipMemcpyAsync(sl.segs.get(), sl.h_segs.get(), P.segs, hipMemcpyHostToDevice, c->stream));
+    a.segs = sl.segs.get<SimSeg>(); a.n_seg = (int32_t)L.segs.size(); a.n_blocks = nblk; a.n_pairs = n_pairs; a.chain = ch.words; a.lb_shift = P.lb_shift;
+    a.meta = c->meta.get<uint32_t>(); a.block_rand = c->block_rand.get<uint32_t>(); a.counters = sl.counters.dev();
+    for (int t = 0; t < 3; ++t) a.out[t] = c->out[slot][t].get<uint8_t>();
+    for (int j = 0; j < 4; ++j) a.status[j] = f.split ? nullptr : c->status_all.get<uint64_t>() + (size_t)j * (size_t)nblk;
+    if (f.split) { a.split_state = c->split_state.get<uint32_t>(); a.split_hand = c->split_hand.get<uint32_t>(); a.split_agg = c->split_agg.get<uint32_t>(); a.split_pre = c->split_pre.get<uint64_t>(); a.split_chunk = c->split_chunk.get<uint64_t>(); }
+    if (P.scratch) { a.flow_scratch = c->flow_scratch.get<uint32_t>(); a.flow_free = c->flow_free.get<uint64_t>(); a.flow_slots = P.flow_slots; }
     sl.group = c->handles[(size_t)L.g->first_handle].group;
     // one operation in front of the kernel: counters, look-back words (the four arrays are contiguous), the scratch slots' free lists, the running values
-    launch_init(c->stream, sl.d_counters, (uint32_t)N_COUNTERS, a.status[0], f.split ? 0 : 4 * (uint64_t)nblk, a.flow_free, a.flow_free ? 256 + 8 * (uint64_t)nblk : 0,
+    launch_init(c->stream, sl.counters.dev(), (uint32_t)N_COUNTERS, a.status[0], f.split ? 0 : 4 * (uint64_t)nblk, a.flow_free, a.flow_free ? 256 + 8 * (uint64_t)nblk : 0,
                 ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry);
     HIPC(c, hipEventRecord(sl.ev_k0, c->stream));
     c->sim_form = (int64_t)f.nthr << 20 | f.lpp << 16 | f.out << 12 | f.dt << 8 | f.wr << 4 | f.split;
     if (!launch_simulate(c->stream, a, f)) { c->err = "simulate: no k_simulate instance for this form"; return DWGSIM_HIP_ERR_FAILED; }
     HIPC(c, hipEventRecord(sl.ev_k1, c->stream));
     sl.cap_mult = c->flow_cap_mult;
-    if (!rerun) launch_failrule(c->stream, a.meta, n_pairs, opens, (uint64_t *)c->fail_summ.p, sl.d_counters, c->d_chain);
+    if (!rerun) launch_failrule(c->stream, a.meta, n_pairs, opens, c->fail_summ.get<uint64_t>(), sl.counters.dev(), c->d_chain.get<uint64_t>());
     if (c->gzip_on) {      // the .gz form of every stream, enqueued behind the text (lengths are read on the device: counters[4 + t])
-        HIPC(c, hipMemsetAsync(sl.gz_status.p, 0, P.gz_status, c->stream));
+        HIPC(c, hipMemsetAsync(sl.gz_status.get(), 0, P.gz_status, c->stream));
         size_t off = 0;
         for (int t = 0; t < 3; ++t) {
             if (P.cap[t] == 0) continue;
-            launch_gzip(c->stream, a.out[t], &sl.d_counters[4 + t], P.cap[t], (uint8_t *)sl.gz_out[t].p, P.gz_cap[t], (uint64_t *)sl.gz_status.p + off, &sl.d_counters[28 + t], &sl.d_counters[24 + t], &sl.d_counters[2],
-                        c->d_crc_table, c->d_crc_shift);
+            launch_gzip(c->stream, a.out[t], &sl.counters.dev()[4 + t], P.cap[t], sl.gz_out[t].get<uint8_t>(), P.gz_cap[t], sl.gz_status.get<uint64_t>() + off, &sl.counters.dev()[28 + t], &sl.counters.dev()[24 + t], &sl.counters.dev()[2],
+                        c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
             off += P.gz_chunks[t];
         }
     }
     HIPC(c, hipEventRecord(sl.ev_end, c->stream));
     HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(sl.h_counters, sl.d_counters, N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(sl.counters.host(), sl.counters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipEventRecord(sl.ev_done, c->stream));
     sl.pending = true;
     return DWGSIM_HIP_OK;
@@ -1793,7 +1770,7 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipEventSynchronize(sl.ev_done));
     sl.pending = false;
-    uint64_t *h = sl.h_counters;
+    uint64_t *h = sl.counters.host();
     if ((h[2] & 2) && !(h[2] & ~(2ull | 8ull)) && c->prm.data_type == 2) {
         // a read outgrew its flow-space buffers: the reference doubles them and goes on (dwgsim.c:296-311); here the batch runs again with twice the
         // capacity (kept for the rest of the job).  Its random reads and failed attempts are settled before the flow model runs, so the chain words
@@ -1828,7 +1805,7 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
     }
     if (out) {
         out->n_pairs = sl.n_pairs; out->n_random = h[3]; out->n_retries = h[1];
-        for (int t = 0; t < 3; ++t) { out->bytes[t] = sl.out_bytes[t]; out->dev_ptr[t] = c->out[slot][t].p; }
+        for (int t = 0; t < 3; ++t) { out->bytes[t] = sl.out_bytes[t]; out->dev_ptr[t] = c->out[slot][t].get(); }
         for (int t = 0; t < 3; ++t) out->gz_bytes[t] = sl.gz_bytes[t];
         for (int t = 0; t < 4; ++t) out->fail_seg[t] = h[16 + t];
         out->fail_carry = h[21];
@@ -1909,7 +1886,7 @@ static int fetch_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst
     const size_t n = (size_t)(gz ? sl.gz_bytes[stream] : sl.out_bytes[stream]);
     if (n > cap) { c->err = "fetch: destination too small"; return DWGSIM_HIP_ERR_ARG; }
     if (n == 0) return DWGSIM_HIP_OK;
-    HIPC(c, hipMemcpyAsync(host_dst, gz ? sl.gz_out[stream].p : c->out[slot][stream].p, n, hipMemcpyDeviceToHost, c->copy_stream));
+    HIPC(c, hipMemcpyAsync(host_dst, gz ? sl.gz_out[stream].get() : c->out[slot][stream].get(), n, hipMemcpyDeviceToHost, c->copy_stream));
     HIPC(c, hipEventRecord(sl.ev_fetched, c->copy_stream));
     sl.fetch_in_flight = true;
     return DWGSIM_HIP_OK;
@@ -1920,12 +1897,10 @@ int dwgsim_hip_set_gzip(dwgsim_hip_ctx_t *c, int on)
 {
     if (!c) return DWGSIM_HIP_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
-    if (on && !c->d_crc_table) {
+    if (on && !c->d_crc_shift) {      // (d_crc_shift is made last: both tables are there when it is)
         std::vector<uint32_t> tab(4 * 256), sh(16 * 1024);
         gz_host_tables(tab.data(), sh.data());
-        HIPC(c, hipMalloc((void **)&c->d_crc_table, tab.size() * 4)); HIPC(c, hipMalloc((void **)&c->d_crc_shift, sh.size() * 4));
-        HIPC(c, hipMemcpy(c->d_crc_table, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-        HIPC(c, hipMemcpy(c->d_crc_shift, sh.data(), sh.size() * 4, hipMemcpyHostToDevice));
+        if (upload(c, c->d_crc_table, tab.data(), tab.size() * 4) || upload(c, c->d_crc_shift, sh.data(), sh.size() * 4)) return DWGSIM_HIP_ERR_DEVICE;
     }
     c->gzip_on = on != 0;
     return DWGSIM_HIP_OK;
@@ -1954,15 +1929,15 @@ int dwgsim_hip_fetch(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, 
     if (n > cap) { c->err = "fetch: destination too small"; return DWGSIM_HIP_ERR_ARG; }
     if (n == 0) return DWGSIM_HIP_OK;
     if (is_page_locked(host_dst)) {   // a pinned (page-locked / registered) destination takes one direct copy at link speed
-        HIPC(c, hipMemcpyAsync(host_dst, c->out[slot][stream].p, n, hipMemcpyDeviceToHost, c->copy_stream));
+        HIPC(c, hipMemcpyAsync(host_dst, c->out[slot][stream].get(), n, hipMemcpyDeviceToHost, c->copy_stream));
         HIPC(c, hipStreamSynchronize(c->copy_stream));
         return DWGSIM_HIP_OK;
     }
     // double-buffered pinned staging: D2H of chunk k+1 overlaps the host copy of chunk k
     const size_t CH = (size_t)16 << 20;
-    if (const int rc = ensure_host(c, c->h_stage, 2 * CH, 2 * CH)) return rc;
-    const uint8_t *src = (const uint8_t *)c->out[slot][stream].p;
-    uint8_t *stage[2] = {(uint8_t *)c->h_stage.p, (uint8_t *)c->h_stage.p + CH};
+    HIPC(c, c->h_stage.reserve(2 * CH, 2 * CH));
+    const uint8_t *src = c->out[slot][stream].get<uint8_t>();
+    uint8_t *stage[2] = {c->h_stage.get<uint8_t>(), c->h_stage.get<uint8_t>() + CH};
     size_t done = 0; int b = 0;
     size_t cur = n < CH ? n : CH;
     HIPC(c, hipMemcpyAsync(stage[0], src, cur, hipMemcpyDeviceToHost, c->copy_stream));
@@ -1983,11 +1958,11 @@ int dwgsim_hip_debug_count_byte(dwgsim_hip_ctx_t *c, int slot, int stream, int b
     HIPC(c, hipSetDevice(c->device));
     Slot &sl = c->slot[slot];
     if (sl.pending) { c->err = "count_byte: wait for the batch first"; return DWGSIM_HIP_ERR_STATE; }
-    HIPC(c, hipMemsetAsync(&c->d_counters[15], 0, sizeof(uint64_t), c->stream));
-    if (sl.out_bytes[stream]) launch_count_byte(c->stream, (const uint8_t *)c->out[slot][stream].p, sl.out_bytes[stream], (uint32_t)(byte & 0xff), &c->d_counters[15]);
-    HIPC(c, hipMemcpyAsync(&c->h_counters[15], &c->d_counters[15], sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemsetAsync(&c->counters.dev()[15], 0, sizeof(uint64_t), c->stream));
+    if (sl.out_bytes[stream]) launch_count_byte(c->stream, c->out[slot][stream].get<uint8_t>(), sl.out_bytes[stream], (uint32_t)(byte & 0xff), &c->counters.dev()[15]);
+    HIPC(c, hipMemcpyAsync(&c->counters.host()[15], &c->counters.dev()[15], sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
-    *count = c->h_counters[15];
+    *count = c->counters.host()[15];
     return DWGSIM_HIP_OK;
 }
 
@@ -1998,25 +1973,24 @@ int dwgsim_hip_debug_gzip(dwgsim_hip_ctx_t *c, const void *text, size_t n, void 
     if (!c || (!text && n) || !out_n) return DWGSIM_HIP_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
     if (const int rc = dwgsim_hip_set_gzip(c, c->gzip_on ? 1 : 0); rc < 0) return rc;
-    if (!c->d_crc_table) { const bool was = c->gzip_on; if (const int rc = dwgsim_hip_set_gzip(c, 1); rc < 0) return rc; c->gzip_on = was; }
+    if (!c->d_crc_shift) { const bool was = c->gzip_on; if (const int rc = dwgsim_hip_set_gzip(c, 1); rc < 0) return rc; c->gzip_on = was; }
     *out_n = 0;
     if (n == 0) return DWGSIM_HIP_OK;
     const size_t gcap = (size_t)gz_capacity(n), nch = (size_t)gz_chunks(n);
-    uint8_t *d_text = nullptr, *d_out = nullptr; uint64_t *d_aux = nullptr;       // aux: [0] length, [1] ticket, [2] total, [3] flags, [4..] look-back words
-    auto cleanup = [&]() { hipFree(d_text); hipFree(d_out); hipFree(d_aux); };
-    if (hipMalloc((void **)&d_text, n + 64) != hipSuccess || hipMalloc((void **)&d_out, gcap + 64) != hipSuccess || hipMalloc((void **)&d_aux, sizeof(uint64_t) * (4 + nch)) != hipSuccess) { cleanup(); c->err = "out of device memory"; return DWGSIM_HIP_ERR_DEVICE; }
+    DevMem text_m, out_m, aux_m;
+    if (reserve(c, text_m, n + 64, n + 64) != hipSuccess || reserve(c, out_m, gcap + 64, gcap + 64) != hipSuccess || reserve(c, aux_m, sizeof(uint64_t) * (4 + nch), sizeof(uint64_t) * (4 + nch)) != hipSuccess) { c->err = "out of device memory"; return DWGSIM_HIP_ERR_DEVICE; }
+    uint8_t *d_text = text_m.get(), *d_out = out_m.get(); uint64_t *d_aux = aux_m.get<uint64_t>();       // aux: [0] length, [1] ticket, [2] total, [3] flags, [4..] look-back words
     const uint64_t n64 = n;
     bool ok = hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c->stream) == hipSuccess && hipMemsetAsync(d_aux, 0, sizeof(uint64_t) * (4 + nch), c->stream) == hipSuccess &&
               hipMemcpyAsync(d_aux, &n64, sizeof n64, hipMemcpyHostToDevice, c->stream) == hipSuccess;
     if (ok) {
-        launch_gzip(c->stream, d_text, &d_aux[0], n, d_out, gcap, &d_aux[4], &d_aux[1], &d_aux[2], &d_aux[3], c->d_crc_table, c->d_crc_shift);
+        launch_gzip(c->stream, d_text, &d_aux[0], n, d_out, gcap, &d_aux[4], &d_aux[1], &d_aux[2], &d_aux[3], c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
         uint64_t res[4] = {0, 0, 0, 0};
         ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(res, d_aux, sizeof res, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
-        if (ok && (res[3] & 8)) { cleanup(); c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
-        if (ok && res[2] > cap) { cleanup(); c->err = "debug_gzip: destination too small"; return DWGSIM_HIP_ERR_ARG; }
+        if (ok && (res[3] & 8)) { c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
+        if (ok && res[2] > cap) { c->err = "debug_gzip: destination too small"; return DWGSIM_HIP_ERR_ARG; }
         if (ok) { ok = hipMemcpy(out, d_out, (size_t)res[2], hipMemcpyDeviceToHost) == hipSuccess; *out_n = (size_t)res[2]; }
     }
-    cleanup();
     if (!ok) { c->err = "debug_gzip: device error"; return DWGSIM_HIP_ERR_DEVICE; }
     return DWGSIM_HIP_OK;
 }

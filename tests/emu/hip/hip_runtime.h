@@ -108,6 +108,7 @@ static inline float __builtin_amdgcn_sqrtf(float x) { return sqrtf(x); }
 // ---- host runtime ----
 typedef int hipError_t;
 #define hipSuccess 0
+#define hipErrorOutOfMemory 2
 typedef struct hipemu_stream *hipStream_t;
 typedef struct hipemu_event { double t; } *hipEvent_t;
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
@@ -120,10 +121,12 @@ static inline hipError_t hipGetDeviceCount(int *n) { *n = 1; return 0; }
 static inline hipError_t hipDeviceGetPCIBusId(char *b, int n, int) { if (n > 0) b[0] = 0; return 1; }      // (no bus on the emulator: the NUMA node is unknown)
 static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) { memset(p, 0, sizeof *p); strcpy(p->name, "cpu-simt-emulator"); strcpy(p->gcnArchName, "emu"); p->multiProcessorCount = 1; return 0; }
 // (exactly n bytes, so that AddressSanitizer sees an access past the REQUESTED size: round 5's advisor found a 16-byte overrun that a size rounded up to 256 hid)
-static inline hipError_t hipMalloc(void **p, size_t n) { *p = nullptr; return posix_memalign(p, 256, n ? n : 1) == 0 ? 0 : 2; }
-static inline hipError_t hipFree(void *p) { free(p); return 0; }
-static inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = nullptr; return posix_memalign(p, 256, n ? n : 1) == 0 ? 0 : 2; }
-static inline hipError_t hipHostFree(void *p) { free(p); return 0; }
+// Both kinds are counted, and an allocation can be made to fail (hip_emu.cpp: hipemu_live_allocs, hipemu_fail_alloc).
+namespace hipemu { hipError_t mem_alloc(void **p, size_t n); void mem_free(void *p); }
+static inline hipError_t hipMalloc(void **p, size_t n) { return hipemu::mem_alloc(p, n); }
+static inline hipError_t hipFree(void *p) { hipemu::mem_free(p); return 0; }
+static inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { return hipemu::mem_alloc(p, n); }
+static inline hipError_t hipHostFree(void *p) { hipemu::mem_free(p); return 0; }
 #define hipHostRegisterDefault 0
 static inline hipError_t hipHostRegister(void *, size_t, unsigned) { return 0; }
 static inline hipError_t hipHostUnregister(void *) { return 0; }

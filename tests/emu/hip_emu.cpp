@@ -8,6 +8,7 @@
 // HIPEMU_WAVES_APART (launch below) runs the waves of a block one at a time between barriers and poisons LDS at every block start.
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
+#include <atomic>
 #include <mutex>
 
 #if defined(__SANITIZE_ADDRESS__)
@@ -237,3 +238,28 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()> &fn
     t_threadIdx = saved[0]; t_blockIdx = saved[1]; t_blockDim = saved[2]; t_gridDim = saved[3];
 }
 } // namespace hipemu
+
+// device and page-locked memory (hipMalloc / hipHostMalloc): live allocations are counted, and the k-th allocation from a given moment can be
+// made to fail with hipErrorOutOfMemory -- tests/test_emu_memory.py checks that every allocation is freed and that a failed one leaves sound state
+namespace {
+std::atomic<long> g_live{0}, g_fail_in{0};
+}
+namespace hipemu {
+hipError_t mem_alloc(void **p, size_t n)
+{
+    *p = nullptr;
+    if (g_fail_in.load() > 0 && g_fail_in.fetch_sub(1) == 1) return hipErrorOutOfMemory;
+    if (posix_memalign(p, 256, n ? n : 1) != 0) { *p = nullptr; return hipErrorOutOfMemory; }
+    ++g_live;
+    return hipSuccess;
+}
+void mem_free(void *p)
+{
+    if (!p) return;
+    --g_live;
+    free(p);
+}
+} // namespace hipemu
+extern "C" long hipemu_live_allocs(void) { return g_live.load(); }
+// k > 0: the k-th allocation from now fails (once); 0: none.  Returns how many allocations the previous request still had to wait for (0: it fired or there was none).
+extern "C" long hipemu_fail_alloc(long k) { return g_fail_in.exchange(k < 0 ? 0 : k); }
