@@ -27,6 +27,9 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <array>
+#include <stddef.h>
+#include <type_traits>
 #include "../../include/dwgsim_hip.h"
 #include "dw_kernels.hpp"
 #include "dw_launch.hpp"
@@ -61,8 +64,29 @@ struct GroupMem {
     // the bitmap (uint32) of 64-cell chunks the last walk may have written
     DevMem d_refview, d_refsumm, d_refsumm2, d_dirty;
     DevEvent ev_walk, ev_walk0;      // end / start of the walk chain on the walk stream
-    HostMem h_wc;                    // page-locked mirror (16 x u64) of the walk's counters (the context's d_wcounters) at the end of THIS group's walk: several groups' walks can be in flight
+    HostMem h_wc;                    // page-locked mirror (a WalkCounters) of the walk's counters (the context's d_wcounters) at the end of THIS group's walk: several groups' walks can be in flight
 };
+
+// The walk's counter block: 16 u64 words, on the device (dwgsim_hip_ctx::d_wcounters) and mirrored per group (GroupMem::h_wc).  The kernels are handed pointers to
+// single words of it, so the layout is the host's alone.  The random walk clears and reads back n_cand .. n_cand_true, the file-driven walk mut_debug (WC_*).
+struct WalkCounters {
+    uint64_t unused0[7];
+    uint64_t n_cand;                                 // candidate sites in the list (0 when a slot overflowed)
+    uint32_t max_del;                                // longest deletion run (k_events -> k_resolve)
+    struct { uint32_t entries, bases; } ins[2];      // insertion-table entries and inserted bases per haplotype (the tot4 of k_resolve / k_apply)
+    uint32_t unused1;
+    uint32_t slot_over;                              // a block of the site scan outgrew its slot: nothing behind it ran
+    uint32_t n_cand_true;                            // ... and the candidates there really are
+    uint64_t mut_debug[2];                           // the file-driven walk: mut_debug verdict before / after the justification (all ones: none)
+    uint64_t n_listed;                               // mutated cells (fetch_mutated_list)
+    uint64_t unused2;
+};
+static_assert(std::is_standard_layout<WalkCounters>::value && sizeof(WalkCounters) == 16 * 8, "the walk's counter block is 16 u64 words");
+static_assert(offsetof(WalkCounters, n_cand) == 7 * 8 && offsetof(WalkCounters, max_del) == 8 * 8 && offsetof(WalkCounters, ins) == 8 * 8 + 4 && offsetof(WalkCounters, slot_over) == 8 * 8 + 6 * 4 &&
+              offsetof(WalkCounters, n_cand_true) == 8 * 8 + 7 * 4 && offsetof(WalkCounters, mut_debug) == 12 * 8 && offsetof(WalkCounters, n_listed) == 14 * 8, "every counter at the word the kernels were given before the block had a type");
+struct WcSpan { size_t off, bytes; };      // the fields `first` through `last`, as bytes of the block
+#define WC_SPAN(first, last) WcSpan{offsetof(WalkCounters, first), offsetof(WalkCounters, last) + sizeof(WalkCounters::last) - offsetof(WalkCounters, first)}
+constexpr WcSpan WC_RANDOM = WC_SPAN(n_cand, n_cand_true), WC_FILE = WC_SPAN(mut_debug, mut_debug), WC_LISTED = WC_SPAN(n_listed, n_listed);
 
 struct Group {
     bool alive = false, mutated = false, walk_pending = false;
@@ -73,7 +97,7 @@ struct Group {
     uint32_t n_ins[2] = {0, 0}, n_ins_bases[2] = {0, 0};
     int fixed_max = 0;               // longest "[prefix_]name"
     uint32_t n_cand = 0;
-    uint32_t n_dirty_words = 0; bool dirty_any = false, dirty_all = false;      // mem.d_dirty: words, any chunk written -- or "everything" after a walk that kept no bitmap (dirty_all)
+    bool dirty_any = false, dirty_all = false;      // mem.d_dirty: any chunk written -- or "everything" after a walk that kept no bitmap (dirty_all)
     // a walk that was enqueued and not yet waited for
     int walk_attempt = 0; uint32_t walk_cap = 0; size_t walk_cap_bases = 0; bool walk_reset = false;
     uint32_t n_patch = 0, n_patch_ev = 0;       // file-driven mutations: patched cells / indel events
@@ -141,7 +165,7 @@ struct dwgsim_hip_ctx {
     Regions regions; bool has_regions = false;                           // -x
     DevMem flow_scratch, flow_free;
     Counters counters;                       // calibrate / count_random / debug hooks (compute stream)
-    DevMem d_wcounters;                      // 16 x u64 (mirrored per group: Group::h_wc): the walk ([7] candidates, [8..11] eight words, [12], [13] mut_debug, [14] listed cells)
+    DevMem d_wcounters;                      // a WalkCounters (mirrored per group: GroupMem::h_wc)
     Counters pcounters;                      // count_random (walk stream)
     Slot slot[DWGSIM_HIP_SLOTS];             // simulate(): up to three batches in flight (kernels | copy-out issued | copy-out landing: dw_job.cpp)
     DevMem d_chain;                          // [0] random reads emitted before the next batch, [1] the abort rule's carry: handed from batch to batch on the device
@@ -153,6 +177,7 @@ struct dwgsim_hip_ctx {
     int n_cu = 0; int flow_slots = 0;      // compute units of the device; "flow_slots": scratch slots per XCD forced by the tests (0: as many as an XCD can hold blocks)
     int64_t walk_cap = -1; bool phases = false; int writer = -1, force_threads = 0; int64_t place_cap = -1; uint64_t place_open = 0; double walk_us = 0, count_us = 0; int split = -1;      // dwgsim_hip_debug_option / _debug_get
     int64_t sim_form = 0;                  // dwgsim_hip_debug_get("sim_form"): the k_simulate form of the last launch
+    int64_t walk_form = 0;                 // dwgsim_hip_debug_get("walk_form"): what the last walk enqueued was made of
     hipEvent_t ev_cnt0 = nullptr, ev_cnt1 = nullptr;
     bool gzip_on = false; DevMem d_crc_table, d_crc_shift;      // dwgsim_hip_set_gzip (u32; d_crc_shift is uploaded last)
     HostMem h_stage;                       // pinned staging for fetch
@@ -198,6 +223,14 @@ int upload(dwgsim_hip_ctx *c, DevMem &b, const void *src, size_t n)
     return 0;
 }
 
+// A host table of a group goes up: room for it and `slack` entries more, then the copy (the vector lives in the GroupMem: the copy may read it after the call)
+template <class T> int upload_table(dwgsim_hip_ctx_t *c, DevMem &d, const std::vector<T> &h, size_t slack)
+{
+    HIPC(c, reserve(c, d, sizeof(T) * h.size(), sizeof(T) * (h.size() + slack)));
+    HIPC(c, hipMemcpyAsync(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, c->walk_stream));
+    return 0;
+}
+
 uint8_t nt4(int ch)      // dwgsim.c:56-73
 {
     switch (ch) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; case '-': return 5; default: return 4; }
@@ -230,6 +263,47 @@ WalkParams walk_params(const dwgsim_hip_ctx *c)
 }
 
 size_t padded_cells(const Group &g) { return (size_t)g.total + CELL_PAD; }
+
+// The state of a group of `padded` cells besides the cells themselves, in bytes: what a restore copies, what clearing the bitmap covers, and (with a little
+// slack: reserve_cell_buffers) what is allocated.  The bitmap: one bit per 64-cell chunk, two words more.
+size_t view_bytes(size_t padded) { return padded / 2; }
+size_t summ_bytes(size_t padded) { return sizeof(uint16_t) * (padded / SUMM_CELLS); }
+size_t summ2_bytes(size_t padded) { return sizeof(uint16_t) * (padded / SUMM2_CELLS); }
+uint32_t dirty_words(size_t padded) { return (uint32_t)((padded + 32 * SUMM_CELLS - 1) / (32 * SUMM_CELLS)); }
+size_t dirty_bytes(size_t padded) { return sizeof(uint32_t) * ((size_t)dirty_words(padded) + 2); }
+
+// Haplotype h's chosen buffers go back to the pristine copies made at upload (the cells: the packed reference)
+enum : unsigned { R_CELLS = 1, R_VIEW = 2, R_SUMM = 4, R_SUMM2 = 8, R_ALL = 15 };
+int restore_pristine(dwgsim_hip_ctx *c, const Group &g, int h, unsigned what, hipStream_t st)
+{
+    const GroupMem &M = g.mem;
+    const size_t padded = padded_cells(g);
+    if (what & R_CELLS) HIPC(c, hipMemcpyAsync(M.d_cells[h].get(), M.d_ref.get(), padded, hipMemcpyDeviceToDevice, st));
+    if (what & R_VIEW) HIPC(c, hipMemcpyAsync(M.d_view[h].get(), M.d_refview.get(), view_bytes(padded), hipMemcpyDeviceToDevice, st));
+    if (what & R_SUMM) HIPC(c, hipMemcpyAsync(M.d_summ[h].get(), M.d_refsumm.get(), summ_bytes(padded), hipMemcpyDeviceToDevice, st));
+    if (what & R_SUMM2) HIPC(c, hipMemcpyAsync(M.d_summ2[h].get(), M.d_refsumm2.get(), summ2_bytes(padded), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// no chunk of the group is dirty
+int clear_dirty(dwgsim_hip_ctx *c, const Group &g, hipStream_t st)
+{
+    HIPC(c, hipMemsetAsync(g.mem.d_dirty.get(), 0, dirty_bytes(padded_cells(g)), st));
+    return 0;
+}
+
+// a span of the walk's counters: filled with a byte on the device; copied to the group's mirror
+hipError_t wc_fill(dwgsim_hip_ctx *c, WcSpan s, int byte, hipStream_t st) { return hipMemsetAsync(c->d_wcounters.get() + s.off, byte, s.bytes, st); }
+hipError_t wc_fetch(dwgsim_hip_ctx *c, const GroupMem &M, WcSpan s, hipStream_t st) { return hipMemcpyAsync(M.h_wc.get() + s.off, c->d_wcounters.get() + s.off, s.bytes, hipMemcpyDeviceToHost, st); }
+
+// The four insertion tables of haplotype h: the group's device buffer, the host vector of t and the bytes it holds (up: dwgsim_hip_mutate_async; down:
+// fetch_mutated_list, which sizes t first)
+struct InsTable { void *dev, *host; size_t bytes; };
+std::array<InsTable, 4> ins_tables(const GroupMem &M, int h, HostIns &t)
+{
+    return {{{M.d_ins_pos[h].get(), t.pos.data(), sizeof(int32_t) * t.pos.size()}, {M.d_ins_len[h].get(), t.len.data(), sizeof(uint32_t) * t.len.size()},
+             {M.d_ins_off[h].get(), t.off.data(), sizeof(uint32_t) * t.off.size()}, {M.d_ins_bases[h].get(), t.bases.data(), t.bases.size()}}};
+}
 
 SegTab seg_tab(const Group &g)
 {
@@ -475,7 +549,7 @@ dwgsim_hip_ctx_t *dwgsim_hip_create(const dwgsim_hip_params_t *p, int device, in
         const size_t cnt_bytes = N_COUNTERS * sizeof(uint64_t);
         auto counters = [&](Counters &k) -> int { HIPC(c, reserve(c, k.d, cnt_bytes, cnt_bytes)); HIPC(c, k.h.reserve(cnt_bytes, cnt_bytes)); return 0; };
         if (counters(c->counters)) return -1;
-        HIPC(c, reserve(c, c->d_wcounters, 16 * sizeof(uint64_t), 16 * sizeof(uint64_t)));
+        HIPC(c, reserve(c, c->d_wcounters, sizeof(WalkCounters), sizeof(WalkCounters)));
         if (counters(c->pcounters)) return -1;
         HIPC(c, reserve(c, c->d_chain, 4 * sizeof(uint64_t), 4 * sizeof(uint64_t)));
         HIPC(c, hipMemset(c->d_chain.get(), 0, 4 * sizeof(uint64_t)));
@@ -690,6 +764,139 @@ static bool is_page_locked(const void *p)
     return false;
 }
 
+// ---- dwgsim_hip_add_contigs, step by step (build_group runs them in order; what they enqueue goes to the walk stream) ----
+
+// A free group slot, reset, with the memory of a dropped group if one is large enough for `want` cells (the smallest such; none more than four times too large)
+static int take_group(dwgsim_hip_ctx_t *c, size_t want)
+{
+    int gid = -1;
+    for (size_t i = 0; i < c->groups.size(); ++i) if (!c->groups[i].alive) { gid = (int)i; break; }
+    if (gid < 0) { c->groups.emplace_back(); gid = (int)c->groups.size() - 1; }
+    Group &g = c->groups[(size_t)gid];
+    g = Group();
+    int best = -1;
+    for (size_t i = 0; i < c->pool.size(); ++i) {
+        const size_t cap = c->pool[i].d_ref.cap();
+        if (cap >= want && cap <= 4 * want + (1u << 20) && (best < 0 || cap < c->pool[(size_t)best].d_ref.cap())) best = (int)i;
+    }
+    if (best >= 0) { g.mem = std::move(c->pool[(size_t)best]); c->pool.erase(c->pool.begin() + best); }
+    return gid;
+}
+
+// The events, the counter mirror and the buffers of cells of a group of `padded` cells.  The buffers of cells go and come together (d_ref's capacity stands
+// for all of them); views and summaries hold 32 bytes more than a restore copies.
+static int reserve_cell_buffers(dwgsim_hip_ctx_t *c, GroupMem &M, size_t padded)
+{
+    HIPC(c, M.ev_walk.create()); HIPC(c, M.ev_walk0.create());
+    HIPC(c, M.h_wc.reserve(sizeof(WalkCounters), sizeof(WalkCounters)));
+    if (M.d_ref.cap() >= padded) return 0;
+    const size_t view = view_bytes(padded) + 32, summ = summ_bytes(padded) + 32, summ2 = summ2_bytes(padded) + 32;
+    const struct { DevMem *buf; size_t bytes; } cellbufs[] = {
+        {&M.d_ref, padded}, {&M.d_cells[0], padded}, {&M.d_view[0], view}, {&M.d_summ[0], summ}, {&M.d_summ2[0], summ2},
+        {&M.d_cells[1], padded}, {&M.d_view[1], view}, {&M.d_summ[1], summ}, {&M.d_summ2[1], summ2},
+        {&M.d_refview, view}, {&M.d_refsumm, summ}, {&M.d_refsumm2, summ2}, {&M.d_dirty, dirty_bytes(padded)}};
+    for (const auto &b : cellbufs) b.buf->reset();
+    for (const auto &b : cellbufs) HIPC(c, reserve(c, *b.buf, b.bytes, b.bytes));
+    return 0;
+}
+
+// The sequence goes up into c->up_ascii.  One copy when the caller's buffers already are the group layout inside ONE page-locked
+// allocation (ascii[k] = ascii[0] + start[k], zero bytes between the contigs): nothing is staged and the call need not wait -- the
+// buffers must then stay as they are until dwgsim_hip_mutate_wait returned.  A few contigs: one copy each into a zeroed device buffer.
+// Many: packed into page-locked staging first (one copy instead of thousands).  must_wait: the call may only return once the walk
+// stream has read the caller's buffers (every form but the first).
+static int upload_sequence(dwgsim_hip_ctx_t *c, int n, const uint8_t *const *ascii, const int64_t *lens, const int64_t *starts, int64_t total, size_t padded, bool &must_wait)
+{
+    if (ensure(c, c->up_ascii, padded)) return DWGSIM_HIP_ERR_DEVICE;
+    uint8_t *d_ascii = c->up_ascii.get();
+    must_wait = true;
+    bool laid_out = true;
+    for (int k = 0; k < n && laid_out; ++k) if (lens[k] > 0 && ascii[k] != ascii[0] + starts[k]) laid_out = false;
+    if (laid_out && n > 0 && ascii[0] && is_page_locked(ascii[0])) {
+        HIPC(c, hipMemcpyAsync(d_ascii, ascii[0], (size_t)total, hipMemcpyHostToDevice, c->walk_stream));
+        HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream));
+        must_wait = false;
+    } else if (n <= 8) {
+        HIPC(c, hipMemsetAsync(d_ascii, 0, padded, c->walk_stream));
+        for (int k = 0; k < n; ++k) if (lens[k] > 0) HIPC(c, hipMemcpyAsync(d_ascii + starts[k], ascii[k], (size_t)lens[k], hipMemcpyHostToDevice, c->walk_stream));
+    } else {
+        if (c->up_in_flight) { HIPC(c, hipEventSynchronize(c->ev_up)); c->up_in_flight = false; }
+        HIPC(c, c->h_up.reserve((size_t)total, (size_t)total + (size_t)total / 4 + 4096));
+        uint8_t *h_up = c->h_up.get();
+        for (int k = 0; k < n; ++k) {
+            const int64_t end = starts[k] + lens[k], next = k + 1 < n ? starts[k + 1] : total;
+            if (lens[k] > 0) memcpy(h_up + starts[k], ascii[k], (size_t)lens[k]);
+            memset(h_up + end, 0, (size_t)(next - end));
+        }
+        HIPC(c, hipMemcpyAsync(d_ascii, h_up, (size_t)total, hipMemcpyHostToDevice, c->walk_stream));
+        HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream));
+        HIPC(c, hipEventRecord(c->ev_up, c->walk_stream)); c->up_in_flight = true;
+    }
+    return 0;
+}
+
+// The pristine state, from the uploaded sequence: the packed reference and both haplotypes' cells; the read views and summaries of the unmutated
+// group, once -- the pristine copies, and what both haplotypes start from (a walk then rewrites only the chunks it touches); a zeroed bitmap
+static int make_pristine(dwgsim_hip_ctx_t *c, const Group &g)
+{
+    const GroupMem &M = g.mem;
+    const int64_t n_cells = (int64_t)padded_cells(g) & ~(int64_t)15;
+    uint8_t *ref = M.d_ref.get();
+    launch_pack(c->walk_stream, c->up_ascii.get(), ref, M.d_cells[0].get(), M.d_cells[1].get(), n_cells);
+    launch_make_view(c->walk_stream, ref, ref, n_cells, g.total, M.d_refview.get(), M.d_view[0].get(), M.d_refsumm.get<uint16_t>(), M.d_summ[0].get<uint16_t>(), M.d_refsumm2.get<uint16_t>(), M.d_summ2[0].get<uint16_t>());
+    if (const int rc = restore_pristine(c, g, 1, R_VIEW | R_SUMM | R_SUMM2, c->walk_stream)) return rc;
+    if (const int rc = clear_dirty(c, g, c->walk_stream)) return rc;
+    HIPC(c, hipGetLastError());
+    return 0;
+}
+
+// Segment table, name pool and (-x) target regions of a group: made on the host, uploaded
+static int upload_group_tables(dwgsim_hip_ctx_t *c, Group &g)
+{
+    GroupMem &M = g.mem;
+    const int n = (int)g.m.size();
+    M.h_seg.assign((size_t)(3 * n + 1), 0);
+    for (int k = 0; k < n; ++k) { M.h_seg[(size_t)k] = g.m[(size_t)k].start; M.h_seg[(size_t)(n + 1 + k)] = (int32_t)g.m[(size_t)k].l; M.h_seg[(size_t)(2 * n + 1 + k)] = (int32_t)g.m[(size_t)k].contig_index; }
+    M.h_seg[(size_t)n] = (int32_t)g.total;
+    if (const int rc = upload_table(c, M.d_seg, M.h_seg, 64)) return rc;
+    M.h_names.clear();
+    for (Member &m : g.m) {      // '@' + "[prefix_]name", zero padded to >= 256 + 16 bytes (the kernel stages 128 bytes in LDS), entries 16-byte aligned
+        const std::string nf = c->read_prefix.empty() ? m.name : c->read_prefix + "_" + m.name;
+        m.name_fixed_len = (int32_t)nf.size(); m.name_off = (uint32_t)M.h_names.size();
+        if (m.name_fixed_len > g.fixed_max) g.fixed_max = m.name_fixed_len;
+        const size_t room = ((nf.size() + 1 < 256 ? 272 : nf.size() + 1 + 16) + 15) & ~(size_t)15;
+        M.h_names.resize(M.h_names.size() + room, 0);
+        M.h_names[m.name_off] = '@'; memcpy(&M.h_names[m.name_off + 1], nf.data(), nf.size());
+    }
+    if (const int rc = upload_table(c, M.d_names, M.h_names, 4096)) return rc;
+    M.h_reg.clear();
+    if (!c->has_regions) return 0;
+    for (Member &m : g.m) {      // [starts | ends] of the contig's regions; fragments are placed on their total length
+        std::vector<int32_t> st, en; int64_t tot = 0;
+        for (size_t q = 0; q < c->regions.contig.size(); ++q) if (c->regions.contig[q] == m.contig_index) { st.push_back((int32_t)c->regions.start[q]); en.push_back((int32_t)c->regions.end[q]); tot += c->regions.end[q] - c->regions.start[q]; }
+        m.reg_off = (int32_t)M.h_reg.size(); m.n_reg = (int32_t)st.size(); m.l_place = tot;
+        M.h_reg.insert(M.h_reg.end(), st.begin(), st.end()); M.h_reg.insert(M.h_reg.end(), en.begin(), en.end());
+    }
+    M.h_reg.push_back(0);
+    return upload_table(c, M.d_reg, M.h_reg, 64);
+}
+
+// Everything a new group needs on the device, enqueued on the walk stream.  A step that fails returns at once: the caller undoes the group.
+static int build_group(dwgsim_hip_ctx_t *c, Group &g, const uint8_t *const *ascii, const int64_t *lens, const int64_t *starts)
+{
+    const int n = (int)g.m.size();
+    const size_t padded = padded_cells(g);
+    bool must_wait = true;
+    if (const int rc = reserve_cell_buffers(c, g.mem, padded)) return rc;
+    if (const int rc = upload_sequence(c, n, ascii, lens, starts, g.total, padded, must_wait)) return rc;
+    if (const int rc = make_pristine(c, g)) return rc;
+    if (const int rc = upload_group_tables(c, g)) return rc;
+    // -m / -b / -v: the file's entries for these contigs are resolved now, while the sequence is at hand (mut.c:644-745)
+    if (c->has_mutin) for (int k = 0; k < n; ++k) resolve_mutation_input(c->mutin, g.m[(size_t)k].contig_index, ascii[k], lens[k], (uint32_t)c->prm.seed, c->prm.is_hap != 0, g.m[(size_t)k].rc);
+    if (must_wait) HIPC(c, hipStreamSynchronize(c->walk_stream));
+    return 0;
+}
+
 int dwgsim_hip_add_contigs(dwgsim_hip_ctx_t *c, int n, const char *const *names, const uint8_t *const *ascii, const int64_t *lens, const uint32_t *contig_index)
 {
     if (!c || n < 1 || !names || !ascii || !lens || !contig_index) { if (c) c->err = "bad contig arguments"; return DWGSIM_HIP_ERR_ARG; }
@@ -698,114 +905,12 @@ int dwgsim_hip_add_contigs(dwgsim_hip_ctx_t *c, int n, const char *const *names,
     const int64_t total = dwgsim_hip_group_layout(lens, n, starts.data());
     if (total < 0 || total > (int64_t)INT32_MAX - 2 * GROUP_ALIGN) { c->err = "dwgsim-hip: the contigs of one group must stay below 2^31 cells in all (add them in smaller groups)\n"; return DWGSIM_HIP_ERR_ARG; }
     HIPC(c, hipSetDevice(c->device));
-    int gid = -1;
-    for (size_t i = 0; i < c->groups.size(); ++i) if (!c->groups[i].alive) { gid = (int)i; break; }
-    if (gid < 0) { c->groups.emplace_back(); gid = (int)c->groups.size() - 1; }
+    const int gid = take_group(c, (size_t)total + CELL_PAD);
     Group &g = c->groups[(size_t)gid];
-    g = Group();
-    {   // memory of a dropped group, if one is large enough (the smallest such; none more than four times too large)
-        const size_t want = (size_t)total + CELL_PAD;
-        int best = -1;
-        for (size_t i = 0; i < c->pool.size(); ++i) {
-            const size_t cap = c->pool[i].d_ref.cap();
-            if (cap >= want && cap <= 4 * want + (1u << 20) && (best < 0 || cap < c->pool[(size_t)best].d_ref.cap())) best = (int)i;
-        }
-        if (best >= 0) { g.mem = std::move(c->pool[(size_t)best]); c->pool.erase(c->pool.begin() + best); }
-    }
-    GroupMem &M = g.mem;
     g.alive = true; g.total = total; g.first_handle = (int)c->handles.size();
     g.m.resize((size_t)n);
     for (int k = 0; k < n; ++k) { Member &m = g.m[(size_t)k]; m.name = names[k]; m.l = m.l_place = lens[k]; m.contig_index = contig_index[k]; m.start = (int32_t)starts[(size_t)k]; }
-    const size_t padded = padded_cells(g);
-    bool synced = true;
-    auto fill = [&]() -> int {
-        HIPC(c, M.ev_walk.create()); HIPC(c, M.ev_walk0.create());
-        HIPC(c, M.h_wc.reserve(16 * sizeof(uint64_t), 16 * sizeof(uint64_t)));
-        if (M.d_ref.cap() < padded) {      // the buffers of cells go and come together (d_ref's capacity stands for all of them)
-            DevMem *cellbufs[] = {&M.d_ref, &M.d_cells[0], &M.d_view[0], &M.d_summ[0], &M.d_summ2[0], &M.d_cells[1], &M.d_view[1], &M.d_summ[1], &M.d_summ2[1], &M.d_refview, &M.d_refsumm, &M.d_refsumm2, &M.d_dirty};
-            for (DevMem *b : cellbufs) b->reset();
-            const size_t view = padded / 2 + 32, summ = sizeof(uint16_t) * (padded / SUMM_CELLS + 16), summ2 = sizeof(uint16_t) * (padded / SUMM2_CELLS + 16);
-            const size_t sizes[] = {padded, padded, view, summ, summ2, padded, view, summ, summ2, view, summ, summ2, sizeof(uint32_t) * ((padded + 32 * SUMM_CELLS - 1) / (32 * SUMM_CELLS) + 2)};
-            for (size_t i = 0; i < sizeof sizes / sizeof sizes[0]; ++i) HIPC(c, reserve(c, *cellbufs[i], sizes[i], sizes[i]));
-        }
-        g.n_dirty_words = (uint32_t)((padded + 32 * SUMM_CELLS - 1) / (32 * SUMM_CELLS));
-        if (ensure(c, c->up_ascii, padded)) return DWGSIM_HIP_ERR_DEVICE;
-        uint8_t *d_ascii = c->up_ascii.get();
-        // The sequence goes up on the walk stream.  One copy when the caller's buffers already are the group layout inside ONE page-locked
-        // allocation (ascii[k] = ascii[0] + start[k], zero bytes between the contigs): nothing is staged and the call does not wait -- the
-        // buffers must then stay as they are until dwgsim_hip_mutate_wait returned.  A few contigs: one copy each into a zeroed device buffer.
-        // Many: packed into page-locked staging first (one copy instead of thousands).
-        bool laid_out = true;
-        for (int k = 0; k < n && laid_out; ++k) if (lens[k] > 0 && ascii[k] != ascii[0] + starts[(size_t)k]) laid_out = false;
-        if (laid_out && n > 0 && ascii[0] && is_page_locked(ascii[0])) {
-            HIPC(c, hipMemcpyAsync(d_ascii, ascii[0], (size_t)total, hipMemcpyHostToDevice, c->walk_stream));
-            HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream));
-            synced = false;
-        } else if (n <= 8) {
-            HIPC(c, hipMemsetAsync(d_ascii, 0, padded, c->walk_stream));
-            for (int k = 0; k < n; ++k) if (lens[k] > 0) HIPC(c, hipMemcpyAsync(d_ascii + starts[(size_t)k], ascii[k], (size_t)lens[k], hipMemcpyHostToDevice, c->walk_stream));
-        } else {
-            if (c->up_in_flight) { HIPC(c, hipEventSynchronize(c->ev_up)); c->up_in_flight = false; }
-            HIPC(c, c->h_up.reserve((size_t)total, (size_t)total + (size_t)total / 4 + 4096));
-            uint8_t *h_up = c->h_up.get();
-            for (int k = 0; k < n; ++k) {
-                const int64_t end = starts[(size_t)k] + lens[k], next = k + 1 < n ? starts[(size_t)k + 1] : total;
-                if (lens[k] > 0) memcpy(h_up + starts[(size_t)k], ascii[k], (size_t)lens[k]);
-                memset(h_up + end, 0, (size_t)(next - end));
-            }
-            HIPC(c, hipMemcpyAsync(d_ascii, h_up, (size_t)total, hipMemcpyHostToDevice, c->walk_stream));
-            HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream));
-            HIPC(c, hipEventRecord(c->ev_up, c->walk_stream)); c->up_in_flight = true;
-        }
-        uint8_t *ref = M.d_ref.get(), *refview = M.d_refview.get();
-        uint16_t *refsumm = M.d_refsumm.get<uint16_t>(), *refsumm2 = M.d_refsumm2.get<uint16_t>();
-        launch_pack(c->walk_stream, d_ascii, ref, M.d_cells[0].get(), M.d_cells[1].get(), (int64_t)padded & ~(int64_t)15);
-        // the read views and summaries of the unmutated group, once: the pristine copies, and what both haplotypes start from (a walk then rewrites
-        // only the chunks it touches)
-        launch_make_view(c->walk_stream, ref, ref, (int64_t)padded & ~(int64_t)15, g.total, refview, M.d_view[0].get(), refsumm, M.d_summ[0].get<uint16_t>(), refsumm2, M.d_summ2[0].get<uint16_t>());
-        HIPC(c, hipMemcpyAsync(M.d_view[1].get(), refview, padded / 2, hipMemcpyDeviceToDevice, c->walk_stream));
-        HIPC(c, hipMemcpyAsync(M.d_summ[1].get(), refsumm, sizeof(uint16_t) * (padded / SUMM_CELLS), hipMemcpyDeviceToDevice, c->walk_stream));
-        HIPC(c, hipMemcpyAsync(M.d_summ2[1].get(), refsumm2, sizeof(uint16_t) * (padded / SUMM2_CELLS), hipMemcpyDeviceToDevice, c->walk_stream));
-        HIPC(c, hipMemsetAsync(M.d_dirty.get(), 0, sizeof(uint32_t) * ((size_t)g.n_dirty_words + 2), c->walk_stream));
-        HIPC(c, hipGetLastError());
-        // segment table, name pool, target regions
-        std::vector<int32_t> &h_seg = M.h_seg, &h_reg = M.h_reg; std::vector<uint8_t> &h_names = M.h_names;
-        h_seg.assign((size_t)(3 * n + 1), 0);
-        for (int k = 0; k < n; ++k) { h_seg[(size_t)k] = g.m[(size_t)k].start; h_seg[(size_t)(n + 1 + k)] = (int32_t)g.m[(size_t)k].l; h_seg[(size_t)(2 * n + 1 + k)] = (int32_t)g.m[(size_t)k].contig_index; }
-        h_seg[(size_t)n] = (int32_t)total;
-        HIPC(c, reserve(c, M.d_seg, sizeof(int32_t) * h_seg.size(), sizeof(int32_t) * (h_seg.size() + 64)));
-        HIPC(c, hipMemcpyAsync(M.d_seg.get(), h_seg.data(), sizeof(int32_t) * h_seg.size(), hipMemcpyHostToDevice, c->walk_stream));
-        h_names.clear();
-        for (int k = 0; k < n; ++k) {      // '@' + "[prefix_]name", zero padded to >= 256 + 16 bytes (the kernel stages 128 bytes in LDS), entries 16-byte aligned
-            Member &m = g.m[(size_t)k];
-            const std::string nf = c->read_prefix.empty() ? m.name : c->read_prefix + "_" + m.name;
-            m.name_fixed_len = (int32_t)nf.size(); m.name_off = (uint32_t)h_names.size();
-            if (m.name_fixed_len > g.fixed_max) g.fixed_max = m.name_fixed_len;
-            const size_t room = ((nf.size() + 1 < 256 ? 272 : nf.size() + 1 + 16) + 15) & ~(size_t)15;
-            h_names.resize(h_names.size() + room, 0);
-            h_names[m.name_off] = '@'; memcpy(&h_names[m.name_off + 1], nf.data(), nf.size());
-        }
-        HIPC(c, reserve(c, M.d_names, h_names.size(), h_names.size() + 4096));
-        HIPC(c, hipMemcpyAsync(M.d_names.get(), h_names.data(), h_names.size(), hipMemcpyHostToDevice, c->walk_stream));
-        h_reg.clear();
-        if (c->has_regions) {
-            for (int k = 0; k < n; ++k) {
-                Member &m = g.m[(size_t)k];
-                std::vector<int32_t> st, en; int64_t tot = 0;
-                for (size_t q = 0; q < c->regions.contig.size(); ++q) if (c->regions.contig[q] == m.contig_index) { st.push_back((int32_t)c->regions.start[q]); en.push_back((int32_t)c->regions.end[q]); tot += c->regions.end[q] - c->regions.start[q]; }
-                m.reg_off = (int32_t)h_reg.size(); m.n_reg = (int32_t)st.size(); m.l_place = tot;
-                h_reg.insert(h_reg.end(), st.begin(), st.end()); h_reg.insert(h_reg.end(), en.begin(), en.end());
-            }
-            h_reg.push_back(0);
-            HIPC(c, reserve(c, M.d_reg, sizeof(int32_t) * h_reg.size(), sizeof(int32_t) * (h_reg.size() + 64)));
-            HIPC(c, hipMemcpyAsync(M.d_reg.get(), h_reg.data(), sizeof(int32_t) * h_reg.size(), hipMemcpyHostToDevice, c->walk_stream));
-        }
-        // -m / -b / -v: the file's entries for these contigs are resolved now, while the sequence is at hand (mut.c:644-745)
-        if (c->has_mutin) for (int k = 0; k < n; ++k) resolve_mutation_input(c->mutin, g.m[(size_t)k].contig_index, ascii[k], lens[k], (uint32_t)c->prm.seed, c->prm.is_hap != 0, g.m[(size_t)k].rc);
-        if (synced) HIPC(c, hipStreamSynchronize(c->walk_stream));
-        return 0;
-    };
-    const int rc = fill();
+    const int rc = build_group(c, g, ascii, lens, starts.data());
     if (rc != 0) { (void)hipStreamSynchronize(c->walk_stream); g = Group(); return rc; }      // no half-built group stays behind a failed call
     for (int k = 0; k < n; ++k) c->handles.push_back(HandleRef{gid, k});
     return g.first_handle;
@@ -923,10 +1028,6 @@ static int ensure_ins(dwgsim_hip_ctx_t *c, Group &g, int h, size_t entries, size
     return DWGSIM_HIP_OK;
 }
 
-// One attempt of the walk of a whole group, enqueued on the walk stream without any host read-back in between: buffers are sized for a
-// capacity (candidate sites are a Binomial(l, mut_rate) draw: mean + 8 sigma), the kernels take their element counts from device memory, and
-// the read-back at the end (dwgsim_hip_mutate_wait) also tells whether a capacity was exceeded -- then the walk is simply run again with
-// exact sizes.
 // the read views and summaries of both haplotypes, made from every cell
 static void make_views(hipStream_t st, const Group &g)
 {
@@ -939,121 +1040,201 @@ static void make_views(hipStream_t st, const Group &g)
 static void dirty_chunks(hipStream_t st, bool restore, const Group &g)
 {
     const GroupMem &M = g.mem;
-    launch_dirty_chunks(st, restore, M.d_dirty.get<uint32_t>(), g.n_dirty_words, g.total, M.d_ref.get(), M.d_refview.get(), M.d_refsumm.get<uint16_t>(), M.d_refsumm2.get<uint16_t>(),
+    launch_dirty_chunks(st, restore, M.d_dirty.get<uint32_t>(), dirty_words(padded_cells(g)), g.total, M.d_ref.get(), M.d_refview.get(), M.d_refsumm.get<uint16_t>(), M.d_refsumm2.get<uint16_t>(),
                         M.d_cells[0].get(), M.d_cells[1].get(), M.d_view[0].get(), M.d_view[1].get(), M.d_summ[0].get<uint16_t>(), M.d_summ[1].get<uint16_t>(), M.d_summ2[0].get<uint16_t>(), M.d_summ2[1].get<uint16_t>());
 }
 
-static int enqueue_walk(dwgsim_hip_ctx_t *c, Group &g)
+// left-justification of the events of a walk: the cluster-parallel form or ("justify_seq", the cross-check) one thread for the whole group
+static void justify(dwgsim_hip_ctx_t *c, hipStream_t st, const Event *ev, Count n, const ContigDev &cd)
 {
-    const WalkParams wp = walk_params(c);
-    const int64_t total = g.total;
-    const size_t padded = padded_cells(g);
+    if (c->seq_justify) launch_justify_seq(st, ev, n, cd);
+    else launch_justify(st, ev, n, cd, c->w_lo.get<int32_t>(), c->w_sufmin.get<int32_t>(), c->w_bound.get<uint8_t>());
+}
+
+// dwgsim_hip_debug_get("walk_form"): restore 0 none / 1 the dirty chunks / 2 whole buffers
+static int64_t pack_walk_form(int attempt, bool file_driven, bool slots, int restore, bool dense)
+{
+    return (int64_t)attempt << 16 | (file_driven ? 1 : 0) << 12 | (slots ? 1 : 0) << 8 | restore << 4 | (dense ? 1 : 0);
+}
+
+// The walk of a group with file-driven mutations (-m / -b / -v, mut.c:644-745): the host resolved the entries (dwgsim_hip_mutate_async collected them), the
+// GPU scatters them into the cells and left-justifies the indels; the views are made from every cell.  mut_debug runs before and after the justification.
+static int walk_file_driven(dwgsim_hip_ctx_t *c, Group &g)
+{
     hipStream_t st = c->walk_stream;
-    const SegTab seg = seg_tab(g);
     const GroupMem &M = g.mem;
-    uint64_t *wcnt = c->d_wcounters.get<uint64_t>(), *wc = M.h_wc.get<uint64_t>();      // the walk's counters and the group's mirror of them
+    WalkCounters *wc = c->d_wcounters.get<WalkCounters>();
+    const uint32_t np = g.n_patch, nev = g.n_patch_ev;
+    const size_t nev1 = nev ? nev : 1;
+    if (np && (ensure(c, c->w_ppos, sizeof(int32_t) * np) || ensure(c, c->w_pcells, sizeof(uint16_t) * np) || ensure(c, c->w_ev, sizeof(Event) * nev1) ||
+               ensure(c, c->w_lo, sizeof(int32_t) * nev1) || ensure(c, c->w_sufmin, sizeof(int32_t) * (nev1 + 64)) || ensure(c, c->w_bound, nev1))) return DWGSIM_HIP_ERR_DEVICE;      // (+ 64: segment minima of k_sufmin)
+    c->walk_form = pack_walk_form(g.walk_attempt, true, false, g.walk_reset ? 2 : 0, true);
     HIPC(c, hipEventRecord(M.ev_walk0.get(), st));
-    if (c->has_mutin) {      // file-driven mutations (mut.c:644-745): the host resolved the entries, the GPU scatters and left-justifies
-        const uint32_t np = g.n_patch, nev = g.n_patch_ev;
-        if (g.walk_reset) for (int h = 0; h < 2; ++h) HIPC(c, hipMemcpyAsync(M.d_cells[h].get(), M.d_ref.get(), padded, hipMemcpyDeviceToDevice, st));
-        HIPC(c, hipMemsetAsync(&wcnt[12], 0xff, 2 * sizeof(uint64_t), st));
-        if (np) {
-            if (ensure(c, c->w_ppos, sizeof(int32_t) * np) || ensure(c, c->w_pcells, sizeof(uint16_t) * np) || ensure(c, c->w_ev, sizeof(Event) * (nev ? nev : 1)) ||
-                ensure(c, c->w_lo, sizeof(int32_t) * (nev ? nev : 1)) || ensure(c, c->w_sufmin, sizeof(int32_t) * ((nev ? nev : 1) + 64)) || ensure(c, c->w_bound, nev ? nev : 1)) return DWGSIM_HIP_ERR_DEVICE;      // (+ 64: segment minima of k_sufmin)
-            HIPC(c, hipMemcpyAsync(c->w_ppos.get(), c->h_ppos.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
-            HIPC(c, hipMemcpyAsync(c->w_pcells.get(), c->h_pcells.data(), sizeof(uint16_t) * np, hipMemcpyHostToDevice, st));
-            if (nev) HIPC(c, hipMemcpyAsync(c->w_ev.get(), c->h_pev.data(), sizeof(Event) * nev, hipMemcpyHostToDevice, st));
-            launch_apply_patches(st, c->w_ppos.get<int32_t>(), c->w_pcells.get<uint16_t>(), np, M.d_cells[0].get(), M.d_cells[1].get());
-            const ContigDev cd = group_dev(g);
-            launch_mut_debug(st, M.d_ref.get(), M.d_cells[0].get(), M.d_cells[1].get(), total, &wcnt[12]);      // mut.c:753
-            if (nev) {
-                if (c->seq_justify) launch_justify_seq(st, c->w_ev.get<Event>(), Count{nullptr, nev}, cd);
-                else launch_justify(st, c->w_ev.get<Event>(), Count{nullptr, nev}, cd, c->w_lo.get<int32_t>(), c->w_sufmin.get<int32_t>(), c->w_bound.get<uint8_t>());
-            }
-            launch_mut_debug(st, M.d_ref.get(), M.d_cells[0].get(), M.d_cells[1].get(), total, &wcnt[13]);      // mut.c:757
-        }
-        make_views(st, g);
-        g.dirty_all = true;
-        HIPC(c, hipGetLastError());
-        HIPC(c, hipMemcpyAsync(&wc[12], &wcnt[12], 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIPC(c, hipEventRecord(M.ev_walk.get(), st));
-        return DWGSIM_HIP_OK;
+    if (g.walk_reset) for (int h = 0; h < 2; ++h) if (const int rc = restore_pristine(c, g, h, R_CELLS, st)) return rc;
+    HIPC(c, wc_fill(c, WC_FILE, 0xff, st));
+    if (np) {
+        HIPC(c, hipMemcpyAsync(c->w_ppos.get(), c->h_ppos.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
+        HIPC(c, hipMemcpyAsync(c->w_pcells.get(), c->h_pcells.data(), sizeof(uint16_t) * np, hipMemcpyHostToDevice, st));
+        if (nev) HIPC(c, hipMemcpyAsync(c->w_ev.get(), c->h_pev.data(), sizeof(Event) * nev, hipMemcpyHostToDevice, st));
+        launch_apply_patches(st, c->w_ppos.get<int32_t>(), c->w_pcells.get<uint16_t>(), np, M.d_cells[0].get(), M.d_cells[1].get());
+        launch_mut_debug(st, M.d_ref.get(), M.d_cells[0].get(), M.d_cells[1].get(), g.total, &wc->mut_debug[0]);      // mut.c:753
+        if (nev) justify(c, st, c->w_ev.get<Event>(), Count{nullptr, nev}, group_dev(g));
+        launch_mut_debug(st, M.d_ref.get(), M.d_cells[0].get(), M.d_cells[1].get(), g.total, &wc->mut_debug[1]);      // mut.c:757
     }
-    const uint32_t nblk = (uint32_t)((total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
-    if (ensure(c, c->scratch_status, ((size_t)nblk + 2) * sizeof(uint64_t))) return DWGSIM_HIP_ERR_DEVICE;      // look-back words of k_site_scan_list + its ticket
-    uint64_t *d_status = c->scratch_status.get<uint64_t>(), *d_ticket = d_status + nblk;
+    make_views(st, g);
+    g.dirty_all = true;
+    HIPC(c, hipGetLastError());
+    HIPC(c, wc_fetch(c, M, WC_FILE, st));
+    HIPC(c, hipEventRecord(M.ev_walk.get(), st));
+    return DWGSIM_HIP_OK;
+}
+
+// What one attempt of the random walk of a group takes, decided before anything is reserved or enqueued
+enum class Restore { None, Chunks, All };
+struct WalkPlan {
+    uint32_t cap; size_t ncap, cap_bases;      // candidate capacity (ncap: what the buffers are sized for, at least 1); inserted-base pool per haplotype
+    uint32_t nblk;                             // look-back words of k_site_scan_list (+ its ticket, + 1)
+    bool use_slots; uint32_t nbs, slot_cap; size_t slot_bytes;      // the slot form of the site scan: blocks, entries per slot, bytes of all slots
+    Restore restore;                           // what goes back to the pristine copies first
+    bool dense;                                // views from every cell (the cross-check forms) / from the bitmap of dirty chunks
+};
+
+static WalkPlan walk_plan(const dwgsim_hip_ctx_t *c, const Group &g)
+{
+    WalkPlan P;
+    P.cap = g.walk_cap; P.ncap = P.cap ? P.cap : 1; P.cap_bases = g.walk_cap_bases;
+    P.nblk = (uint32_t)((g.total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
+    // candidate sites -> ordered list.  First attempt: every block into a slot of its own, no block waits for another (dw_walk.hip k_site_scan_slots: mean +
+    // 8 sigma + 32 entries per block of 65 536 positions); a re-run, a mutation rate at which the slots would be as large as the list itself, or
+    // "site_slots" = 0: one kernel with a decoupled look-back
+    P.nbs = site_scan_blocks(g.total);
+    const double m = (double)site_scan_block_positions() * (c->prm.mut_rate > 0 ? c->prm.mut_rate : 0.0);
+    P.slot_cap = (uint32_t)std::min<double>((double)site_scan_block_positions(), m + 8.0 * sqrt(m + 1.0) + 32.0);
+    if (c->site_slot_cap >= 0) P.slot_cap = (uint32_t)std::max<int64_t>(1, c->site_slot_cap);
+    P.slot_bytes = (size_t)P.nbs * P.slot_cap * sizeof(int32_t);
+    P.use_slots = g.walk_attempt == 0 && c->site_slots != 0 && P.nbs > 0 && (c->site_slots > 0 || P.slot_bytes <= std::max<size_t>((size_t)64 << 20, P.ncap * 16));
     // where the group stands: fresh from the upload, or with the chunks the previous walk wrote -- those go back to the pristine copies --, or (a
     // capacity re-run, a walk that kept no bitmap) all of it
-    if (g.walk_attempt > 0 || g.dirty_all) {
-        for (int h = 0; h < 2; ++h) {
-            HIPC(c, hipMemcpyAsync(M.d_cells[h].get(), M.d_ref.get(), padded, hipMemcpyDeviceToDevice, st));
-            HIPC(c, hipMemcpyAsync(M.d_view[h].get(), M.d_refview.get(), padded / 2, hipMemcpyDeviceToDevice, st));
-            HIPC(c, hipMemcpyAsync(M.d_summ[h].get(), M.d_refsumm.get(), sizeof(uint16_t) * (padded / SUMM_CELLS), hipMemcpyDeviceToDevice, st));
-            HIPC(c, hipMemcpyAsync(M.d_summ2[h].get(), M.d_refsumm2.get(), sizeof(uint16_t) * (padded / SUMM2_CELLS), hipMemcpyDeviceToDevice, st));
-        }
-        HIPC(c, hipMemsetAsync(M.d_dirty.get(), 0, sizeof(uint32_t) * ((size_t)g.n_dirty_words + 2), st));
-        g.dirty_all = false; g.dirty_any = false;
-    } else if (g.dirty_any) {
-        dirty_chunks(st, true, g);
-        HIPC(c, hipMemsetAsync(M.d_dirty.get(), 0, sizeof(uint32_t) * ((size_t)g.n_dirty_words + 2), st));
-        g.dirty_any = false;
-    }
-    const uint32_t cap = g.walk_cap; const size_t cap_bases = g.walk_cap_bases;
-    const size_t ncap = cap ? cap : 1;
-    if (ensure(c, c->w_cand, sizeof(int32_t) * ncap) || ensure(c, c->w_ev, sizeof(Event) * ncap) ||
-        ensure(c, c->w_flags, sizeof(uint4) * (ncap + 64)) ||      // (+ 64 rows / entries: the segment totals of k_scan4, the segment minima of k_sufmin)
-        ensure(c, c->w_lo, sizeof(int32_t) * ncap) || ensure(c, c->w_sufmin, sizeof(int32_t) * (ncap + 64)) ||
-        ensure(c, c->w_bound, ncap)) return DWGSIM_HIP_ERR_DEVICE;
-    // insertion tables: at most one entry per candidate; the base pools are checked on the device
-    for (int h = 0; h < 2; ++h) if (const int rc = ensure_ins(c, g, h, ncap, cap_bases)) return rc;
+    P.restore = g.walk_attempt > 0 || g.dirty_all ? Restore::All : g.dirty_any ? Restore::Chunks : Restore::None;
+    P.dense = c->seq_justify || c->dense_view;
+    return P;
+}
+
+// room for the plan: the context's walk scratch and the group's insertion tables (at most one entry per candidate; the base pools are checked on the device)
+static int walk_reserve(dwgsim_hip_ctx_t *c, Group &g, const WalkPlan &P)
+{
+    if (ensure(c, c->scratch_status, ((size_t)P.nblk + 2) * sizeof(uint64_t)) ||
+        ensure(c, c->w_cand, sizeof(int32_t) * P.ncap) || ensure(c, c->w_ev, sizeof(Event) * P.ncap) ||
+        ensure(c, c->w_flags, sizeof(uint4) * (P.ncap + 64)) ||      // (+ 64 rows / entries: the segment totals of k_scan4, the segment minima of k_sufmin)
+        ensure(c, c->w_lo, sizeof(int32_t) * P.ncap) || ensure(c, c->w_sufmin, sizeof(int32_t) * (P.ncap + 64)) ||
+        ensure(c, c->w_bound, P.ncap)) return DWGSIM_HIP_ERR_DEVICE;
+    for (int h = 0; h < 2; ++h) if (const int rc = ensure_ins(c, g, h, P.ncap, P.cap_bases)) return rc;
+    if (P.use_slots && (ensure(c, c->w_slots, P.slot_bytes) || ensure(c, c->w_slot_aux, 2 * (size_t)P.nbs * sizeof(uint32_t)))) return DWGSIM_HIP_ERR_DEVICE;
+    return DWGSIM_HIP_OK;
+}
+
+// The kernels of the planned attempt: candidate sites, events, the cells, left-justification, the views of what was written
+static int walk_launch(dwgsim_hip_ctx_t *c, Group &g, const WalkPlan &P)
+{
+    hipStream_t st = c->walk_stream;
+    const WalkParams wp = walk_params(c);
+    const SegTab seg = seg_tab(g);
+    const GroupMem &M = g.mem;
+    WalkCounters *wc = c->d_wcounters.get<WalkCounters>();
     int32_t *d_cand = c->w_cand.get<int32_t>(); Event *d_ev = c->w_ev.get<Event>(); uint4 *d_flags = c->w_flags.get<uint4>();
-    uint32_t *d_small = reinterpret_cast<uint32_t *>(&wcnt[8]);   // [0] max_del, [1..4] tot4: eight words in counters[8..11], so that one copy brings counters[7..11] back
-    const Count nc{&wcnt[7], cap};
-    HIPC(c, hipMemsetAsync(&wcnt[7], 0, 5 * sizeof(uint64_t), st));
-    // K1: candidate sites -> ordered list, from the pristine 4-bit view.  First attempt: every block into a slot of its own, no block waits for another
-    // (dw_walk.hip k_site_scan_slots: mean + 8 sigma + 32 entries per block of 65 536 positions); a re-run, a mutation rate at which the slots would
-    // be as large as the list itself, or "site_slots" = 0: one kernel with a decoupled look-back
-    {
-        const uint32_t nbs = site_scan_blocks(total);
-        const double m = (double)site_scan_block_positions() * (c->prm.mut_rate > 0 ? c->prm.mut_rate : 0.0);
-        uint32_t slot_cap = (uint32_t)std::min<double>((double)site_scan_block_positions(), m + 8.0 * sqrt(m + 1.0) + 32.0);
-        if (c->site_slot_cap >= 0) slot_cap = (uint32_t)std::max<int64_t>(1, c->site_slot_cap);
-        const size_t slot_bytes = (size_t)nbs * slot_cap * sizeof(int32_t);
-        const bool use_slots = g.walk_attempt == 0 && c->site_slots != 0 && nbs > 0 && (c->site_slots > 0 || slot_bytes <= std::max<size_t>((size_t)64 << 20, (size_t)ncap * 16));
-        if (use_slots) {
-            if (ensure(c, c->w_slots, slot_bytes) || ensure(c, c->w_slot_aux, 2 * (size_t)nbs * sizeof(uint32_t))) return DWGSIM_HIP_ERR_DEVICE;
-            launch_site_scan_slots(st, M.d_refview.get(), total, seg, wp, c->w_slots.get<int32_t>(), slot_cap, c->w_slot_aux.get<uint32_t>(), d_cand, cap, &wcnt[7], &d_small[6]);
-        } else {
-            HIPC(c, hipMemsetAsync(d_status, 0, ((size_t)nblk + 2) * sizeof(uint64_t), st));
-            launch_site_scan_list(st, M.d_refview.get(), total, seg, wp, d_status, d_ticket, d_cand, cap, &wcnt[7]);
-        }
+    uint32_t *tot4 = &wc->ins[0].entries;
+    const Count nc{&wc->n_cand, P.cap};
+    HIPC(c, wc_fill(c, WC_RANDOM, 0, st));
+    // K1: candidate sites -> ordered list, from the pristine 4-bit view
+    if (P.use_slots) launch_site_scan_slots(st, M.d_refview.get(), g.total, seg, wp, c->w_slots.get<int32_t>(), P.slot_cap, c->w_slot_aux.get<uint32_t>(), d_cand, P.cap, &wc->n_cand, &wc->slot_over);
+    else {
+        uint64_t *d_status = c->scratch_status.get<uint64_t>();      // the look-back words, and behind them the ticket
+        HIPC(c, hipMemsetAsync(d_status, 0, ((size_t)P.nblk + 2) * sizeof(uint64_t), st));
+        launch_site_scan_list(st, M.d_refview.get(), g.total, seg, wp, d_status, d_status + P.nblk, d_cand, P.cap, &wc->n_cand);
     }
     // K2: events, liveness, insertion-table allocation
-    launch_events(st, d_cand, nc, M.d_ref.get(), seg, wp, d_ev, &d_small[0]);
-    launch_resolve(st, d_ev, nc, &d_small[0], d_flags, &d_small[1]);
+    launch_events(st, d_cand, nc, M.d_ref.get(), seg, wp, d_ev, &wc->max_del);
+    launch_resolve(st, d_ev, nc, &wc->max_del, d_flags, tot4);
     // K3 + K4
     ContigDev cd = group_dev(g);
-    cd.tot4 = &d_small[1]; cd.cap_bases[0] = (uint32_t)std::min<size_t>(ins_bases_cap(g, 0), 0xFFFFFFFFu); cd.cap_bases[1] = (uint32_t)std::min<size_t>(ins_bases_cap(g, 1), 0xFFFFFFFFu);
+    cd.tot4 = tot4; cd.cap_bases[0] = (uint32_t)std::min<size_t>(ins_bases_cap(g, 0), 0xFFFFFFFFu); cd.cap_bases[1] = (uint32_t)std::min<size_t>(ins_bases_cap(g, 1), 0xFFFFFFFFu);
     launch_apply(st, d_ev, nc, d_flags, cd, wp);
     // mut_debug (mut.c:753, :757) cannot fire on randomly drawn mutations and is not run here: a substitution always changes the base
     // ((c + 1..3) & 3, mut.c:621), a homozygous one writes the same cell to both haplotypes and a heterozygous one leaves the other
     // haplotype's cell as it was -- the reference base, also under a deletion or an insertion, before and after left-justification
     // (which only moves an indel over bases equal to its own).  File-driven mutations (-m / -b / -v, above) can violate all three.
-    if (c->seq_justify || c->dense_view) {      // (the cross-check forms: one thread justifies the whole group / the views are made from every cell as rounds 1-4 did)
-        if (c->seq_justify) launch_justify_seq(st, d_ev, nc, cd); else launch_justify(st, d_ev, nc, cd, c->w_lo.get<int32_t>(), c->w_sufmin.get<int32_t>(), c->w_bound.get<uint8_t>());
+    justify(c, st, d_ev, nc, cd);
+    if (P.dense) {      // (the cross-check forms: the views are made from every cell as rounds 1-4 did)
         make_views(st, g);
         g.dirty_all = true;
     } else {
-        launch_justify(st, d_ev, nc, cd, c->w_lo.get<int32_t>(), c->w_sufmin.get<int32_t>(), c->w_bound.get<uint8_t>());
         // the chunks the walk may have written (every live event from the lower end of its justification scan to its last cell): their views and summaries
         launch_mark_dirty(st, d_ev, nc, c->w_lo.get<int32_t>(), M.d_dirty.get<uint32_t>());
         dirty_chunks(st, false, g);
         g.dirty_any = true;
     }
     HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(&wc[7], &wcnt[7], 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));      // [7] candidates, [8..11] the eight words
-    HIPC(c, hipEventRecord(M.ev_walk.get(), st));
     return DWGSIM_HIP_OK;
+}
+
+// One attempt of the random walk of a whole group, enqueued on the walk stream without any host read-back in between: buffers are sized for a
+// capacity (candidate sites are a Binomial(l, mut_rate) draw: mean + 8 sigma), the kernels take their element counts from device memory, and
+// the read-back at the end (dwgsim_hip_mutate_wait) also tells whether a capacity was exceeded -- then the walk is simply run again with
+// exact sizes.  Everything is reserved before anything is enqueued: a failed allocation leaves the stream and the group as they were.
+static int walk_random(dwgsim_hip_ctx_t *c, Group &g)
+{
+    const WalkPlan P = walk_plan(c, g);
+    if (const int rc = walk_reserve(c, g, P)) return rc;
+    c->walk_form = pack_walk_form(g.walk_attempt, false, P.use_slots, (int)P.restore, P.dense);
+    hipStream_t st = c->walk_stream;
+    HIPC(c, hipEventRecord(g.mem.ev_walk0.get(), st));
+    if (P.restore == Restore::All) { for (int h = 0; h < 2; ++h) if (const int rc = restore_pristine(c, g, h, R_ALL, st)) return rc; }
+    else if (P.restore == Restore::Chunks) dirty_chunks(st, true, g);
+    if (P.restore != Restore::None) { if (const int rc = clear_dirty(c, g, st)) return rc; g.dirty_all = g.dirty_any = false; }
+    if (const int rc = walk_launch(c, g, P)) return rc;
+    HIPC(c, wc_fetch(c, g.mem, WC_RANDOM, st));
+    HIPC(c, hipEventRecord(g.mem.ev_walk.get(), st));
+    return DWGSIM_HIP_OK;
+}
+
+// File-driven mutations of a whole group in group coordinates: patched cells and indel events into the context's host lists, insertion payloads into hi
+static void collect_file_mutations(dwgsim_hip_ctx_t *c, const Group &g, HostIns (&hi)[2])
+{
+    c->h_ppos.clear(); c->h_pcells.clear(); c->h_pev.clear();
+    for (size_t k = 0; k < g.m.size(); ++k) {
+        const Member &m = g.m[k];
+        for (size_t q = 0; q < m.rc.pos.size(); ++q) {
+            c->h_ppos.push_back(m.rc.pos[q] + m.start); c->h_pcells.push_back(m.rc.cells[q]);
+            if (m.rc.cells[q] & 0x3030) { Event e; e.pos = m.rc.pos[q] + m.start; e.type = 4; e.hap = 3; e.base = 0; e.live = 1; e.len = 1; e.seg = (uint32_t)k; c->h_pev.push_back(e); }
+        }
+        for (int h = 0; h < 2; ++h) for (const InsPayload &ip : m.rc.ins[h]) {
+            hi[h].pos.push_back(ip.pos + m.start); hi[h].len.push_back((uint32_t)ip.bases.size()); hi[h].off.push_back((uint32_t)hi[h].bases.size());
+            hi[h].bases.insert(hi[h].bases.end(), ip.bases.begin(), ip.bases.end());
+        }
+    }
+}
+
+// the insertion tables the file's entries make, into the group's device tables
+static int upload_ins_tables(dwgsim_hip_ctx_t *c, Group &g, HostIns (&hi)[2])
+{
+    for (int h = 0; h < 2; ++h) {
+        const size_t n = hi[h].pos.size(), nb = hi[h].bases.size();
+        g.n_ins[h] = (uint32_t)n; g.n_ins_bases[h] = (uint32_t)nb;
+        if (const int rc = ensure_ins(c, g, h, n ? n : 1, nb ? nb : 1)) return rc;
+        if (n) for (const InsTable &t : ins_tables(g.mem, h, hi[h])) HIPC(c, hipMemcpy(t.dev, t.host, t.bytes, hipMemcpyHostToDevice));
+    }
+    return DWGSIM_HIP_OK;
+}
+
+// The capacities the random walk of a group starts from: candidate sites are a Binomial(l, mut_rate) draw (mean + 8 sigma + 256), eight inserted bases per
+// candidate + 4096 per haplotype.  dwgsim_hip_debug_option("walk_cap"): start too small, exercise the re-run.
+static void initial_walk_caps(const dwgsim_hip_ctx_t *c, Group &g)
+{
+    double mean = 0;
+    for (const Member &m : g.m) mean += (double)m.l * c->prm.mut_rate;
+    g.walk_cap = (uint32_t)std::min<double>((double)g.total, mean + 8.0 * sqrt(mean + 1.0) + 256.0);
+    g.walk_cap_bases = (size_t)g.walk_cap * 8 + 4096;
+    if (c->walk_cap >= 0) { g.walk_cap = (uint32_t)c->walk_cap; g.walk_cap_bases = 1; }
 }
 
 int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
@@ -1071,45 +1252,31 @@ int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
     g.mutated = true; g.n_cand = 0; g.list_valid = false;
     g.walk_attempt = 0;
     if (g.total == 0) return DWGSIM_HIP_OK;
-    if (c->has_mutin) {      // patches, indel events and insertion tables of the whole group, in group coordinates
-        HIPC(c, hipStreamSynchronize(c->walk_stream));      // (an earlier group's walk may still be copying from the host lists below)
-        c->h_ppos.clear(); c->h_pcells.clear(); c->h_pev.clear();
+    if (c->has_mutin) {
+        HIPC(c, hipStreamSynchronize(c->walk_stream));      // (an earlier group's walk may still be copying from the host lists)
         HostIns hi[2];
-        for (size_t k = 0; k < g.m.size(); ++k) {
-            const Member &m = g.m[k];
-            for (size_t q = 0; q < m.rc.pos.size(); ++q) {
-                c->h_ppos.push_back(m.rc.pos[q] + m.start); c->h_pcells.push_back(m.rc.cells[q]);
-                if (m.rc.cells[q] & 0x3030) { Event e; e.pos = m.rc.pos[q] + m.start; e.type = 4; e.hap = 3; e.base = 0; e.live = 1; e.len = 1; e.seg = (uint32_t)k; c->h_pev.push_back(e); }
-            }
-            for (int h = 0; h < 2; ++h) for (const InsPayload &ip : m.rc.ins[h]) {
-                hi[h].pos.push_back(ip.pos + m.start); hi[h].len.push_back((uint32_t)ip.bases.size()); hi[h].off.push_back((uint32_t)hi[h].bases.size());
-                hi[h].bases.insert(hi[h].bases.end(), ip.bases.begin(), ip.bases.end());
-            }
-        }
+        collect_file_mutations(c, g, hi);
         g.n_patch = (uint32_t)c->h_ppos.size(); g.n_patch_ev = (uint32_t)c->h_pev.size();
         g.n_cand = g.n_patch_ev;
-        HIPC(c, hipStreamSynchronize(c->walk_stream));      // (the tables below are copied from short-lived host vectors)
-        for (int h = 0; h < 2; ++h) {
-            const size_t n = hi[h].pos.size(), nb = hi[h].bases.size();
-            g.n_ins[h] = (uint32_t)n; g.n_ins_bases[h] = (uint32_t)nb;
-            if (const int rc = ensure_ins(c, g, h, n ? n : 1, nb ? nb : 1)) return rc;
-            if (n) {
-                HIPC(c, hipMemcpy(g.mem.d_ins_pos[h].get<int32_t>(), hi[h].pos.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-                HIPC(c, hipMemcpy(g.mem.d_ins_len[h].get<uint32_t>(), hi[h].len.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-                HIPC(c, hipMemcpy(g.mem.d_ins_off[h].get<uint32_t>(), hi[h].off.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-                HIPC(c, hipMemcpy(g.mem.d_ins_bases[h].get(), hi[h].bases.data(), nb, hipMemcpyHostToDevice));
-            }
-        }
-    } else {
-        double mean = 0;
-        for (const Member &m : g.m) mean += (double)m.l * c->prm.mut_rate;
-        g.walk_cap = (uint32_t)std::min<double>((double)g.total, mean + 8.0 * sqrt(mean + 1.0) + 256.0);
-        g.walk_cap_bases = (size_t)g.walk_cap * 8 + 4096;
-        if (c->walk_cap >= 0) { g.walk_cap = (uint32_t)c->walk_cap; g.walk_cap_bases = 1; }      // dwgsim_hip_debug_option("walk_cap"): start too small, exercise the re-run
-    }
-    if (const int rc = enqueue_walk(c, g)) return rc;
+        HIPC(c, hipStreamSynchronize(c->walk_stream));      // (the tables are copied from short-lived host vectors)
+        if (const int rc = upload_ins_tables(c, g, hi)) return rc;
+    } else initial_walk_caps(c, g);
+    if (const int rc = c->has_mutin ? walk_file_driven(c, g) : walk_random(c, g)) return rc;
     g.walk_pending = true;
     return DWGSIM_HIP_OK;
+}
+
+// Does the attempt the counters come from fit its capacities?  (A block of the site scan that outgrew its slot: nothing behind it ran, the candidate count was set to 0.)
+static bool walk_fits(const WalkCounters &w, const Group &g)
+{
+    return !w.slot_over && w.n_cand <= g.walk_cap && w.ins[0].bases <= ins_bases_cap(g, 0) && w.ins[1].bases <= ins_bases_cap(g, 1);
+}
+
+// The capacities of the exact re-run (the counts read back are those of the complete candidate list unless it was truncated: generous ones then)
+static void exact_walk_caps(const WalkCounters &w, Group &g)
+{
+    g.walk_cap = (uint32_t)std::min<uint64_t>((uint64_t)g.total, (w.slot_over ? (uint64_t)w.n_cand_true : w.n_cand) + 16);
+    g.walk_cap_bases = std::max<size_t>(g.walk_cap_bases, (size_t)std::max(w.ins[0].bases, w.ins[1].bases) * 2 + (size_t)g.walk_cap * 8 + 4096);
 }
 
 int dwgsim_hip_mutate_wait(dwgsim_hip_ctx_t *c, int contig)
@@ -1119,29 +1286,25 @@ int dwgsim_hip_mutate_wait(dwgsim_hip_ctx_t *c, int contig)
     Group &g = *gp;
     if (!g.walk_pending) return g.mutated ? DWGSIM_HIP_OK : (c->err = "mutate_wait: no walk was enqueued for this group", DWGSIM_HIP_ERR_STATE);
     HIPC(c, hipSetDevice(c->device));
-    for (;;) {
+    const WalkCounters &w = *g.mem.h_wc.get<WalkCounters>();
+    for (;;) {      // wait, verdict, grow, enqueue again
         HIPC(c, hipEventSynchronize(g.mem.ev_walk.get()));
         { float ms = 0; if (hipEventElapsedTime(&ms, g.mem.ev_walk0.get(), g.mem.ev_walk.get()) == hipSuccess) c->walk_us += 1e3 * ms; else (void)hipGetLastError(); }      // (analysis: dwgsim_hip_debug_get "walk_us")
         if (c->has_mutin) {
             g.walk_pending = false;
-            return g.n_patch ? mut_debug_verdict(c, g, g.mem.h_wc.get<uint64_t>()[12], g.mem.h_wc.get<uint64_t>()[13]) : DWGSIM_HIP_OK;
+            return g.n_patch ? mut_debug_verdict(c, g, w.mut_debug[0], w.mut_debug[1]) : DWGSIM_HIP_OK;
         }
-        const uint64_t n_cand = g.mem.h_wc.get<uint64_t>()[7];
-        const uint32_t *h_small = reinterpret_cast<const uint32_t *>(&g.mem.h_wc.get<uint64_t>()[8]);
-        const bool slot_over = h_small[6] != 0;      // a block of the site scan outgrew its slot (nothing behind it ran: the candidate count was set to 0; h_small[7] = the real one)
-        const bool fits = !slot_over && n_cand <= g.walk_cap && h_small[2] <= ins_bases_cap(g, 0) && h_small[4] <= ins_bases_cap(g, 1);
+        const bool fits = walk_fits(w, g);
         if (fits || g.walk_attempt >= 2) {
             g.walk_pending = false;
             if (!fits) { c->err = "mutation walk: capacities still exceeded after an exact re-run"; return DWGSIM_HIP_ERR_FAILED; }
-            g.n_cand = (uint32_t)n_cand;
-            for (int h = 0; h < 2; ++h) { g.n_ins[h] = h_small[1 + 2 * h]; g.n_ins_bases[h] = h_small[2 + 2 * h]; }
+            g.n_cand = (uint32_t)w.n_cand;
+            for (int h = 0; h < 2; ++h) { g.n_ins[h] = w.ins[h].entries; g.n_ins_bases[h] = w.ins[h].bases; }
             return DWGSIM_HIP_OK;
         }
-        // exact sizes (the counts read back are those of the complete candidate list unless it was truncated: take generous ones then)
-        g.walk_cap = (uint32_t)std::min<uint64_t>((uint64_t)g.total, (slot_over ? (uint64_t)h_small[7] : n_cand) + 16);
-        g.walk_cap_bases = std::max<size_t>(g.walk_cap_bases, (size_t)std::max(h_small[2], h_small[4]) * 2 + (size_t)g.walk_cap * 8 + 4096);
+        exact_walk_caps(w, g);
         ++g.walk_attempt;
-        if (const int rc = enqueue_walk(c, g)) { g.walk_pending = false; return rc; }
+        if (const int rc = walk_random(c, g)) { g.walk_pending = false; return rc; }
     }
 }
 
@@ -1274,10 +1437,10 @@ int fetch_mutated_list(dwgsim_hip_ctx_t *c, Group &g)
         if (ensure(c, c->scratch_cnt, (size_t)nblk * sizeof(uint32_t))) return DWGSIM_HIP_ERR_DEVICE;
         uint16_t *d_mask = c->scratch_mask.get<uint16_t>(); uint32_t *d_cnt = c->scratch_cnt.get<uint32_t>();
         launch_collect_mask(st, g.mem.d_cells[0].get(), g.mem.d_cells[1].get(), g.total, d_mask, d_cnt);
-        launch_scan_excl(st, d_cnt, nblk, &c->d_wcounters.get<uint64_t>()[14]);
-        HIPC(c, hipMemcpyAsync(&g.mem.h_wc.get<uint64_t>()[14], &c->d_wcounters.get<uint64_t>()[14], sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        launch_scan_excl(st, d_cnt, nblk, &c->d_wcounters.get<WalkCounters>()->n_listed);
+        HIPC(c, wc_fetch(c, g.mem, WC_LISTED, st));
         HIPC(c, hipStreamSynchronize(st));
-        const uint32_t n = (uint32_t)g.mem.h_wc.get<uint64_t>()[14];
+        const uint32_t n = (uint32_t)g.mem.h_wc.get<WalkCounters>()->n_listed;
         if (n) {
             if (ensure(c, c->l_pos, sizeof(int32_t) * (size_t)n) || ensure(c, c->l_cells, sizeof(uint32_t) * (size_t)n)) return DWGSIM_HIP_ERR_DEVICE;
             launch_compact(st, d_mask, d_cnt, c->l_pos.get<int32_t>(), g.total, n);
@@ -1288,10 +1451,7 @@ int fetch_mutated_list(dwgsim_hip_ctx_t *c, Group &g)
         }
         for (int h = 0; h < 2; ++h) if (g.n_ins[h]) {
             g.ins[h].pos.resize(g.n_ins[h]); g.ins[h].len.resize(g.n_ins[h]); g.ins[h].off.resize(g.n_ins[h]); g.ins[h].bases.resize(g.n_ins_bases[h]);
-            HIPC(c, hipMemcpyAsync(g.ins[h].pos.data(), g.mem.d_ins_pos[h].get<int32_t>(), sizeof(int32_t) * g.n_ins[h], hipMemcpyDeviceToHost, st));
-            HIPC(c, hipMemcpyAsync(g.ins[h].len.data(), g.mem.d_ins_len[h].get<uint32_t>(), sizeof(uint32_t) * g.n_ins[h], hipMemcpyDeviceToHost, st));
-            HIPC(c, hipMemcpyAsync(g.ins[h].off.data(), g.mem.d_ins_off[h].get<uint32_t>(), sizeof(uint32_t) * g.n_ins[h], hipMemcpyDeviceToHost, st));
-            HIPC(c, hipMemcpyAsync(g.ins[h].bases.data(), g.mem.d_ins_bases[h].get(), g.n_ins_bases[h], hipMemcpyDeviceToHost, st));
+            for (const InsTable &t : ins_tables(g.mem, h, g.ins[h])) HIPC(c, hipMemcpyAsync(t.host, t.dev, t.bytes, hipMemcpyDeviceToHost, st));
         }
         HIPC(c, hipStreamSynchronize(st));
     }
@@ -2029,6 +2189,10 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *c, const char *key, int64_t value)
 // "walk_us" / "count_us" = accumulated HIP-event time (microseconds) of the walk chains / random-read counts of this context
 // "sim_form" = the k_simulate form of the last simulate launch (0 before the first): NTHR << 20 | LPP << 16 | OUT << 12 | DT << 8 | WR << 4 | SPLIT,
 // where SPLIT = 1 is the two-kernel form and WR the writer of its second half
+// "walk_form" = what the last mutation walk enqueued was made of (0 before the first): ATTEMPT << 16 | FILE << 12 | SLOTS << 8 | RESTORE << 4 | DENSE -- the
+// attempt (0; 1, 2: the exact re-runs of dwgsim_hip_mutate_wait), FILE 1 the file-driven walk (-m / -b / -v) / 0 the random one, SLOTS 1 the slot form of the
+// site scan / 0 the look-back form (and the file-driven walk, which scans no sites), RESTORE what was put back to the pristine copies first (0 nothing, 1 the
+// dirty chunks, 2 whole buffers), DENSE 1 the views made from every cell / 0 from the dirty bitmap
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
 {
     if (!c || !key || !value) return DWGSIM_HIP_ERR_ARG;
@@ -2037,6 +2201,7 @@ int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
     else if (!strcmp(key, "walk_us")) *value = (int64_t)c->walk_us;           // HIP-event time of the walk chains waited for so far (start of the chain to its end, on the walk stream)
     else if (!strcmp(key, "count_us")) *value = (int64_t)c->count_us;         // ... of the random-read counts (k_place .. k_range_counts)
     else if (!strcmp(key, "sim_form")) *value = c->sim_form;                  // k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> of the last launch, packed
+    else if (!strcmp(key, "walk_form")) *value = c->walk_form;                // attempt, file-driven / random, site-scan form, restore, views of the last walk, packed
     else { c->err = "unknown debug value"; return DWGSIM_HIP_ERR_ARG; }
     return DWGSIM_HIP_OK;
 }

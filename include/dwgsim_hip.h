@@ -412,7 +412,10 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *ctx, const char *key, int64_t valu
  * power of two) the Ion Torrent read capacity has been doubled so far; "walk_us" / "count_us":
  * HIP-event time (microseconds, accumulated) of the context's walk chains / random-read counts on the walk stream; "sim_form": the
  * k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> form of the context's last simulate launch (0 before the first), packed as
- * NTHR << 20 | LPP << 16 | OUT << 12 | DT << 8 | WR << 4 | SPLIT (SPLIT 1: the two-kernel form, WR: the writer of its second half) */
+ * NTHR << 20 | LPP << 16 | OUT << 12 | DT << 8 | WR << 4 | SPLIT (SPLIT 1: the two-kernel form, WR: the writer of its second half); "walk_form": what
+ * the context's last mutation walk enqueued was made of (0 before the first), packed as ATTEMPT << 16 | FILE << 12 | SLOTS << 8 | RESTORE << 4 | DENSE
+ * (ATTEMPT 1, 2: the exact re-runs; FILE 1: the file-driven walk of -m / -b / -v; SLOTS 1 / 0: the slot / look-back form of the site scan; RESTORE: what
+ * went back to the pristine copies first -- 0 nothing, 1 the dirty chunks, 2 whole buffers; DENSE 1 / 0: views made from every cell / from the dirty bitmap) */
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *ctx, const char *key, int64_t *value);
 /* the gzip kernel on arbitrary host bytes (the product only ever feeds it FASTQ text) */
 int dwgsim_hip_debug_gzip(dwgsim_hip_ctx_t *ctx, const void *text, size_t n, void *out, size_t cap, size_t *out_n);

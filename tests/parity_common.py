@@ -390,3 +390,47 @@ def check_walking_a_contig_again(lib, fasta, flags, n=400):
             got.append((ctx.mutations_text(cid), [ctx.fetch(rnd & 1, s, b.bytes[s]) for s in range(3)], cnt))
         assert got[0] == got[1] == got[2] == got[3] == got[4]
         assert len(got[0][0][0]) > 200
+
+
+WALK_RANDOM = "-z 4 -r 0.02 -R 0.5 -I 3 -X 0.6"
+WALK_FILE = "-z 5 -m {IN}/muts_edge.txt"
+# What the host makes a walk of (dwgsim_hip_debug_get("walk_form")), as the code in front of the split of the walk into named steps answered:
+# (flags, debug options, walks of the same group, (ATTEMPT, FILE, SLOTS, RESTORE, DENSE) of the last of them after mutate_async, ... after mutate_wait)
+WALK_FORMS = [
+    (WALK_RANDOM, {}, 1, (0, 0, 1, 0, 0), (0, 0, 1, 0, 0)),                         # fresh from the upload: slots, nothing to restore, views of the dirty chunks
+    (WALK_RANDOM, {}, 2, (0, 0, 1, 1, 0), (0, 0, 1, 1, 0)),                         # walked before: the dirty chunks go back
+    (WALK_RANDOM, {"site_slots": 0}, 1, (0, 0, 0, 0, 0), (0, 0, 0, 0, 0)),
+    (WALK_RANDOM, {"site_slots": 1}, 1, (0, 0, 1, 0, 0), (0, 0, 1, 0, 0)),
+    (WALK_RANDOM, {"site_slot_cap": 3}, 1, (0, 0, 1, 0, 0), (1, 0, 0, 2, 0)),       # a slot outgrown: one re-run, look-back form, everything restored
+    (WALK_RANDOM, {"walk_cap": 7}, 1, (0, 0, 1, 0, 0), (1, 0, 0, 2, 0)),            # the list outgrown: one exact re-run
+    (WALK_RANDOM, {"walk_cap": 7}, 2, (0, 0, 1, 1, 0), (1, 0, 0, 2, 0)),            # (a re-run keeps a bitmap: the next walk restores chunks)
+    (WALK_RANDOM, {"dense_view": 1}, 1, (0, 0, 1, 0, 1), (0, 0, 1, 0, 1)),
+    (WALK_RANDOM, {"dense_view": 1}, 2, (0, 0, 1, 2, 1), (0, 0, 1, 2, 1)),          # dense views keep no bitmap: everything goes back
+    (WALK_RANDOM, {"justify_seq": 1}, 1, (0, 0, 1, 0, 1), (0, 0, 1, 0, 1)),
+    (WALK_FILE, {}, 1, (0, 1, 0, 0, 1), (0, 1, 0, 0, 1)),
+    (WALK_FILE, {}, 2, (0, 1, 0, 2, 1), (0, 1, 0, 2, 1)),
+]
+WALK_FORM_CASES = [(fa, *w) for w in WALK_FORMS for fa in (("tiny.fa", "ex1.fa") if w[0] == WALK_RANDOM else ("tiny.fa",))]      # (the mutation file names tiny.fa's contigs)
+WALK_FORM_IDS = [f"{c[0]}:{'file' if c[1] == WALK_FILE else 'random'}:{c[2]}:x{c[3]}" for c in WALK_FORM_CASES]
+
+
+def check_walk_form(lib, fasta, flags, opts, walks, want_enqueued, want_waited):
+    """The host's decisions about a walk, which no output shows (another choice gives the same bytes, only slower): all contigs of the FASTA as one group,
+    walked `walks` times; the form of the last walk as mutate_async enqueued it and as mutate_wait left it (its last re-run, if it needed one)."""
+    params = api.parse_flags(flags.replace("{IN}", IN_DIR), lib)
+    contigs = api.read_fasta(fasta)
+    unpack = lambda v: (v >> 16, v >> 12 & 15, v >> 8 & 15, v >> 4 & 15, v & 15)
+    with api.Context(params, 0, lib) as ctx:
+        if getattr(params, "_mut_input", None):
+            ctx.set_mutation_input(params._mut_input[0], params._mut_input[1], contigs)
+        for k, v in opts.items():
+            ctx.debug_option(k, v)
+        assert ctx.debug_get("walk_form") == 0
+        cid = ctx.add_contigs(contigs)
+        for _ in range(walks):
+            ctx.mutate_async(cid)
+            enqueued = unpack(ctx.debug_get("walk_form"))
+            ctx.mutate_wait(cid)
+            waited = unpack(ctx.debug_get("walk_form"))
+        assert (enqueued, waited) == (want_enqueued, want_waited)
+        assert len(ctx.mutations_text(cid)[0]) > 100      # (the walk did mutate)

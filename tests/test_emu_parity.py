@@ -6,7 +6,7 @@ import os, subprocess, sys
 import pytest
 
 from dwgsim_amd import api
-from parity_common import compare_case
+from parity_common import compare_case, check_walk_form, WALK_FORM_CASES, WALK_FORM_IDS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 EMU_CASES = [
@@ -616,6 +616,12 @@ def test_k_simulate_form_chosen_by_the_host_on_cpu_emulation(emu_lib, golden_dir
         ctx.mutate(h0)
         assert ctx.simulate_ranges([(h0, 0, 8)], 0, 0).n_pairs == 8
         assert ctx.debug_get("sim_form") == nthr << 20 | lpp << 16 | out << 12 | dt << 8 | wr << 4 | split
+
+
+@pytest.mark.parametrize("fasta,flags,opts,walks,enqueued,waited", WALK_FORM_CASES, ids=WALK_FORM_IDS)
+def test_walk_form_chosen_by_the_host_on_cpu_emulation(emu_lib, golden_dir, fasta, flags, opts, walks, enqueued, waited):
+    """What a mutation walk is made of (dw_host.cpp: attempt, file-driven / random, site-scan form, restore, views), read back through dwgsim_hip_debug_get("walk_form")."""
+    check_walk_form(emu_lib, os.path.join(golden_dir, fasta), flags, opts, walks, enqueued, waited)
 
 
 def test_reads_too_long_for_the_quality_tables_are_refused_on_cpu_emulation(emu_lib, golden_dir):

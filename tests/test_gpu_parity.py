@@ -5,7 +5,7 @@ import pytest
 
 from dwgsim_amd import api
 FLOW_ORDER = "TACGTACGTCTGAGCATCGATCGATGTACAGC"
-from parity_common import CASES, FLOW, compare_case
+from parity_common import CASES, FLOW, compare_case, check_walk_form, WALK_FORM_CASES, WALK_FORM_IDS
 
 pytestmark = pytest.mark.gpu
 
@@ -435,6 +435,11 @@ def test_ion_torrent_read_outgrows_its_buffers(lib, oracle_bin, golden_dir, cap,
 def test_walk_reruns_when_a_capacity_is_exceeded(lib, oracle_bin, repeats_fa):
     """See tests/test_emu_parity.py: forced tiny capacities on the repeat-rich 1.8 Mb contigs."""
     compare_case(lib, oracle_bin, repeats_fa, "-z 32 -M 2 -r 0.2 -R 0.9 -X 0.3 -I 2", debug_options={"walk_cap": 100})
+
+
+@pytest.mark.parametrize("fasta,flags,opts,walks,enqueued,waited", WALK_FORM_CASES, ids=WALK_FORM_IDS)
+def test_walk_form_chosen_by_the_host(lib, golden_dir, fasta, flags, opts, walks, enqueued, waited):
+    check_walk_form(lib, os.path.join(golden_dir, fasta), flags, opts, walks, enqueued, waited)
 
 
 def test_abort_rule_matches_the_reference(lib, oracle_bin, golden_dir):
