@@ -81,7 +81,8 @@ EXPORTS = [
     "dwgsim_hip_selftest_fp64", "dwgsim_hip_selftest_lazy", "dwgsim_hip_selftest_text", "dwgsim_hip_selftest_gap",
     "dwgsim_hip_eval_opts_default", "dwgsim_hip_eval_create", "dwgsim_hip_eval_header", "dwgsim_hip_eval_feed", "dwgsim_hip_eval_finish",
     "dwgsim_hip_eval_table_text", "dwgsim_hip_eval_incorrect_text", "dwgsim_hip_eval_last_error", "dwgsim_hip_eval_destroy",
-    "dwgsim_hip_eval_debug_time", "dwgsim_hip_eval_debug_device_chunk",
+    "dwgsim_hip_eval_debug_time", "dwgsim_hip_eval_debug_device_chunk", "dwgsim_hip_eval_bam_begin", "dwgsim_hip_eval_feed_bam",
+    "dwgsim_hip_eval_debug_device_bam_chunk", "dwgsim_hip_eval_debug_inflate",
 ]
 
 _lib = None
@@ -721,7 +722,8 @@ class EvalOpts(C.Structure):
     """dwgsim_hip_eval_opts_t"""
     _fields_ = [("size", C.c_uint32), ("a", C.c_int32), ("d", C.c_int32), ("e", C.c_int32), ("g", C.c_int32), ("n", C.c_int32),
                 ("q", C.c_int32), ("s", C.c_int32), ("b", C.c_int32), ("c", C.c_int32), ("i", C.c_int32), ("m", C.c_int32),
-                ("p", C.c_int32), ("z", C.c_int32), ("P", C.c_char_p), ("chunk_bytes", C.c_uint64)]
+                ("p", C.c_int32), ("z", C.c_int32), ("P", C.c_char_p), ("chunk_bytes", C.c_uint64),
+                ("inflate_threads", C.c_int32)]
 
 
 class EvalSummary(C.Structure):
@@ -742,6 +744,8 @@ def _bind_eval(lib):
     lib.dwgsim_hip_eval_create.argtypes = [P(EvalOpts), C.c_int, P(C.c_int)]
     lib.dwgsim_hip_eval_header.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     lib.dwgsim_hip_eval_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.dwgsim_hip_eval_bam_begin.argtypes = [C.c_void_p]
+    lib.dwgsim_hip_eval_feed_bam.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.dwgsim_hip_eval_finish.argtypes = [C.c_void_p, P(EvalSummary)]
     lib.dwgsim_hip_eval_table_text.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_size_t)]
     lib.dwgsim_hip_eval_incorrect_text.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_size_t)]
@@ -751,6 +755,8 @@ def _bind_eval(lib):
     lib.dwgsim_hip_eval_destroy.restype = None
     lib.dwgsim_hip_eval_debug_time.argtypes = [C.c_void_p, P(C.c_double)]
     lib.dwgsim_hip_eval_debug_device_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, P(C.c_double)]
+    lib.dwgsim_hip_eval_debug_device_bam_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, P(C.c_double)]
+    lib.dwgsim_hip_eval_debug_inflate.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(C.c_double), P(C.c_uint64)]
 
 
 def load_eval(path: str | None = None):
@@ -774,10 +780,11 @@ class EvalSummaryResult:
 
 
 class EvalContext:
-    """One dwgsim_eval run on one device: header(file 1), feed(...)..., header(file 2), ..., finish().  Options are dwgsim_eval's
-    (a, b, c, d, e, g, i, m, n, p, q, s, z: ints; P: str) plus chunk_bytes."""
+    """One dwgsim_eval run on one device: header(file 1), feed(...)..., header(file 2), ..., finish(); a BAM file is bam_begin(),
+    feed_bam(...)... instead.  Options are dwgsim_eval's (a, b, c, d, e, g, i, m, n, p, q, s, z: ints; P: str) plus chunk_bytes and
+    inflate_threads (host threads that inflate BAM input: 0 is the default of 8, at most 16)."""
 
-    def __init__(self, device: int = 0, lib=None, chunk_bytes: int = 0, **opts):
+    def __init__(self, device: int = 0, lib=None, chunk_bytes: int = 0, inflate_threads: int = 0, **opts):
         self.lib = lib or load()
         o = EvalOpts()
         self.lib.dwgsim_hip_eval_opts_default(C.byref(o))
@@ -790,6 +797,7 @@ class EvalContext:
             else:
                 raise TypeError(f"unknown dwgsim_eval option {k!r}")
         o.chunk_bytes = chunk_bytes
+        o.inflate_threads = inflate_threads
         err = C.c_int(0)
         self.ctx = self.lib.dwgsim_hip_eval_create(C.byref(o), device, C.byref(err))
         if not self.ctx:
@@ -812,6 +820,16 @@ class EvalContext:
         else:
             r = self.lib.dwgsim_hip_eval_feed(self.ctx, buf, n)
         return self._check(r) != EVAL_STOPPED
+
+    def bam_begin(self):
+        """the next file is a BAM file"""
+        self._check(self.lib.dwgsim_hip_eval_bam_begin(self.ctx))
+
+    def feed_bam(self, buf) -> bool:
+        """raw bytes of the BAM file, split anywhere; False once a fatal record has been found.  A container error raises DwgsimError."""
+        n = len(buf)
+        cbuf = buf if isinstance(buf, bytes) else (C.c_char * n).from_buffer_copy(buf)
+        return self._check(self.lib.dwgsim_hip_eval_feed_bam(self.ctx, cbuf, n)) != EVAL_STOPPED
 
     def finish(self):
         """(table text, EvalSummaryResult)"""
@@ -883,6 +901,26 @@ def eval_sam(paths, device: int = 0, lib=None, chunk_bytes: int = 0, read_bytes:
                             if not blk:
                                 break
                             going = ctx.feed(blk)
+                        break
+            finally:
+                if f is not p:
+                    f.close()
+        return ctx.finish()
+
+
+def eval_bam(paths, device: int = 0, lib=None, chunk_bytes: int = 0, read_bytes: int = 8 << 20, **opts):
+    """dwgsim_eval over BAM files (paths, or file objects opened in binary mode): (table_text, EvalSummaryResult), as eval_sam.
+    A file that is not a readable BAM file raises DwgsimError, unless a fatal record in front of the damage ends the run first."""
+    if isinstance(paths, (str, bytes, os.PathLike)):
+        paths = [paths]
+    with EvalContext(device, lib, chunk_bytes, **opts) as ctx:
+        for p in paths:
+            f = open(p, "rb") if isinstance(p, (str, bytes, os.PathLike)) else p
+            try:
+                ctx.bam_begin()
+                while True:
+                    blk = f.read(read_bytes)
+                    if not blk or not ctx.feed_bam(blk):
                         break
             finally:
                 if f is not p:

@@ -6,15 +6,28 @@
 // other slot becomes the filling one: it starts with the last line of the submitted chunk (the context line that -m compares the next record
 // with) and the partial line that did not fit.  So the copy and the kernels of one chunk overlap with the host filling the next.  Results are
 // read back in submission order: the first chunk with a fatal record ends the run, and its record is the first one in file order.
+//
+// BAM files (bam_begin / feed_bam).  The caller's compressed bytes are collected; every complete BGZF block (dw_bam.hpp) becomes a job whose
+// destination in the filling slot follows from the ISIZE of the blocks in front of it, and the jobs of one feed are inflated in place by the
+// worker threads (dw_inflate.hpp; CRC-32 and ISIZE checked per block).  The calling thread then hops over the block_size chain of the new
+// bytes and notes the offset of every whole record.  A slot that cannot take the next block is cut after its last whole record and submitted:
+// text and offsets up, k_eval_bam_records, result back; the other slot continues with that last record as context and the partial record
+// behind it.  The first blocks of a file are inflated aside until the BAM header is complete; its reference list becomes the targets.
+// A container error (framing, inflate, CRC, ISIZE, magic, header, a file that ends inside something) first evaluates the whole records in
+// front of it: a fatal record there wins; otherwise the call returns DWGSIM_HIP_ERR_FAILED and last_error says what and where.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
+#include <time.h>
 #include <array>
 #include <deque>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
+#include "dw_bam.hpp"
 #include "dw_eval_launch.hpp"
 #include "dw_mem.hpp"
 #include "../../include/dwgsim_hip.h"
@@ -25,16 +38,22 @@ namespace {
 
 constexpr size_t DEFAULT_CHUNK = 32ull << 20, MIN_CHUNK = 4096, MAX_CHUNK = 1ull << 30;
 constexpr int32_t WIN_LO = -EVAL_WIN / 2;
+constexpr int DEFAULT_INFLATE_THREADS = 8, MAX_INFLATE_THREADS = 16;
+constexpr size_t MAX_BATCH = 4096;      // BGZF blocks per inflate_blocks call
+enum { FMT_SAM = 0, FMT_BAM = 1 };
 const char BREAK_LINE[] = "************************************************************\n";
 
 struct Slot {
-    HostMem h_text, h_res;      // page-locked: the text (its capacity is the slot's), an EvalRes
+    HostMem h_text, h_res, h_offs;      // page-locked: the text (its capacity is the slot's), an EvalRes, the record offsets of a BAM chunk
     DevMem d_text, d_ends, d_tiles, d_res, d_spill, d_flags;      // text, u32, u32, EvalRes, u64, u8
     hipStream_t st = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     size_t fill = 0, ctx_len = 0, len = 0;
     uint32_t has_ctx = 0;
     bool busy = false;
+    int fmt = FMT_SAM;          // of the context record and what follows it
+    uint32_t n_offs = 0;        // BAM: whole records found so far (the context record is the first), and where the next one starts
+    size_t hop = 0;
 };
 
 } // namespace
@@ -63,6 +82,17 @@ struct dwgsim_hip_eval_ctx {
     std::string incorrect, table, stderr_text;
     double kernel_ms = 0;
     int32_t floor_score = ev::MINAS;
+    // the current file's format, and the state of a BAM stream
+    int fmt = FMT_SAM;
+    int inflate_threads = DEFAULT_INFLATE_THREADS;
+    std::unique_ptr<bam::InflatePool> pool;
+    std::vector<uint8_t> zbuf;          // compressed bytes not yet consumed: zbuf[zhead] is byte zpos of the file
+    size_t zhead = 0;
+    uint64_t zpos = 0;
+    bool in_header = false, bam_stop = false, broken = false;
+    std::vector<uint8_t> hdr_bytes;     // inflated bytes while the header is incomplete
+    bam::Header bh;
+    std::vector<bam::InflateJob> jobs;
 };
 
 namespace {
@@ -89,6 +119,7 @@ int slot_alloc(dwgsim_hip_eval_ctx *c, Slot &S, size_t cap)
     CK(exact(S.d_res, sizeof(EvalRes)));
     CK(exact(S.d_spill, (cap / 8 + 1) * sizeof(uint64_t)));
     CK(exact(S.d_flags, cap));
+    CK(exact(S.h_offs, (cap / ev::BAM_FIXED + 8) * sizeof(uint32_t)));       // a whole BAM record has more than 32 bytes
     CK(exact(S.h_text, cap));
     return DWGSIM_HIP_OK;
 }
@@ -128,7 +159,7 @@ std::string fatal_text(const dwgsim_hip_eval_ctx *c, int code, const std::string
         }
     }
     switch (code) {
-    case ev::E_MALFORMED: return error_block("process_bam", nullptr, "[dwgsim_eval-hip] malformed SAM record", true);
+    case ev::E_MALFORMED: return error_block("process_bam", nullptr, "[dwgsim_eval-hip] malformed SAM record", true);      // (BAM too: the model's wording)
     case ev::E_PREFIX: return error_block("process_bam", var.c_str(), "[dwgsim_eval] could not match read name with given read name prefix (-P)", true);
     case ev::E_NAME: return error_block("process_bam", var.c_str(), "[dwgsim_eval] read was not generated by dwgsim?", true);
     case ev::E_CONTIG:
@@ -147,6 +178,12 @@ ev::Opts dev_opts(const dwgsim_hip_eval_ctx *c)
     o.P_len = c->o.P ? (int32_t)c->P.size() : -1;
     o.P = c->d_P.get<char>();
     return o;
+}
+
+uint32_t bam_records_grid(uint32_t n_rec)
+{
+    const uint32_t g = (n_rec + 255) / 256;      // one record per lane
+    return g < 1 ? 1 : g > 1024 ? 1024 : g;
 }
 
 uint32_t records_grid(size_t len)
@@ -181,6 +218,11 @@ int process_oldest(dwgsim_hip_eval_ctx *c)
         c->failed = true;
         c->code = (int)(r.err & 0xff);
         c->err_rec = c->records + rec;
+        if (S.fmt == FMT_BAM) {
+            c->err_line.clear();
+            if (c->code != ev::E_MALFORMED) bam::record_to_sam(S.h_text.get() + S.h_offs.get<uint32_t>()[rec + S.has_ctx], c->bh, c->err_line);
+            return DWGSIM_HIP_OK;
+        }
         const char *p = S.h_text.get<char>();
         for (uint64_t i = 0; i < rec + S.has_ctx; ++i) p = (const char *)memchr(p, '\n', S.h_text.get<char>() + S.len - p) + 1;
         c->err_line.assign(p, (const char *)memchr(p, '\n', S.h_text.get<char>() + S.len - p) - p);
@@ -196,6 +238,14 @@ int process_oldest(dwgsim_hip_eval_ctx *c)
     if (c->o.p && n_rec) {
         std::vector<uint8_t> fl(n_rec);
         CK(hipMemcpy(fl.data(), S.d_flags.get(), n_rec, hipMemcpyDeviceToHost));
+        if (S.fmt == FMT_BAM) {
+            for (uint32_t i = 0; i < n_rec; ++i)
+                if (fl[i]) {
+                    bam::record_to_sam(S.h_text.get() + S.h_offs.get<uint32_t>()[i + S.has_ctx], c->bh, c->incorrect);
+                    c->incorrect += '\n';
+                }
+            return DWGSIM_HIP_OK;
+        }
         const char *p = S.h_text.get<char>() + S.ctx_len, *end = S.h_text.get<char>() + S.len;
         for (uint32_t i = 0; i < n_rec; ++i) {
             const char *e = (const char *)memchr(p, '\n', end - p) + 1;
@@ -215,6 +265,27 @@ int drain(dwgsim_hip_eval_ctx *c)
     return DWGSIM_HIP_OK;
 }
 
+// The filling slot's chunk [0, cut) is on its stream: the other slot becomes the filling one (its results are read first when it is still
+// busy) and starts with the chunk's last record [lb, cut), the context record, and what follows the chunk.
+int hand_over(dwgsim_hip_eval_ctx *c, size_t cut, size_t lb)
+{
+    Slot &S = c->s[c->cur];
+    S.busy = true;
+    c->pending.push_back(c->cur);
+    c->cur ^= 1;
+    Slot &T = c->s[c->cur];
+    if (T.busy) {
+        const int r = process_oldest(c);
+        if (r) return r;
+    }
+    const size_t ctx = cut - lb, rest = S.fill - cut;
+    memcpy(T.h_text.get<char>(), S.h_text.get<char>() + lb, ctx);
+    memcpy(T.h_text.get<char>() + ctx, S.h_text.get<char>() + cut, rest);
+    T.ctx_len = ctx; T.has_ctx = 1; T.fill = ctx + rest; T.fmt = S.fmt;
+    S.fill = 0;
+    return DWGSIM_HIP_OK;
+}
+
 // submit the filling slot's text up to `cut` (just past a newline); the other slot continues with the context line and the rest
 int submit(dwgsim_hip_eval_ctx *c, size_t cut)
 {
@@ -229,23 +300,35 @@ int submit(dwgsim_hip_eval_ctx *c, size_t cut)
     CK(hipGetLastError());
     CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st));
     CK(hipEventRecord(S.e1, S.st));
-    S.busy = true;
-    c->pending.push_back(c->cur);
-
-    c->cur ^= 1;
-    Slot &T = c->s[c->cur];
-    if (T.busy) {
-        const int r = process_oldest(c);
-        if (r) return r;
-    }
     // the last line of the submitted chunk, then what follows it
     size_t lb = cut - 1;
     while (lb > 0 && S.h_text.get<char>()[lb - 1] != '\n') --lb;
-    const size_t ctx = cut - lb, rest = S.fill - cut;
-    memcpy(T.h_text.get<char>(), S.h_text.get<char>() + lb, ctx);
-    memcpy(T.h_text.get<char>() + ctx, S.h_text.get<char>() + cut, rest);
-    T.ctx_len = ctx; T.has_ctx = 1; T.fill = ctx + rest;
-    S.fill = 0;
+    return hand_over(c, cut, lb);
+}
+
+// the whole records of the filling slot (BAM): text and offsets up, one kernel, result back
+int submit_bam(dwgsim_hip_eval_ctx *c)
+{
+    Slot &S = c->s[c->cur];
+    const size_t cut = S.hop;
+    const uint32_t n = S.n_offs;
+    S.len = cut;
+    *S.h_res.get<EvalRes>() = EvalRes{~0ull, 0, n, 0};
+    CK(hipEventRecord(S.e0, S.st));
+    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, S.st));
+    CK(hipMemcpyAsync(S.d_ends.get(), S.h_offs.get(), n * sizeof(uint32_t), hipMemcpyHostToDevice, S.st));
+    CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st));
+    const EvalRecArgs A = rec_args(c, S.d_text.get(), S.d_ends.get<uint32_t>(), S.d_res.get<EvalRes>(), S.d_spill.get<uint64_t>(), c->o.p ? S.d_flags.get() : nullptr, S.has_ctx);
+    launch_eval_bam_chunk(S.st, A, bam_records_grid(n - S.has_ctx));
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st));
+    CK(hipEventRecord(S.e1, S.st));
+    const int r = hand_over(c, cut, S.h_offs.get<uint32_t>()[n - 1]);
+    if (r) return r;
+    Slot &T = c->s[c->cur];
+    T.h_offs.get<uint32_t>()[0] = 0;
+    T.n_offs = 1; T.hop = T.ctx_len;
+    S.n_offs = 0; S.hop = 0;
     return DWGSIM_HIP_OK;
 }
 
@@ -259,12 +342,17 @@ int grow(dwgsim_hip_eval_ctx *c)
     std::string keep(F.h_text.get<char>(), F.fill);
     for (Slot &S : c->s) if ((r = slot_alloc(c, S, cap))) return r;
     memcpy(F.h_text.get<char>(), keep.data(), keep.size());
+    if (F.fmt == FMT_BAM && F.has_ctx) F.h_offs.get<uint32_t>()[0] = 0;      // (grow is for a slot without a whole record behind its context)
     return DWGSIM_HIP_OK;
 }
+
+int end_bam_file(dwgsim_hip_eval_ctx *c);
 
 // the filling slot's complete lines, and a last line without its newline
 int end_file(dwgsim_hip_eval_ctx *c)
 {
+    if (c->broken) return DWGSIM_HIP_ERR_FAILED;
+    if (c->fmt == FMT_BAM) return end_bam_file(c);
     Slot &F = c->s[c->cur];
     if (F.fill > F.ctx_len && F.h_text.get<char>()[F.fill - 1] != '\n') {
         if (F.fill == F.h_text.cap()) {
@@ -281,6 +369,8 @@ int end_file(dwgsim_hip_eval_ctx *c)
     }
     return drain(c);
 }
+
+int build_targets(dwgsim_hip_eval_ctx *c);
 
 int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
 {
@@ -303,6 +393,12 @@ int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
         }
         p = e + 1;
     }
+    return build_targets(c);
+}
+
+// c->names / c->off (the @SQ names of a SAM header, or the reference list of a BAM file): the hash, and the device copies
+int build_targets(dwgsim_hip_eval_ctx *c)
+{
     const int32_t nt = (int32_t)c->off.size() - 1;
     uint32_t hs = 2;
     while (hs < 2u * (uint32_t)nt) hs <<= 1;
@@ -322,6 +418,204 @@ int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
     if (const int r = upload(c, c->d_hash, c->hash.data(), hs * sizeof(int32_t))) return r;
     c->tg.names = c->d_names.get<char>(); c->tg.off = c->d_off.get<uint32_t>(); c->tg.hash = c->d_hash.get<int32_t>(); c->tg.n = nt; c->tg.hmask = hs - 1;
     return DWGSIM_HIP_OK;
+}
+
+// ---- BAM stream ----
+
+// the whole records that the filling slot's new bytes complete; a block_size that no record can have ends the stream with that record
+void hop_records(dwgsim_hip_eval_ctx *c)
+{
+    Slot &F = c->s[c->cur];
+    const uint8_t *t = F.h_text.get();
+    uint32_t *offs = F.h_offs.get<uint32_t>();
+    while (F.fill - F.hop >= 4) {
+        const uint32_t bs = bam::le32(t + F.hop);
+        if (bs < ev::BAM_FIXED || bs > ev::BAM_MAX_BLOCK) {
+            offs[F.n_offs++] = (uint32_t)F.hop;
+            F.hop += 4;
+            F.fill = F.hop;
+            c->bam_stop = true;
+            return;
+        }
+        if (F.fill - F.hop - 4 < bs) return;
+        offs[F.n_offs++] = (uint32_t)F.hop;
+        F.hop += 4 + (size_t)bs;
+    }
+}
+
+// `need` free bytes in the filling slot: its whole records are submitted, or, when it has none, both slots grow
+int bam_room(dwgsim_hip_eval_ctx *c, size_t need)
+{
+    for (;;) {
+        Slot &F = c->s[c->cur];
+        if (F.h_text.cap() - F.fill >= need) return DWGSIM_HIP_OK;
+        const int r = F.n_offs > F.has_ctx ? submit_bam(c) : grow(c);
+        if (r) return r;
+    }
+}
+
+// A container error at byte `at` of the compressed file.  The whole records in front of it are evaluated first: a fatal record wins.
+int container_error(dwgsim_hip_eval_ctx *c, const char *why, uint64_t at)
+{
+    Slot &F = c->s[c->cur];
+    int r = DWGSIM_HIP_OK;
+    if (F.n_offs > F.has_ctx && !c->failed) r = submit_bam(c);
+    if (!r) r = drain(c);
+    if (r) return r;
+    if (c->failed) return DWGSIM_HIP_EVAL_STOPPED;
+    char buf[64];
+    snprintf(buf, sizeof buf, " at byte %llu of the compressed file", (unsigned long long)at);
+    c->err = std::string("BAM input: ") + why + buf;
+    c->broken = true;
+    return DWGSIM_HIP_ERR_FAILED;
+}
+
+// the header is complete: targets, the -p header text, and the bytes behind it as the first record bytes
+int bam_header_done(dwgsim_hip_eval_ctx *c, size_t hlen)
+{
+    c->in_header = false;
+    if (!c->seen_header && c->o.p) c->incorrect = c->bh.text;
+    c->seen_header = true;
+    c->names = c->bh.names;
+    c->off = c->bh.off;
+    int r = build_targets(c);
+    if (r) return r;
+    const size_t rest = c->hdr_bytes.size() - hlen;
+    if ((r = bam_room(c, rest))) return r;
+    Slot &F = c->s[c->cur];
+    if (rest) memcpy(F.h_text.get() + F.fill, c->hdr_bytes.data() + hlen, rest);
+    F.fill += rest;
+    std::vector<uint8_t>().swap(c->hdr_bytes);
+    hop_records(c);
+    return DWGSIM_HIP_OK;
+}
+
+// everything that the collected compressed bytes allow
+int bam_pump(dwgsim_hip_eval_ctx *c)
+{
+    if (!c->pool) c->pool.reset(new bam::InflatePool(c->inflate_threads));
+    while (!c->failed && !c->bam_stop) {
+        const uint8_t *z = c->zbuf.data() + c->zhead;
+        const size_t avail = c->zbuf.size() - c->zhead;
+        const char *why = nullptr;
+        bam::BgzfBlock b;
+        if (c->in_header) {
+            const int k = bam::bgzf_block_at(z, avail, &b, &why);
+            if (k == 0) break;
+            if (k < 0) return container_error(c, why, c->zpos);
+            const size_t at = c->hdr_bytes.size();
+            c->hdr_bytes.resize(at + b.isize);
+            bam::InflateJob j = {z + b.data_off, b.data_len, c->hdr_bytes.data() + at, b.isize, b.crc, nullptr};
+            bam::inflate_blocks(*c->pool, &j, 1);
+            if (j.error) return container_error(c, j.error, c->zpos);
+            c->zhead += b.size; c->zpos += b.size;
+            const int64_t hl = bam::parse_header(c->hdr_bytes.data(), c->hdr_bytes.size(), &c->bh, &why);
+            if (hl < 0) return container_error(c, why, c->zpos);
+            if (hl > 0) {
+                const int r = bam_header_done(c, (size_t)hl);
+                if (r) return r;
+            }
+            continue;
+        }
+        // the complete blocks that fit into the filling slot, each at the place that the ISIZE values in front of it give
+        Slot *F = &c->s[c->cur];
+        size_t room = F->h_text.cap() - F->fill, used = 0, zused = 0;
+        c->jobs.clear();
+        int k;
+        while ((k = bam::bgzf_block_at(z + zused, avail - zused, &b, &why)) == 1 && c->jobs.size() < MAX_BATCH) {
+            if (b.isize > room - used) {
+                if (!c->jobs.empty()) break;
+                const int r = bam_room(c, b.isize);
+                if (r) return r;
+                F = &c->s[c->cur];
+                room = F->h_text.cap() - F->fill;
+            }
+            c->jobs.push_back({z + zused + b.data_off, b.data_len, F->h_text.get() + F->fill + used, b.isize, b.crc, nullptr});
+            used += b.isize; zused += b.size;
+        }
+        if (c->jobs.empty() && k == 0) break;
+        bam::inflate_blocks(*c->pool, c->jobs.data(), c->jobs.size());
+        // the blocks in front of the first bad one count
+        size_t zgood = 0;
+        const uint8_t *zb = z;
+        for (const bam::InflateJob &j : c->jobs) {
+            if (j.error) { why = j.error; k = -1; break; }
+            F->fill += j.isize;
+            bam::bgzf_block_at(zb, avail - zgood, &b, &why);
+            zgood += b.size; zb += b.size;
+        }
+        c->zhead += zgood; c->zpos += zgood;
+        hop_records(c);
+        if (c->bam_stop) break;
+        if (k < 0) return container_error(c, why, c->zpos);
+    }
+    if (c->bam_stop && !c->failed) {
+        // the record that cannot be one is the last of the stream
+        int r = submit_bam(c);
+        if (!r) r = drain(c);
+        if (r) return r;
+    }
+    return c->failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
+}
+
+void bam_compact(dwgsim_hip_eval_ctx *c)
+{
+    c->zbuf.erase(c->zbuf.begin(), c->zbuf.begin() + (ptrdiff_t)c->zhead);
+    c->zhead = 0;
+}
+
+// the end of a BAM file: it must end at a block boundary, behind the header, and between two records
+int end_bam_file(dwgsim_hip_eval_ctx *c)
+{
+    Slot &F = c->s[c->cur];
+    if (!c->failed && !c->bam_stop) {
+        const char *why = c->zbuf.size() > c->zhead ? "the file ends inside a BGZF block" : c->in_header ? "the file ends inside the BAM header"
+                        : F.fill > F.hop ? "the file ends inside a record" : nullptr;
+        if (why) {
+            // (a fatal record in front of the end is the run's result, not an error of this call)
+            const int r = container_error(c, why, c->zpos + (c->zbuf.size() - c->zhead));
+            return r == DWGSIM_HIP_EVAL_STOPPED ? DWGSIM_HIP_OK : r;
+        }
+    }
+    if (F.n_offs > F.has_ctx && !c->failed) {
+        const int r = submit_bam(c);
+        if (r) return r;
+    }
+    c->zbuf.clear(); c->zhead = 0;
+    return drain(c);
+}
+
+// The context record of the filling slot in the format of the file that begins (-m compares across files of different formats): a record
+// of the other format with the same QNAME and FLAG.  A name that the other format cannot hold equals no name there: no context then.
+void convert_ctx(dwgsim_hip_eval_ctx *c, int fmt)
+{
+    Slot &F = c->s[c->cur];
+    if (F.has_ctx && F.fmt != fmt && !c->failed) {
+        const ev::Prev pv = F.fmt == FMT_SAM ? ev::sam_prev(F.h_text.get<char>(), (uint32_t)F.ctx_len - 1) : ev::bam_prev(F.h_text.get());
+        const std::string q(pv.qname, pv.qlen);
+        std::string rec;
+        const bool fits = !q.empty() && q.size() <= (size_t)ev::MAX_QNAME && q.find_first_of(fmt == FMT_SAM ? "\t\n" : std::string(1, '\0')) == std::string::npos;
+        if (fits && fmt == FMT_SAM) {
+            rec = q + "\t" + std::to_string(pv.flag) + "\n";
+        } else if (fits) {
+            rec.assign(4 + ev::BAM_FIXED, '\0');
+            auto put32 = [&](size_t at, uint32_t v) { for (int k = 0; k < 4; ++k) rec[at + k] = (char)(v >> (8 * k)); };
+            put32(0, ev::BAM_FIXED + (uint32_t)q.size() + 1);
+            put32(4, ~0u); put32(8, ~0u); put32(24, ~0u); put32(28, ~0u);      // refID, pos, next_refID, next_pos: -1
+            rec[12] = (char)(q.size() + 1);
+            rec[18] = (char)(pv.flag & 0xff); rec[19] = (char)(pv.flag >> 8);
+            rec += q;
+            rec += '\0';
+        }
+        memcpy(F.h_text.get<char>(), rec.data(), rec.size());
+        F.has_ctx = fits ? 1 : 0;
+        F.ctx_len = F.fill = rec.size();
+    }
+    F.fmt = fmt;
+    if (fmt == FMT_BAM) {
+        if (F.has_ctx) F.h_offs.get<uint32_t>()[0] = 0;
+        F.n_offs = F.has_ctx; F.hop = F.ctx_len;
+    }
 }
 
 void format_table(dwgsim_hip_eval_ctx *c, const std::vector<unsigned long long> &h)
@@ -398,7 +692,7 @@ extern "C" {
 void dwgsim_hip_eval_opts_default(dwgsim_hip_eval_opts_t *o)
 {
     memset(o, 0, sizeof *o);
-    o->size = sizeof *o;
+    o->size = sizeof *o;        // (inflate_threads 0: the default)
     o->d = 1; o->e = -1; o->g = 5; o->s = -1;
 }
 
@@ -406,13 +700,19 @@ dwgsim_hip_eval_ctx_t *dwgsim_hip_eval_create(const dwgsim_hip_eval_opts_t *opts
 {
     int dummy;
     if (!err) err = &dummy;
-    if (!opts || opts->size != sizeof(dwgsim_hip_eval_opts_t) || opts->d == 0 ||
-        (opts->chunk_bytes && (opts->chunk_bytes < MIN_CHUNK || opts->chunk_bytes > MAX_CHUNK))) {
+    // (a caller built against ABI version 1 passes the options without inflate_threads)
+    const size_t v1_size = offsetof(dwgsim_hip_eval_opts_t, inflate_threads);
+    if (!opts || (opts->size != sizeof(dwgsim_hip_eval_opts_t) && opts->size != v1_size) || opts->d == 0 ||
+        (opts->chunk_bytes && (opts->chunk_bytes < MIN_CHUNK || opts->chunk_bytes > MAX_CHUNK)) ||
+        (opts->size > v1_size && opts->inflate_threads < 0)) {
         *err = DWGSIM_HIP_ERR_ARG;
         return nullptr;
     }
     auto *c = new dwgsim_hip_eval_ctx;
-    c->o = *opts;
+    dwgsim_hip_eval_opts_default(&c->o);
+    memcpy(&c->o, opts, opts->size);
+    c->o.size = sizeof c->o;
+    if (c->o.inflate_threads) c->inflate_threads = c->o.inflate_threads > MAX_INFLATE_THREADS ? MAX_INFLATE_THREADS : c->o.inflate_threads;
     if (opts->P) c->P = opts->P;
     c->o.P = opts->P ? c->P.c_str() : nullptr;
     c->device = device;
@@ -441,14 +741,43 @@ int dwgsim_hip_eval_header(dwgsim_hip_eval_ctx_t *c, const char *text, size_t le
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
     int r = end_file(c);
     if (r) return r;
+    c->fmt = FMT_SAM;
+    convert_ctx(c, FMT_SAM);
     if (!c->seen_header && c->o.p) c->incorrect.assign(text, len);
     c->seen_header = true;
     return upload_targets(c, text, len);
 }
 
-int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
+int dwgsim_hip_eval_bam_begin(dwgsim_hip_eval_ctx_t *c)
 {
     if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
+    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    const int r = end_file(c);
+    if (r) return r;
+    c->fmt = FMT_BAM;
+    convert_ctx(c, FMT_BAM);
+    c->zbuf.clear(); c->zhead = 0; c->zpos = 0;
+    c->hdr_bytes.clear();
+    c->in_header = true; c->bam_stop = false;
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_feed_bam(dwgsim_hip_eval_ctx_t *c, const void *buf, size_t len)
+{
+    if (!c || c->finished || c->fmt != FMT_BAM || (len && !buf)) return DWGSIM_HIP_ERR_STATE;
+    if (c->broken) return DWGSIM_HIP_ERR_FAILED;
+    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    if (c->failed || c->bam_stop) return c->failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
+    c->zbuf.insert(c->zbuf.end(), (const uint8_t *)buf, (const uint8_t *)buf + len);
+    const int r = bam_pump(c);
+    bam_compact(c);
+    return r;
+}
+
+int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
+{
+    if (!c || c->finished || c->fmt != FMT_SAM) return DWGSIM_HIP_ERR_STATE;
+    if (c->broken) return DWGSIM_HIP_ERR_FAILED;
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
     c->seen_header = true;      // the first file's header is empty when feed comes first
     while (len && !c->failed) {
@@ -573,6 +902,86 @@ int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *c, const void *tex
     hipEventElapsedTime(&t, e0.get(), e1.get());
     *ms = t / reps;
     return rc;
+}
+
+int dwgsim_hip_eval_debug_device_bam_chunk(dwgsim_hip_eval_ctx_t *c, const void *records, size_t len, int reps, double *ms)
+{
+    if (!c || !records || !len || len > MAX_CHUNK * 2ull || reps < 1 || !ms) return DWGSIM_HIP_ERR_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    // the offsets of the whole records, as hop_records finds them
+    std::vector<uint32_t> offs;
+    const uint8_t *t = (const uint8_t *)records;
+    for (size_t q = 0; len - q >= 4;) {
+        const uint32_t bs = bam::le32(t + q);
+        if (bs < ev::BAM_FIXED || bs > ev::BAM_MAX_BLOCK || len - q - 4 < bs) break;
+        offs.push_back((uint32_t)q);
+        q += 4 + (size_t)bs;
+    }
+    if (offs.empty()) return DWGSIM_HIP_ERR_ARG;
+    const size_t n = offs.size();
+    DevMem dev, d_offs, res, spill;
+    DevEvent e0, e1;
+    auto exact = [](DevMem &b, size_t k) { return b.reserve(k, k) != hipSuccess; };
+    if (exact(dev, len) || exact(d_offs, n * sizeof(uint32_t)) || exact(res, sizeof(EvalRes)) || exact(spill, (n + 1) * sizeof(uint64_t)) || e0.create() || e1.create()) {
+        c->err = "debug_device_bam_chunk: out of device memory";
+        return DWGSIM_HIP_ERR_NOMEM;
+    }
+    hipStream_t st = c->s[0].st;
+    const EvalRes init = {~0ull, 0, (uint32_t)n, 0};
+    if (hipMemcpy(dev.get(), records, len, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_offs.get(), offs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        c->err = "debug_device_bam_chunk: upload failed";
+        return DWGSIM_HIP_ERR_DEVICE;
+    }
+    int rc = DWGSIM_HIP_OK;
+    const EvalRecArgs A = rec_args(c, dev.get(), d_offs.get<uint32_t>(), res.get<EvalRes>(), spill.get<uint64_t>(), nullptr, 0);
+    double total = 0;
+    for (int i = 0; i < reps && rc == DWGSIM_HIP_OK; ++i) {
+        // (the result words are set outside the timed span: a BAM chunk's count comes from the host)
+        if (hipMemcpy(res.get(), &init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) { rc = DWGSIM_HIP_ERR_DEVICE; break; }
+        hipEventRecord(e0.get(), st);
+        launch_eval_bam_chunk(st, A, bam_records_grid((uint32_t)n));
+        hipEventRecord(e1.get(), st);
+        if (hipStreamSynchronize(st) != hipSuccess) { c->err = "debug_device_bam_chunk: kernel failed"; rc = DWGSIM_HIP_ERR_DEVICE; break; }
+        float ms1 = 0;
+        hipEventElapsedTime(&ms1, e0.get(), e1.get());
+        total += ms1;
+    }
+    *ms = total / reps;
+    return rc;
+}
+
+int dwgsim_hip_eval_debug_inflate(const void *bam_bytes, size_t len, int threads, int reps, double *ms, uint64_t *out_bytes)
+{
+    if (!bam_bytes || !len || threads < 1 || threads > MAX_INFLATE_THREADS || reps < 1 || !ms || !out_bytes) return DWGSIM_HIP_ERR_ARG;
+    const uint8_t *z = (const uint8_t *)bam_bytes;
+    std::vector<bam::InflateJob> jobs;
+    uint64_t total = 0;
+    for (size_t at = 0; at < len;) {
+        bam::BgzfBlock b;
+        const char *why;
+        if (bam::bgzf_block_at(z + at, len - at, &b, &why) != 1) return DWGSIM_HIP_ERR_ARG;
+        jobs.push_back({z + at + b.data_off, b.data_len, nullptr, b.isize, b.crc, nullptr});
+        total += b.isize; at += b.size;
+    }
+    std::vector<uint8_t> out(total + 1);
+    uint64_t to = 0;
+    for (bam::InflateJob &j : jobs) { j.dst = out.data() + to; to += j.isize; }
+    bam::InflatePool pool(threads);
+    double best = 0;
+    for (int i = 0; i < reps; ++i) {
+        timespec t0, t1;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        // in batches, as feed_bam hands them over
+        for (size_t k = 0; k < jobs.size(); k += MAX_BATCH) bam::inflate_blocks(pool, jobs.data() + k, jobs.size() - k < MAX_BATCH ? jobs.size() - k : MAX_BATCH);
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        const double d = (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6;
+        if (i == 0 || d < best) best = d;
+        for (const bam::InflateJob &j : jobs) if (j.error) return DWGSIM_HIP_ERR_FAILED;
+    }
+    *ms = best;
+    *out_bytes = total;
+    return DWGSIM_HIP_OK;
 }
 
 } // extern "C"

@@ -9,6 +9,10 @@
 //                   histogram: an LDS window of EVAL_WIN scores x 5 classes plus one bin for the floor score (the unmapped records of -a 1..3),
 //                   merged into the 64-bit global histogram once per block; a score outside both goes to the spill list, which the host adds.
 // The histogram is fused into k_eval_records: the per-record (class, score) words never go to memory.
+//
+// A chunk of a BAM file is whole binary records instead, led by the same kind of context record, and comes with the offset of every record:
+//   k_eval_bam_records  the same body as k_eval_records behind another front (parse_bam_record instead of parse_sam_line); the three newline
+//                       kernels are not launched.
 #include <hip/hip_runtime.h>
 #include "dw_eval.hpp"
 #include "dw_eval_launch.hpp"
@@ -104,23 +108,51 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_lines(const uint8_t *text, 
             if (((w[k] >> (8 * b)) & 0xff) == '\n') ends[o++] = (uint32_t)(at + 4 * k + b);
 }
 
-__global__ __launch_bounds__(EV_THREADS) void k_eval_records(EvalRecArgs A)
+// The two record fronts.  Record li of the chunk (the context record, when there is one, is record 0) becomes an ev::Rec, and the record in
+// front of it an ev::Prev; everything after that is the same for both formats (eval_records_body).
+struct SamFront {
+    // line li = (ends[li-1], ends[li])
+    static __device__ __forceinline__ bool rec(const EvalRecArgs &A, uint32_t li, ev::Rec *r)
+    {
+        const uint32_t b = li ? A.ends[li - 1] + 1 : 0, e = A.ends[li];
+        return ev::parse_sam_line((const char *)A.text + b, e - b, r);
+    }
+    static __device__ __forceinline__ ev::Prev prev(const EvalRecArgs &A, uint32_t li)
+    {
+        const uint32_t pb = li >= 2 ? A.ends[li - 2] + 1 : 0, pe = A.ends[li - 1];
+        return ev::sam_prev((const char *)A.text + pb, pe - pb);
+    }
+};
+
+struct BamFront {
+    // record li starts at ends[li] (its block_size field); the host has checked that all of it lies inside the chunk
+    static __device__ __forceinline__ bool rec(const EvalRecArgs &A, uint32_t li, ev::Rec *r)
+    {
+        const uint8_t *p = A.text + A.ends[li];
+        return ev::parse_bam_record(p, ev::ld32(p), A.tg.n, r);
+    }
+    static __device__ __forceinline__ ev::Prev prev(const EvalRecArgs &A, uint32_t li) { return ev::bam_prev(A.text + A.ends[li - 1]); }
+};
+
+// one lane per record, grid-stride; h: the block's LDS histogram, 5 x (EVAL_WIN + 1)
+template <class Front> __device__ __forceinline__ void eval_records_body(const EvalRecArgs &A, uint32_t *h)
 {
-    __shared__ uint32_t h[5 * (EVAL_WIN + 1)];
     for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS) h[i] = 0;
     __syncthreads();
 
     const uint32_t n_lines = A.res->n_lines;
     const uint32_t n_rec = n_lines > A.has_ctx ? n_lines - A.has_ctx : 0;
-    const char *text = (const char *)A.text;
     uint32_t n_local = 0;
     for (uint32_t r = blockIdx.x * EV_THREADS + threadIdx.x; r < n_rec; r += gridDim.x * EV_THREADS) {
         const uint32_t li = r + A.has_ctx;
-        const uint32_t b = li ? A.ends[li - 1] + 1 : 0, e = A.ends[li];
-        const char *prev = nullptr;
-        uint32_t pb = 0, pe = 0;
-        if (li) { pb = li >= 2 ? A.ends[li - 2] + 1 : 0; pe = A.ends[li - 1]; prev = text + pb; }
-        const ev::Out o = ev::eval_line(text + b, e - b, prev, pe - pb, A.opt, A.tg);
+        ev::Rec R;
+        ev::Out o = {ev::E_MALFORMED, 0, 0, -1, 0};
+        if (Front::rec(A, li, &R)) {
+            ev::Prev pv;
+            const bool have_prev = A.opt.m && li;
+            if (have_prev) pv = Front::prev(A, li);
+            o = ev::eval_rec(R, have_prev ? &pv : nullptr, A.opt, A.tg);
+        }
         bool incorrect = false;
         if (o.code) {
             atomicMin((unsigned long long *)&A.res->err, (unsigned long long)(((uint64_t)r << 8) | (uint32_t)o.code));
@@ -145,6 +177,20 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_records(EvalRecArgs A)
         if (h[i]) atomicAdd((unsigned long long *)&A.hist[i], (unsigned long long)h[i]);
 }
 
+__global__ __launch_bounds__(EV_THREADS) void k_eval_records(EvalRecArgs A)
+{
+    __shared__ uint32_t h[5 * (EVAL_WIN + 1)];
+    eval_records_body<SamFront>(A, h);
+}
+
+// a BAM chunk: A.ends holds the byte offset of every record of the chunk (host-made: dw_eval.cpp hops over the block_size chain), and
+// A.res->n_lines their number; no newline kernels run
+__global__ __launch_bounds__(EV_THREADS) void k_eval_bam_records(EvalRecArgs A)
+{
+    __shared__ uint32_t h[5 * (EVAL_WIN + 1)];
+    eval_records_body<BamFront>(A, h);
+}
+
 void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tile_count, uint32_t grid_records)
 {
     const uint32_t tiles = (uint32_t)((len + EV_TILE - 1) / EV_TILE);
@@ -154,6 +200,11 @@ void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint3
         hipLaunchKernelGGL(k_eval_lines, dim3(tiles), dim3(EV_THREADS), 0, st, A.text, len, (const uint32_t *)tile_count, A.ends);
     }
     hipLaunchKernelGGL(k_eval_records, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A);
+}
+
+void launch_eval_bam_chunk(hipStream_t st, const EvalRecArgs &A, uint32_t grid_records)
+{
+    hipLaunchKernelGGL(k_eval_bam_records, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A);
 }
 
 } // namespace dw

@@ -13,13 +13,13 @@ constexpr int EVAL_WIN = 2048;            // scores held in LDS per class (plus 
 struct EvalRes {
     unsigned long long err;     // (record << 8) | code of the first fatal record, ~0 when none
     unsigned long long n;       // the n of the reference (pairs or single-end reads)
-    uint32_t n_lines;           // lines of the chunk, context line included
+    uint32_t n_lines;           // lines (BAM: records, set by the host) of the chunk, context line included
     uint32_t n_spill;           // entries of the spill list
 };
 
 struct EvalRecArgs {
     const uint8_t *text;
-    uint32_t *ends;
+    uint32_t *ends;             // SAM: the position of every newline (device-made).  BAM: the offset of every record (host-made)
     EvalRes *res;
     unsigned long long *hist;   // 5 x (EVAL_WIN + 1): class-major; bin EVAL_WIN of a class = floor_score
     uint64_t *spill;            // (uint32 score << 32) | class
@@ -32,5 +32,6 @@ struct EvalRecArgs {
 };
 
 void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tile_count, uint32_t grid_records);
+void launch_eval_bam_chunk(hipStream_t st, const EvalRecArgs &A, uint32_t grid_records);
 
 } // namespace dw

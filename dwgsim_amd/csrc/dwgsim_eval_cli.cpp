@@ -1,4 +1,6 @@
-// dwgsim_eval-hip -- the dwgsim_eval command line (reference src/dwgsim_eval.c main / run) over the dwgsim_hip_eval_* C-ABI.  SAM text only.
+// dwgsim_eval-hip -- the dwgsim_eval command line (reference src/dwgsim_eval.c main / run) over the dwgsim_hip_eval_* C-ABI.
+// Input is BAM unless -S is given, as for the reference.  Without -S the first two bytes of every input are read before a device is opened:
+// when one of them is not gzip's 1f 8b the input is text, and the message that asks for -S is printed.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,7 +21,7 @@ static int print_usage(const dwgsim_hip_eval_opts_t *a)
     fprintf(f, "Program: dwgsim_eval-hip (short read simulation evaluator, MI355X hot path of dwgsim_eval)\n");
     fprintf(f, "Version: %s\n", PACKAGE_VERSION);
     fprintf(f, "Contact: Nils Homer <dnaa-help@lists.sourceforge.net>\n\n");
-    fprintf(f, "Usage: dwgsim_eval-hip [options] -S <in.sam> [<in2.sam> ...]   (- reads stdin)\n\n");
+    fprintf(f, "Usage: dwgsim_eval-hip [options] <in.bam> [<in2.bam> ...]   or   -S <in.sam> [<in2.sam> ...]   (- reads stdin)\n\n");
     fprintf(f, "Options:\n");
     fprintf(f, "\t-a\tINT\tsplit by [%d]:\n", a->a);
     fprintf(f, "\t\t\t\t\t0: by mapping quality\n");
@@ -34,7 +36,7 @@ static int print_usage(const dwgsim_hip_eval_opts_t *a)
     fprintf(f, "\t-n\tINT\tnumber of raw input paired-end reads (otherwise, inferred from all SAM records present) [%d]\n", a->n);
     fprintf(f, "\t-q\tINT\tconsider only alignments with this mapping quality or greater [%d]\n", a->q);
     fprintf(f, "\t-z\t\tinput contains only single end reads [%s]\n", tf(a->z));
-    fprintf(f, "\t-S\t\tinput is SAM (required: BAM is not supported) [%s]\n", tf(0));
+    fprintf(f, "\t-S\t\tinput is SAM (default: BAM) [%s]\n", tf(0));
     fprintf(f, "\t-p\t\tprint incorrect alignments [%s]\n", tf(a->p));
     fprintf(f, "\t-s\tINT\tconsider only alignments with the number of specified SNPs [%d]\n", a->s);
     fprintf(f, "\t-e\tINT\tconsider only alignments with the number of specified errors [%d]\n", a->e);
@@ -75,6 +77,25 @@ static int run_file(dwgsim_hip_eval_ctx_t *ctx, FILE *in)
     return DWGSIM_HIP_OK;
 }
 
+// one BAM file: `lead` (the bytes already read from it), then the rest, as they come
+static int run_bam_file(dwgsim_hip_eval_ctx_t *ctx, FILE *in, const std::string &lead)
+{
+    int r = dwgsim_hip_eval_bam_begin(ctx);
+    if (r) return r;
+    if ((r = dwgsim_hip_eval_feed_bam(ctx, lead.data(), lead.size()))) return r;
+    std::vector<char> buf(8u << 20);
+    size_t got;
+    while ((got = fread(buf.data(), 1, buf.size(), in)) > 0)
+        if ((r = dwgsim_hip_eval_feed_bam(ctx, buf.data(), got))) return r;
+    return DWGSIM_HIP_OK;
+}
+
+static void open_error(const char *path, int e)
+{
+    fprintf(stderr, "%s\rIn function \"run\": Fatal Error[OpenFileError]. Variable/Value: %s.\nMessage: Could not open file for reading.\n", BREAK_LINE, path);
+    fprintf(stderr, "The file stream error was:: %s\n ***** Exiting due to errors *****\n%s", strerror(e), BREAK_LINE);
+}
+
 int main(int argc, char *argv[])
 {
     dwgsim_hip_eval_opts_t o;
@@ -83,6 +104,8 @@ int main(int argc, char *argv[])
     std::string P;
     const char *chunk = getenv("DWGSIM_EVAL_CHUNK");      // text bytes per device chunk (tests use small ones)
     if (chunk) o.chunk_bytes = strtoull(chunk, nullptr, 10);
+    const char *threads = getenv("DWGSIM_EVAL_THREADS");  // host threads that inflate BAM input
+    if (threads) o.inflate_threads = atoi(threads);
     int c;
     while ((c = getopt(argc, argv, "a:d:e:g:m:n:q:s:bchimpzSP:")) >= 0) {
         switch (c) {
@@ -106,9 +129,28 @@ int main(int argc, char *argv[])
         }
     }
     if (argc == optind) return print_usage(&o);
+    // BAM: every input is opened and its first two bytes are kept
+    std::vector<FILE *> files;
+    std::vector<std::string> leads;
+    std::vector<int> open_errno;
     if (!S) {
-        fprintf(stderr, "dwgsim_eval-hip: only SAM text is supported: pass -S (samtools view -h in.bam | dwgsim_eval-hip -S -)\n");
-        return 1;
+        bool text = false, std_in = false;
+        for (int i = optind; i < argc; ++i) {
+            const bool is_stdin = !strcmp(argv[i], "-");
+            FILE *in = is_stdin ? (std_in ? nullptr : stdin) : fopen(argv[i], "rb");
+            open_errno.push_back(in ? 0 : is_stdin ? EBADF : errno);
+            std_in |= is_stdin;
+            char two[2];
+            const size_t got = in ? fread(two, 1, 2, in) : 0;
+            files.push_back(in);
+            leads.emplace_back(two, got);
+            // (a file that cannot be opened is reported in its turn, as with -S)
+            if ((in || is_stdin) && !(got == 2 && (unsigned char)two[0] == 0x1f && (unsigned char)two[1] == 0x8b)) text = true;
+        }
+        if (text) {
+            fprintf(stderr, "dwgsim_eval-hip: only SAM text is supported: pass -S (samtools view -h in.bam | dwgsim_eval-hip -S -)\n");
+            return 1;
+        }
     }
     if (o.d == 0) {
         fprintf(stderr, "dwgsim_eval-hip: -d must not be 0\n");
@@ -123,11 +165,20 @@ int main(int argc, char *argv[])
     fputs("Analyzing...\nCurrently on:\n0", stderr);
     int r = DWGSIM_HIP_OK;
     for (int i = optind; i < argc && r == DWGSIM_HIP_OK; ++i) {
+        if (!S) {
+            FILE *in = files[i - optind];
+            if (!in) {
+                open_error(argv[i], open_errno[i - optind]);
+                dwgsim_hip_eval_destroy(ctx);
+                return 1;
+            }
+            r = run_bam_file(ctx, in, leads[i - optind]);
+            if (in != stdin) fclose(in);
+            continue;
+        }
         FILE *in = strcmp(argv[i], "-") ? fopen(argv[i], "rb") : stdin;
         if (!in) {
-            const int e = errno;
-            fprintf(stderr, "%s\rIn function \"run\": Fatal Error[OpenFileError]. Variable/Value: %s.\nMessage: Could not open file for reading.\n", BREAK_LINE, argv[i]);
-            fprintf(stderr, "The file stream error was:: %s\n ***** Exiting due to errors *****\n%s", strerror(e), BREAK_LINE);
+            open_error(argv[i], errno);
             dwgsim_hip_eval_destroy(ctx);
             return 1;
         }

@@ -337,10 +337,11 @@ const char *dwgsim_hip_job_last_error(const dwgsim_hip_job_t *job);
 void dwgsim_hip_job_destroy(dwgsim_hip_job_t *job);
 
 /* ====================================================================================================================================
- * dwgsim_eval: score SAM alignments of simulated reads (reference src/dwgsim_eval.c; DESIGN.md "dwgsim_eval-hip").  SAM text only.
+ * dwgsim_eval: score SAM or BAM alignments of simulated reads (reference src/dwgsim_eval.c; DESIGN.md "dwgsim_eval-hip").
  * A context evaluates one run: header(file 1), feed(records of file 1)..., header(file 2), feed..., finish, then the texts.  One device.
+ * A BAM file is bam_begin, feed_bam(its raw bytes)... instead of header, feed...; SAM and BAM files may be mixed in one run.
  * ==================================================================================================================================== */
-#define DWGSIM_HIP_EVAL_ABI_VERSION 1
+#define DWGSIM_HIP_EVAL_ABI_VERSION 2
 /* fatal record errors (dwgsim_hip_eval_summary_t.error_code): the first record of the run, in file order, that has one decides */
 #define DWGSIM_HIP_EVAL_E_MALFORMED       1   /* not a SAM record (fewer than 11 fields, FLAG / POS / MAPQ out of range, ...) */
 #define DWGSIM_HIP_EVAL_E_PREFIX          2   /* "could not match read name with given read name prefix (-P)" */
@@ -360,6 +361,7 @@ typedef struct dwgsim_hip_eval_opts {
     int32_t b, c, i, m, p, z;       /* flags, 0 */
     const char *P;                  /* -P, NULL: none (copied at create) */
     uint64_t chunk_bytes;           /* text per device chunk; 0: 32 MiB.  At least 4 KiB */
+    int32_t inflate_threads;        /* (ABI 2) host threads that inflate BGZF blocks; 0: 8.  At most 16; 1: the calling thread alone */
 } dwgsim_hip_eval_opts_t;
 
 typedef struct dwgsim_hip_eval_summary {
@@ -381,6 +383,12 @@ dwgsim_hip_eval_ctx_t *dwgsim_hip_eval_create(const dwgsim_hip_eval_opts_t *opts
 int dwgsim_hip_eval_header(dwgsim_hip_eval_ctx_t *ctx, const char *text, size_t len);
 /* record text of the current file, split anywhere.  DWGSIM_HIP_EVAL_STOPPED once a fatal record has been found */
 int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *ctx, const char *buf, size_t len);
+/* starts the next file, a BAM file (and ends the file before it, as dwgsim_hip_eval_header does): its targets are its binary reference list */
+int dwgsim_hip_eval_bam_begin(dwgsim_hip_eval_ctx_t *ctx);
+/* raw bytes of the current BAM file (BGZF), split anywhere.  DWGSIM_HIP_EVAL_STOPPED as for feed.  A container error (not BGZF, inflate,
+ * CRC-32 or ISIZE mismatch, bad BAM magic or header, and -- at the next begin / header / finish -- a file that ends inside a block, the
+ * header or a record) is DWGSIM_HIP_ERR_FAILED once the records in front of it hold no fatal one; last_error says what and where */
+int dwgsim_hip_eval_feed_bam(dwgsim_hip_eval_ctx_t *ctx, const void *buf, size_t len);
 int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *ctx, dwgsim_hip_eval_summary_t *summary);
 /* after finish without a fatal error: the 19 '#' lines and the rows (stdout of dwgsim_eval after the -p part) */
 int dwgsim_hip_eval_table_text(dwgsim_hip_eval_ctx_t *ctx, const char **txt, size_t *len);
@@ -393,6 +401,11 @@ void dwgsim_hip_eval_destroy(dwgsim_hip_eval_ctx_t *ctx);
  * except for the histogram, which this adds to. */
 int dwgsim_hip_eval_debug_time(dwgsim_hip_eval_ctx_t *ctx, double *kernel_ms);
 int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *ctx, const void *text, size_t len, int reps, double *ms);
+/* the same for a BAM chunk: `len` bytes of whole BAM records (uncompressed, no header; the targets are those of the context's current BAM
+ * file), k_eval_bam_records alone, *ms = time per evaluation.  And the inflater alone, without a device: all BGZF blocks of the `len` bytes of a
+ * BAM file on `threads` host threads, *ms = the best of `reps` passes, *out_bytes = the inflated size. */
+int dwgsim_hip_eval_debug_device_bam_chunk(dwgsim_hip_eval_ctx_t *ctx, const void *records, size_t len, int reps, double *ms);
+int dwgsim_hip_eval_debug_inflate(const void *bam, size_t len, int threads, int reps, double *ms, uint64_t *out_bytes);
 
 /* ====================================================================================================================================
  * TEST / ANALYSIS HOOKS -- everything below this line is NOT part of the drop-in surface.  A binding of the reference needs none of it; the

@@ -2,7 +2,11 @@
   kernel   text already in device memory (uploaded beforehand), the four kernels of one chunk only (dwgsim_hip_eval_debug_device_chunk)
   e2e      text in page-locked host memory fed through dwgsim_hip_eval_feed: copy into the context's slots, upload, kernels, results
   model    tests/eval_model.py, the plain-Python model, on one core
-Prints one JSON line.  Usage: python tools/eval_throughput.py [--mib 1024] [--reps 5] [--model-mib 16]"""
+With --bam the same records are also measured as a BAM file (level 6, 64 KiB BGZF blocks, written by tests/bam_io.py):
+  bam_kernel   the uncompressed records in device memory, k_eval_bam_records alone (dwgsim_hip_eval_debug_device_bam_chunk)
+  bam_inflate  the BGZF blocks inflated on 1, 4, 8 and 16 host threads, no device involved (dwgsim_hip_eval_debug_inflate)
+  bam_e2e      the BAM bytes fed through dwgsim_hip_eval_feed_bam at 1, 4, 8 and 16 inflate threads: GB/s of uncompressed BAM, records/s
+Prints one JSON line.  Usage: python tools/eval_throughput.py [--mib 1024] [--reps 5] [--model-mib 16] [--bam]"""
 import argparse, ctypes as C, json, os, random, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,6 +22,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--model-mib", type=int, default=16)
     ap.add_argument("--a", type=int, default=3)
+    ap.add_argument("--bam", action="store_true")
     args = ap.parse_args()
     contigs = [("chr%d" % i, 200_000_000) for i in range(1, 23)]
     rng = random.Random(5)
@@ -60,6 +65,9 @@ def main():
     out["e2e_GBps"] = n_bytes / best / 1e9
     out["e2e_Mrec_s"] = n_recs / best / 1e6
 
+    if args.bam:
+        bam_throughput(lib, args, head, block, k, out)
+
     sub = block * max(1, (args.model_mib << 20) // len(block))
     t0 = time.perf_counter()
     M.run([head + sub], M.Opts(a=args.a))
@@ -67,6 +75,55 @@ def main():
     out["model_GBps"] = len(sub) / dt / 1e9
     out["model_Mrec_s"] = sub.count(b"\n") / dt / 1e6
     print(json.dumps(out))
+
+
+def bam_throughput(lib, args, head, block, k, out):
+    import bam_io as B
+    payload, offs = B.bam_payload(head + block)
+    hdr, recs = payload[:offs[0]], payload[offs[0]:]
+    n_recs = len(offs) * k
+    # whole blocks of records only, so that the file is the header's blocks followed by k copies of the records' blocks
+    rec_blocks = B.bgzf(recs, eof=False)
+    bam = B.bgzf(hdr, eof=False) + rec_blocks * k + B.EOF_BLOCK
+    raw = recs * k
+    out.update({"bam_file_bytes": len(bam), "bam_record_bytes": len(raw), "bam_records": n_recs})
+
+    with api.EvalContext(a=args.a) as ctx:
+        ctx.bam_begin()
+        ctx.feed_bam(B.bgzf(hdr, eof=False))
+        ms = C.c_double()
+        r = lib.dwgsim_hip_eval_debug_device_bam_chunk(ctx.ctx, raw, len(raw), 1, C.byref(ms))      # warm-up
+        r = r or lib.dwgsim_hip_eval_debug_device_bam_chunk(ctx.ctx, raw, len(raw), args.reps, C.byref(ms))
+        if r:
+            raise SystemExit("device BAM chunk failed: %d" % r)
+        out["bam_kernel_ms"] = ms.value
+        out["bam_kernel_GBps"] = len(raw) / ms.value / 1e6
+        out["bam_kernel_Mrec_s"] = n_recs / ms.value / 1e3
+
+    pinned = lib.dwgsim_hip_host_alloc(len(bam))
+    if not pinned:
+        raise SystemExit("host_alloc failed")
+    C.memmove(pinned, bam, len(bam))
+    for t in (1, 4, 8, 16):
+        ms, nb = C.c_double(), C.c_uint64()
+        if lib.dwgsim_hip_eval_debug_inflate(C.c_void_p(pinned), len(bam), t, args.reps, C.byref(ms), C.byref(nb)):
+            raise SystemExit("inflate failed")
+        out["bam_inflate_GBps_t%d" % t] = nb.value / ms.value / 1e6
+        best = None
+        for _ in range(args.reps):
+            with api.EvalContext(a=args.a, inflate_threads=t) as ctx:
+                ctx.bam_begin()
+                t0 = time.perf_counter()
+                step = 8 << 20
+                for i in range(0, len(bam), step):
+                    lib.dwgsim_hip_eval_feed_bam(ctx.ctx, C.c_void_p(pinned + i), min(step, len(bam) - i))
+                table, sm = ctx.finish()
+                dt = time.perf_counter() - t0
+            assert sm.status == 0 and sm.records == n_recs, (sm.status, sm.records, n_recs)
+            best = dt if best is None else min(best, dt)
+        out["bam_e2e_GBps_t%d" % t] = (len(raw) + len(hdr)) / best / 1e9
+        out["bam_e2e_Mrec_s_t%d" % t] = n_recs / best / 1e6
+    lib.dwgsim_hip_host_free(C.c_void_p(pinned))
 
 
 if __name__ == "__main__":
