@@ -83,6 +83,7 @@ EXPORTS = [
     "dwgsim_hip_eval_table_text", "dwgsim_hip_eval_incorrect_text", "dwgsim_hip_eval_last_error", "dwgsim_hip_eval_destroy",
     "dwgsim_hip_eval_debug_time", "dwgsim_hip_eval_debug_device_chunk", "dwgsim_hip_eval_bam_begin", "dwgsim_hip_eval_feed_bam",
     "dwgsim_hip_eval_debug_device_bam_chunk", "dwgsim_hip_eval_debug_inflate",
+    "dwgsim_hip_eval_set_breakdown", "dwgsim_hip_eval_breakdown_text",
 ]
 
 _lib = None
@@ -757,6 +758,8 @@ def _bind_eval(lib):
     lib.dwgsim_hip_eval_debug_device_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, P(C.c_double)]
     lib.dwgsim_hip_eval_debug_device_bam_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, P(C.c_double)]
     lib.dwgsim_hip_eval_debug_inflate.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(C.c_double), P(C.c_uint64)]
+    lib.dwgsim_hip_eval_set_breakdown.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    lib.dwgsim_hip_eval_breakdown_text.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_size_t)]
 
 
 def load_eval(path: str | None = None):
@@ -777,14 +780,18 @@ class EvalSummaryResult:
     records: int
     stderr: bytes            # dwgsim_eval's stderr text
     incorrect: bytes = b""   # -p: the first header and the incorrectly mapped records
+    breakdown: dict = field(default_factory=dict)     # "snps=0", "errors=8+", "indels=1+", "end=2", ... -> that stratum's table text
 
 
 class EvalContext:
     """One dwgsim_eval run on one device: header(file 1), feed(...)..., header(file 2), ..., finish(); a BAM file is bam_begin(),
     feed_bam(...)... instead.  Options are dwgsim_eval's (a, b, c, d, e, g, i, m, n, p, q, s, z: ints; P: str) plus chunk_bytes and
-    inflate_threads (host threads that inflate BAM input: 0 is the default of 8, at most 16)."""
+    inflate_threads (host threads that inflate BAM input: 0 is the default of 8, at most 16).  breakdown: a comma list of snps, errors, indels,
+    end -- finish() then also gives the table of every stratum of those dimensions (summary.breakdown), from the same pass; breakdown_cap: snps
+    and errors have the strata 0 ... cap-1 and cap+ (0: 8, at most 32)."""
 
-    def __init__(self, device: int = 0, lib=None, chunk_bytes: int = 0, inflate_threads: int = 0, **opts):
+    def __init__(self, device: int = 0, lib=None, chunk_bytes: int = 0, inflate_threads: int = 0, breakdown: str | None = None,
+                 breakdown_cap: int = 0, **opts):
         self.lib = lib or load()
         o = EvalOpts()
         self.lib.dwgsim_hip_eval_opts_default(C.byref(o))
@@ -802,6 +809,19 @@ class EvalContext:
         self.ctx = self.lib.dwgsim_hip_eval_create(C.byref(o), device, C.byref(err))
         if not self.ctx:
             raise DwgsimError(f"dwgsim_hip_eval_create failed ({err.value})")
+        self._breakdown = False
+        if breakdown or breakdown_cap:
+            if self.set_breakdown(breakdown, breakdown_cap) < 0:
+                why = self.lib.dwgsim_hip_eval_last_error(self.ctx).decode(errors="replace")
+                self.close()
+                raise DwgsimError(why)
+
+    def set_breakdown(self, dims, cap: int = 0) -> int:
+        """dwgsim_hip_eval_set_breakdown: its return value (0, or a negative DWGSIM_HIP_ERR_*)"""
+        r = self.lib.dwgsim_hip_eval_set_breakdown(self.ctx, dims.encode() if isinstance(dims, str) else dims, cap)
+        if r == 0:
+            self._breakdown = bool(dims)
+        return r
 
     def _check(self, r: int):
         if r < 0:
@@ -842,6 +862,9 @@ class EvalContext:
         self._check(self.lib.dwgsim_hip_eval_incorrect_text(self.ctx, C.byref(txt), C.byref(ln)))
         inc = C.string_at(txt, ln.value) if ln.value else b""
         res = EvalSummaryResult(sm.status, sm.error_code, sm.error_record, sm.n, sm.records, C.string_at(sm.stderr_text, sm.stderr_len), inc)
+        if self._breakdown:
+            self._check(self.lib.dwgsim_hip_eval_breakdown_text(self.ctx, C.byref(txt), C.byref(ln)))
+            res.breakdown = split_breakdown(C.string_at(txt, ln.value) if ln.value else b"")
         return table, res
 
     def debug_time_ms(self) -> float:
@@ -865,6 +888,18 @@ class EvalContext:
             self.close()
         except Exception:
             pass
+
+
+def split_breakdown(text: bytes) -> dict:
+    """the sections of dwgsim_hip_eval_breakdown_text: {"snps=0": table text, ...} in the text's order"""
+    out, key = {}, None
+    for line in text.splitlines(keepends=True):
+        if line.startswith(b"## "):
+            key = line[3:].strip().decode()
+            out[key] = b""
+        elif key is not None:
+            out[key] += line
+    return out
 
 
 def split_sam_header(data: bytes):

@@ -13,6 +13,9 @@
 // bytes and notes the offset of every whole record.  A slot that cannot take the next block is cut after its last whole record and submitted:
 // text and offsets up, k_eval_bam_records, result back; the other slot continues with that last record as context and the partial record
 // behind it.  The first blocks of a file are inflated aside until the BAM header is complete; its reference list becomes the targets.
+// Breakdown (set_breakdown; dw_eval.hpp BREAKDOWN).  The same chunks go through the breakdown form of the record kernel, which counts into the
+// strata of the selected dimensions (dw_eval_launch.hpp EvalBdArgs) instead of the one histogram.  finish() makes the main table from the sum of
+// the first selected dimension's strata and one section per stratum; tables, sections and the dimension list are dw_eval_table.hpp's.
 // A container error (framing, inflate, CRC, ISIZE, magic, header, a file that ends inside something) first evaluates the whole records in
 // front of it: a fatal record there wins; otherwise the call returns DWGSIM_HIP_ERR_FAILED and last_error says what and where.
 #include <hip/hip_runtime.h>
@@ -29,6 +32,7 @@
 #include <vector>
 #include "dw_bam.hpp"
 #include "dw_eval_launch.hpp"
+#include "dw_eval_table.hpp"
 #include "dw_mem.hpp"
 #include "../../include/dwgsim_hip.h"
 
@@ -73,7 +77,13 @@ struct dwgsim_hip_eval_ctx {
     DevMem d_names, d_off, d_hash;      // char, u32, i32
     ev::Targets tg = {};
     DevMem d_P, d_hist;                 // char, unsigned long long
-    std::map<int32_t, std::array<uint64_t, 5>> spill;
+    evt::Rows spill;
+    // the breakdown: what is selected, its device counters, its part of the spill lists, its text
+    evt::Breakdown bd;
+    evt::BreakdownCounts bdc;
+    DevMem d_bdhist;                    // unsigned long long
+    std::string bd_text;
+    bool begun = false;                 // a header, bam_begin or feed call has been made
     uint64_t n = 0, records = 0;
     bool failed = false, finished = false, seen_header = false;
     int code = 0;
@@ -200,6 +210,31 @@ EvalRecArgs rec_args(dwgsim_hip_eval_ctx *c, const uint8_t *text, uint32_t *ends
     return A;
 }
 
+EvalBdArgs bd_args(dwgsim_hip_eval_ctx *c)
+{
+    const evt::Breakdown &b = c->bd;
+    EvalBdArgs B;
+    B.hist = c->d_bdhist.get<unsigned long long>(); B.n_rows = (uint32_t)b.n_rows; B.win = b.win; B.win_lo = b.win_lo; B.cap = b.cap;
+    B.row_snps = b.row[ev::D_SNPS]; B.row_errors = b.row[ev::D_ERRORS]; B.row_indels = b.row[ev::D_INDELS]; B.row_end = b.row[ev::D_END];
+    return B;
+}
+
+// the breakdown form's blocks have twice the lanes
+uint32_t bd_grid(uint32_t plain_grid) { return (plain_grid + 1) / 2; }
+
+// the record kernels of a SAM chunk / a BAM chunk, in the form that the run uses
+void launch_chunk(dwgsim_hip_eval_ctx *c, hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tiles)
+{
+    if (c->bd.on) launch_eval_chunk_bd(st, A, bd_args(c), len, tiles, bd_grid(records_grid(len)));
+    else launch_eval_chunk(st, A, len, tiles, records_grid(len));
+}
+
+void launch_bam_chunk(dwgsim_hip_eval_ctx *c, hipStream_t st, const EvalRecArgs &A, uint32_t n_rec)
+{
+    if (c->bd.on) launch_eval_bam_chunk_bd(st, A, bd_args(c), bd_grid(bam_records_grid(n_rec)));
+    else launch_eval_bam_chunk(st, A, bam_records_grid(n_rec));
+}
+
 // the results of the oldest submitted chunk
 int process_oldest(dwgsim_hip_eval_ctx *c)
 {
@@ -233,7 +268,8 @@ int process_oldest(dwgsim_hip_eval_ctx *c)
     if (r.n_spill) {
         std::vector<uint64_t> sp(r.n_spill);
         CK(hipMemcpy(sp.data(), S.d_spill.get<uint64_t>(), sp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        for (uint64_t w : sp) c->spill[(int32_t)(uint32_t)(w >> 32)][(int)(w & 7)]++;
+        if (c->bd.on) for (uint64_t w : sp) c->bdc.add_spill(c->bd, w, &c->spill);
+        else for (uint64_t w : sp) c->spill[(int32_t)(uint32_t)(w >> 32)][(int)(w & 7)]++;
     }
     if (c->o.p && n_rec) {
         std::vector<uint8_t> fl(n_rec);
@@ -296,7 +332,7 @@ int submit(dwgsim_hip_eval_ctx *c, size_t cut)
     CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, S.st));
     CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st));
     const EvalRecArgs A = rec_args(c, S.d_text.get(), S.d_ends.get<uint32_t>(), S.d_res.get<EvalRes>(), S.d_spill.get<uint64_t>(), c->o.p ? S.d_flags.get() : nullptr, S.has_ctx);
-    launch_eval_chunk(S.st, A, cut, S.d_tiles.get<uint32_t>(), records_grid(cut));
+    launch_chunk(c, S.st, A, cut, S.d_tiles.get<uint32_t>());
     CK(hipGetLastError());
     CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st));
     CK(hipEventRecord(S.e1, S.st));
@@ -319,7 +355,7 @@ int submit_bam(dwgsim_hip_eval_ctx *c)
     CK(hipMemcpyAsync(S.d_ends.get(), S.h_offs.get(), n * sizeof(uint32_t), hipMemcpyHostToDevice, S.st));
     CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st));
     const EvalRecArgs A = rec_args(c, S.d_text.get(), S.d_ends.get<uint32_t>(), S.d_res.get<EvalRes>(), S.d_spill.get<uint64_t>(), c->o.p ? S.d_flags.get() : nullptr, S.has_ctx);
-    launch_eval_bam_chunk(S.st, A, bam_records_grid(n - S.has_ctx));
+    launch_bam_chunk(c, S.st, A, n - S.has_ctx);
     CK(hipGetLastError());
     CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st));
     CK(hipEventRecord(S.e1, S.st));
@@ -618,71 +654,21 @@ void convert_ctx(dwgsim_hip_eval_ctx *c, int fmt)
     }
 }
 
+// the main table of a plain run: the spill lists' counts and the window h
 void format_table(dwgsim_hip_eval_ctx *c, const std::vector<unsigned long long> &h)
 {
-    std::map<int32_t, std::array<uint64_t, 5>> rows = c->spill;
-    for (int k = 0; k <= EVAL_WIN; ++k)
-        for (int cl = 0; cl < 5; ++cl) {
-            const uint64_t v = h[(size_t)cl * (EVAL_WIN + 1) + k];
-            if (v) rows[k < EVAL_WIN ? WIN_LO + k : c->floor_score][cl] += v;
-        }
-    int64_t lo = 0, hi = 0;
-    uint64_t total = 0, m_total = 0, u_total = 0;
-    for (auto &kv : rows) {
-        lo = kv.first < lo ? kv.first : lo;
-        hi = kv.first > hi ? kv.first : hi;
-        const auto &r = kv.second;
-        total += r[0] + r[1] + r[2] + r[3] + r[4];
-        m_total += r[0] + r[1] + r[2];
-        u_total += r[3] + r[4];
-    }
-    const int w = total ? (int)(1 + log10((double)total)) : 1;
-    std::string &t = c->table;
-    t = std::string("# thr | the minimum ") + (c->o.a == 0 ? "mapping quality" : "alignment score") + " threshold\n";
-    t += "# mc | the number of correctly mapped reads that should be mapped at the threshold\n"
-         "# mi | the number of incorrectly mapped reads that should be mapped at the threshold\n"
-         "# mu | the number of unmapped reads that should be mapped at the threshold\n"
-         "# um | the number of mapped reads that should be unmapped at the threshold\n"
-         "# uu | the number of unmapped reads that should be unmapped at the threshold\n"
-         "# mc + mi + mu + um + uu | the total number of reads at the threshold\n"
-         "# mc' | the number of correctly mapped reads that should be mapped at or greater than that threshold\n"
-         "# mi' | the number of incorrectly mapped reads that should be mapped at or greater than that threshold\n"
-         "# mu' | the number of unmapped reads that should be mapped at or greater than that threshold\n"
-         "# um' | the number of mapped reads that should be unmapped at or greater than that threshold\n"
-         "# uu' | the number of unmapped reads that should be unmapped at or greater than that threshold\n"
-         "# mc' + mi' + mu' + um' + uu' | the total number of reads at or greater than the threshold\n"
-         "# (mc / (mc' + mi' + mu')) | sensitivity: the fraction of mappable reads that are mapped correctly at the threshold\n"
-         "# (mc / (mc' + mi')) | positive predictive value: the fraction of mapped mappable reads that are mapped correctly at the threshold\n"
-         "# (um / (um' + uu')) | false discovery rate: the fraction of random reads that are mapped at the threshold\n"
-         "# (mc' / (mc' + mi' + mu')) | sensitivity: the fraction of mappable reads that are mapped correctly at or greater than the threshold\n"
-         "# (mc' / (mc' + mi')) | positive predictive value: the fraction of mapped mappable reads that are mapped correctly at or greater than the threshold\n"
-         "# (um' / (um' + uu')) | false discovery rate: the fraction of random reads that are mapped at or greater than the threshold\n";
-    uint64_t sum[5] = {0, 0, 0, 0, 0}, mm_total = 0;
-    char buf[512];
-    const std::array<uint64_t, 5> zero = {0, 0, 0, 0, 0};
-    auto it = rows.rbegin();
-    for (int64_t sc = hi; sc >= lo; --sc) {
-        while (it != rows.rend() && it->first > sc) ++it;
-        const std::array<uint64_t, 5> &r = (it != rows.rend() && it->first == sc) ? it->second : zero;
-        for (int k = 0; k < 5; ++k) sum[k] += r[k];
-        mm_total += r[0] + r[1];
-        double den = (double)(r[0] + r[1] + r[2]);
-        const double sens_at = den == 0 ? 0. : r[0] / den;
-        const double sens_ge = m_total == 0 ? 0. : sum[0] / (double)m_total;
-        den = (double)(r[0] + r[1]);
-        const double ppv_at = den == 0 ? 0. : r[0] / den;
-        const double ppv_ge = mm_total == 0 ? 0. : sum[0] / (double)mm_total;
-        den = (double)(r[3] + r[4]);
-        const double fdr_at = den == 0 ? 0. : r[3] / den;
-        const double fdr_ge = u_total == 0 ? 0. : sum[3] / (double)u_total;
-        const int32_t thr = (int32_t)((uint32_t)(int32_t)sc * (uint32_t)c->o.d);
-        int k = snprintf(buf, sizeof buf, "%.2d ", thr);
-        const uint64_t v[12] = {r[0], r[1], r[2], r[3], r[4], r[0] + r[1] + r[2] + r[3] + r[4], sum[0], sum[1], sum[2], sum[3], sum[4],
-                                sum[0] + sum[1] + sum[2] + sum[3] + sum[4]};
-        for (int j = 0; j < 12; ++j) k += snprintf(buf + k, sizeof buf - k, "%*llu ", w, (unsigned long long)v[j]);
-        snprintf(buf + k, sizeof buf - k, "%.3e %.3e %.3e %.3e %.3e %.3e\n", sens_at, ppv_at, fdr_at, sens_ge, ppv_ge, fdr_ge);
-        t += buf;
-    }
+    evt::Rows rows = c->spill;
+    evt::add_window(rows, h.data(), EVAL_WIN, WIN_LO, c->floor_score);
+    c->table = evt::table_text(rows, c->o.a, c->o.d);
+}
+
+// the main table and the sections of a breakdown run
+void format_breakdown(dwgsim_hip_eval_ctx *c, const std::vector<unsigned long long> &counters)
+{
+    evt::Rows rows = c->spill;
+    evt::add_main_window(c->bd, counters.data(), c->floor_score, &rows);
+    c->table = evt::table_text(rows, c->o.a, c->o.d);
+    c->bd_text = evt::breakdown_text(c->bd, c->bdc, counters.data(), c->floor_score, c->o.a, c->o.d);
 }
 
 } // namespace
@@ -739,6 +725,7 @@ int dwgsim_hip_eval_header(dwgsim_hip_eval_ctx_t *c, const char *text, size_t le
 {
     if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    c->begun = true;
     int r = end_file(c);
     if (r) return r;
     c->fmt = FMT_SAM;
@@ -752,6 +739,7 @@ int dwgsim_hip_eval_bam_begin(dwgsim_hip_eval_ctx_t *c)
 {
     if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    c->begun = true;
     const int r = end_file(c);
     if (r) return r;
     c->fmt = FMT_BAM;
@@ -779,7 +767,7 @@ int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
     if (!c || c->finished || c->fmt != FMT_SAM) return DWGSIM_HIP_ERR_STATE;
     if (c->broken) return DWGSIM_HIP_ERR_FAILED;
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    c->seen_header = true;      // the first file's header is empty when feed comes first
+    c->seen_header = c->begun = true;      // the first file's header is empty when feed comes first
     while (len && !c->failed) {
         Slot &F = c->s[c->cur];
         if (F.fill == F.h_text.cap()) {
@@ -809,9 +797,15 @@ int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *c, dwgsim_hip_eval_summary_t *
         c->table.clear();
         c->incorrect.clear();
     } else {
-        std::vector<unsigned long long> h(5 * (EVAL_WIN + 1));
-        CK(hipMemcpy(h.data(), c->d_hist.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        format_table(c, h);
+        if (c->bd.on) {
+            std::vector<unsigned long long> counters(c->bd.counters());
+            CK(hipMemcpy(counters.data(), c->d_bdhist.get(), counters.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            format_breakdown(c, counters);
+        } else {
+            std::vector<unsigned long long> h(5 * (EVAL_WIN + 1));
+            CK(hipMemcpy(h.data(), c->d_hist.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            format_table(c, h);
+        }
         char buf[128];
         snprintf(buf, sizeof buf, "\r%llu\n", (unsigned long long)c->n);
         c->stderr_text += buf;
@@ -846,6 +840,33 @@ int dwgsim_hip_eval_incorrect_text(dwgsim_hip_eval_ctx_t *c, const char **txt, s
 {
     if (!c || !c->finished || !txt || !len) return DWGSIM_HIP_ERR_STATE;
     *txt = c->incorrect.c_str(); *len = c->incorrect.size();
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_set_breakdown(dwgsim_hip_eval_ctx_t *c, const char *dims, int cap)
+{
+    if (!c || c->finished || c->begun) return DWGSIM_HIP_ERR_STATE;
+    evt::Breakdown b;
+    if (const char *why = evt::parse_breakdown(dims, cap, c->o.a, EVAL_BD_CTRS, EVAL_WIN, &b)) {
+        c->err = why;
+        return DWGSIM_HIP_ERR_ARG;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    c->bd = evt::Breakdown();
+    c->d_bdhist.reset();
+    if (b.on) {
+        const size_t bytes = b.counters() * sizeof(unsigned long long);
+        CK(c->d_bdhist.reserve(bytes, bytes));
+        CK(hipMemset(c->d_bdhist.get(), 0, bytes));
+    }
+    c->bd = b;
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_breakdown_text(dwgsim_hip_eval_ctx_t *c, const char **txt, size_t *len)
+{
+    if (!c || !c->finished || !txt || !len) return DWGSIM_HIP_ERR_STATE;
+    *txt = c->bd_text.c_str(); *len = c->bd_text.size();
     return DWGSIM_HIP_OK;
 }
 
@@ -894,7 +915,7 @@ int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *c, const void *tex
     for (int i = 0; i < reps; ++i) {
         hipMemsetAsync(res.get(), 0xff, 8, st);
         hipMemsetAsync(res.get() + 8, 0, sizeof(EvalRes) - 8, st);
-        launch_eval_chunk(st, A, len, tiles.get<uint32_t>(), records_grid(len));
+        launch_chunk(c, st, A, len, tiles.get<uint32_t>());
     }
     hipEventRecord(e1.get(), st);
     if (hipStreamSynchronize(st) != hipSuccess) { c->err = "debug_device_chunk: kernel failed"; rc = DWGSIM_HIP_ERR_DEVICE; }
@@ -940,7 +961,7 @@ int dwgsim_hip_eval_debug_device_bam_chunk(dwgsim_hip_eval_ctx_t *c, const void 
         // (the result words are set outside the timed span: a BAM chunk's count comes from the host)
         if (hipMemcpy(res.get(), &init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) { rc = DWGSIM_HIP_ERR_DEVICE; break; }
         hipEventRecord(e0.get(), st);
-        launch_eval_bam_chunk(st, A, bam_records_grid((uint32_t)n));
+        launch_bam_chunk(c, st, A, (uint32_t)n);
         hipEventRecord(e1.get(), st);
         if (hipStreamSynchronize(st) != hipSuccess) { c->err = "debug_device_bam_chunk: kernel failed"; rc = DWGSIM_HIP_ERR_DEVICE; break; }
         float ms1 = 0;

@@ -13,6 +13,11 @@
 // A chunk of a BAM file is whole binary records instead, led by the same kind of context record, and comes with the offset of every record:
 //   k_eval_bam_records  the same body as k_eval_records behind another front (parse_bam_record instead of parse_sam_line); the three newline
 //                       kernels are not launched.
+//
+// With a breakdown (dw_eval.hpp BREAKDOWN) the two record kernels are replaced by k_eval_records_bd / k_eval_bam_records_bd: the same fronts and
+// the same per-record work, but a record is counted once per selected dimension, in its stratum of that dimension (EvalBdArgs lays the counters
+// out).  A block has 512 lanes and 32 768 16-bit counters, two to an LDS word (64 KiB, two blocks per CU); it merges them into the 64-bit global
+// counters before any of them can reach 2^16, that is every BD_FLUSH_ITERS turns of its record loop, and at its end.
 #include <hip/hip_runtime.h>
 #include "dw_eval.hpp"
 #include "dw_eval_launch.hpp"
@@ -191,6 +196,100 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_bam_records(EvalRecArgs A)
     eval_records_body<BamFront>(A, h);
 }
 
+// ---- the breakdown form ----
+constexpr int BD_THREADS = (int)EVAL_BD_THREADS;
+constexpr uint32_t BD_FLUSH_ITERS = 65535u / BD_THREADS;        // a block counts fewer than 2^16 records between two merges
+static_assert(BD_FLUSH_ITERS >= 1 && BD_FLUSH_ITERS * BD_THREADS < 65536u, "a 16-bit counter must not wrap between two merges");
+
+// the block's nonzero counters into the global ones, and zero again (the caller puts barriers around it)
+__device__ __forceinline__ void bd_merge(uint32_t *h, uint32_t n_words, unsigned long long *hist)
+{
+    for (uint32_t i = threadIdx.x; i < n_words; i += BD_THREADS) {
+        const uint32_t v = h[i];
+        if (!v) continue;
+        h[i] = 0;
+        if (v & 0xffffu) atomicAdd(&hist[2 * i], (unsigned long long)(v & 0xffffu));
+        if (v >> 16) atomicAdd(&hist[2 * i + 1], (unsigned long long)(v >> 16));
+    }
+}
+
+// one more record in counter (row * 5 + cls) * (win + 1) + bin
+__device__ __forceinline__ void bd_count(uint32_t *h, uint32_t row, uint32_t cls, uint32_t bins, uint32_t bin)
+{
+    const uint32_t k = (row * 5 + cls) * bins + bin;
+    if (k < EVAL_BD_CTRS) atomicAdd(&h[k >> 1], 1u << ((k & 1) * 16));
+}
+
+// one lane per record, block-stride (every lane of a block makes the same number of turns); h: EVAL_BD_CTRS / 2 words
+template <class Front> __device__ __forceinline__ void eval_records_bd_body(const EvalRecArgs &A, const EvalBdArgs &B, uint32_t *h)
+{
+    const uint32_t bins = B.win + 1, n_words = (B.n_rows * 5 * bins + 1) / 2;
+    for (uint32_t i = threadIdx.x; i < n_words; i += BD_THREADS) h[i] = 0;
+    __syncthreads();
+
+    const uint32_t n_lines = A.res->n_lines;
+    const uint32_t n_rec = n_lines > A.has_ctx ? n_lines - A.has_ctx : 0;
+    uint32_t n_local = 0, turns = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * BD_THREADS; base < n_rec; base += (uint64_t)gridDim.x * BD_THREADS) {
+        const uint64_t r64 = base + threadIdx.x;
+        if (r64 < n_rec) {
+            const uint32_t r = (uint32_t)r64, li = r + A.has_ctx;
+            ev::Rec R;
+            ev::Out o = {ev::E_MALFORMED, 0, 0, -1, 0};
+            ev::Strata sv = {0, 0, 0, 0};
+            if (Front::rec(A, li, &R)) {
+                ev::Prev pv;
+                const bool have_prev = A.opt.m && li;
+                if (have_prev) pv = Front::prev(A, li);
+                o = ev::eval_rec_bd(R, have_prev ? &pv : nullptr, A.opt, A.tg, &sv);
+            }
+            bool incorrect = false;
+            if (o.code) {
+                atomicMin((unsigned long long *)&A.res->err, (unsigned long long)(((uint64_t)r << 8) | (uint32_t)o.code));
+            } else if (!o.skipped) {
+                n_local += (uint32_t)o.n_inc;
+                if (o.cls >= 0) {
+                    incorrect = o.cls == ev::MI || o.cls == ev::UM;
+                    const uint32_t s_snps = ev::capped(sv.snps, B.cap), s_errors = ev::capped(sv.errors, B.cap), s_indels = sv.indels ? 1 : 0, s_end = sv.end ? 1 : 0;
+                    const int64_t d = (int64_t)o.score - B.win_lo;
+                    if ((d >= 0 && d < (int64_t)B.win) || o.score == A.floor_score) {
+                        const uint32_t bin = (d >= 0 && d < (int64_t)B.win) ? (uint32_t)d : B.win, cls = (uint32_t)o.cls;
+                        if (B.row_snps >= 0) bd_count(h, (uint32_t)B.row_snps + s_snps, cls, bins, bin);
+                        if (B.row_errors >= 0) bd_count(h, (uint32_t)B.row_errors + s_errors, cls, bins, bin);
+                        if (B.row_indels >= 0) bd_count(h, (uint32_t)B.row_indels + s_indels, cls, bins, bin);
+                        if (B.row_end >= 0) bd_count(h, (uint32_t)B.row_end + s_end, cls, bins, bin);
+                    } else {
+                        const uint32_t k = atomicAdd(&A.res->n_spill, 1u);
+                        A.spill[k] = ev::bd_spill_pack(o.score, o.cls, s_snps, s_errors, s_indels, s_end);
+                    }
+                }
+            }
+            if (A.flags) A.flags[r] = incorrect ? 1 : 0;
+        }
+        if (++turns == BD_FLUSH_ITERS) {
+            turns = 0;
+            __syncthreads();
+            bd_merge(h, n_words, B.hist);
+            __syncthreads();
+        }
+    }
+    if (n_local) atomicAdd((unsigned long long *)&A.res->n, (unsigned long long)n_local);
+    __syncthreads();
+    bd_merge(h, n_words, B.hist);
+}
+
+__global__ __launch_bounds__(BD_THREADS) void k_eval_records_bd(EvalRecArgs A, EvalBdArgs B)
+{
+    __shared__ uint32_t hb[EVAL_BD_CTRS / 2];
+    eval_records_bd_body<SamFront>(A, B, hb);
+}
+
+__global__ __launch_bounds__(BD_THREADS) void k_eval_bam_records_bd(EvalRecArgs A, EvalBdArgs B)
+{
+    __shared__ uint32_t hb[EVAL_BD_CTRS / 2];
+    eval_records_bd_body<BamFront>(A, B, hb);
+}
+
 void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tile_count, uint32_t grid_records)
 {
     const uint32_t tiles = (uint32_t)((len + EV_TILE - 1) / EV_TILE);
@@ -205,6 +304,22 @@ void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint3
 void launch_eval_bam_chunk(hipStream_t st, const EvalRecArgs &A, uint32_t grid_records)
 {
     hipLaunchKernelGGL(k_eval_bam_records, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A);
+}
+
+void launch_eval_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint64_t len, uint32_t *tile_count, uint32_t grid_records)
+{
+    const uint32_t tiles = (uint32_t)((len + EV_TILE - 1) / EV_TILE);
+    if (tiles) {
+        hipLaunchKernelGGL(k_eval_count, dim3(tiles), dim3(EV_THREADS), 0, st, A.text, len, tile_count);
+        hipLaunchKernelGGL(k_eval_scan, dim3(1), dim3(EV_THREADS), 0, st, tile_count, tiles, A.res);
+        hipLaunchKernelGGL(k_eval_lines, dim3(tiles), dim3(EV_THREADS), 0, st, A.text, len, (const uint32_t *)tile_count, A.ends);
+    }
+    hipLaunchKernelGGL(k_eval_records_bd, dim3(grid_records ? grid_records : 1), dim3(BD_THREADS), 0, st, A, B);
+}
+
+void launch_eval_bam_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint32_t grid_records)
+{
+    hipLaunchKernelGGL(k_eval_bam_records_bd, dim3(grid_records ? grid_records : 1), dim3(BD_THREADS), 0, st, A, B);
 }
 
 } // namespace dw

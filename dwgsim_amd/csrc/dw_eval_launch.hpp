@@ -31,7 +31,26 @@ struct EvalRecArgs {
     ev::Targets tg;
 };
 
+// The breakdown form (dw_eval.hpp BREAKDOWN) counts every record once per selected dimension, in that dimension's stratum, instead of once in
+// A.hist.  Counter ((row_d + stratum) * 5 + class) * (win + 1) + bin: bin k < win = score win_lo + k, bin win = floor_score.  The host chooses win
+// so that all counters of the selected dimensions fit into the block's EVAL_BD_CTRS 16-bit LDS counters; the main table is the sum of the first
+// selected dimension's strata.  A score outside the window goes to A.spill as one ev::bd_spill_pack word.  A.hist and A.win_lo are not read.
+constexpr uint32_t EVAL_BD_CTRS = 32768;          // 16-bit counters per block: 64 KiB of LDS
+
+struct EvalBdArgs {
+    unsigned long long *hist;   // n_rows * 5 * (win + 1) counters, rounded up to an even number
+    uint32_t n_rows;            // strata of all selected dimensions
+    uint32_t win;
+    int32_t win_lo;
+    int32_t cap;
+    int32_t row_snps, row_errors, row_indels, row_end;      // the first row of each dimension, -1: not selected
+};
+
 void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tile_count, uint32_t grid_records);
 void launch_eval_bam_chunk(hipStream_t st, const EvalRecArgs &A, uint32_t grid_records);
+// the breakdown forms; their blocks have EVAL_BD_THREADS lanes
+constexpr uint32_t EVAL_BD_THREADS = 512;
+void launch_eval_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint64_t len, uint32_t *tile_count, uint32_t grid_records);
+void launch_eval_bam_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint32_t grid_records);
 
 } // namespace dw

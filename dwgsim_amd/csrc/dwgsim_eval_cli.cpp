@@ -1,6 +1,7 @@
 // dwgsim_eval-hip -- the dwgsim_eval command line (reference src/dwgsim_eval.c main / run) over the dwgsim_hip_eval_* C-ABI.
 // Input is BAM unless -S is given, as for the reference.  Without -S the first two bytes of every input are read before a device is opened:
 // when one of them is not gzip's 1f 8b the input is text, and the message that asks for -S is printed.
+// -B LIST and -K INT are this program's own (both letters are free in the reference's option string): the breakdown's sections follow the table.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,6 +43,8 @@ static int print_usage(const dwgsim_hip_eval_opts_t *a)
     fprintf(f, "\t-e\tINT\tconsider only alignments with the number of specified errors [%d]\n", a->e);
     fprintf(f, "\t-i\t\tconsider only alignments with indels [%s]\n", tf(a->i));
     fprintf(f, "\t-P\tSTRING\ta read prefix that was prepended to each read name [%s]\n", a->P ? a->P : "not using");
+    fprintf(f, "\t-B\tLIST\talso print the table of every stratum of these dimensions, comma separated: snps,errors,indels,end [%s]\n", "not using");
+    fprintf(f, "\t-K\tINT\twith -B: snps and errors have the strata 0 ... INT-1 and INT+ (1 to 32; 0: the default) [%d]\n", 8);
     fprintf(f, "\t-h\t\tprint this help message\n");
     return 1;
 }
@@ -102,12 +105,15 @@ int main(int argc, char *argv[])
     dwgsim_hip_eval_opts_default(&o);
     int S = 0;
     std::string P;
+    const char *B = nullptr;      // -B, -K: the breakdown (dwgsim_hip_eval_set_breakdown)
+    int K = 0;
+    bool have_K = false;
     const char *chunk = getenv("DWGSIM_EVAL_CHUNK");      // text bytes per device chunk (tests use small ones)
     if (chunk) o.chunk_bytes = strtoull(chunk, nullptr, 10);
     const char *threads = getenv("DWGSIM_EVAL_THREADS");  // host threads that inflate BAM input
     if (threads) o.inflate_threads = atoi(threads);
     int c;
-    while ((c = getopt(argc, argv, "a:d:e:g:m:n:q:s:bchimpzSP:")) >= 0) {
+    while ((c = getopt(argc, argv, "a:d:e:g:m:n:q:s:bchimpzSP:B:K:")) >= 0) {
         switch (c) {
         case 'a': o.a = atoi(optarg); break;
         case 'b': o.b = 1; break;
@@ -125,10 +131,25 @@ int main(int argc, char *argv[])
         case 'e': o.e = atoi(optarg); break;
         case 'i': o.i = 1; break;
         case 'P': P = optarg; o.P = P.c_str(); break;
+        case 'B': B = optarg; break;
+        case 'K': {
+            char *end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < 0 || v > 32) {
+                fprintf(stderr, "dwgsim_eval-hip: -K must be a number from 0 (the default of 8) to 32\n");
+                return 1;
+            }
+            K = (int)v; have_K = true;
+            break;
+        }
         default: fprintf(stderr, "Unrecognized option: -%c\n", c); return 1;
         }
     }
     if (argc == optind) return print_usage(&o);
+    if (have_K && !B) {
+        fprintf(stderr, "dwgsim_eval-hip: -K has a meaning only with -B\n");
+        return 1;
+    }
     // BAM: every input is opened and its first two bytes are kept
     std::vector<FILE *> files;
     std::vector<std::string> leads;
@@ -160,6 +181,11 @@ int main(int argc, char *argv[])
     dwgsim_hip_eval_ctx_t *ctx = dwgsim_hip_eval_create(&o, 0, &err);
     if (!ctx) {
         fprintf(stderr, "dwgsim_eval-hip: cannot start the evaluator on device 0 (error %d)\n", err);
+        return 1;
+    }
+    if (B && dwgsim_hip_eval_set_breakdown(ctx, B, K) != DWGSIM_HIP_OK) {
+        fprintf(stderr, "dwgsim_eval-hip: -B / -K: %s\n", dwgsim_hip_eval_last_error(ctx));
+        dwgsim_hip_eval_destroy(ctx);
         return 1;
     }
     fputs("Analyzing...\nCurrently on:\n0", stderr);
@@ -205,6 +231,7 @@ int main(int argc, char *argv[])
         size_t n;
         if (o.p && dwgsim_hip_eval_incorrect_text(ctx, &t, &n) == DWGSIM_HIP_OK) fwrite(t, 1, n, stdout);
         if (dwgsim_hip_eval_table_text(ctx, &t, &n) == DWGSIM_HIP_OK) fwrite(t, 1, n, stdout);
+        if (B && dwgsim_hip_eval_breakdown_text(ctx, &t, &n) == DWGSIM_HIP_OK) fwrite(t, 1, n, stdout);
         fflush(stdout);
     }
     fwrite(sm.stderr_text + skip, 1, sm.stderr_len - skip, stderr);

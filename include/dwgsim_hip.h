@@ -394,11 +394,21 @@ int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *ctx, dwgsim_hip_eval_summary_t
 int dwgsim_hip_eval_table_text(dwgsim_hip_eval_ctx_t *ctx, const char **txt, size_t *len);
 /* with -p: the first file's header and the incorrectly mapped records, verbatim, in input order */
 int dwgsim_hip_eval_incorrect_text(dwgsim_hip_eval_ctx_t *ctx, const char **txt, size_t *len);
+/* Breakdown: the table of every stratum of the chosen dimensions, computed in the same pass as the main table (off by default).
+ * dims: a comma list of snps (n_sub_1, as -s), errors (n_err_1, as -e), indels (the record's own end, as -i), end (first / second end); NULL or
+ * empty: off.  cap: snps and errors have the strata 0 ... cap-1 and cap+ (everything else, negative values too); 0: 8, at most 32.  A record that
+ * enters the main table is counted in one stratum of every dimension, so "snps=k" is the table of a run with -s k.  To be called after create and
+ * before the first header / bam_begin / feed: DWGSIM_HIP_ERR_STATE later; DWGSIM_HIP_ERR_ARG for an unknown or repeated name or a cap outside 0 ... 32. */
+int dwgsim_hip_eval_set_breakdown(dwgsim_hip_eval_ctx_t *ctx, const char *dims, int cap);
+/* after finish: empty when the breakdown is off or the run ended in a fatal record, else one section per stratum -- the line "## snps=0\n"
+ * ("## snps=8+", "## errors=3", "## indels=0", "## indels=1+", "## end=1", "## end=2") and that stratum's table as in table_text -- in the order
+ * snps, errors, indels, end, strata ascending, empty strata included (the one-row-of-zeros table) */
+int dwgsim_hip_eval_breakdown_text(dwgsim_hip_eval_ctx_t *ctx, const char **txt, size_t *len);
 const char *dwgsim_hip_eval_last_error(const dwgsim_hip_eval_ctx_t *ctx);
 void dwgsim_hip_eval_destroy(dwgsim_hip_eval_ctx_t *ctx);
 /* test hooks: the device time (ms, HIP events) of the chunks so far; and kernel-only throughput: `len` bytes of record lines (host memory)
  * are uploaded once and then evaluated `reps` times as one chunk from device memory, *ms = time per evaluation.  The run's counts are untouched
- * except for the histogram, which this adds to. */
+ * except for the histogram, which this adds to.  With a breakdown set, both device_chunk hooks run the breakdown form of the record kernel. */
 int dwgsim_hip_eval_debug_time(dwgsim_hip_eval_ctx_t *ctx, double *kernel_ms);
 int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *ctx, const void *text, size_t len, int reps, double *ms);
 /* the same for a BAM chunk: `len` bytes of whole BAM records (uncompressed, no header; the targets are those of the context's current BAM

@@ -6,7 +6,10 @@ With --bam the same records are also measured as a BAM file (level 6, 64 KiB BGZ
   bam_kernel   the uncompressed records in device memory, k_eval_bam_records alone (dwgsim_hip_eval_debug_device_bam_chunk)
   bam_inflate  the BGZF blocks inflated on 1, 4, 8 and 16 host threads, no device involved (dwgsim_hip_eval_debug_inflate)
   bam_e2e      the BAM bytes fed through dwgsim_hip_eval_feed_bam at 1, 4, 8 and 16 inflate threads: GB/s of uncompressed BAM, records/s
-Prints one JSON line.  Usage: python tools/eval_throughput.py [--mib 1024] [--reps 5] [--model-mib 16] [--bam]"""
+With --breakdown every kernel and e2e figure is measured again in the same run with a breakdown set (dwgsim_hip_eval_set_breakdown): all four
+dimensions at the default cap (keys bd_*, and bd_*_ratio = breakdown / plain time) and, for the kernels, at cap 32 (keys bd32_*).
+--bam-threads LIST (default 1,4,8,16) chooses the inflate thread counts of bam_inflate and bam_e2e.
+Prints one JSON line.  Usage: python tools/eval_throughput.py [--mib 1024] [--reps 5] [--model-mib 16] [--a 3] [--bam] [--bam-threads 8] [--breakdown]"""
 import argparse, ctypes as C, json, os, random, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +26,8 @@ def main():
     ap.add_argument("--model-mib", type=int, default=16)
     ap.add_argument("--a", type=int, default=3)
     ap.add_argument("--bam", action="store_true")
+    ap.add_argument("--breakdown", action="store_true")
+    ap.add_argument("--bam-threads", default="1,4,8,16")
     args = ap.parse_args()
     contigs = [("chr%d" % i, 200_000_000) for i in range(1, 23)]
     rng = random.Random(5)
@@ -35,35 +40,40 @@ def main():
     out = {"bytes": n_bytes, "records": n_recs, "a": args.a}
 
     lib = api.load()
-    with api.EvalContext(a=args.a) as ctx:
-        ctx.header(head)
-        ms = C.c_double()
-        r = lib.dwgsim_hip_eval_debug_device_chunk(ctx.ctx, text, n_bytes, 1, C.byref(ms))      # warm-up
-        r = r or lib.dwgsim_hip_eval_debug_device_chunk(ctx.ctx, text, n_bytes, args.reps, C.byref(ms))
-        if r:
-            raise SystemExit("device chunk failed: %d" % r)
-        out["kernel_ms"] = ms.value
-        out["kernel_GBps"] = n_bytes / ms.value / 1e6
-        out["kernel_Mrec_s"] = n_recs / ms.value / 1e3
+    forms = FORMS if args.breakdown else FORMS[:1]
+    for pre, kw in forms:
+        with api.EvalContext(a=args.a, **kw) as ctx:
+            ctx.header(head)
+            ms = C.c_double()
+            r = lib.dwgsim_hip_eval_debug_device_chunk(ctx.ctx, text, n_bytes, 1, C.byref(ms))      # warm-up
+            r = r or lib.dwgsim_hip_eval_debug_device_chunk(ctx.ctx, text, n_bytes, args.reps, C.byref(ms))
+            if r:
+                raise SystemExit("device chunk failed: %d" % r)
+            out[pre + "kernel_ms"] = ms.value
+            out[pre + "kernel_GBps"] = n_bytes / ms.value / 1e6
+            out[pre + "kernel_Mrec_s"] = n_recs / ms.value / 1e3
+            if pre:
+                out[pre + "kernel_ratio"] = ms.value / out["kernel_ms"]
 
     pinned = lib.dwgsim_hip_host_alloc(n_bytes)
     if not pinned:
         raise SystemExit("host_alloc failed")
     C.memmove(pinned, text, n_bytes)
-    best = None
-    for _ in range(args.reps):
-        with api.EvalContext(a=args.a) as ctx:
-            ctx.header(head)
-            t0 = time.perf_counter()
-            lib.dwgsim_hip_eval_feed(ctx.ctx, C.c_void_p(pinned), n_bytes)
-            table, sm = ctx.finish()
-            dt = time.perf_counter() - t0
-        assert sm.status == 0 and sm.records == n_recs
-        best = dt if best is None else min(best, dt)
+    for pre, kw in forms[:2]:
+        best = None
+        for _ in range(args.reps):
+            with api.EvalContext(a=args.a, **kw) as ctx:
+                ctx.header(head)
+                t0 = time.perf_counter()
+                lib.dwgsim_hip_eval_feed(ctx.ctx, C.c_void_p(pinned), n_bytes)
+                table, sm = ctx.finish()
+                dt = time.perf_counter() - t0
+            assert sm.status == 0 and sm.records == n_recs
+            best = dt if best is None else min(best, dt)
+        out[pre + "e2e_s"] = best
+        out[pre + "e2e_GBps"] = n_bytes / best / 1e9
+        out[pre + "e2e_Mrec_s"] = n_recs / best / 1e6
     lib.dwgsim_hip_host_free(C.c_void_p(pinned))
-    out["e2e_s"] = best
-    out["e2e_GBps"] = n_bytes / best / 1e9
-    out["e2e_Mrec_s"] = n_recs / best / 1e6
 
     if args.bam:
         bam_throughput(lib, args, head, block, k, out)
@@ -77,6 +87,10 @@ def main():
     print(json.dumps(out))
 
 
+# key prefix and EvalContext arguments of the plain form, of the breakdown at the default cap, and of the breakdown at cap 32
+FORMS = [("", {}), ("bd_", {"breakdown": "snps,errors,indels,end"}), ("bd32_", {"breakdown": "snps,errors,indels,end", "breakdown_cap": 32})]
+
+
 def bam_throughput(lib, args, head, block, k, out):
     import bam_io as B
     payload, offs = B.bam_payload(head + block)
@@ -88,41 +102,46 @@ def bam_throughput(lib, args, head, block, k, out):
     raw = recs * k
     out.update({"bam_file_bytes": len(bam), "bam_record_bytes": len(raw), "bam_records": n_recs})
 
-    with api.EvalContext(a=args.a) as ctx:
-        ctx.bam_begin()
-        ctx.feed_bam(B.bgzf(hdr, eof=False))
-        ms = C.c_double()
-        r = lib.dwgsim_hip_eval_debug_device_bam_chunk(ctx.ctx, raw, len(raw), 1, C.byref(ms))      # warm-up
-        r = r or lib.dwgsim_hip_eval_debug_device_bam_chunk(ctx.ctx, raw, len(raw), args.reps, C.byref(ms))
-        if r:
-            raise SystemExit("device BAM chunk failed: %d" % r)
-        out["bam_kernel_ms"] = ms.value
-        out["bam_kernel_GBps"] = len(raw) / ms.value / 1e6
-        out["bam_kernel_Mrec_s"] = n_recs / ms.value / 1e3
+    forms = FORMS if args.breakdown else FORMS[:1]
+    for pre, kw in forms:
+        with api.EvalContext(a=args.a, **kw) as ctx:
+            ctx.bam_begin()
+            ctx.feed_bam(B.bgzf(hdr, eof=False))
+            ms = C.c_double()
+            r = lib.dwgsim_hip_eval_debug_device_bam_chunk(ctx.ctx, raw, len(raw), 1, C.byref(ms))      # warm-up
+            r = r or lib.dwgsim_hip_eval_debug_device_bam_chunk(ctx.ctx, raw, len(raw), args.reps, C.byref(ms))
+            if r:
+                raise SystemExit("device BAM chunk failed: %d" % r)
+            out[pre + "bam_kernel_ms"] = ms.value
+            out[pre + "bam_kernel_GBps"] = len(raw) / ms.value / 1e6
+            out[pre + "bam_kernel_Mrec_s"] = n_recs / ms.value / 1e3
+            if pre:
+                out[pre + "bam_kernel_ratio"] = ms.value / out["bam_kernel_ms"]
 
     pinned = lib.dwgsim_hip_host_alloc(len(bam))
     if not pinned:
         raise SystemExit("host_alloc failed")
     C.memmove(pinned, bam, len(bam))
-    for t in (1, 4, 8, 16):
+    for t in [int(x) for x in args.bam_threads.split(",")]:
         ms, nb = C.c_double(), C.c_uint64()
         if lib.dwgsim_hip_eval_debug_inflate(C.c_void_p(pinned), len(bam), t, args.reps, C.byref(ms), C.byref(nb)):
             raise SystemExit("inflate failed")
         out["bam_inflate_GBps_t%d" % t] = nb.value / ms.value / 1e6
-        best = None
-        for _ in range(args.reps):
-            with api.EvalContext(a=args.a, inflate_threads=t) as ctx:
-                ctx.bam_begin()
-                t0 = time.perf_counter()
-                step = 8 << 20
-                for i in range(0, len(bam), step):
-                    lib.dwgsim_hip_eval_feed_bam(ctx.ctx, C.c_void_p(pinned + i), min(step, len(bam) - i))
-                table, sm = ctx.finish()
-                dt = time.perf_counter() - t0
-            assert sm.status == 0 and sm.records == n_recs, (sm.status, sm.records, n_recs)
-            best = dt if best is None else min(best, dt)
-        out["bam_e2e_GBps_t%d" % t] = (len(raw) + len(hdr)) / best / 1e9
-        out["bam_e2e_Mrec_s_t%d" % t] = n_recs / best / 1e6
+        for pre, kw in forms[:2]:
+            best = None
+            for _ in range(args.reps):
+                with api.EvalContext(a=args.a, inflate_threads=t, **kw) as ctx:
+                    ctx.bam_begin()
+                    t0 = time.perf_counter()
+                    step = 8 << 20
+                    for i in range(0, len(bam), step):
+                        lib.dwgsim_hip_eval_feed_bam(ctx.ctx, C.c_void_p(pinned + i), min(step, len(bam) - i))
+                    table, sm = ctx.finish()
+                    dt = time.perf_counter() - t0
+                assert sm.status == 0 and sm.records == n_recs, (sm.status, sm.records, n_recs)
+                best = dt if best is None else min(best, dt)
+            out[pre + "bam_e2e_GBps_t%d" % t] = (len(raw) + len(hdr)) / best / 1e9
+            out[pre + "bam_e2e_Mrec_s_t%d" % t] = n_recs / best / 1e6
     lib.dwgsim_hip_host_free(C.c_void_p(pinned))
 
 
