@@ -283,6 +283,7 @@ def check_gpu_gzip(lib, fasta, flags, sizes):
     exactly the text of that stream (the property the reference's own test checks of its .gz files, testdata/test.sh:21-26); switching it
     off again leaves the text path untouched.  `sizes`: pairs per call (1 pair: one short member; many pairs: several 32 KiB members)."""
     import gzip, zlib
+    from gzip_stream import read_member, huffman, literal_histogram
     contigs = api.read_fasta(fasta)
     params = api.parse_flags(flags, lib)
     name, arr = contigs[0]
@@ -305,9 +306,10 @@ def check_gpu_gzip(lib, fasta, flags, sizes):
                     continue
                 assert gzip.decompress(gz) == txt, (n, s)
                 # member by member: each is a complete gzip file of at most 32 KiB of text (a multiple of 4 bytes long)
-                off, n_members, total, view = 0, 0, 0, memoryview(gz)
+                off, n_members, total, view, starts = 0, 0, 0, memoryview(gz), []
                 while off < len(gz):
                     d = zlib.decompressobj(31)
+                    starts.append(off)
                     chunk = bytes(view[off:off + 40000])          # (a member is < 40 000 bytes)
                     part = d.decompress(chunk)
                     used = len(chunk) - len(d.unused_data)
@@ -315,6 +317,13 @@ def check_gpu_gzip(lib, fasta, flags, sizes):
                     total += len(part); n_members += 1; off += used
                 assert total == len(txt) and n_members == (len(txt) + 32767) // 32768
                 assert len(gz) < 0.6 * len(txt) + 300 * n_members
+                # the matches earn their place: a full member's codes take fewer bits than ANY literal-only block of its text could (the unlimited
+                # Huffman cost of its bytes is a lower bound of those, so strictly and with no margin; tests/gzip_stream.py, which checks the whole
+                # stream).  The first three full members and the last one of every stream: the reader is Python.
+                full = len(txt) // 32768
+                for j in sorted(set(range(min(full, 3))) | ({full - 1} if full else set())):
+                    chunk, blk = txt[j * 32768:(j + 1) * 32768], read_member(gz, starts[j])["blocks"][0]
+                    assert blk["type"] == 2 and blk["data_bits"] < huffman(literal_histogram(chunk))[0], (n, s, j)
         ctx.set_gzip(False)
         b = ctx.simulate(cid, 0, sizes[0], 0, 0)
         assert list(b.gz_bytes) == [0, 0, 0] and [ctx.fetch(0, s, b.bytes[s]) for s in range(3)] == keep
@@ -348,14 +357,15 @@ def check_record_writers(lib, oracle_bin, tmpdir, flags, name_len):
 
 def check_gzip_kernel_on_hard_inputs(lib, scale=0):
     """k_gzip on bytes the simulator never produces: one repeated byte, every byte value, random bytes (incompressible: the member must still
-    fit its image), a Fibonacci histogram (unlimited Huffman codes would be 20+ bits deep: the counts are halved until 15 suffice), sizes
-    around the 32 KiB member boundary.  gunzip(members) must give the input back."""
+    fit its image), Fibonacci counts shuffled (46 367 bytes in two members whose unlimited Huffman codes are 14 and 16 deep: one of them takes one
+    round of the depth limit; the inputs that really need it -- codes 16 to 20 deep, held against the package-merge optimum -- are the chains of
+    tests/gzip_stream.py), sizes around the 32 KiB member boundary.  gunzip(members) must give the input back."""
     import gzip, random
     rnd = random.Random(5)
     fib = [1, 1]
     while len(fib) < 22:
         fib.append(fib[-1] + fib[-2])
-    fib_bytes = b"".join(bytes([65 + k]) * f for k, f in enumerate(fib))        # 28 656 bytes, depth 21 without a limit
+    fib_bytes = b"".join(bytes([65 + k]) * f for k, f in enumerate(fib))        # 46 367 bytes
     fib_mixed = bytearray(fib_bytes); rnd.shuffle(fib_mixed)
     cases = [b"A", b"AB", b"\n" * 7, b"G" * 32769, bytes(range(256)) * 3, bytes(rnd.randrange(256) for _ in range(33000)), bytes(fib_mixed)]
     if scale:       # (the emulation needs seconds per member: the long cases run on the GPU only)
