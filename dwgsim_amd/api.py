@@ -45,6 +45,7 @@ class Range(C.Structure):
 MUT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t)
 READS_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int)
 MSG_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
+HAP_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)      # (ABI 6) dwgsim_hip_job_haplotype_fn: the next piece of a haplotype's FASTA
 READS_AT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int)      # (ABI 5) pieces with their offset, from several threads
 
 
@@ -84,6 +85,7 @@ EXPORTS = [
     "dwgsim_hip_eval_debug_time", "dwgsim_hip_eval_debug_device_chunk", "dwgsim_hip_eval_bam_begin", "dwgsim_hip_eval_feed_bam",
     "dwgsim_hip_eval_debug_device_bam_chunk", "dwgsim_hip_eval_debug_inflate",
     "dwgsim_hip_eval_set_breakdown", "dwgsim_hip_eval_breakdown_text",
+    "dwgsim_hip_haplotype_fasta", "dwgsim_hip_haplotype_layout", "dwgsim_hip_haplotype_fetch", "dwgsim_hip_job_set_haplotype_sink",
 ]
 
 _lib = None
@@ -170,6 +172,10 @@ def load(path: str | None = None):
     lib.dwgsim_hip_debug_gzip.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, P(C.c_size_t)]
     lib.dwgsim_hip_set_gzip.argtypes = [C.c_void_p, C.c_int]
     lib.dwgsim_hip_fetch_gz_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    lib.dwgsim_hip_haplotype_fasta.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_uint64)]
+    lib.dwgsim_hip_haplotype_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_uint64), P(C.c_uint64), P(C.c_int64)]
+    lib.dwgsim_hip_haplotype_fetch.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
+    lib.dwgsim_hip_job_set_haplotype_sink.argtypes = [C.c_void_p, HAP_CB, C.c_void_p, C.c_int]
     if hasattr(lib, "dwgsim_hip_eval_create"):
         _bind_eval(lib)
     if path is None:
@@ -292,6 +298,7 @@ class JobResult:
     sim_kernel_ms: float = 0.0
     walk_ms: float = 0.0
     flow_cap_mult: int = 1                           # Ion Torrent: by how much the read capacity had grown at the end of the job (run_job)
+    haplotypes: dict = field(default_factory=dict)   # haplotypes=True: {0: bytes, 1: bytes}, the two mutated haplotypes as FASTA
 
 
 VCF_HEADER_POST = (
@@ -426,6 +433,20 @@ class Context:
         finally:
             self.lib.dwgsim_hip_mutlist_free(L)
 
+    def haplotype_fasta(self, cid: int, hap: int, width: int = 60) -> bytes:
+        """The FASTA text of haplotype `hap` (0 or 1) of the whole group cid belongs to: one record per contig, lines of `width` bases (0: one line)."""
+        n = C.c_uint64(0)
+        self._chk(self.lib.dwgsim_hip_haplotype_fasta(self.h, cid, hap, width, C.byref(n)))
+        buf = C.create_string_buffer(n.value if n.value else 1)
+        self._chk(self.lib.dwgsim_hip_haplotype_fetch(self.h, hap, 0, buf, n.value))
+        return buf.raw[:n.value]
+
+    def haplotype_layout(self, cid: int, hap: int):
+        """(offset, bytes, bases): where the contig's record lies in its group's text (after haplotype_fasta), and the haplotype's length"""
+        off, n, b = C.c_uint64(0), C.c_uint64(0), C.c_int64(0)
+        self._chk(self.lib.dwgsim_hip_haplotype_layout(self.h, cid, hap, C.byref(off), C.byref(n), C.byref(b)))
+        return off.value, n.value, b.value
+
     def count_random(self, cid: int, first_ii: int, n_pairs: int) -> int:
         n = C.c_uint64(0)
         self._chk(self.lib.dwgsim_hip_count_random(self.h, cid, first_ii, n_pairs, C.byref(n)))
@@ -557,7 +578,8 @@ def split_ranges(ranges, batch_pairs):
         yield batch
 
 
-def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22, fetch: bool = True, lib=None, debug_options=None, group_bp: int = 0, check_list_form: bool = False) -> JobResult:
+def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22, fetch: bool = True, lib=None, debug_options=None, group_bp: int = 0, check_list_form: bool = False,
+            haplotypes: bool = False, hap_width: int = 60) -> JobResult:
     """dwgsim_core (dwgsim.c:419-1121) over the C-ABI: header pass, then schedule -> mutate -> mutations text -> simulate in
     read-index batches.  group_bp = 0: contig after contig, as the reference walks them.  group_bp > 0: consecutive contigs are resident
     together in groups of up to group_bp bases (dwgsim_hip_add_contigs): one walk per group, batches that run across contig boundaries."""
@@ -567,6 +589,7 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
     want_reads = params.output_type != 2
     vcf = bytearray()
     txt = bytearray()
+    haps = {0: bytearray(), 1: bytearray()}
     if want_mut:
         vcf += b"##fileformat=VCFv4.1\n"
         for name, arr in contigs:
@@ -604,6 +627,9 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
                     if b"".join(a for a, _ in tv) != b"".join(ctx.mutations_text(h0 + k)[0] for k in range(len(grp))) or \
                        b"".join(b for _, b in tv) != b"".join(ctx.mutations_text(h0 + k)[1] for k in range(len(grp))):
                         raise DwgsimError("mutations_take / mutlist_text differs from mutations_text")
+            if haplotypes:
+                for hap in (0, 1):
+                    haps[hap] += ctx.haplotype_fasta(h0, hap, hap_width)
             ranges = [(h0 + k, 0, ent[3]) for k, ent in enumerate(grp) if want_reads and ent[3] > 0]
             for batch in split_ranges(ranges, batch_pairs):
                 b = ctx.simulate_ranges(batch, rand_ii, 0)
@@ -623,11 +649,13 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
     res.mutations_txt = bytes(txt)
     res.mutations_vcf = bytes(vcf)
     res.streams = {k: bytes(v) for k, v in res.streams.items()}
+    if haplotypes:
+        res.haplotypes = {k: bytes(v) for k, v in haps.items()}
     return res
 
 
 def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True, batch_pairs: int = 0, group_bp: int = 0, min_share: int = 0,
-                lib=None, keep_output: bool = True, offset_sink: bool = False) -> JobResult:
+                lib=None, keep_output: bool = True, offset_sink: bool = False, haplotypes: bool = False, hap_width: int = 60) -> JobResult:
     """The same job through the JOB level of the C-ABI (dwgsim_hip_job_*): the library schedules, groups, shards over `devices`
     (default: all) and delivers in file order; the sink below only collects.  Streams are returned as text (gzip members are
     decompressed here)."""
@@ -667,6 +695,13 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
             at_pieces[stream].append((offset, n, bool(gz), blob, text_n))
         return 0
 
+    hap_pieces = []      # (hap, bytes) in the order of the calls
+
+    def on_hap(user, hap, data, n):
+        hap_pieces.append((hap, C.string_at(data, n) if n else b""))
+        return 0
+
+    hap_cb = HAP_CB(on_hap)
     sink = JobSink(None, MUT_CB(on_mut), READS_CB(on_reads), MSG_CB(lambda u, m: None), READS_AT_CB(on_reads_at) if offset_sink else READS_AT_CB())
     opt = JobOptions(1 if gzip_on_gpu else 0, 1, batch_pairs, group_bp, min_share)
     err = C.c_int(0)
@@ -682,6 +717,8 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
         names = (C.c_char_p * n)(*[nm.encode() for nm, _ in contigs])
         lens = (C.c_int64 * n)(*[len(a) for _, a in contigs])
         chk(lib.dwgsim_hip_job_set_contig_table(job, names, lens, n))
+        if haplotypes:
+            chk(lib.dwgsim_hip_job_set_haplotype_sink(job, hap_cb, None, hap_width))
         if getattr(params, "_regions", None):
             chk(lib.dwgsim_hip_job_set_regions(job, params._regions.encode()))
         if getattr(params, "_mut_input", None):
@@ -714,6 +751,9 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
     res.mutations_txt, res.mutations_vcf = bytes(txt), bytes(vcf)
     res.streams = {k: bytes(v) for k, v in res.streams.items()}
     res.delivered_text_bytes = dict(order["text_n"])
+    if haplotypes:
+        res.haplotypes = {h: b"".join(p for q, p in hap_pieces if q == h) for h in (0, 1)}
+        res.haplotype_pieces = [(q, len(p)) for q, p in hap_pieces]
     return res
 
 

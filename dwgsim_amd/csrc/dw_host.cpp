@@ -64,6 +64,7 @@ struct GroupMem {
     // the bitmap (uint32) of 64-cell chunks the last walk may have written
     DevMem d_refview, d_refsumm, d_refsumm2, d_dirty;
     DevEvent ev_walk, ev_walk0;      // end / start of the walk chain on the walk stream
+    DevMem d_hap_text[2], d_hap_rec, d_hap_pool;      // dwgsim_hip_haplotype_fasta (empty until it is called): each haplotype's FASTA text; the records and header lines of the text made last
     HostMem h_wc;                    // page-locked mirror (a WalkCounters) of the walk's counters (the context's d_wcounters) at the end of THIS group's walk: several groups' walks can be in flight
 };
 
@@ -103,6 +104,8 @@ struct Group {
     uint32_t n_patch = 0, n_patch_ev = 0;       // file-driven mutations: patched cells / indel events
     // the mutated cells of the finished walk, fetched once for mutations_text
     bool list_valid = false; std::vector<int32_t> pos; std::vector<uint32_t> cells; HostIns ins[2];
+    // the FASTA text of each finished haplotype (mem.d_hap_text), made on request: its width and size, and per contig where the record lies and its bases
+    struct HapText { bool valid = false; int width = 0; uint64_t bytes = 0; std::vector<uint64_t> off, len; std::vector<int64_t> bases; } hap_text[2];
 };
 
 struct HandleRef { int group = -1, k = 0; };
@@ -181,6 +184,9 @@ struct dwgsim_hip_ctx {
     hipEvent_t ev_cnt0 = nullptr, ev_cnt1 = nullptr;
     bool gzip_on = false; DevMem d_crc_table, d_crc_shift;      // dwgsim_hip_set_gzip (u32; d_crc_shift is uploaded last)
     HostMem h_stage;                       // pinned staging for fetch
+    hipStream_t hap_stream = nullptr;      // dwgsim_hip_haplotype_fetch: copies of its own (made at the first call), not behind the batches' copy-outs
+    DevEvent hap_ev[6]; double hap_len_us = 0, hap_write_us = 0, hap_copy_us = 0; bool hap_yardstick = false;      // "hap_len_us" / "hap_write_us" / "hap_copy_us", "hap_yardstick" (dwgsim_hip_debug_get / _option)
+    int hap_cur[2] = {-1, -1};             // ... and the group whose text the last dwgsim_hip_haplotype_fasta call for that haplotype built or found
     std::string txt, vcf;
 };
 
@@ -734,6 +740,7 @@ void dwgsim_hip_destroy(dwgsim_hip_ctx_t *c)
     if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
     if (c->walk_stream) hipStreamSynchronize(c->walk_stream);
     if (c->count_stream) hipStreamSynchronize(c->count_stream);
+    if (c->hap_stream) { hipStreamSynchronize(c->hap_stream); hipStreamDestroy(c->hap_stream); }
     if (c->ev_up) hipEventDestroy(c->ev_up);
     if (c->ev_cnt0) hipEventDestroy(c->ev_cnt0);
     if (c->ev_cnt1) hipEventDestroy(c->ev_cnt1);
@@ -935,6 +942,7 @@ int dwgsim_hip_drop_contig(dwgsim_hip_ctx_t *c, int contig)
     for (int s = 0; s < DWGSIM_HIP_SLOTS; ++s) if (c->slot[s].pending && !c->slot[s].empty && c->slot[s].group == gid) { c->err = "drop_contig: a batch that reads this group has not been waited for (dwgsim_hip_wait first)"; return DWGSIM_HIP_ERR_STATE; }
     if (g->walk_pending) hipEventSynchronize(g->mem.ev_walk.get());
     for (size_t k = 0; k < g->m.size(); ++k) { if (c->chain_contig == g->first_handle + (int)k) c->chain_contig = -1; c->handles[(size_t)g->first_handle + k].group = -1; }
+    for (int h = 0; h < 2; ++h) if (c->hap_cur[h] == gid) c->hap_cur[h] = -1;
     // the group's memory waits for the next group (at most three sets are kept: the one that has waited longest goes -- a set that no later
     // group can use, e.g. one more than four times too large, does not stay for the life of the context; round 5 dropped the smallest)
     c->pool.push_back(std::move(g->mem));
@@ -1250,6 +1258,7 @@ int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
     g.walk_reset = g.mutated;      // walked before: the cells start again from the resident packed reference
     for (int h = 0; h < 2; ++h) g.n_ins[h] = g.n_ins_bases[h] = 0;
     g.mutated = true; g.n_cand = 0; g.list_valid = false;
+    for (int h = 0; h < 2; ++h) g.hap_text[h].valid = false;
     g.walk_attempt = 0;
     if (g.total == 0) return DWGSIM_HIP_OK;
     if (c->has_mutin) {
@@ -1520,6 +1529,134 @@ int dwgsim_hip_mutlist_text(dwgsim_hip_mutlist_t *L, int k, const char **txt, si
 }
 
 void dwgsim_hip_mutlist_free(dwgsim_hip_mutlist_t *L) { delete L; }
+
+// ---- the two finished haplotypes as FASTA text (dw_walk.hip k_hap_len / k_hap_headers / k_hap_write) ----
+// On the walk stream, behind the group's walk: emitted bases per block of cells, their scan, the records placed by the host from the prefix at every
+// contig's first block, then the text.  The call returns when the text is complete (what it enqueues is two passes over the cells).
+int dwgsim_hip_haplotype_fasta(dwgsim_hip_ctx_t *c, int contig, int hap, int width, uint64_t *bytes)
+{
+    Group *gp = get_group(c, contig);
+    if (!gp) return DWGSIM_HIP_ERR_ARG;
+    Group &g = *gp;
+    if (hap < 0 || hap > 1 || width < 0) { c->err = "haplotype_fasta: hap must be 0 or 1 and width >= 0"; return DWGSIM_HIP_ERR_ARG; }
+    if (!g.mutated || g.walk_pending) { c->err = "mutate_contig must run first"; return DWGSIM_HIP_ERR_STATE; }
+    const int gid = (int)(gp - c->groups.data());
+    Group::HapText &T = g.hap_text[hap];
+    if (!(T.valid && T.width == width)) {
+        HIPC(c, hipSetDevice(c->device));
+        T.valid = false;
+        // (the scan of the blocks is a 32-bit one: cells and inserted bases of a group stay below 2^32 together; the TEXT offsets are 64-bit)
+        if ((uint64_t)g.total + g.n_ins_bases[hap] > 0xFFFFFFFFull) { c->err = "haplotype_fasta: more than 2^32 bases in one group"; return DWGSIM_HIP_ERR_UNSUP; }
+        GroupMem &M = g.mem;
+        hipStream_t st = c->walk_stream;
+        const size_t n = g.m.size();
+        const uint32_t nblk = (uint32_t)((g.total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
+        if (ensure(c, c->scratch_cnt, ((size_t)nblk + 1) * sizeof(uint32_t))) return DWGSIM_HIP_ERR_DEVICE;
+        uint32_t *d_cnt = c->scratch_cnt.get<uint32_t>();
+        HapDev hd[2]; fill_haps(g, hd);
+        const SegTab seg = seg_tab(g);
+        std::vector<uint32_t> pre((size_t)nblk + 1, 0);      // emitted bases in front of every block, and (the last entry) of the group
+        for (DevEvent &e : c->hap_ev) HIPC(c, e.create());
+        if (nblk) {
+            HIPC(c, hipMemsetAsync(d_cnt + nblk, 0, sizeof(uint32_t), st));
+            HIPC(c, hipEventRecord(c->hap_ev[0].get(), st));
+            launch_hap_len(st, hd[hap], seg, g.total, d_cnt);
+            launch_scan_excl(st, d_cnt, nblk + 1, nullptr);
+            HIPC(c, hipEventRecord(c->hap_ev[1].get(), st));
+            HIPC(c, hipMemcpyAsync(pre.data(), d_cnt, ((size_t)nblk + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPC(c, hipStreamSynchronize(st));
+        }
+        std::vector<HapRec> rec(n); std::vector<uint8_t> pool;
+        T.off.assign(n, 0); T.len.assign(n, 0); T.bases.assign(n, 0);
+        uint64_t at = 0;
+        for (size_t k = 0; k < n; ++k) {
+            const Member &m = g.m[k];
+            const size_t b0 = (size_t)(m.start / SCAN_POS_PER_BLOCK), b1 = m.l > 0 ? (size_t)((m.start + m.l + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK) : b0;
+            HapRec &R = rec[k];
+            R.rec_off = at; R.hdr_off = (uint32_t)pool.size(); R.hdr_len = (uint32_t)m.name.size() + 2; R.base0 = pre[b0]; R.n_bases = pre[b1] - pre[b0]; R.pad_ = 0;
+            pool.push_back('>'); pool.insert(pool.end(), m.name.begin(), m.name.end()); pool.push_back('\n');
+            const uint64_t body = R.n_bases ? (uint64_t)R.n_bases + (width ? ((uint64_t)R.n_bases + (uint64_t)width - 1) / (uint64_t)width : 1u) : 0u;
+            T.off[k] = at; T.len[k] = R.hdr_len + body; T.bases[k] = R.n_bases;
+            at += T.len[k];
+        }
+        if (ensure(c, M.d_hap_text[hap], (size_t)at + 64) || ensure(c, M.d_hap_rec, sizeof(HapRec) * n) || ensure(c, M.d_hap_pool, pool.size())) return DWGSIM_HIP_ERR_DEVICE;
+        HIPC(c, hipMemcpyAsync(M.d_hap_rec.get(), rec.data(), sizeof(HapRec) * n, hipMemcpyHostToDevice, st));
+        HIPC(c, hipMemcpyAsync(M.d_hap_pool.get(), pool.data(), pool.size(), hipMemcpyHostToDevice, st));
+        HIPC(c, hipEventRecord(c->hap_ev[2].get(), st));
+        launch_hap_write(st, hd[hap], seg, g.total, d_cnt, M.d_hap_rec.get<HapRec>(), (uint32_t)n, M.d_hap_pool.get(), (uint32_t)width, M.d_hap_text[hap].get());
+        HIPC(c, hipEventRecord(c->hap_ev[3].get(), st));
+        HIPC(c, hipGetLastError());
+        DevMem yard;      // "hap_yardstick" (measurement only): a device-to-device copy of as many bytes as the text, behind it on the same stream (the second of two is timed)
+        if (c->hap_yardstick && at) {
+            HIPC(c, reserve(c, yard, (size_t)at, (size_t)at));
+            HIPC(c, hipMemcpyAsync(yard.get(), M.d_hap_text[hap].get(), (size_t)at, hipMemcpyDeviceToDevice, st));
+            HIPC(c, hipEventRecord(c->hap_ev[4].get(), st));
+            HIPC(c, hipMemcpyAsync(yard.get(), M.d_hap_text[hap].get(), (size_t)at, hipMemcpyDeviceToDevice, st));
+            HIPC(c, hipEventRecord(c->hap_ev[5].get(), st));
+        }
+        HIPC(c, hipStreamSynchronize(st));      // (the records and header lines go up from vectors of this call)
+        {   // (analysis: dwgsim_hip_debug_get "hap_len_us" / "hap_write_us" / "hap_copy_us", of the text built last)
+            float ms = 0;
+            c->hap_len_us = nblk && hipEventElapsedTime(&ms, c->hap_ev[0].get(), c->hap_ev[1].get()) == hipSuccess ? 1e3 * ms : 0;
+            c->hap_write_us = hipEventElapsedTime(&ms, c->hap_ev[2].get(), c->hap_ev[3].get()) == hipSuccess ? 1e3 * ms : 0;
+            c->hap_copy_us = yard && hipEventElapsedTime(&ms, c->hap_ev[4].get(), c->hap_ev[5].get()) == hipSuccess ? 1e3 * ms : 0;
+            (void)hipGetLastError();
+        }
+        T.width = width; T.bytes = at; T.valid = true;
+    }
+    c->hap_cur[hap] = gid;
+    if (bytes) *bytes = T.bytes;
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_haplotype_layout(dwgsim_hip_ctx_t *c, int contig, int hap, uint64_t *offset, uint64_t *bytes, int64_t *bases)
+{
+    int km = 0;
+    Group *gp = get_group(c, contig, &km);
+    if (!gp) return DWGSIM_HIP_ERR_ARG;
+    if (hap < 0 || hap > 1) { c->err = "haplotype_layout: hap must be 0 or 1"; return DWGSIM_HIP_ERR_ARG; }
+    const Group::HapText &T = gp->hap_text[hap];
+    if (!T.valid) { c->err = "haplotype_layout: dwgsim_hip_haplotype_fasta must run first"; return DWGSIM_HIP_ERR_STATE; }
+    if (offset) *offset = T.off[(size_t)km];
+    if (bytes) *bytes = T.len[(size_t)km];
+    if (bases) *bases = T.bases[(size_t)km];
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_haplotype_fetch(dwgsim_hip_ctx_t *c, int hap, uint64_t offset, void *host_dst, size_t n)
+{
+    if (!c) return DWGSIM_HIP_ERR_ARG;
+    if (hap < 0 || hap > 1 || (!host_dst && n)) { c->err = "bad haplotype_fetch arguments"; return DWGSIM_HIP_ERR_ARG; }
+    const int gid = c->hap_cur[hap];
+    if (gid < 0 || !c->groups[(size_t)gid].alive || !c->groups[(size_t)gid].hap_text[hap].valid) { c->err = "haplotype_fetch: dwgsim_hip_haplotype_fasta must run first"; return DWGSIM_HIP_ERR_STATE; }
+    const Group &g = c->groups[(size_t)gid];
+    const uint64_t total = g.hap_text[hap].bytes;
+    if (offset > total || (uint64_t)n > total - offset) { c->err = "haplotype_fetch: past the end of the text"; return DWGSIM_HIP_ERR_ARG; }
+    if (n == 0) return DWGSIM_HIP_OK;
+    HIPC(c, hipSetDevice(c->device));
+    if (!c->hap_stream) HIPC(c, hipStreamCreate(&c->hap_stream));
+    const uint8_t *src = g.mem.d_hap_text[hap].get<uint8_t>() + offset;
+    if (is_page_locked(host_dst)) {
+        HIPC(c, hipMemcpyAsync(host_dst, src, n, hipMemcpyDeviceToHost, c->hap_stream));
+        HIPC(c, hipStreamSynchronize(c->hap_stream));
+        return DWGSIM_HIP_OK;
+    }
+    // double-buffered page-locked staging, as dwgsim_hip_fetch: the copy of chunk k+1 overlaps the host copy of chunk k
+    const size_t CH = (size_t)16 << 20;
+    HIPC(c, c->h_stage.reserve(2 * CH, 2 * CH));
+    uint8_t *stage[2] = {c->h_stage.get<uint8_t>(), c->h_stage.get<uint8_t>() + CH};
+    size_t done = 0; int b = 0;
+    size_t cur = n < CH ? n : CH;
+    HIPC(c, hipMemcpyAsync(stage[0], src, cur, hipMemcpyDeviceToHost, c->hap_stream));
+    while (done < n) {
+        HIPC(c, hipStreamSynchronize(c->hap_stream));
+        const size_t next_off = done + cur, next = next_off < n ? ((n - next_off) < CH ? (n - next_off) : CH) : 0;
+        if (next) HIPC(c, hipMemcpyAsync(stage[b ^ 1], src + next_off, next, hipMemcpyDeviceToHost, c->hap_stream));
+        memcpy((uint8_t *)host_dst + done, stage[b], cur);
+        done += cur; cur = next; b ^= 1;
+    }
+    return DWGSIM_HIP_OK;
+}
 
 // ---- read simulation ----
 namespace {
@@ -2181,6 +2318,7 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *c, const char *key, int64_t value)
     else if (!strcmp(key, "flow_slots")) c->flow_slots = (int)value;
     else if (!strcmp(key, "ion_lds")) c->ion_lds = (int)value;
     else if (!strcmp(key, "flow_cap")) c->flow_cap_forced = (int)value;
+    else if (!strcmp(key, "hap_yardstick")) c->hap_yardstick = value != 0;      // dwgsim_hip_haplotype_fasta also times a device-to-device copy of the text's size ("hap_copy_us")
     else { c->err = "unknown debug option"; return DWGSIM_HIP_ERR_ARG; }
     return DWGSIM_HIP_OK;
 }
@@ -2201,6 +2339,9 @@ int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
     else if (!strcmp(key, "walk_us")) *value = (int64_t)c->walk_us;           // HIP-event time of the walk chains waited for so far (start of the chain to its end, on the walk stream)
     else if (!strcmp(key, "count_us")) *value = (int64_t)c->count_us;         // ... of the random-read counts (k_place .. k_range_counts)
     else if (!strcmp(key, "sim_form")) *value = c->sim_form;                  // k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> of the last launch, packed
+    else if (!strcmp(key, "hap_len_us")) *value = (int64_t)c->hap_len_us;     // the haplotype text built last: HIP-event time of its length pass + scan,
+    else if (!strcmp(key, "hap_write_us")) *value = (int64_t)c->hap_write_us; // ... of its header and write kernels,
+    else if (!strcmp(key, "hap_copy_us")) *value = (int64_t)c->hap_copy_us;   // ... and ("hap_yardstick") of a device-to-device copy of its size
     else if (!strcmp(key, "walk_form")) *value = c->walk_form;                // attempt, file-driven / random, site-scan form, restore, views of the last walk, packed
     else { c->err = "unknown debug value"; return DWGSIM_HIP_ERR_ARG; }
     return DWGSIM_HIP_OK;

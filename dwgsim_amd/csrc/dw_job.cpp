@@ -168,6 +168,7 @@ struct dwgsim_hip_job {
         uint64_t tot_len = 0;         // (start_threads: the regions' total once -x is in force)
         size_t stage_want = 0;        // room for the largest group, so that a staging buffer is page-locked once
         std::string regions_path, mutin_path; int mutin_type = -1;
+        dwgsim_hip_job_haplotype_fn hap_fn = nullptr; void *hap_user = nullptr; int hap_width = 60;      // dwgsim_hip_job_set_haplotype_sink
     } cfg;
 
     // CALLER: touched only by the thread that calls the job_ functions (the ABI allows one at a time).  The workers see the staging through
@@ -316,6 +317,16 @@ struct Worker {
     struct MutTask { MutList list; std::vector<std::string> names; };
     std::thread mut_thread; std::mutex mm; std::condition_variable mcv; std::deque<MutTask> mq; bool mut_quit = false;
 
+    // (device 0) the haplotype FASTA (dwgsim_hip_job_set_haplotype_sink): behind a group's walk the worker has both texts made on the device -- two passes
+    // over the cells on the walk stream -- and then copies them out piece by piece into a few page-locked buffers, BETWEEN the group's batches and only
+    // while a buffer is free (pump_haplotypes), so that a slow sink holds up no batch; a thread of its own hands the pieces to the sink in order.  Only
+    // before the group's memory goes back, or the next group's texts are made, does the worker wait for buffers.
+    static constexpr size_t HAP_PIECE = (size_t)32 << 20; static constexpr int HAP_BUFS = 3;
+    struct HapPiece { int hap; HostMem *buf; size_t len; };
+    std::thread hap_thread; std::mutex hm; std::condition_variable hcv; std::deque<HapPiece> hq; bool hap_quit = false;
+    std::vector<std::unique_ptr<HostMem>> hap_bufs; std::vector<HostMem *> hap_free;
+    struct HapState { bool active = false; int h = -1, hap = 0; uint64_t off = 0, bytes[2] = {0, 0}; } hs;      // the group whose texts are on their way out
+
     bool ok() const { return !j->failed.load(); }
     void fail_ctx() { job_fail(j, std::string("dwgsim-hip: ") + dwgsim_hip_last_error(x)); }
     bool mine(const GroupJob &g, int b) const { return b % g.nd == j->cfg.vrank(d); }
@@ -346,6 +357,61 @@ struct Worker {
         mcv.notify_all();
         mut_thread.join();
     }
+
+    void hap_loop()      // the pieces in the order the worker made them: each haplotype's file in order
+    {
+        for (;;) {
+            HapPiece t;
+            {
+                std::unique_lock<std::mutex> lk(hm);
+                hcv.wait(lk, [&]() { return hap_quit || !hq.empty(); });
+                if (hq.empty()) return;
+                t = hq.front(); hq.pop_front();
+            }
+            if (ok() && j->cfg.hap_fn(j->cfg.hap_user, t.hap, t.buf->p, t.len) != 0) job_fail(j, "dwgsim-hip: the sink refused the haplotype text");
+            { std::lock_guard<std::mutex> lk(hm); hap_free.push_back(t.buf); }
+            hcv.notify_all();
+        }
+    }
+    void hap_stop()
+    {
+        if (!hap_thread.joinable()) return;
+        { std::lock_guard<std::mutex> lk(hm); hap_quit = true; }
+        hcv.notify_all();
+        hap_thread.join();
+    }
+    // a page-locked buffer for the next piece; wait = false: nullptr when none is free
+    HostMem *hap_take_buf(bool wait)
+    {
+        std::unique_lock<std::mutex> lk(hm);
+        if (hap_free.empty() && (int)hap_bufs.size() < HAP_BUFS) { hap_bufs.push_back(std::make_unique<HostMem>()); hap_free.push_back(hap_bufs.back().get()); }
+        if (hap_free.empty() && wait) hcv.wait(lk, [&]() { return !hap_free.empty() || !ok(); });
+        if (hap_free.empty()) return nullptr;
+        HostMem *b = hap_free.back(); hap_free.pop_back();
+        return b;
+    }
+    // as many pieces of the current group's texts as there are free buffers (wait: all that is left of them); false: the job has failed
+    bool pump_haplotypes(bool wait)
+    {
+        while (hs.active) {
+            if (!ok()) return false;
+            if (hs.off >= hs.bytes[hs.hap]) { hs.off = 0; if (++hs.hap == 2) hs.active = false; continue; }
+            HostMem *b = hap_take_buf(wait);
+            if (!b) return ok() && !wait;
+            const uint64_t left = hs.bytes[hs.hap] - hs.off;
+            const size_t len = left < HAP_PIECE ? (size_t)left : HAP_PIECE;
+            bool fine = b->cap >= len || b->grow(len <= ((size_t)1 << 20) ? (size_t)1 << 20 : HAP_PIECE, 0);
+            if (!fine) job_fail(j, "dwgsim-hip: cannot allocate page-locked host memory for the haplotype text");
+            else if (dwgsim_hip_haplotype_fetch(x, hs.hap, hs.off, b->p, len) < 0) { fail_ctx(); fine = false; }
+            if (!fine) { std::lock_guard<std::mutex> lk(hm); hap_free.push_back(b); return false; }
+            { std::lock_guard<std::mutex> lk(hm); hq.push_back(HapPiece{hs.hap, b, len}); }
+            hcv.notify_all();
+            hs.off += len;
+        }
+        return true;
+    }
+    // the group's memory is about to go back: what is left of its texts goes out first
+    bool flush_haplotypes(int h) { return !(hs.active && hs.h == h) || pump_haplotypes(true); }
 
     int prep(const std::shared_ptr<GroupJob> &g)      // upload (asynchronous: the staging is page-locked and in group layout) and enqueue the walk
     {
@@ -440,6 +506,7 @@ struct Worker {
             if (j->cfg.sink.reads_at) { B.sized = true; assign_offsets(j); j->cv.notify_all(); }      // this batch's offsets, and those of any batch behind it that was only waiting for its sizes
         }
         if (pb.b < 2 * j->cfg.VD) trace(j, "dev %d group %d: batch %d kernels done, copy issued (%.1f MB)", d, pb.g->id, pb.b, j->cfg.has_sink() ? (n[0] + n[1] + n[2]) / 1e6 : 0.0);
+        if (pb.last_of_group && !flush_haplotypes(pb.h)) return false;
         if (pb.last_of_group && dwgsim_hip_drop_contig(x, pb.h) < 0) { fail_ctx(); return false; }      // (the kernels of the group's last batch are done: nothing reads it any more)
         return true;
     }
@@ -491,6 +558,7 @@ struct Worker {
     {
         pin_thread_to_device_node(j->cfg.devices[(size_t)d]);
         if (j->cfg.vrank(d) == 0 && j->cfg.want_mut && j->cfg.sink.mutations) mut_thread = std::thread([this]() { mut_loop(); });
+        if (j->cfg.vrank(d) == 0 && j->cfg.hap_fn) hap_thread = std::thread([this]() { hap_loop(); });
         bool fine = true;
         for (;;) {
             std::shared_ptr<GroupJob> g;
@@ -515,6 +583,7 @@ struct Worker {
         if (!fine || !ok()) abandon();
         if (ahead.g && !ahead.walked) (void)dwgsim_hip_mutate_wait(x, ahead.h);
         mut_stop();
+        hap_stop();
     }
 
     // ---- one group: process() and its steps ----
@@ -522,7 +591,7 @@ struct Worker {
     {
         if (!takes_part(*g)) return pass_by(*g);      // a small group is not worth a copy on every device
         Resident cur;
-        return adopt_or_prepare(g, cur) && hand_mutations_on(cur) && exchange_counts(cur) && run_batches(cur);
+        return adopt_or_prepare(g, cur) && hand_mutations_on(cur) && hand_haplotypes_on(cur) && exchange_counts(cur) && run_batches(cur);
     }
 
     bool pass_by(GroupJob &g)
@@ -562,6 +631,18 @@ struct Worker {
         return true;
     }
 
+    // (device 0) both haplotypes' FASTA text is made on the device now -- before the next group's walk is enqueued on the same stream -- and starts to go out
+    bool hand_haplotypes_on(const Resident &cur)
+    {
+        if (!hap_thread.joinable()) return true;
+        if (!pump_haplotypes(true)) return false;      // (what is left of the group in front, whose last batches may still be in flight: haplotype_fetch reads the text made last)
+        hs = HapState(); hs.h = cur.h;
+        for (int hap = 0; hap < 2; ++hap) if (dwgsim_hip_haplotype_fasta(x, cur.h, hap, j->cfg.hap_width, &hs.bytes[hap]) < 0) { fail_ctx(); return false; }
+        hs.active = true;
+        trace(j, "dev %d group %d: haplotype text made (%.1f MB)", d, cur.g->id, (hs.bytes[0] + hs.bytes[1]) / 1e6);
+        return pump_haplotypes(false);
+    }
+
     // several devices: my batches' random reads are counted and published; then every device's counts, and the group's base, are waited for
     bool exchange_counts(Resident &cur)
     {
@@ -588,6 +669,7 @@ struct Worker {
         std::vector<int> todo;
         for (int b = 0; b < (int)g.batch.size(); ++b) if (mine(g, b)) todo.push_back(b);
         if (todo.empty()) {      // nothing to simulate here (device 0 of a small group, or -o 2): the group's memory goes back at once
+            if (!flush_haplotypes(h)) return false;
             if (dwgsim_hip_drop_contig(x, h) < 0) { fail_ctx(); return false; }
             return look_ahead(g);
         }
@@ -609,6 +691,7 @@ struct Worker {
             Pending &pb = fl.back(); pb.slot = slot; pb.b = b; pb.h = h; pb.g = cur.g; pb.last_of_group = q + 1 == todo.size();
             for (size_t t = 0; t + 1 < fl.size(); ++t) if (!stage_a(fl[t])) return false;
             while ((int)fl.size() >= DWGSIM_HIP_SLOTS) { if (!stage_b(fl.front())) return false; fl.pop_front(); }
+            if (!pump_haplotypes(false)) return false;
             if (!look_ahead(g)) return false;
         }
         return ok();
@@ -877,6 +960,14 @@ int dwgsim_hip_job_set_mutation_input(dwgsim_hip_job_t *j, int type, const char 
 {
     if (!j || !path || type < 0 || type > 2 || j->me.started) return arg_error(j, DWGSIM_HIP_ERR_ARG, "job: the mutation input must be set before the first contig");
     j->cfg.mutin_type = type; j->cfg.mutin_path = path;
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_job_set_haplotype_sink(dwgsim_hip_job_t *j, dwgsim_hip_job_haplotype_fn fn, void *user, int width)
+{
+    if (!j || width < 0) return arg_error(j, DWGSIM_HIP_ERR_ARG, "job: the haplotype line width must not be negative");
+    if (j->me.started) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: the haplotype sink must be set before the first contig");
+    j->cfg.hap_fn = fn; j->cfg.hap_user = user; j->cfg.hap_width = width;
     return DWGSIM_HIP_OK;
 }
 

@@ -87,6 +87,11 @@ struct ContigDev {             // a group of contigs in its coordinate space (a 
     uint32_t cap_bases[2];  // ... and the capacity of the inserted-base pools
 };
 
+// One record of a haplotype FASTA (dw_walk.hip k_hap_headers / k_hap_write), one per contig of the group: where it lies in the group's text, its header
+// line ('>' + name + '\n') in the header pool, the emitted bases of the group in front of the contig's first block (k_hap_len, scanned) and its own
+struct HapRec { uint64_t rec_off; uint32_t hdr_off, hdr_len, base0, n_bases; uint32_t pad_; };
+constexpr int HAP_WINDOW = 8192;         // k_hap_write: characters a block stages in LDS at a time (a block of 4096 cells emits more only where insertions make it)
+
 // An element count that is either known on the host or still being produced on the device: kernels are launched for `host`
 // elements (an exact count, or the capacity the buffers were sized for) and work on min(*dev, host).
 struct Count { const uint64_t *dev; uint32_t host; };

@@ -25,6 +25,8 @@ void launch_make_view(hipStream_t st, const uint8_t *cells0, const uint8_t *cell
 void launch_apply_patches(hipStream_t st, const int32_t *pos, const uint16_t *cells, uint32_t n, uint8_t *h0, uint8_t *h1);
 void launch_collect_mask(hipStream_t st, const uint8_t *h0, const uint8_t *h1, int64_t l, uint16_t *mask, uint32_t *block_count);
 void launch_gather(hipStream_t st, const int32_t *pos, uint32_t n, const uint8_t *ref, const uint8_t *h0, const uint8_t *h1, uint32_t *cells);
+void launch_hap_len(hipStream_t st, HapDev h, SegTab seg, int64_t l, uint32_t *block_count);      // the haplotype FASTA: emitted bases per block of SCAN_POS_PER_BLOCK cells ...
+void launch_hap_write(hipStream_t st, HapDev h, SegTab seg, int64_t l, const uint32_t *block_base, const HapRec *rec, uint32_t n_rec, const uint8_t *pool, uint32_t width, uint8_t *text);      // ... and, from their scan and the records the host placed, the text
 void launch_place(hipStream_t st, const SimArgs &a);
 bool launch_simulate(hipStream_t st, const SimArgs &a, const SimForm &f);      // false: the form has no instance
 void launch_calibrate(hipStream_t st, const CalibArgs &a);

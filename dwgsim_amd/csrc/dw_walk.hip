@@ -13,6 +13,7 @@
 //     k_apply_patches file-driven mutations (-m / -b / -v) resolved on the host, scattered here
 //     k_collect_mask / k_gather   list of mutated cells for the host's txt/vcf writer
 //     k_mut_debug     the reference's consistency asserts (mut.c:379-425)
+//     k_hap_len / k_hap_headers / k_hap_write   the two finished haplotypes as FASTA text (on request only)     HBM: 1 B in, ~1 B out / base, twice
 //     k_make_view     4-bit read view of a finished haplotype (what base extraction reads) + its two levels of summaries (what the random-read count reads)
 //
 // Byte/integer work only: no MFMA.  Host-callable launchers (dw_launch.hpp) are at the end.
@@ -742,8 +743,136 @@ __global__ void k_gather(const int32_t *__restrict__ pos, uint32_t n, const uint
 }
 
 // ------------------------------------------------------------------------------------------------
+// The two finished haplotypes as FASTA text (no counterpart in the reference; DESIGN.md "6d").  The cells are what the reads are drawn from
+// (dw_read.hpp, the episode loop), so the text restates them, forward strand: an unmutated or substituted cell gives its base, a DELETE cell
+// nothing, an INSERT cell its base and then the inserted bases P[0 .. n) in table order; codes 0-3 print ACGT, every other code N.  A block
+// takes SCAN_POS_PER_BLOCK cells, a thread sixteen of them (one load); contigs start at multiples of GROUP_ALIGN, so a block lies inside one
+// contig (or in the padding behind one, which is never emitted).  k_hap_len: emitted bases per block; k_scan_excl over the blocks; the host
+// places the records (HapRec); k_hap_headers + k_hap_write: the text.  The kernels only read the cells and the insertion tables.
+// ------------------------------------------------------------------------------------------------
+DW_DEV uint32_t hap_char(uint32_t code) { return code < 4u ? (0x54474341u >> (8u * code)) & 0xffu : (uint32_t)'N'; }
+DW_DEV uint32_t hap_cell(const uint4 &v, int q) { const uint32_t w = (q & 8) ? ((q & 4) ? v.w : v.z) : ((q & 4) ? v.y : v.x); return (w >> (8 * (q & 3))) & 0xffu; }
+// the insertion an INSERT cell at group coordinate g stands for: its table entry, or n_ins (a cell without one emits its own base alone)
+DW_DEV uint32_t hap_ins_entry(const HapDev &h, int64_t g)
+{
+    const uint32_t idx = ins_find(h, g);
+    return idx < h.n_ins && (int64_t)h.ins_pos[idx] == g ? idx : h.n_ins;
+}
+// bases the first nv of the sixteen cells v at group coordinate g emit
+DW_DEV uint32_t hap_emitted(const HapDev &h, int64_t g, const uint4 &v, int nv)
+{
+    if (((v.x | v.y | v.z | v.w) & 0x10101010u) == 0) return (uint32_t)nv;      // neither an INSERT nor a DELETE cell among them (the rare path below looks at each)
+    uint32_t n = 0;
+    for (int q = 0; q < nv; ++q) {
+        const uint32_t ty = hap_cell(v, q) & TMASK;
+        if (ty == T_DEL) continue;
+        ++n;
+        if (ty == T_INS) { const uint32_t idx = hap_ins_entry(h, g + q); if (idx < h.n_ins) n += h.ins_len[idx]; }
+    }
+    return n;
+}
+__global__ void __launch_bounds__(SCAN_THREADS) k_hap_len(HapDev h, SegTab seg, uint32_t *__restrict__ block_count)
+{
+    __shared__ uint32_t sm[17];
+    const int64_t g0 = (int64_t)blockIdx.x * SCAN_POS_PER_BLOCK, g = g0 + (int64_t)threadIdx.x * SCAN_POS_PER_THREAD;
+    const uint32_t sk = seg_of(seg, g0);
+    const int64_t end = (int64_t)seg.start[sk] + seg.len[sk];      // (g >= end: the padding behind the contig)
+    uint32_t cnt = 0;
+    if (g < end) { const uint4 v = *reinterpret_cast<const uint4 *>(h.cells + g); cnt = hap_emitted(h, g, v, end - g < 16 ? (int)(end - g) : 16); }
+    uint32_t total;
+    (void)block_excl_scan(cnt, sm, &total);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+// the header lines, a block per record in turn (a contig without bases has no block of k_hap_write)
+__global__ void __launch_bounds__(64) k_hap_headers(const HapRec *__restrict__ rec, uint32_t n_rec, const uint8_t *__restrict__ pool, uint8_t *__restrict__ text)
+{
+    for (uint32_t k = blockIdx.x; k < n_rec; k += gridDim.x) {
+        const HapRec R = rec[k];
+        for (uint32_t i = threadIdx.x; i < R.hdr_len; i += blockDim.x) text[R.rec_off + i] = pool[R.hdr_off + i];
+    }
+}
+// The bases of a record in lines of `width` characters (0: one line), each ended by '\n': base b of the record is byte b + b / width of its body.
+// A block owns the bytes from its first base to the next block's first base -- the line ends between them included, and the body's last byte
+// if it holds the record's last base.  It stages its bases in LDS, a window of HAP_WINDOW at a time, and streams its byte range out: whole
+// aligned 16-byte words as one store each, the ragged ends -- a word it shares with a neighbour, or with the header -- byte by byte, so that
+// no byte is written by two blocks and none is read back.
+__global__ void __launch_bounds__(SCAN_THREADS) k_hap_write(HapDev h, SegTab seg, const uint32_t *__restrict__ block_base, const HapRec *__restrict__ rec, uint32_t width, uint8_t *__restrict__ text)
+{
+    __shared__ uint32_t sm[17];
+    __shared__ uint32_t s_txt[HAP_WINDOW / 4];
+    uint8_t *const stage = reinterpret_cast<uint8_t *>(s_txt);
+    const int64_t g0 = (int64_t)blockIdx.x * SCAN_POS_PER_BLOCK, g = g0 + (int64_t)threadIdx.x * SCAN_POS_PER_THREAD;
+    const uint32_t sk = seg_of(seg, g0);
+    const int64_t end = (int64_t)seg.start[sk] + seg.len[sk];
+    uint4 v = make_uint4(0, 0, 0, 0); int nv = 0; uint32_t cnt = 0;
+    if (g < end) { v = *reinterpret_cast<const uint4 *>(h.cells + g); nv = end - g < 16 ? (int)(end - g) : 16; cnt = hap_emitted(h, g, v, nv); }
+    uint32_t total;
+    const uint32_t off = block_excl_scan(cnt, sm, &total);
+    if (total == 0) return;                                          // (the whole block: padding, or deleted cells alone)
+    const HapRec R = rec[sk];
+    const uint32_t B = block_base[blockIdx.x] - R.base0, len = R.n_bases;      // the block's first base in its record; the record's bases (> 0 here)
+    const uint64_t body = R.rec_off + R.hdr_len;
+    const uint64_t body_bytes = (uint64_t)len + (width ? ((uint64_t)len + width - 1) / width : 1u);
+    const bool plain = ((v.x | v.y | v.z | v.w) & 0x10101010u) == 0;
+    for (uint32_t w0 = 0; w0 < total; w0 += HAP_WINDOW) {
+        const uint32_t nb = total - w0 < (uint32_t)HAP_WINDOW ? total - w0 : (uint32_t)HAP_WINDOW;      // bases [w0, w0 + nb) of the block in this window
+        if (w0) __syncthreads();                                     // (the window before has been streamed out)
+        if (cnt && off < w0 + nb && off + cnt > w0) {
+            uint32_t e = off;
+            auto put = [&](uint32_t code) { if (e >= w0 && e - w0 < nb) stage[e - w0] = (uint8_t)hap_char(code); ++e; };
+            for (int q = 0; q < nv; ++q) {
+                const uint32_t c = hap_cell(v, q), ty = c & TMASK;
+                if (ty == T_DEL) continue;
+                put(c & 0xfu);
+                if (!plain && ty == T_INS) {
+                    const uint32_t idx = hap_ins_entry(h, g + q);
+                    if (idx < h.n_ins) { const uint32_t n = h.ins_len[idx]; const uint8_t *P = h.ins_bases + h.ins_off[idx]; for (uint32_t j = 0; j < n; ++j) put(P[j]); }
+                }
+            }
+        }
+        __syncthreads();
+        const uint32_t b0 = B + w0, b1 = b0 + nb;                    // ... of the record
+        const uint32_t r0 = width ? b0 % width : 0u;                 // column of base b0 in its line
+        const uint64_t aS = body + b0 + (width ? b0 / width : 0u);
+        const uint64_t aE = body + (b1 == len ? body_bytes : (uint64_t)b1 + (width ? b1 / width : 0u));
+        for (uint64_t wa = (aS & ~(uint64_t)15) + 16u * (uint64_t)threadIdx.x; wa < aE; wa += 16u * (uint64_t)SCAN_THREADS) {
+            const int first = wa < aS ? (int)(aS - wa) : 0;          // bytes of the word in front of the block's range
+            // byte `first` of the word is byte d of the window's text: its line and column, then one step per byte
+            const uint32_t d = (uint32_t)(wa + (uint64_t)first - aS), x = r0 + d;
+            uint32_t line = 0, col = x;
+            if (width) { line = x / (width + 1u); col = x - line * (width + 1u); }
+            uint32_t bl = line * width + col - r0;                   // the window's base at (or, on a line end, behind) that byte
+            uint32_t out[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                if (i < first || wa + (uint64_t)i >= aE) continue;
+                const bool nl = width && col == width;
+                const uint32_t ch = (nl || bl >= nb) ? (uint32_t)'\n' : (uint32_t)stage[bl];      // (bl = nb: the record's last byte behind a line that is not full)
+                if (nl) col = 0; else { ++col; ++bl; }
+                out[i >> 2] |= ch << (8 * (i & 3));
+            }
+            if (first == 0 && wa + 16u <= aE) *reinterpret_cast<uint4 *>(text + wa) = make_uint4(out[0], out[1], out[2], out[3]);
+            else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) if (i >= first && wa + (uint64_t)i < aE) text[wa + (uint64_t)i] = (uint8_t)(out[i >> 2] >> (8 * (i & 3)));
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host-side launchers (declared in dw_launch.hpp)
 // ------------------------------------------------------------------------------------------------
+void launch_hap_len(hipStream_t st, HapDev h, SegTab seg, int64_t l, uint32_t *block_count)
+{
+    if (l > 0) hipLaunchKernelGGL(k_hap_len, dim3(cdiv((uint64_t)l, SCAN_POS_PER_BLOCK)), dim3(SCAN_THREADS), 0, st, h, seg, block_count);
+}
+// block_base: the scanned counts of launch_hap_len; rec: n_rec records, one per contig of seg; pool: their header lines
+void launch_hap_write(hipStream_t st, HapDev h, SegTab seg, int64_t l, const uint32_t *block_base, const HapRec *rec, uint32_t n_rec, const uint8_t *pool, uint32_t width, uint8_t *text)
+{
+    if (n_rec) hipLaunchKernelGGL(k_hap_headers, dim3(n_rec < 4096u ? n_rec : 4096u), dim3(64), 0, st, rec, n_rec, pool, text);
+    if (l > 0) hipLaunchKernelGGL(k_hap_write, dim3(cdiv((uint64_t)l, SCAN_POS_PER_BLOCK)), dim3(SCAN_THREADS), 0, st, h, seg, block_base, rec, width, text);
+}
 void launch_pack(hipStream_t st, const uint8_t *ascii, uint8_t *ref, uint8_t *h0, uint8_t *h1, int64_t l)
 {
     const uint64_t nchunk = (uint64_t)(l + 15) >> 4;

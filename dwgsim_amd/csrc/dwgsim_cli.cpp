@@ -22,6 +22,9 @@
 //                          the per-stream delivery threads spent inside the sink, i.e. the rate ONE delivery thread can sustain (the job level's ceiling per stream)
 //     DWGSIM_HIP_SINK_ORDERED  the FASTQ pieces through the ordered sink (one delivering thread per file, write() in file order) instead of the offset sink (one
 //                          thread per device and file, pwrite() at the piece's place: the default when the members are made on the GPU)
+//     DWGSIM_HIP_HAPLOTYPES  anything but empty or "0": also write the two mutated haplotypes the reads are drawn from, <prefix>.hap1.fa and <prefix>.hap2.fa
+//                          (plain text, assembled on the GPU; a record per simulated contig, the contig's plain name; removed again if the job fails)
+//     DWGSIM_HIP_HAPLOTYPES_WIDTH  bases per line of those files (default 60; 0: the whole sequence on one line)
 //     DWGSIM_HIP_SOLO      "r/W": measurement aid (dw_job.cpp) -- this process's one device does what device r of a W-device job does, nothing else
 #include <stdio.h>
 #include <stdlib.h>
@@ -445,6 +448,12 @@ struct FileSink {
         if (s->fp_vcf && fwrite(vcf, 1, vl, s->fp_vcf) != vl) return 1;
         return 0;
     }
+    FILE *fp_hap[2] = {nullptr, nullptr};      // DWGSIM_HIP_HAPLOTYPES: <prefix>.hap1.fa / .hap2.fa
+    static int haplotype(void *u, int hap, const void *data, size_t len)      // (dwgsim_hip_job_set_haplotype_sink: one thread, each file's pieces in order)
+    {
+        FileSink *s = (FileSink *)u;
+        return s->fp_hap[hap] && fwrite(data, 1, len, s->fp_hap[hap]) == len ? 0 : 1;
+    }
     std::atomic<uint64_t> written[3] = {{0}, {0}, {0}};      // bytes that went to file `stream` through reads_at
     // pieces with their place (dwgsim_hip_job_sink_t::reads_at): several threads per file, pwrite
     static int reads_at(void *u, int stream, uint64_t offset, const void *data, size_t len, size_t text_len, int)
@@ -651,11 +660,19 @@ int main(int argc, char **argv)
     if (has_bwa) { fs.fgz[0] = fopen((p + ".bwa.read1.fastq.gz").c_str(), "wb"); fs.fgz[1] = fopen((p + ".bwa.read2.fastq.gz").c_str(), "wb"); if (!fs.fgz[0] || !fs.fgz[1]) { fprintf(stderr, "fail to open FASTQ outputs\n"); return give_up(1); } }
     if (has_bfast) { fs.fgz[2] = fopen((p + ".bfast.fastq.gz").c_str(), "wb"); if (!fs.fgz[2]) { fprintf(stderr, "fail to open FASTQ outputs\n"); return give_up(1); } }
     for (int s = 0; s < 3; ++s) if (fs.fgz[s]) setvbuf(fs.fgz[s], nullptr, _IONBF, 0);      // deliveries are megabytes: no second copy through stdio
+    const char *hap_env = getenv("DWGSIM_HIP_HAPLOTYPES");
+    const bool want_hap = hap_env && hap_env[0] && strcmp(hap_env, "0");
+    int hap_width = 60;
+    if (want_hap) {
+        if (const char *e = getenv("DWGSIM_HIP_HAPLOTYPES_WIDTH")) { char *end; const long v = strtol(e, &end, 10); if (end == e || *end || v < 0 || v > INT_MAX) { fprintf(stderr, "dwgsim-hip: DWGSIM_HIP_HAPLOTYPES_WIDTH must be a number >= 0\n"); return give_up(1); } hap_width = (int)v; }
+        fs.fp_hap[0] = fopen((p + ".hap1.fa").c_str(), "wb"); fs.fp_hap[1] = fopen((p + ".hap2.fa").c_str(), "wb");
+        if (!fs.fp_hap[0] || !fs.fp_hap[1]) { fprintf(stderr, "dwgsim-hip: fail to open the haplotype files for '%s'\n", out_prefix); return give_up(1); }
+    }
     std::unique_ptr<DeflatePool> pool;
     if (!gpu_gzip && want_reads) { pool = std::make_unique<DeflatePool>(nthreads, gz_level); fs.pool = pool.get(); }
 
     dwgsim_hip_job_t *job = job_made.get();
-    if (!job) { fprintf(stderr, "dwgsim-hip: cannot set the job up (error %d)\n", job_err); return 1; }
+    if (!job) { fprintf(stderr, "dwgsim-hip: cannot set the job up (error %d)\n", job_err); if (want_hap) { (void)unlink((p + ".hap1.fa").c_str()); (void)unlink((p + ".hap2.fa").c_str()); } return 1; }
     int rc = 0;
     auto job_error = [&]() { const char *e = dwgsim_hip_job_last_error(job); if (rc == 0) fprintf(stderr, "%s%s", e, (e[0] && e[strlen(e) - 1] != '\n') ? "\n" : ""); rc = 1; };
     {
@@ -663,6 +680,7 @@ int main(int argc, char **argv)
         if (dwgsim_hip_job_set_contig_table(job, nm.data(), tab_lens.data(), (int)nm.size()) < 0) job_error();
         if (rc == 0 && !regions_fn.empty() && dwgsim_hip_job_set_regions(job, regions_fn.c_str()) < 0) job_error();             // dwgsim.c:499-506
         if (rc == 0 && muts_type >= 0 && dwgsim_hip_job_set_mutation_input(job, muts_type, muts_fn.c_str()) < 0) job_error();   // dwgsim.c:494-497
+        if (rc == 0 && want_hap && dwgsim_hip_job_set_haplotype_sink(job, FileSink::haplotype, &fs, hap_width) < 0) job_error();
         if (rc == 0 && dwgsim_hip_job_prepare(job, nullptr) < 0) job_error();
     }
     const double t_ctx = now_s();
@@ -707,6 +725,10 @@ int main(int argc, char **argv)
     if (timing) { timespec ts; clock_gettime(CLOCK_REALTIME, &ts); const double e = ts.tv_sec + ts.tv_nsec * 1e-9; fprintf(stderr, "[dwgsim-hip-clock] main entered at %.3f, output complete at %.3f (seconds since the epoch)\n", e - (t_out_done - t_start) - (now_s() - t_out_done), e - (now_s() - t_out_done)); }
     if (fs.fp_txt) fclose(fs.fp_txt);
     if (fs.fp_vcf) fclose(fs.fp_vcf);
+    for (int h = 0; h < 2; ++h) if (fs.fp_hap[h]) {      // (a failed job leaves no partial haplotype file)
+        if (fclose(fs.fp_hap[h]) != 0 && rc == 0) { fprintf(stderr, "dwgsim-hip: writing the haplotype files failed\n"); rc = 1; }
+        if (rc != 0) (void)unlink((p + (h ? ".hap2.fa" : ".hap1.fa")).c_str());
+    }
     for (int s = 0; s < 3; ++s) close_gz(fs.fgz[s], gz_level, fs.written[s].load());
     if (getenv("DWGSIM_HIP_TEARDOWN")) { dwgsim_hip_job_destroy(job); return rc; }
     // everything has been delivered and the files are closed: the process ends here.  Handing back device memory, page-locked buffers and the

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define DWGSIM_HIP_ABI_VERSION 5
+#define DWGSIM_HIP_ABI_VERSION 6
 
 /* error codes (negative) */
 #define DWGSIM_HIP_OK            0
@@ -197,6 +197,23 @@ dwgsim_hip_mutlist_t *dwgsim_hip_mutations_take(dwgsim_hip_ctx_t *ctx, int conti
 int dwgsim_hip_mutlist_text(dwgsim_hip_mutlist_t *list, int k, const char **txt, size_t *txt_len, const char **vcf, size_t *vcf_len);
 void dwgsim_hip_mutlist_free(dwgsim_hip_mutlist_t *list);
 
+/* (ABI 6) The two mutated haplotypes as FASTA text, assembled on the device from the finished cells (no counterpart in the reference; DESIGN.md "6d").
+ * The reads are drawn from the cells, so the text restates them, forward strand: an unmutated or substituted cell gives its base, a deleted cell
+ * nothing, a cell with an insertion its own base and then the inserted bases in the order mutations.txt prints them.  The cells hold base codes:
+ * A, C, G and T come back as upper case, every other character of the input (lower-case letters are folded first; N, IUPAC codes, '-', '.') as N.
+ * One record per contig of the group, in the order they were added: '>' + the contig's name + '\n' (the plain name: no -P prefix), then the bases in
+ * lines of `width` characters, each line ended by '\n' (width 0: the whole sequence on one line; a haplotype without bases has the header line alone).
+ * haplotype_fasta builds the text of haplotype `hap` (0 or 1) of the whole GROUP `contig` belongs to; it stays in device memory, *bytes (optional) = its
+ * size.  DWGSIM_HIP_ERR_STATE before the group's walk has finished, DWGSIM_HIP_ERR_ARG for another hap or a negative width.  The text is kept per group
+ * and haplotype until the group is dropped or walked again: a call with the same width finds it there, one with another width builds it again.
+ * haplotype_layout (after haplotype_fasta for that group and hap): where the contig's record lies in the group's text (offset, bytes; header included)
+ * and the haplotype's length in bases; any of the three may be NULL.
+ * haplotype_fetch copies n bytes from `offset` of the text the LAST haplotype_fasta call for `hap` built or found, to host memory: a page-locked
+ * destination directly, a pageable one through the context's page-locked staging (as dwgsim_hip_fetch).  DWGSIM_HIP_ERR_ARG past the end of the text. */
+int dwgsim_hip_haplotype_fasta(dwgsim_hip_ctx_t *ctx, int contig, int hap, int width, uint64_t *bytes);
+int dwgsim_hip_haplotype_layout(dwgsim_hip_ctx_t *ctx, int contig, int hap, uint64_t *offset, uint64_t *bytes, int64_t *bases);
+int dwgsim_hip_haplotype_fetch(dwgsim_hip_ctx_t *ctx, int hap, uint64_t offset, void *host_dst, size_t n);
+
 /* Number of random reads among pairs [first_ii, first_ii + n_pairs) of the contig (for sharding:
  * rand_ii is a running count over all earlier pairs, dwgsim.c:1042,1096). */
 int dwgsim_hip_count_random(dwgsim_hip_ctx_t *ctx, int contig, uint64_t first_ii, uint64_t n_pairs,
@@ -308,6 +325,13 @@ typedef struct dwgsim_hip_job_options {
     uint64_t min_share;      /* a group is spread over fewer devices while a device's share would stay below this many pairs (0: 65536) */
 } dwgsim_hip_job_options_t;
 
+/* (ABI 6) The mutated haplotypes as FASTA (dwgsim_hip_haplotype_fasta), through a call of its own: dwgsim_hip_job_sink_t has no size member, so it
+ * cannot grow.  fn gets the next piece of the file of haplotype `hap` (0 or 1): the pieces of one haplotype arrive in file order, each at most 32 MiB,
+ * from ONE thread of the job (pieces of the two haplotypes alternate group by group); `data` is page-locked memory of the job, reused once the call
+ * has returned.  The records are those of the contigs the job simulates, in FASTA order: a contig dwgsim_core passes over (DWGSIM_HIP_SKIP_*) has
+ * none, as it has no mutations and no reads.  Made by the first device alone; independent of -M.  A non-zero return fails the job.  width as for
+ * dwgsim_hip_haplotype_fasta.  To be called before dwgsim_hip_job_prepare / the first contig: DWGSIM_HIP_ERR_STATE later; fn == NULL: off. */
+typedef int (*dwgsim_hip_job_haplotype_fn)(void *user, int hap, const void *data, size_t len);
 /* devices == NULL or n_devices <= 0: every HIP device the process sees.  options == NULL: GPU gzip, defaults. */
 dwgsim_hip_job_t *dwgsim_hip_job_create(const dwgsim_hip_params_t *p, const int *devices, int n_devices, const dwgsim_hip_job_sink_t *sink,
                                         const dwgsim_hip_job_options_t *options, int *err);
@@ -316,6 +340,7 @@ dwgsim_hip_job_t *dwgsim_hip_job_create(const dwgsim_hip_params_t *p, const int 
 int dwgsim_hip_job_set_contig_table(dwgsim_hip_job_t *job, const char *const *names, const int64_t *lens, int n);
 int dwgsim_hip_job_set_regions(dwgsim_hip_job_t *job, const char *path);
 int dwgsim_hip_job_set_mutation_input(dwgsim_hip_job_t *job, int type, const char *path);
+int dwgsim_hip_job_set_haplotype_sink(dwgsim_hip_job_t *job, dwgsim_hip_job_haplotype_fn fn, void *user, int width);
 /* optional: parse the files above and start the device threads now (errors of -x / -m / -b / -v surface here instead of at the first contig) */
 int dwgsim_hip_job_prepare(dwgsim_hip_job_t *job, uint64_t *total_len);
 /* The body of the contig loop (dwgsim.c:519-625 and everything below it) for the next contig of the FASTA.  Returns the pairs scheduled for
@@ -438,7 +463,9 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *ctx, const char *key, int64_t valu
  * NTHR << 20 | LPP << 16 | OUT << 12 | DT << 8 | WR << 4 | SPLIT (SPLIT 1: the two-kernel form, WR: the writer of its second half); "walk_form": what
  * the context's last mutation walk enqueued was made of (0 before the first), packed as ATTEMPT << 16 | FILE << 12 | SLOTS << 8 | RESTORE << 4 | DENSE
  * (ATTEMPT 1, 2: the exact re-runs; FILE 1: the file-driven walk of -m / -b / -v; SLOTS 1 / 0: the slot / look-back form of the site scan; RESTORE: what
- * went back to the pristine copies first -- 0 nothing, 1 the dirty chunks, 2 whole buffers; DENSE 1 / 0: views made from every cell / from the dirty bitmap) */
+ * went back to the pristine copies first -- 0 nothing, 1 the dirty chunks, 2 whole buffers; DENSE 1 / 0: views made from every cell / from the dirty bitmap);
+ * "hap_len_us" / "hap_write_us": HIP-event time (microseconds) of the length pass + scan / of the header and write kernels of the haplotype text built
+ * last (dwgsim_hip_haplotype_fasta); "hap_copy_us": with the option "hap_yardstick" = 1, of a device-to-device copy of that text's size behind it */
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *ctx, const char *key, int64_t *value);
 /* the gzip kernel on arbitrary host bytes (the product only ever feeds it FASTQ text) */
 int dwgsim_hip_debug_gzip(dwgsim_hip_ctx_t *ctx, const void *text, size_t n, void *out, size_t cap, size_t *out_n);
