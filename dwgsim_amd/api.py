@@ -86,6 +86,7 @@ EXPORTS = [
     "dwgsim_hip_eval_debug_device_bam_chunk", "dwgsim_hip_eval_debug_inflate",
     "dwgsim_hip_eval_set_breakdown", "dwgsim_hip_eval_breakdown_text",
     "dwgsim_hip_haplotype_fasta", "dwgsim_hip_haplotype_layout", "dwgsim_hip_haplotype_fetch", "dwgsim_hip_job_set_haplotype_sink",
+    "dwgsim_hip_debug_sim_instances",
 ]
 
 _lib = None
@@ -176,6 +177,7 @@ def load(path: str | None = None):
     lib.dwgsim_hip_haplotype_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_uint64), P(C.c_uint64), P(C.c_int64)]
     lib.dwgsim_hip_haplotype_fetch.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
     lib.dwgsim_hip_job_set_haplotype_sink.argtypes = [C.c_void_p, HAP_CB, C.c_void_p, C.c_int]
+    lib.dwgsim_hip_debug_sim_instances.argtypes = [P(C.c_int64), C.c_int]
     if hasattr(lib, "dwgsim_hip_eval_create"):
         _bind_eval(lib)
     if path is None:
@@ -185,6 +187,21 @@ def load(path: str | None = None):
 
 class DwgsimError(RuntimeError):
     pass
+
+
+def unpack_sim_form(v: int):
+    """(LPP, OUT, DT, NTHR, WR, SPLIT) of a value of debug_get("sim_form") / dwgsim_hip_debug_sim_instances"""
+    return (v >> 16 & 15, v >> 12 & 15, v >> 8 & 15, v >> 20, v >> 4 & 15, v & 15)
+
+
+def sim_instances(lib=None):
+    """(ABI 7) dwgsim_hip_debug_sim_instances: the k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> instances the library was built with, as tuples in list order"""
+    lib = lib or load()
+    n = lib.dwgsim_hip_debug_sim_instances(None, 0)
+    out = (C.c_int64 * n)()
+    if lib.dwgsim_hip_debug_sim_instances(out, n) != n:
+        raise DwgsimError("dwgsim_hip_debug_sim_instances: the count changed between two calls")
+    return [unpack_sim_form(v) for v in out]
 
 
 def default_params(lib=None) -> Params:
@@ -299,6 +316,7 @@ class JobResult:
     walk_ms: float = 0.0
     flow_cap_mult: int = 1                           # Ion Torrent: by how much the read capacity had grown at the end of the job (run_job)
     haplotypes: dict = field(default_factory=dict)   # haplotypes=True: {0: bytes, 1: bytes}, the two mutated haplotypes as FASTA
+    sim_forms: set = field(default_factory=set)      # debug_get("sim_form") after every simulate call of the job (run_job): the k_simulate forms it ran
 
 
 VCF_HEADER_POST = (
@@ -633,6 +651,7 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
             ranges = [(h0 + k, 0, ent[3]) for k, ent in enumerate(grp) if want_reads and ent[3] > 0]
             for batch in split_ranges(ranges, batch_pairs):
                 b = ctx.simulate_ranges(batch, rand_ii, 0)
+                res.sim_forms.add(ctx.debug_get("sim_form"))
                 res.kernel_ms += b.kernel_ms
                 res.sim_kernel_ms += b.sim_kernel_ms
                 res.n_retries += b.n_retries

@@ -2347,4 +2347,12 @@ int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
     return DWGSIM_HIP_OK;
 }
 
+// ... and the k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> instances the library was built with (dw_simulate.hip DW_SIM_ALL, the list launch_simulate looks a
+// form up in): their number; out (may be NULL) gets at most cap of them, packed as "sim_form" above with SPLIT the template parameter -- 0 the single
+// kernel, 1 / 2 the first / second half of the two-kernel form.  Needs no context and no device.
+int dwgsim_hip_debug_sim_instances(int64_t *out, int cap)
+{
+    return sim_instances(out, cap);
+}
+
 } // extern "C"

@@ -1431,6 +1431,16 @@ DW_CAT(DW_SIM_PART_, DW_PART)(DW_SIM_INSTANCE)
 #endif
 
 #if DW_HAS(0)
+// test hook (dwgsim_hip_debug_sim_instances): the instances of the list, packed as debug_get("sim_form") packs a form, with SPLIT the template parameter
+int sim_instances(int64_t *out, int cap)
+{
+#define DW_SIM_PACKED(LPP, OUT, DT, NTHR, WR, SPLIT) (int64_t)(NTHR) << 20 | (LPP) << 16 | (OUT) << 12 | (DT) << 8 | (WR) << 4 | (SPLIT),
+    static const int64_t list[] = {DW_SIM_ALL(DW_SIM_PACKED)};
+    const int n = (int)(sizeof list / sizeof list[0]);
+    for (int i = 0; out && i < n && i < cap; i++) out[i] = list[i];
+    return n;
+}
+
 // the form the host chose (dw_host.cpp sim_form): its entry in the list, or both halves and k_split_scan between them
 bool launch_simulate(hipStream_t st, const SimArgs &a, const SimForm &f)
 {

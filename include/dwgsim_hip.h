@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define DWGSIM_HIP_ABI_VERSION 6
+#define DWGSIM_HIP_ABI_VERSION 7
 
 /* error codes (negative) */
 #define DWGSIM_HIP_OK            0
@@ -467,6 +467,11 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *ctx, const char *key, int64_t valu
  * "hap_len_us" / "hap_write_us": HIP-event time (microseconds) of the length pass + scan / of the header and write kernels of the haplotype text built
  * last (dwgsim_hip_haplotype_fasta); "hap_copy_us": with the option "hap_yardstick" = 1, of a device-to-device copy of that text's size behind it */
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *ctx, const char *key, int64_t *value);
+/* (ABI 7) the k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> instances the library was built with, from the list that instantiates them and in which a
+ * launch looks its form up: returns their number and writes at most `cap` of them to `out` (may be NULL), each packed as "sim_form" above with SPLIT
+ * the template parameter -- 0: the single kernel, 1 / 2: the first / second half of the two-kernel form.  A form with SPLIT 1 that "sim_form" reports,
+ * (l, o, d, n, w, 1), runs the instances (l, 1, d, n, 1, 1) and (l, o, d, n, w, 2).  Needs no context and no device. */
+int dwgsim_hip_debug_sim_instances(int64_t *out, int cap);
 /* the gzip kernel on arbitrary host bytes (the product only ever feeds it FASTQ text) */
 int dwgsim_hip_debug_gzip(dwgsim_hip_ctx_t *ctx, const void *text, size_t n, void *out, size_t cap, size_t *out_n);
 /* occurrences of `byte` in one finished stream of a slot, counted on the device (whole-output checks without a copy-out) */
