@@ -1,6 +1,8 @@
 """The plain-Python model of dwgsim_eval (tests/eval_model.py) against hand-worked answers for the SAM fixtures in tests/golden/eval.
 Every expected count below was worked out by reading the fixture's records (comments give the reasoning); the model has to reproduce them.
 The GPU evaluator and its CPU emulation are then held to the model (tests/test_eval_emu.py, tests/test_gpu_eval.py)."""
+# The model's own anchor is no longer these fixtures alone: tests/test_eval_reference.py holds it (and the kernels) to the recorded answers of
+# the unmodified reference evaluator (tests/golden/eval_reference_runs.json).
 import os
 import pytest
 
