@@ -848,6 +848,20 @@ struct FifoWriter {
         putn(v, cnt);
     }
     DW_DEV void put4(uint32_t w) { if (probe::off(1)) return; Unal4 x; x.v = w; *reinterpret_cast<Unal4 *>(f + wp) = x; wp += 4; if (wp >= BURST) drain(); }
+    // The lockstep sequence line (dw_simulate.hip): appends WITHOUT a drain test, so that the lanes of a wave -- whose wp differ -- walk the drain body once
+    // together instead of one after the other.  poke8 / poke4 write `off` places past the write position and leave it where it is; the caller keeps
+    // wp + off <= BURST (poke8) resp. wp + off + 4 <= BURST + 8 (poke4): the store ends inside the FIFO's BURST + 8 bytes.  advance(n) then moves wp and
+    // tests once.  burst32: the FIFO is empty and stands at a unit's start (wp == skip == 0): one whole unit goes from registers to dst, past the FIFO.
+    DW_DEV void poke8(uint32_t off, uint64_t v) { if (probe::off(1)) return; Unal8 x; x.v = v; *reinterpret_cast<Unal8 *>(f + wp + off) = x; }
+    DW_DEV void poke4(uint32_t off, uint32_t v) { if (probe::off(1)) return; Unal4 x; x.v = v; *reinterpret_cast<Unal4 *>(f + wp + off) = x; }
+    DW_DEV void burst32(uint4 lo, uint4 hi)
+    {
+        static_assert(BURST == 32u && !DUAL, "a unit of two dwordx4 stores, one stream");
+        if (probe::off(1)) return;
+        if (probe::off(2)) probe::keep(lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w);
+        else { *reinterpret_cast<uint4 *>(dst) = lo; *reinterpret_cast<uint4 *>(dst + 16) = hi; }
+        dst += 32u;
+    }
     DW_DEV void put16(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { putn((uint64_t)a | ((uint64_t)b << 32), 8); putn((uint64_t)c | ((uint64_t)d << 32), 8); }
     DW_DEV void flush()
     {

@@ -467,6 +467,8 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
     // (SOLiD: the BFAST records' lengths are not a function of the BWA records' -- the name counts differ --: their bytes are a second word, on a chain of its own walked
     // by wave 1 at the same time: still one front)
     constexpr bool ONE_LB = (DT == 0 || DT == 1) && SPLIT == 0;
+    // the sequence line in lockstep 32-byte units (below, "write the record(s)"): Illumina, one kernel, bases staged in LDS, one output family through FifoWriter<32, false>
+    constexpr bool SEQ_LOCKSTEP = DT == 0 && SPLIT == 0 && WR == 1 && NTHR == SIM_THREADS && OUT != 3;
     const int LB_SHIFT = a.lb_shift;      // (bits of the byte sum; the host sizes it to the launch and refuses one whose two sums would not fit 62 bits: dw_host.cpp)
     const int tid = (int)threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
@@ -916,6 +918,43 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
                 }
             }
             for (int w = 2 * full16; w * 8 < s_out; ++w) put_last_word(rec_word(w), s_out - w * 8);      // the last, shorter group
+        } else if constexpr (SEQ_LOCKSTEP) {
+            // The lanes of a wave reach this line with different wp (record address mod 32, name length): appended with a drain test each, some lane
+            // drained after nearly every sixteen bases and the whole wave walked the drain body -- LDS reads, a wait, two stores -- with most lanes masked
+            // off.  Here the line is cut per lane at the 32-byte units of its own destination, so that every lane does the same thing at the same time:
+            //   head  the first na = 32 - wp bases (the whole read if it is shorter) fill the FIFO's unit: four guarded appends, then ONE drain for all lanes
+            //         (through drain(): a record whose first unit has not left yet keeps its skip);
+            //   body  whole units of 32 bases from base na on, cut out of the staged words with one v_alignbit each (base na stands at nibble na & 7 of
+            //         word na >> 3: the same shift for every unit of the lane) and stored from registers, two aligned dwordx4: no FIFO, no drain test;
+            //   tail  the < 32 bases left and "\n+\n" into the empty FIFO, one drain test (at most 34 bytes).
+            // (staged words: word w of this lane at lds[w * nthr], nw of them; a unit that starts on a word boundary would read one word past its last)
+            auto &fw = o.a;
+            auto staged = [&](int w) -> uint32_t { return w < nw ? lds[w * nthr] : 0u; };
+            auto chars8 = [&](uint32_t nib) -> uint64_t { return (uint64_t)base_chars4(nib) | ((uint64_t)base_chars4(nib >> 16) << 32); };
+            const int na = s_out < 32 - (int)fw.wp ? s_out : 32 - (int)fw.wp;      // 1 .. 32
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (8 * k < na) fw.poke8(8u * (uint32_t)k, chars8(lds[k * nthr]));      // (wp + 8 k < wp + na <= 32; base 8 k exists)
+            fw.advance((uint32_t)na);
+            const uint32_t sh = 4u * ((uint32_t)na & 7u);
+            const int left = s_out - na, rem = left & 31;
+            int wi = na >> 3;
+            uint32_t r0 = left > 0 ? staged(wi) : 0u;
+            for (int c = left >> 5; c > 0; --c, wi += 4) {      // (a lane with a unit to write has drained above: wp == skip == 0)
+                const uint32_t r1 = lds[(wi + 1) * nthr], r2 = lds[(wi + 2) * nthr], r3 = lds[(wi + 3) * nthr], r4 = staged(wi + 4);
+                const uint32_t n0 = __builtin_amdgcn_alignbit(r1, r0, sh), n1 = __builtin_amdgcn_alignbit(r2, r1, sh);
+                const uint32_t n2 = __builtin_amdgcn_alignbit(r3, r2, sh), n3 = __builtin_amdgcn_alignbit(r4, r3, sh);
+                fw.burst32(make_uint4(base_chars4(n0), base_chars4(n0 >> 16), base_chars4(n1), base_chars4(n1 >> 16)),
+                           make_uint4(base_chars4(n2), base_chars4(n2 >> 16), base_chars4(n3), base_chars4(n3 >> 16)));
+                r0 = r4;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (8 * k < rem) {      // (rem > 0: wp == 0, the eight bytes end at 32 or before)
+                const uint32_t r1 = staged(wi + k + 1);
+                fw.poke8(8u * (uint32_t)k, chars8(__builtin_amdgcn_alignbit(r1, r0, sh)));
+                r0 = r1;
+            }
+            fw.poke4((uint32_t)rem, (uint32_t)'\n' | ((uint32_t)'+' << 8) | ((uint32_t)'\n' << 16));      // (wp + rem <= 31: a short read has rem == 0 and wp + na <= 31)
+            fw.advance((uint32_t)rem + 3u);
         } else {
         int w = 0;
         for (; (w + 2) * 8 <= s_out; w += 2) {
@@ -924,7 +963,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
         }
         for (; w * 8 < s_out; ++w) put_last_word(rec_word(w), s_out - w * 8);
         }
-        o.put('\n'); o.put('+'); o.put('\n');
+        if constexpr (!SEQ_LOCKSTEP) { o.put('\n'); o.put('+'); o.put('\n'); }
         o.rebase();
         }
         if (SPLIT == 0) wave_priority(0);      // (a wave none of whose lanes has a record)
