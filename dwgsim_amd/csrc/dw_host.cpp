@@ -178,7 +178,7 @@ struct dwgsim_hip_ctx {
     int flow_cap_mult = 1;                 // Ion Torrent: the read capacity is flow_read_capacity() times this; doubled when a read outgrew it (the reference doubles its buffers, dwgsim.c:296-311)
     int ion_lds = -1;                      // "ion_lds" (tests): where the Ion Torrent read buffers live (fill_sim_args)
     int n_cu = 0; int flow_slots = 0;      // compute units of the device; "flow_slots": scratch slots per XCD forced by the tests (0: as many as an XCD can hold blocks)
-    int64_t walk_cap = -1; bool phases = false; int writer = -1, force_threads = 0; int64_t place_cap = -1; uint64_t place_open = 0; double walk_us = 0, count_us = 0; int split = -1;      // dwgsim_hip_debug_option / _debug_get
+    int64_t walk_cap = -1; bool phases = false; int writer = -1, force_threads = 0; int64_t place_cap = -1; uint64_t place_open = 0; double walk_us = 0, count_us = 0; int split = -1, qrows = 1;      // dwgsim_hip_debug_option / _debug_get
     int64_t sim_form = 0;                  // dwgsim_hip_debug_get("sim_form"): the k_simulate form of the last launch
     int64_t walk_form = 0;                 // dwgsim_hip_debug_get("walk_form"): what the last walk enqueued was made of
     hipEvent_t ev_cnt0 = nullptr, ev_cnt1 = nullptr;
@@ -1802,6 +1802,8 @@ static void fill_sim_args(const dwgsim_hip_ctx_t *c, const Group &g, const SimFo
     a.rand_fixed = c->d_rand_fixed.get(); a.rand_fixed_len = c->rand_fixed_len;
     a.sim_threads = f.nthr; a.fifo = f.wr != 0; a.split = f.split; a.ion_lds = f.dt == 3;
     a.cap = f.cap; a.lds_words = f.lds_words; a.flow_stack_words = f.stack_words;
+    // the quality line in the staging rows: the instances that write the sequence line in lockstep units (dw_simulate.hip SEQ_LOCKSTEP), from 72 bytes per lane on
+    a.qrows = (c->qrows != 0 && f.dt == 0 && f.split == 0 && f.wr == 1 && f.nthr == SIM_THREADS && f.out != 3 && f.lds_words >= 18) ? 1 : 0;
     a.flow = c->d_flow.get(); a.flow_len = (int32_t)c->flow.size();
     for (int j = 0; j < 2; ++j) {      // Illumina / SOLiD: the gap chain of a read end's error sites runs at the largest threshold of its ramp (dw_simulate.hip; thresholds as dwgsim_hip_create made them)
         const int n = c->prm.length[j];
@@ -2300,7 +2302,8 @@ int dwgsim_hip_debug_gzip(dwgsim_hip_ctx_t *c, const void *text, size_t n, void 
 // "walk_seg_min" = n runs the walk's two serial scans in their segmented form from a capacity of n candidates on (default 16384; 0 restores it),
 // "place_cap" = n gives the lists of pairs that k_place leaves open room for n entries each (exercises the second, full-size run),
 // "split" = 0 / 1 runs the Illumina read kernel as one kernel with look-backs / as two kernels with the offsets computed in between (-1: two for reads of
-// up to 100 bases).
+// up to 100 bases),
+// "qrows" = 0 keeps the quality line of the single Illumina kernel on the per-lane FIFO where it would run in the wave's staging rows (reads of 137 bases on).
 int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *c, const char *key, int64_t value)
 {
     if (!c || !key) return DWGSIM_HIP_ERR_ARG;
@@ -2315,6 +2318,7 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *c, const char *key, int64_t value)
     else if (!strcmp(key, "walk_seg_min")) walk_debug_seg_min((uint32_t)value);      // (process-wide)
     else if (!strcmp(key, "place_cap")) c->place_cap = value;
     else if (!strcmp(key, "split")) c->split = (int)value;
+    else if (!strcmp(key, "qrows")) c->qrows = (int)value;
     else if (!strcmp(key, "flow_slots")) c->flow_slots = (int)value;
     else if (!strcmp(key, "ion_lds")) c->ion_lds = (int)value;
     else if (!strcmp(key, "flow_cap")) c->flow_cap_forced = (int)value;

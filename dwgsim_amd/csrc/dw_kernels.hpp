@@ -223,6 +223,7 @@ struct SimArgs {
     const uint8_t *flow;           // Ion Torrent: flow order as base codes (dwgsim_opt.c:404-407), device memory, 64 bytes, followed by the log2 table of the gap draws (FLOW_LG_ENTRIES words)
     uint64_t flow_gap_r[2]; int32_t flow_gap_s[2];      // Ion Torrent, per read end: flow_gap_params of its threshold e_thr[j][0]
     uint64_t err_thr_max[2], err_gap_r[2]; int32_t err_gap_s[2], err_ramp[2];      // Illumina / SOLiD, per read end: the largest threshold of the error ramp, flow_gap_params of it, and whether any position's threshold is lower (those sites are thinned)
+    int32_t qrows;                 // 1: the quality line of the lockstep instances runs in the wave's staging rows (dw_simulate.hip QROWS: lds_words >= 18; "qrows" = 0 switches it off)
 };
 
 } // namespace dw

@@ -170,7 +170,7 @@ DW_DEV ReadRes gen_read(const HapDev &h, int64_t l, int64_t start, int step, int
         if (k < 0) break;
     }
     if (k != s) { r.ext_coor = -10; return r; }
-    if (na) sink.put(k >> 3, accw, na);      // the ragged last word of an episode
+    if (na) sink.put((k - na) >> 3, accw, na);      // the ragged last word of an episode (word k >> 3, from the word's first base k - na: k == s here, and an index made of s alone is a loop invariant of the caller's attempts, held in a register through all of them)
     return r;
 }
 
@@ -751,10 +751,12 @@ struct Writer {               // sequential byte stream of one record -> 16-byte
 // bytes [from, upto) of a unit (the ragged first / last unit of a record) from the FIFO at f to dst: rising sizes until the position is aligned (or the
 // next piece would pass upto), then falling sizes.  (The rare paths of k_simulate -- these, the exact fp64 quality try -- make up a third of its code
 // inlined at every use (94 KB against 57 KB called); the called form measured 1 % slower at 2 x 150 -o 1, 0.5 % faster at -o 0: profiles/r05_bench_lines_final.txt)
-template <uint32_t BURST>
+struct Al8 { uint64_t v; };                                                 // eight bytes of a FIFO (8-byte aligned) ...
+struct __attribute__((packed, aligned(4))) Al4x8 { uint64_t v; };           // ... and of a row buffer, which is only 4-byte aligned (FifoWriter::rows_take)
+template <uint32_t BURST, class L8 = Al8>      // L8: how the eight bytes at a multiple of 8 from f are read
 DW_DEV void fifo_store_range(const uint8_t *f, uint8_t *dst, uint32_t from, uint32_t upto)
 {
-    auto ld8 = [&](uint32_t b) { return *reinterpret_cast<const uint64_t *>(f + b); };
+    auto ld8 = [&](uint32_t b) { return reinterpret_cast<const L8 *>(f + b)->v; };
     auto st16 = [&](uint32_t b) { *reinterpret_cast<uint4 *>(dst + b) = make_uint4((uint32_t)ld8(b), (uint32_t)(ld8(b) >> 32), (uint32_t)ld8(b + 8), (uint32_t)(ld8(b + 8) >> 32)); };
     uint32_t b = from;
     if ((b & 1u) && b + 1 <= upto) { dst[b] = f[b]; b += 1; }
@@ -863,6 +865,40 @@ struct FifoWriter {
         dst += 32u;
     }
     DW_DEV void put16(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { putn((uint64_t)a | ((uint64_t)b << 32), 8); putn((uint64_t)c | ((uint64_t)d << 32), 8); }
+    // The quality line in a ROW BUFFER (dw_simulate.hip QROWS): `row` -- at least 72 bytes of LDS, 4-byte aligned, this lane's alone -- takes the FIFO's place
+    // for the rest of the record.  The record's first unit has left (skip == 0) and fewer than 32 bytes are pending; they move over.  From there on
+    // rows_append lays down up to eight bytes WITHOUT a test, and the caller takes rows_unit -- 32 bytes from the buffer's front to dst, the up to 32 bytes
+    // behind them to the front -- for every lane with wp >= 32 at points it chooses, the same for all lanes of a wave, often enough that no append starts
+    // past byte 63 (the eight bytes end at 72).  rows_flush: the < 32 bytes left.
+    DW_DEV void rows_take(uint8_t *row)
+    {
+        static_assert(BURST == 32u && !DUAL, "a unit of two dwordx4 stores, one stream");
+        if (!(probe::off(1))) {
+#pragma unroll
+            for (uint32_t b = 0; b < 32u; b += 8u) { Al4x8 x; x.v = ld8(b); *reinterpret_cast<Al4x8 *>(row + b) = x; }
+        }
+        f = row; skip = 0;
+    }
+    DW_DEV void rows_append(uint64_t v, uint32_t cnt) { if (probe::off(1)) return; Unal8 x; x.v = v; *reinterpret_cast<Unal8 *>(f + wp) = x; wp += cnt; }
+    DW_DEV void rows_unit()                      // 32 <= wp <= 64
+    {
+        auto ld = [&](uint32_t b) { return reinterpret_cast<const Al4x8 *>(f + b)->v; };
+        if (!(probe::off(2))) {
+            const uint64_t a = ld(0), b = ld(8), c = ld(16), d = ld(24);
+            *reinterpret_cast<uint4 *>(dst) = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+            *reinterpret_cast<uint4 *>(dst + 16) = make_uint4((uint32_t)c, (uint32_t)(c >> 32), (uint32_t)d, (uint32_t)(d >> 32));
+        }
+        const uint64_t t0 = ld(32), t1 = ld(40), t2 = ld(48), t3 = ld(56);
+        Al4x8 x;
+        x.v = t0; *reinterpret_cast<Al4x8 *>(f) = x; x.v = t1; *reinterpret_cast<Al4x8 *>(f + 8) = x;
+        x.v = t2; *reinterpret_cast<Al4x8 *>(f + 16) = x; x.v = t3; *reinterpret_cast<Al4x8 *>(f + 24) = x;
+        dst += 32u; wp -= 32u;
+    }
+    DW_DEV void rows_flush()
+    {
+        if (!(probe::off(2))) { if (wp) fifo_store_range<BURST, Al4x8>(f, dst, 0u, wp); }
+        dst += wp; wp = skip = 0;
+    }
     DW_DEV void flush()
     {
         if (!(probe::off(2))) { if (wp > skip) store_range(skip, wp); if (DUAL) store_range_b(bdone, wp); }

@@ -342,8 +342,10 @@ DW_DEV uint32_t quality_block(const U4 &b, const QualLazy &ql, double sigma, con
 // The quality line of one read end, block by block (dwgsim.c:899-918): put(blk, n) receives the next n (1 .. 8) characters, little-endian in blk,
 // upper bytes zero.  n_chars characters in all; skip_first: the first one is drawn but not written (SOLiD BWA records drop the first colour's
 // quality, dwgsim.c:950-955).
-template <class F>
-DW_DEV void for_each_quality_block(const SimParams &p, RngKey key, uint32_t dom, uint64_t ii, uint32_t att, const uint32_t *qbw, int nq, int n_chars, bool skip_first, F &&put)
+// trip(n) is called at the end of every trip of the loop, n = trips made so far (1, 2, ...): the same number in every lane of a wave that is still in the
+// loop, whatever the lanes' put calls were -- what a caller keys wave-uniform work on.
+template <class F, class T>
+DW_DEV void for_each_quality_block(const SimParams &p, RngKey key, uint32_t dom, uint64_t ii, uint32_t att, const uint32_t *qbw, int nq, int n_chars, bool skip_first, F &&put, T &&trip)
 {
     auto deliver = [&](uint64_t blk, uint32_t nb, int pos) {       // clip to the line's length, drop the first character if asked to
         if ((int)nb > n_chars - pos) { nb = (uint32_t)(n_chars - pos); blk &= (1ull << (8 * nb)) - 1ull; }
@@ -363,6 +365,7 @@ DW_DEV void for_each_quality_block(const SimParams &p, RngKey key, uint32_t dom,
                 for (int b = 0; b < 8; ++b) { int32_t q = (int8_t)(((b < 4 ? lo : hi) >> (8 * (b & 3))) & 0xffu); q = q < 33 ? 33 : q > 73 ? 73 : q; blk |= (uint64_t)(uint32_t)q << (8 * b); }
             }
             deliver(blk, 8, pos);
+            trip((uint32_t)(pos >> 3) + 1u);
         }
         return;
     }
@@ -374,7 +377,13 @@ DW_DEV void for_each_quality_block(const SimParams &p, RngKey key, uint32_t dom,
         const uint32_t nb = quality_block(b, ql, p.quality_std, qbw, nq, pos, blk);
         deliver(blk, nb, pos);
         pos += (int)nb;
+        trip(t);
     }
+}
+template <class F>
+DW_DEV void for_each_quality_block(const SimParams &p, RngKey key, uint32_t dom, uint64_t ii, uint32_t att, const uint32_t *qbw, int nq, int n_chars, bool skip_first, F &&put)
+{
+    for_each_quality_block(p, key, dom, ii, att, qbw, nq, n_chars, skip_first, put, [](uint32_t) {});
 }
 
 // sum over i < c of the hexadecimal digits of b + i: what the running index adds to the names of c consecutive random reads (dwgsim.c:1044-1048)
@@ -443,7 +452,7 @@ template <int LPP, int OUT, int DT, int NTHR, int WR, int SPLIT>
 __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT)) k_simulate(SimArgs a)
 {
     static_assert(SPLIT == 0 || ((DT == 0 || DT == 3) && NTHR == SIM_THREADS), "the two-kernel form exists for the Illumina variants and for Ion Torrent with its buffers in LDS, 256-lane blocks");
-    DW_DYN_SHARED(uint32_t, dyn_lds);                                    // [lds_words][blockDim] packed bases
+    DW_DYN_SHARED(uint32_t, dyn_lds);                                    // [lds_words][blockDim] packed bases (the lockstep instances: [wave][lds_words][64], LSTR below)
     __shared__ uint32_t sm_all[4][16];     // one scratch row per scanned quantity: each is written once
     uint32_t (*const sm_bytes)[16] = sm_all, (*const sm_rand)[16] = sm_all + 3, (*const sm_one)[16] = sm_all;      // (the three-look-back forms: bytes in rows 0-2, random reads in row 3)
     __shared__ uint32_t s_ticket, s_slot;
@@ -469,6 +478,10 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
     constexpr bool ONE_LB = (DT == 0 || DT == 1) && SPLIT == 0;
     // the sequence line in lockstep 32-byte units (below, "write the record(s)"): Illumina, one kernel, bases staged in LDS, one output family through FifoWriter<32, false>
     constexpr bool SEQ_LOCKSTEP = DT == 0 && SPLIT == 0 && WR == 1 && NTHR == SIM_THREADS && OUT != 3;
+    // Those instances stage BY WAVE: word w of lane l of wave v at dyn_lds[v * lds_words * 64 + w * 64 + l] (the others: word w of lane t of the block at
+    // [w * nthr + t]) -- the same banks, the same total; but the words a wave stages are then one contiguous region that no other wave touches, and once the
+    // wave's sequence lines are written it is free: the quality line's row buffers stand there (below, QROWS)
+    constexpr int LSTR = SEQ_LOCKSTEP ? 64 : NTHR;      // words between two staged words of a lane
     const int LB_SHIFT = a.lb_shift;      // (bits of the byte sum; the host sizes it to the launch and refuses one whose two sums would not fit 62 bits: dw_host.cpp)
     const int tid = (int)threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
@@ -482,8 +495,8 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
     const size_t stage_words = SPLIT == 2 ? 0 : DT == 3 ? (size_t)(a.lds_words + a.flow_stack_words) : DT == 2 ? (size_t)a.flow_stack_words : GS ? 0 : (size_t)a.lds_words;      // (the second half of the two-kernel form reads its bases from HBM)
     uint32_t *const s_qb = dyn_lds + stage_words * nthr;
     if (SPLIT != 1) for (int q = tid; q < 2 * a.qb_words; q += nthr) s_qb[q] = (q < a.qb_words ? a.qbase[0] : a.qbase[1])[q < a.qb_words ? q : q - a.qb_words];
-    // this lane's text FIFO (record writer), behind the tables
-    uint8_t *const s_fifo = reinterpret_cast<uint8_t *>(dyn_lds + (((stage_words * nthr + 2 * (size_t)a.qb_words) + 3) & ~(size_t)3)) + (size_t)tid * (WR == 2 ? SIM_FIFO_BYTES_WIDE : SIM_FIFO_BYTES);
+    // this lane's text FIFO (record writer), behind the tables (worked out where a record is begun: the lane's number is alive up to there anyway, its product need not be)
+    auto lane_fifo = [&]() { return reinterpret_cast<uint8_t *>(dyn_lds + (((stage_words * nthr + 2 * (size_t)a.qb_words) + 3) & ~(size_t)3)) + (size_t)tid * (WR == 2 ? SIM_FIFO_BYTES_WIDE : SIM_FIFO_BYTES); };
     // (the first half of the two-kernel form, Illumina: s_lg, which the error sites below read at arbitrary entries, needs a barrier of its own -- Ion Torrent
     // has the one in front of fill_flow_tables)
     if (SPLIT == 0 || (SPLIT == 1 && !ION)) __syncthreads();
@@ -504,12 +517,12 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
     const uint64_t pair = sg->pair_off + pair_in;                 // inside the launch
     const RngKey key{a.p.seed, uniform_u32(sg->contig_index)};
     const int s = sel_len(a, j);
-    // this lane's packed bases: word w at lds[w * nthr].  Illumina / SOLiD: 4 bits per base; Ion Torrent: the one in-place buffer of the flow model,
+    // this lane's packed bases: word w at lds[w * LSTR].  Illumina / SOLiD: 4 bits per base; Ion Torrent: the one in-place buffer of the flow model,
     // 2 bits per base, a.lds_words words for a.cap = 16 a.lds_words bases (dw_read.hpp flow_errors), in LDS (DT = 3) or in a scratch slot (DT = 2);
     // the run stack of its pass 2 (a.flow_stack_words words per lane) is in LDS either way
     // (second half of the two-kernel form: the tile's staged bases where the first half left them, read once, in batches of eight words)
     uint32_t *lds = GS ? a.flow_scratch + (size_t)uniform_u32(s_slot) * ((size_t)(DT == 2 ? flow_words_per_lane(a.lds_words) : a.lds_words) * nthr) + tid
-                  : SPLIT == 2 ? a.split_state + (size_t)t * ((size_t)a.lds_words * nthr) + tid : dyn_lds + tid;
+                  : SPLIT == 2 ? a.split_state + (size_t)t * ((size_t)a.lds_words * nthr) + tid : SEQ_LOCKSTEP ? dyn_lds + wave * (a.lds_words * 64) + lane : dyn_lds + tid;
     uint32_t *const flow_stk = dyn_lds + (DT == 3 ? (size_t)a.lds_words * nthr : 0) + tid;
     const int capb = 16 * a.lds_words;              // (Ion Torrent) bases the buffer holds
 
@@ -545,9 +558,9 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
                     const bool rev = (j ? pd.strand1 : pd.strand0) != 0;
                     rr = gen_read(sel_hap(a, sc, pd.hap), sc.l, start, step, s, rev ? 1 : 0, FlowSink{lds, nthr, rev ? (capb >> 3) - 1 : ((capb - s) & ~7) >> 3, rev});
                 }
-                else if (probe::off(8)) { rr = ReadRes{(int32_t)start, 0, 0, 0, 0}; for (int w = 0; w * 8 < s; ++w) lds[w * nthr] = 0x32103210u; }
+                else if (probe::off(8)) { rr = ReadRes{(int32_t)start, 0, 0, 0, 0}; for (int w = 0; w * 8 < s; ++w) lds[w * LSTR] = 0x32103210u; }
                 else
-                rr = gen_read(sel_hap(a, sc, pd.hap), sc.l, start, step, s, j ? pd.strand1 : pd.strand0, WordSink{lds, nthr});
+                rr = gen_read(sel_hap(a, sc, pd.hap), sc.l, start, step, s, j ? pd.strand1 : pd.strand0, WordSink{lds, LSTR});
                 ok = rr.ext_coor >= 0 && rr.num_n <= a.p.max_n;
             }
         }
@@ -592,7 +605,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
             uint32_t pairs = (w & 2) ? ((w & 1) ? rb[3] : rb[2]) : ((w & 1) ? rb[1] : rb[0]);
             const int rem = s - 16 * w;
             if (rem < 16) pairs &= (1u << (2 * rem)) - 1u;
-            lds[w * nthr] = pairs;
+            lds[w * LSTR] = pairs;
         }
     } else
     if (valid && !(probe::off(4))) {
@@ -609,19 +622,19 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
                     prev_base = word >> 28;
                     word = (word ^ prevw) & 0x33333333u;
                 }
-                lds[w * nthr] = word & live;
+                lds[w * LSTR] = word & live;
             }
         } else {
             if (DT == 1) {                       // SOLiD: bases -> colours (dwgsim.c:845-858): colour = previous base ^ base, 4 if either is not ACGT; the adaptor counts as 'A' (:849)
                 uint32_t prev_base = 0;
                 for (int w = 0; w < nw; ++w) {
-                    uint32_t word = lds[w * nthr];
+                    uint32_t word = lds[w * LSTR];
                     const uint32_t prevw = (word << 4) | prev_base;
                     prev_base = word >> 28;
                     const uint32_t n = (word | prevw) & 0x44444444u;
                     word = ((word ^ prevw) & 0x33333333u & ~((n >> 1) | (n >> 2))) | n;
                     const int rem = s - 8 * w;
-                    lds[w * nthr] = rem >= 8 ? word : word & ((1u << (4 * rem)) - 1u);
+                    lds[w * LSTR] = rem >= 8 ? word : word & ((1u << (4 * rem)) - 1u);
                 }
             }
             // error sites (dwgsim.c:237 `drand48() < e[i]`, once per base that is not N): the gap chain of the read end at the largest rate of its ramp, thinned
@@ -646,7 +659,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
                     // first form of round 6 drew a block per ERROR, in a loop of its own whose trip count was the wave's largest error count)
                     if (k4 == 0u) { const U4 q2 = rng_block(key, D_SUB0 + (uint32_t)j, ii, att, 0, m >> 2); sw[0] = q2.x; sw[1] = q2.y; sw[2] = q2.z; sw[3] = q2.w; }
                     const int w = (int)(S >> 3), sh = 4 * (int)(S & 7u);
-                    const uint32_t word = lds[w * nthr];
+                    const uint32_t word = lds[w * LSTR];
                     bool hit = ((word >> sh) & 4u) == 0u;                                    // N bases / colour 4 take no error
                     if (ramp && hit) {                                                      // thinning: kept with probability thr[S] / thr_max (site m's own word)
                         const uint64_t ti = thr64[S];
@@ -657,7 +670,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
                         const uint32_t rwd = (k4 & 2u) ? ((k4 & 1u) ? sw[3] : sw[2]) : ((k4 & 1u) ? sw[1] : sw[0]);
                         const uint32_t add = 1u + (uint32_t)(((uint64_t)rwd * 3u) >> 32);      // (int)(u * 3.0 + 1), exact
                         const uint32_t c = (((word >> sh) & 3u) + add) & 3u;
-                        lds[w * nthr] = (word & ~(0xFu << sh)) | (c << sh);
+                        lds[w * LSTR] = (word & ~(0xFu << sh)) | (c << sh);
                         ++n_err; if (DT == 1 && S == 0u) err_first = 1;
                     }
                     ++m;
@@ -788,7 +801,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
                                     att | (is_rand ? 1u << 14 : 0u) | ((uint32_t)pd.strand0 << 15) | ((uint32_t)pd.strand1 << 16) | (ION ? (uint32_t)s_out << 17 : 0u));      // (Ion Torrent: the read's length after errors, < 2^15: the host checks the capacity)
         reinterpret_cast<uint4 *>(a.split_hand)[(size_t)t * nthr + tid] = hm;
         uint32_t *gs = a.split_state + (size_t)t * ((size_t)a.lds_words * nthr) + tid;
-        if (valid) for (int w = 0, n_w = ION ? (s_out + 15) >> 4 : nw; w < n_w; ++w) gs[(size_t)w * nthr] = lds[w * nthr];
+        if (valid) for (int w = 0, n_w = ION ? (s_out + 15) >> 4 : nw; w < n_w; ++w) gs[(size_t)w * nthr] = lds[w * LSTR];
         __syncthreads();
         if (tid == 0) { uint32_t r = 0, t1 = 0, t2 = 0; for (int w = 0; w < nwaves; ++w) { r += sm_rand[0][w]; t1 += sm_bytes[0][w]; t2 += sm_bytes[1][w]; } reinterpret_cast<uint4 *>(a.split_agg)[t] = make_uint4(r, t1, t2, 0u); }
         return;
@@ -824,7 +837,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
             for (int which = 0; which < 2; ++which) {            // 0: BWA stream of this end, 1: BFAST
                 if (!(OUT & (1 << which))) continue;
                 Out2<1, WR> o;
-                o.init(s_fifo, which ? a.out[2] + off_bf : (j ? a.out[1] : a.out[0]) + off_bwa, nullptr);
+                o.init(lane_fifo(), which ? a.out[2] + off_bf : (j ? a.out[1] : a.out[0]) + off_bwa, nullptr);
                 put_name_fixed(o, is_rand ? s_fixed[1] : s_fixed[0], is_rand ? a.rand_fixed : name_fixed, fixed_len);
                 if (is_rand) put_rand_tail(o, rand_ii);
                 else put_pair_tail(o, x0, x1, pd.strand0, pd.strand1,           // (value selects: a struct select would go through memory)
@@ -833,7 +846,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
                 else { o.put('\n'); o.put('A'); }
                 const int first = which ? 0 : 1;                // BWA skips the first colour and its quality
                 for (int w = 0; w * 8 < s_out; ++w) {
-                    const uint32_t word = lds[w * nthr];
+                    const uint32_t word = lds[w * LSTR];
                     const uint32_t c0 = which ? colour_digits4(word) : base_chars4(word), c1 = which ? colour_digits4(word >> 16) : base_chars4(word >> 16);
                     const int lo = w == 0 ? first : 0, hi = s_out - w * 8 < 8 ? s_out - w * 8 : 8;
                     if (lo == 0 && hi == 8) { o.put4(c0); o.put4(c1); }
@@ -853,7 +866,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
         const bool rec = valid && s_out > 0;
         Out2<OUT, WR> o;
         if (rec) {
-        o.init(s_fifo, (OUT & 1) ? (j ? a.out[1] : a.out[0]) + off_bwa : nullptr, (OUT & 2) ? a.out[2] + off_bf : nullptr);
+        o.init(lane_fifo(), (OUT & 1) ? (j ? a.out[1] : a.out[0]) + off_bwa : nullptr, (OUT & 2) ? a.out[2] + off_bf : nullptr);
         if (!(probe::off(16))) {
         put_name_fixed(o, is_rand ? s_fixed[1] : s_fixed[0], is_rand ? a.rand_fixed : name_fixed, fixed_len);
         if (is_rand) put_rand_tail(o, rand_ii);
@@ -868,7 +881,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
         // orientation of the flow model; reverse strand: base i of the record = base s_out-1-i of it (dwgsim.c:408-414): the eight positions ending at
         // s_out-1-8w, fetched together and turned round
         auto rec_word = [&](int w) -> uint32_t {
-            if (!ION) return lds[w * nthr];
+            if (!ION) return lds[w * LSTR];
             const Buf2 B{lds, nthr, a.lds_words};
             if (!flow_reversed) return pairs_to_nibbles(B.get8(8 * w));
             const int lo = s_out - 8 - 8 * w;                   // first position of the window (negative in the last, partial word)
@@ -883,13 +896,13 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
             for (int g0 = 0; g0 < full16; g0 += 4) {
                 uint32_t r[8];
 #pragma unroll
-                for (int k = 0; k < 8; ++k) r[k] = (g0 + (k >> 1) < full16) ? lds[(size_t)(2 * g0 + k) * nthr] : 0u;
+                for (int k = 0; k < 8; ++k) r[k] = (g0 + (k >> 1) < full16) ? lds[(size_t)(2 * g0 + k) * LSTR] : 0u;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) if (g0 + q < full16) o.put16(base_chars4(r[2 * q]), base_chars4(r[2 * q] >> 16), base_chars4(r[2 * q + 1]), base_chars4(r[2 * q + 1] >> 16));
             }
             if (s_out & 15) {                                     // the last, shorter group
                 const int w = 2 * full16, rem = s_out - 8 * w;
-                const uint32_t wa = lds[(size_t)w * nthr], wb = rem > 8 ? lds[(size_t)(w + 1) * nthr] : 0u;
+                const uint32_t wa = lds[(size_t)w * LSTR], wb = rem > 8 ? lds[(size_t)(w + 1) * LSTR] : 0u;
                 put_last_word(wa, rem);
                 if (rem > 8) put_last_word(wb, rem - 8);
             }
@@ -927,20 +940,20 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
             //   body  whole units of 32 bases from base na on, cut out of the staged words with one v_alignbit each (base na stands at nibble na & 7 of
             //         word na >> 3: the same shift for every unit of the lane) and stored from registers, two aligned dwordx4: no FIFO, no drain test;
             //   tail  the < 32 bases left and "\n+\n" into the empty FIFO, one drain test (at most 34 bytes).
-            // (staged words: word w of this lane at lds[w * nthr], nw of them; a unit that starts on a word boundary would read one word past its last)
+            // (staged words: word w of this lane at lds[w * LSTR], nw of them; a unit that starts on a word boundary would read one word past its last)
             auto &fw = o.a;
-            auto staged = [&](int w) -> uint32_t { return w < nw ? lds[w * nthr] : 0u; };
+            auto staged = [&](int w) -> uint32_t { return w < nw ? lds[w * LSTR] : 0u; };
             auto chars8 = [&](uint32_t nib) -> uint64_t { return (uint64_t)base_chars4(nib) | ((uint64_t)base_chars4(nib >> 16) << 32); };
             const int na = s_out < 32 - (int)fw.wp ? s_out : 32 - (int)fw.wp;      // 1 .. 32
 #pragma unroll
-            for (int k = 0; k < 4; ++k) if (8 * k < na) fw.poke8(8u * (uint32_t)k, chars8(lds[k * nthr]));      // (wp + 8 k < wp + na <= 32; base 8 k exists)
+            for (int k = 0; k < 4; ++k) if (8 * k < na) fw.poke8(8u * (uint32_t)k, chars8(lds[k * LSTR]));      // (wp + 8 k < wp + na <= 32; base 8 k exists)
             fw.advance((uint32_t)na);
             const uint32_t sh = 4u * ((uint32_t)na & 7u);
             const int left = s_out - na, rem = left & 31;
             int wi = na >> 3;
             uint32_t r0 = left > 0 ? staged(wi) : 0u;
             for (int c = left >> 5; c > 0; --c, wi += 4) {      // (a lane with a unit to write has drained above: wp == skip == 0)
-                const uint32_t r1 = lds[(wi + 1) * nthr], r2 = lds[(wi + 2) * nthr], r3 = lds[(wi + 3) * nthr], r4 = staged(wi + 4);
+                const uint32_t r1 = lds[(wi + 1) * LSTR], r2 = lds[(wi + 2) * LSTR], r3 = lds[(wi + 3) * LSTR], r4 = staged(wi + 4);
                 const uint32_t n0 = __builtin_amdgcn_alignbit(r1, r0, sh), n1 = __builtin_amdgcn_alignbit(r2, r1, sh);
                 const uint32_t n2 = __builtin_amdgcn_alignbit(r3, r2, sh), n3 = __builtin_amdgcn_alignbit(r4, r3, sh);
                 fw.burst32(make_uint4(base_chars4(n0), base_chars4(n0 >> 16), base_chars4(n1), base_chars4(n1 >> 16)),
@@ -969,10 +982,44 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
         if (SPLIT == 0) wave_priority(0);      // (a wave none of whose lanes has a record)
         DW_PROBE_MARK(a, 5); // sequence line
         // qualities (dwgsim.c:899-918): up to eight characters per Philox block of the read end's try stream, appended as they come
+        // QROWS (the SEQ_LOCKSTEP instances from 72 bytes of staging per lane on: a.qrows, block-uniform).  Appended through the FIFO, every Philox block's
+        // characters end in `if (wp >= 32) drain()`, and with the lanes of a wave out of phase some lane drains in nearly every trip: the wave walks the drain
+        // body -- LDS reads, a wait, two stores -- 26 times per line where a lane needs 4.7 drains.  But behind its sequence lines a wave never reads its staged
+        // bases again, and they are staged by wave (LSTR above): once every lane of the wave is here -- the ballot between two compiler barriers is the point of
+        // reconvergence --, the wave's region is 64 buffers of 4 lds_words >= 72 bytes, lane l's at byte l * 4 lds_words.  The buffer takes the FIFO's pending
+        // bytes and its place (FifoWriter::rows_take: the same f / wp / dst, no skip), a block's characters go down with one 8-byte store and no test, and on
+        // every FOURTH trip -- the trip count is the same in all lanes still in the loop -- the lanes with wp >= 32 take one unit together.  wp < 32 at the top
+        // of each group of four trips, so after four appends of at most 8 it is at most 63: the last store starts at 55 at the latest, the line's '\n' at 63,
+        // and ends at 72.  A lane that leaves the loop inside a group has at most 56 bytes pending with its '\n': one more unit, then the ragged rest.
+        // A wave with a record whose first unit has not left yet (skip != 0: a read end much shorter than its mate, -1 151 -2 16) goes the old way as a whole.
+        bool rows = false;
+        if constexpr (SEQ_LOCKSTEP) {
+            if (a.qrows) {
+                asm volatile("" ::: "memory");
+                rows = __ballot(rec && o.a.skip != 0u) == 0;
+                asm volatile("" ::: "memory");
+            }
+        }
+        if (SEQ_LOCKSTEP && rows) {
+            if constexpr (SEQ_LOCKSTEP) if (rec) {
+                auto &fw = o.a;
+                // (from the staging pointer, whose life ends here, not from the lane's number, which would have to live through the sequence line for it:
+                // lds = dyn_lds + wave * lds_words * 64 + lane, and the wave's part is a multiple of 64)
+                const uint32_t at = (uint32_t)(lds - dyn_lds);
+                fw.rows_take(reinterpret_cast<uint8_t *>(dyn_lds + (at & ~63u)) + (at & 63u) * (4u * (uint32_t)a.lds_words));
+                for_each_quality_block(a.p, key, D_QUAL0 + (uint32_t)j, ii, att, s_qb + (j ? a.qb_words : 0), s, s_out, false,
+                                       [&](uint64_t blk, uint32_t nb) { fw.rows_append(blk, nb); },
+                                       [&](uint32_t trips) { if ((trips & 3u) == 0u) { if (fw.wp >= 32u) fw.rows_unit(); } });
+                fw.rows_append((uint64_t)'\n', 1);
+                if (fw.wp >= 32u) fw.rows_unit();
+                fw.rows_flush();
+            }
+        } else {
         if (rec) {
             for_each_quality_block(a.p, key, D_QUAL0 + (uint32_t)j, ii, att, s_qb + (j ? a.qb_words : 0), s, s_out, false, [&](uint64_t blk, uint32_t nb) { o.putn(blk, nb); });
         }
         if (rec) { o.put('\n'); o.flush(); }
+        }
     }
     DW_PROBE_MARK(a, 6);     // quality line
     if (GS) {                // the scratch slot goes back to this XCD's free list once every wave's accesses to it are done

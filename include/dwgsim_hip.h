@@ -451,7 +451,8 @@ int dwgsim_hip_eval_debug_inflate(const void *bam, size_t len, int threads, int 
  * room for n candidates (exercises the exact re-run); "walk_seg_min" = n: segmented form of the walk's serial scans from n candidates on;
  * "writer" = 0 / 1: force the register / LDS-FIFO record writer; "sim_threads" = 64 / 256: force the one-wave blocks of the long-read variant / the 256-lane blocks (where their reads fit LDS);
  * "place_cap" = n: room for n undecided pairs per list in dwgsim_hip_count_random* (exercises its second run); "split" = 0 / 1: the Illumina
- * read kernel as one kernel with look-backs / as two kernels with the offsets computed in between (default: two for reads of up to 100 bases); "flow_slots" = n:
+ * read kernel as one kernel with look-backs / as two kernels with the offsets computed in between (default: two for reads of up to 100 bases); "qrows" = 0: the quality line of
+ * the single Illumina kernel stays on the per-lane FIFO where it would run in the wave's staging rows (reads of 137 bases on); "flow_slots" = n:
  * n scratch slots per XCD for the Ion Torrent read buffers / the long reads of the one-wave blocks (blocks wait for slots); "flow_cap" = n: the Ion Torrent
  * read capacity a job starts from (a read that outgrows it makes the batch run again with twice the room); "phases" = 1: print the phase
  * split of the -DDW_PHASE_TIMING analysis build. */
