@@ -50,8 +50,8 @@ const char BREAK_LINE[] = "*****************************************************
 struct Slot {
     HostMem h_text, h_res, h_offs;      // page-locked: the text (its capacity is the slot's), an EvalRes, the record offsets of a BAM chunk
     DevMem d_text, d_ends, d_tiles, d_res, d_spill, d_flags;      // text, u32, u32, EvalRes, u64, u8
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevStream st;               // (dwgsim_hip_eval_destroy waits for it before the context goes: the order in which the members then go does not matter)
+    DevEvent e0, e1;
     size_t fill = 0, ctx_len = 0, len = 0;
     uint32_t has_ctx = 0;
     bool busy = false;
@@ -241,10 +241,10 @@ int process_oldest(dwgsim_hip_eval_ctx *c)
     const int k = c->pending.front();
     c->pending.pop_front();
     Slot &S = c->s[k];
-    CK(hipStreamSynchronize(S.st));
+    CK(hipStreamSynchronize(S.st.get()));
     S.busy = false;
     float ms = 0;
-    if (hipEventElapsedTime(&ms, S.e0, S.e1) == hipSuccess) c->kernel_ms += ms;
+    if (hipEventElapsedTime(&ms, S.e0.get(), S.e1.get()) == hipSuccess) c->kernel_ms += ms;
     if (c->failed) return DWGSIM_HIP_OK;
     const EvalRes r = *S.h_res.get<EvalRes>();
     const uint32_t n_rec = r.n_lines - S.has_ctx;
@@ -328,14 +328,14 @@ int submit(dwgsim_hip_eval_ctx *c, size_t cut)
     Slot &S = c->s[c->cur];
     S.len = cut;
     *S.h_res.get<EvalRes>() = EvalRes{~0ull, 0, 0, 0};
-    CK(hipEventRecord(S.e0, S.st));
-    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, S.st));
-    CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st));
+    CK(hipEventRecord(S.e0.get(), S.st.get()));
+    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, S.st.get()));
+    CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st.get()));
     const EvalRecArgs A = rec_args(c, S.d_text.get(), S.d_ends.get<uint32_t>(), S.d_res.get<EvalRes>(), S.d_spill.get<uint64_t>(), c->o.p ? S.d_flags.get() : nullptr, S.has_ctx);
-    launch_chunk(c, S.st, A, cut, S.d_tiles.get<uint32_t>());
+    launch_chunk(c, S.st.get(), A, cut, S.d_tiles.get<uint32_t>());
     CK(hipGetLastError());
-    CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st));
-    CK(hipEventRecord(S.e1, S.st));
+    CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st.get()));
+    CK(hipEventRecord(S.e1.get(), S.st.get()));
     // the last line of the submitted chunk, then what follows it
     size_t lb = cut - 1;
     while (lb > 0 && S.h_text.get<char>()[lb - 1] != '\n') --lb;
@@ -350,15 +350,15 @@ int submit_bam(dwgsim_hip_eval_ctx *c)
     const uint32_t n = S.n_offs;
     S.len = cut;
     *S.h_res.get<EvalRes>() = EvalRes{~0ull, 0, n, 0};
-    CK(hipEventRecord(S.e0, S.st));
-    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, S.st));
-    CK(hipMemcpyAsync(S.d_ends.get(), S.h_offs.get(), n * sizeof(uint32_t), hipMemcpyHostToDevice, S.st));
-    CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st));
+    CK(hipEventRecord(S.e0.get(), S.st.get()));
+    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, S.st.get()));
+    CK(hipMemcpyAsync(S.d_ends.get(), S.h_offs.get(), n * sizeof(uint32_t), hipMemcpyHostToDevice, S.st.get()));
+    CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st.get()));
     const EvalRecArgs A = rec_args(c, S.d_text.get(), S.d_ends.get<uint32_t>(), S.d_res.get<EvalRes>(), S.d_spill.get<uint64_t>(), c->o.p ? S.d_flags.get() : nullptr, S.has_ctx);
-    launch_bam_chunk(c, S.st, A, n - S.has_ctx);
+    launch_bam_chunk(c, S.st.get(), A, n - S.has_ctx);
     CK(hipGetLastError());
-    CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st));
-    CK(hipEventRecord(S.e1, S.st));
+    CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st.get()));
+    CK(hipEventRecord(S.e1.get(), S.st.get()));
     const int r = hand_over(c, cut, S.h_offs.get<uint32_t>()[n - 1]);
     if (r) return r;
     Slot &T = c->s[c->cur];
@@ -710,8 +710,7 @@ dwgsim_hip_eval_ctx_t *dwgsim_hip_eval_create(const dwgsim_hip_eval_opts_t *opts
     const size_t cap = opts->chunk_bytes ? opts->chunk_bytes : DEFAULT_CHUNK;
     for (Slot &S : c->s) {
         if (slot_alloc(c, S, cap)) return fail(DWGSIM_HIP_ERR_DEVICE);
-        if (hipStreamCreate(&S.st) != hipSuccess || hipEventCreate(&S.e0) != hipSuccess || hipEventCreate(&S.e1) != hipSuccess)
-            return fail(DWGSIM_HIP_ERR_DEVICE);
+        if (S.st.create() != hipSuccess || S.e0.create() != hipSuccess || S.e1.create() != hipSuccess) return fail(DWGSIM_HIP_ERR_DEVICE);
     }
     const size_t hb = 5 * (EVAL_WIN + 1) * sizeof(unsigned long long);
     if (c->d_hist.reserve(hb, hb) != hipSuccess || hipMemset(c->d_hist.get(), 0, hb) != hipSuccess) return fail(DWGSIM_HIP_ERR_DEVICE);
@@ -876,12 +875,7 @@ void dwgsim_hip_eval_destroy(dwgsim_hip_eval_ctx_t *c)
 {
     if (!c) return;
     hipSetDevice(c->device);
-    for (Slot &S : c->s) {
-        if (S.st) hipStreamSynchronize(S.st);
-        if (S.st) hipStreamDestroy(S.st);
-        if (S.e0) hipEventDestroy(S.e0);
-        if (S.e1) hipEventDestroy(S.e1);
-    }
+    for (Slot &S : c->s) if (S.st) hipStreamSynchronize(S.st.get());      // (by name: the members' destructors only give handles and memory back)
     delete c;
 }
 
@@ -904,7 +898,7 @@ int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *c, const void *tex
         c->err = "debug_device_chunk: out of device memory";
         return DWGSIM_HIP_ERR_NOMEM;
     }
-    hipStream_t st = c->s[0].st;
+    hipStream_t st = c->s[0].st.get();
     if (hipMemcpy(dev.get(), text, len, hipMemcpyHostToDevice) != hipSuccess) {
         c->err = "debug_device_chunk: upload failed";
         return DWGSIM_HIP_ERR_DEVICE;
@@ -947,7 +941,7 @@ int dwgsim_hip_eval_debug_device_bam_chunk(dwgsim_hip_eval_ctx_t *c, const void 
         c->err = "debug_device_bam_chunk: out of device memory";
         return DWGSIM_HIP_ERR_NOMEM;
     }
-    hipStream_t st = c->s[0].st;
+    hipStream_t st = c->s[0].st.get();
     const EvalRes init = {~0ull, 0, (uint32_t)n, 0};
     if (hipMemcpy(dev.get(), records, len, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_offs.get(), offs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {

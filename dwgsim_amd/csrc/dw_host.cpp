@@ -12,6 +12,8 @@
 // ranges of several of them -- so a job of thousands of small contigs (the reference's contig loop, dwgsim.c:519-625, has no fixed cost per
 // contig) pays the walk chain, the launches and the host synchronisations once per group instead of once per contig.  A group of one contig
 // is the plain case.
+// Every device resource has an owner (dw_mem.hpp: DevMem, HostMem, DevEvent, DevStream), so a context is created in named steps (open_streams ..
+// upload_rand_name) that may fail anywhere, and destroyed by waiting for its streams and deleting it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -120,7 +122,7 @@ struct Counters {                   // a device counter block and its page-locke
 
 struct Slot {                       // one of the two batches a context can have in flight
     Counters counters;
-    hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_end = nullptr, ev_done = nullptr, ev_fetched = nullptr;
+    DevEvent ev_k0, ev_k1, ev_end, ev_done, ev_fetched;
     bool pending = false, empty = true, fetch_in_flight = false;
     int group = -1;                 // the group the batch in flight reads
     uint64_t n_pairs = 0, out_bytes[3] = {0, 0, 0}, gz_bytes[3] = {0, 0, 0};
@@ -133,23 +135,43 @@ struct Slot {                       // one of the two batches a context can have
 
 } // namespace
 
+// Every member that owns something of the device (DevMem, HostMem, DevEvent, DevStream, and the groups, pool and slots made of them) gives it back in its destructor,
+// in the reverse of the order below.  Any order is safe: dwgsim_hip_destroy synchronises every stream that exists before it deletes the context, so nothing in
+// flight reads a buffer, waits for an event or runs on a stream when the first member goes, and no member's destructor looks at another member.
 struct dwgsim_hip_ctx {
     dwgsim_hip_params_t prm;
     std::string read_prefix;
-    std::vector<uint8_t> flow;            // Ion Torrent flow order as base codes
-    DevMem d_flow;
+    // What dwgsim_hip_create's upload steps make once per context (upload_flow_order, upload_error_tables per read end, upload_rand_name); fill_sim_args hands them to the kernels
+    struct Tables {
+        std::vector<uint8_t> flow;            // Ion Torrent flow order as base codes
+        DevMem d_flow;                        // ... its 64 bytes on the device, and behind them the log2 table of the gap draws
+        double e_by[2] = {0, 0};
+        DevMem d_thr[2];                         // u64
+        DevMem d_thr32[2]; int e_full = 0;       // u32
+        DevMem d_qbase[2]; int32_t qb_words = 1;      // u32
+        DevMem d_rand_fixed; int32_t rand_fixed_len = 0;
+    } tab;
+    // The test / analysis knobs dwgsim_hip_debug_option sets and the values dwgsim_hip_debug_get reads back (the keys in quotes; what each means: at those two functions)
+    struct Debug {
+        int site_slots = -1; int64_t site_slot_cap = -1;      // "site_slots": -1 choose, 0 the look-back form, 1 the slot form; "site_slot_cap": a slot size to start from (tests: the overflow re-run)
+        bool seq_justify = false, dense_view = false;      // "justify_seq", "dense_view": the cross-check forms of the walk (one thread justifies a whole group; the views are made from every cell)
+        int flow_cap_forced = 0;               // "flow_cap" (tests): the capacity a job starts from, instead of flow_read_capacity()
+        int ion_lds = -1;                      // "ion_lds" (tests): where the Ion Torrent read buffers live (fill_sim_args)
+        int flow_slots = 0;                    // "flow_slots": scratch slots per XCD forced by the tests (0: as many as an XCD can hold blocks)
+        int64_t walk_cap = -1, place_cap = -1; bool phases = false;      // "walk_cap", "place_cap": capacities to start too small from (-1: the product's own); "phases": print the phase split of the -DDW_PHASE_TIMING build
+        int writer = -1, force_threads = 0, split = -1, qrows = 1;      // "writer", "sim_threads", "split", "qrows": the k_simulate form forced (choose_sim_form)
+        uint64_t place_open = 0; double walk_us = 0, count_us = 0;      // "place_open", "walk_us", "count_us": read back
+        int64_t sim_form = 0;                  // dwgsim_hip_debug_get("sim_form"): the k_simulate form of the last launch
+        int64_t walk_form = 0;                 // dwgsim_hip_debug_get("walk_form"): what the last walk enqueued was made of
+        double hap_len_us = 0, hap_write_us = 0, hap_copy_us = 0; bool hap_yardstick = false;      // "hap_len_us" / "hap_write_us" / "hap_copy_us", "hap_yardstick" (dwgsim_hip_debug_get / _option)
+    } dbg;
     int device = 0;
-    hipStream_t stream = nullptr;            // simulate: kernels of the batches
-    hipStream_t copy_stream = nullptr;       // device -> host copies of finished text
-    hipStream_t walk_stream = nullptr;       // uploads, the mutation walk, the mutated-cell list: a group can be prepared while another one is being simulated
-    hipStream_t count_stream = nullptr;      // count_random (k_place ..): behind the walk of ITS group only (an event), not behind the walks of groups issued later --
-                                             // on the walk stream the count of step k+1 waited for the walks of steps k+2, k+3 (round 6: profiles/r06_solo_rank_entry.txt)
+    DevStream stream;            // simulate: kernels of the batches
+    DevStream copy_stream;       // device -> host copies of finished text
+    DevStream walk_stream;       // uploads, the mutation walk, the mutated-cell list: a group can be prepared while another one is being simulated
+    DevStream count_stream;      // count_random (k_place ..): behind the walk of ITS group only (an event), not behind the walks of groups issued later --
+                                 // on the walk stream the count of step k+1 waited for the walks of steps k+2, k+3 (round 6: profiles/r06_solo_rank_entry.txt)
     std::string err;
-    double e_by[2] = {0, 0};
-    DevMem d_thr[2];                         // u64
-    DevMem d_thr32[2]; int e_full = 0;       // u32
-    DevMem d_qbase[2]; int32_t qb_words = 1;      // u32
-    DevMem d_rand_fixed; int32_t rand_fixed_len = 0;
     std::vector<Group> groups;
     std::vector<GroupMem> pool;              // the device memory, events and page-locked mirrors of dropped groups, handed to the next add_contigs whose cells fit: a
                                              // job of many groups pays its hipMalloc / hipFree (each a device-wide synchronisation) once, not at every group end
@@ -158,12 +180,10 @@ struct dwgsim_hip_ctx {
     DevMem meta, fail_summ, block_rand, status_all, out[DWGSIM_HIP_SLOTS][3], split_state, split_hand, split_agg, split_pre, split_chunk;
     // walk-stream working set (grow-only)
     DevMem w_slots, w_slot_aux;      // the site scan's per-block slots (dw_walk.hip k_site_scan_slots) and their counts / bases
-    int site_slots = -1; int64_t site_slot_cap = -1;      // "site_slots": -1 choose, 0 the look-back form, 1 the slot form; "site_slot_cap": a slot size to start from (tests: the overflow re-run)
     DevMem scratch_mask, scratch_cnt, scratch_status, w_cand, w_ev, w_flags, w_lo, w_sufmin, w_bound, w_ppos, w_pcells, up_ascii, l_pos, l_cells, place_segs, place_rand, place_list, place_aux;
-    HostMem h_up; hipEvent_t ev_up = nullptr; bool up_in_flight = false;      // page-locked staging of a group's sequence
+    HostMem h_up; DevEvent ev_up; bool up_in_flight = false;      // page-locked staging of a group's sequence
     HostMem h_place_segs, h_range_rand;      // page-locked: count_random's range table and its result per range
     std::vector<int32_t> h_ppos; std::vector<uint16_t> h_pcells; std::vector<Event> h_pev;      // file-driven mutations of the group being walked
-    bool seq_justify = false, dense_view = false;      // "justify_seq", "dense_view": the cross-check forms of the walk (one thread justifies a whole group; the views are made from every cell)
     MutInput mutin; bool has_mutin = false;                             // -m / -b / -v
     Regions regions; bool has_regions = false;                           // -x
     DevMem flow_scratch, flow_free;
@@ -174,19 +194,14 @@ struct dwgsim_hip_ctx {
     DevMem d_chain;                          // [0] random reads emitted before the next batch, [1] the abort rule's carry: handed from batch to batch on the device
     int chain_contig = -1; uint64_t chain_next_ii = 0;      // which (contig, read index) the carry continues
     bool has_carry_override = false; uint64_t carry_override = 0;
-    int flow_cap_forced = 0;               // "flow_cap" (tests): the capacity a job starts from, instead of flow_read_capacity()
     int flow_cap_mult = 1;                 // Ion Torrent: the read capacity is flow_read_capacity() times this; doubled when a read outgrew it (the reference doubles its buffers, dwgsim.c:296-311)
-    int ion_lds = -1;                      // "ion_lds" (tests): where the Ion Torrent read buffers live (fill_sim_args)
-    int n_cu = 0; int flow_slots = 0;      // compute units of the device; "flow_slots": scratch slots per XCD forced by the tests (0: as many as an XCD can hold blocks)
-    int64_t walk_cap = -1; bool phases = false; int writer = -1, force_threads = 0; int64_t place_cap = -1; uint64_t place_open = 0; double walk_us = 0, count_us = 0; int split = -1, qrows = 1;      // dwgsim_hip_debug_option / _debug_get
-    int64_t sim_form = 0;                  // dwgsim_hip_debug_get("sim_form"): the k_simulate form of the last launch
-    int64_t walk_form = 0;                 // dwgsim_hip_debug_get("walk_form"): what the last walk enqueued was made of
-    hipEvent_t ev_cnt0 = nullptr, ev_cnt1 = nullptr;
+    int n_cu = 0;                          // compute units of the device
+    DevEvent ev_cnt0, ev_cnt1;
     bool gzip_on = false; DevMem d_crc_table, d_crc_shift;      // dwgsim_hip_set_gzip (u32; d_crc_shift is uploaded last)
     HostMem h_stage;                       // pinned staging for fetch
-    hipStream_t hap_stream = nullptr;      // dwgsim_hip_haplotype_fetch: copies of its own (made at the first call), not behind the batches' copy-outs
-    DevEvent hap_ev[6]; double hap_len_us = 0, hap_write_us = 0, hap_copy_us = 0; bool hap_yardstick = false;      // "hap_len_us" / "hap_write_us" / "hap_copy_us", "hap_yardstick" (dwgsim_hip_debug_get / _option)
-    int hap_cur[2] = {-1, -1};             // ... and the group whose text the last dwgsim_hip_haplotype_fasta call for that haplotype built or found
+    DevStream hap_stream;                  // dwgsim_hip_haplotype_fetch: copies of its own (made at the first call), not behind the batches' copy-outs
+    DevEvent hap_ev[6];                    // dwgsim_hip_haplotype_fasta: the ends of its passes (dbg.hap_*_us)
+    int hap_cur[2] = {-1, -1};             // ... and the group whose text the last call for that haplotype built or found
     std::string txt, vcf;
 };
 
@@ -201,7 +216,7 @@ hipError_t dev_malloc(dwgsim_hip_ctx *c, void **p, size_t bytes)
     hipError_t e = DevKind::alloc(p, bytes);
     if (e == hipSuccess || c->pool.empty()) return e;
     (void)hipGetLastError();
-    hipStreamSynchronize(c->walk_stream);
+    hipStreamSynchronize(c->walk_stream.get());
     c->pool.clear();
     return DevKind::alloc(p, bytes);
 }
@@ -233,7 +248,7 @@ int upload(dwgsim_hip_ctx *c, DevMem &b, const void *src, size_t n)
 template <class T> int upload_table(dwgsim_hip_ctx_t *c, DevMem &d, const std::vector<T> &h, size_t slack)
 {
     HIPC(c, reserve(c, d, sizeof(T) * h.size(), sizeof(T) * (h.size() + slack)));
-    HIPC(c, hipMemcpyAsync(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, c->walk_stream));
+    HIPC(c, hipMemcpyAsync(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, c->walk_stream.get()));
     return 0;
 }
 
@@ -264,7 +279,7 @@ WalkParams walk_params(const dwgsim_hip_ctx *c)
     w.indel_min = c->prm.indel_min; w.is_hap = c->prm.is_hap; w.seed = (uint32_t)c->prm.seed;
     w.mut_thr = !(c->prm.mut_rate > 0) ? 0 : c->prm.mut_rate >= 1.0 ? 0x100000000ull : (uint64_t)ceil(c->prm.mut_rate * 4294967296.0);   // exact scaling by 2^32
     flow_gap_params(w.mut_thr, &w.gap_r, &w.gap_s);
-    w.lg = reinterpret_cast<const uint32_t *>(c->d_flow.get() + 64);      // (behind the flow order: made in dwgsim_hip_create for every context)
+    w.lg = reinterpret_cast<const uint32_t *>(c->tab.d_flow.get() + 64);      // (behind the flow order: made in dwgsim_hip_create for every context)
     return w;
 }
 
@@ -353,6 +368,18 @@ Group *get_group(dwgsim_hip_ctx_t *c, int contig, int *k = nullptr)
 }
 
 int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// What the device self-tests (dwgsim_hip_selftest_*) share: n zeroed u64 words on `device`, run(words) launches on the null stream (0, or an error code), the words come back in out
+template <class Run> int selftest_words(int device, size_t n, uint64_t *out, Run run)
+{
+    if (!out || hipSetDevice(device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    DevMem d;
+    if (d.reserve(n * sizeof(uint64_t), n * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
+    hipMemset(d.get(), 0, n * sizeof(uint64_t));
+    if (const int rc = run(d.get<uint64_t>())) return rc;
+    const hipError_t e = hipMemcpy(out, d.get(), n * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
+}
 
 } // namespace
 
@@ -509,10 +536,165 @@ static int flow_base_capacity(const dwgsim_hip_ctx *c)
 {
     const int lmax = c->prm.length[0] > c->prm.length[1] ? c->prm.length[0] : c->prm.length[1];
     const double emax = c->prm.e_start[0] > c->prm.e_start[1] ? c->prm.e_start[0] : c->prm.e_start[1];
-    return c->flow_cap_forced > 0 ? c->flow_cap_forced : flow_read_capacity(lmax, emax, c->flow);
+    return c->dbg.flow_cap_forced > 0 ? c->dbg.flow_cap_forced : flow_read_capacity(lmax, emax, c->tab.flow);
 }
 
 static int set_err(int *err, int v) { if (err) *err = v; return v; }
+
+// ---- dwgsim_hip_create, step by step (each fills one part of the context and returns 0 or the error code; create runs them in order) ----
+
+// The four streams every context has, and the events that are not a slot's or a group's
+static int open_streams(dwgsim_hip_ctx *c)
+{
+    HIPC(c, hipSetDevice(c->device));
+    // What prepares the NEXT group (upload, walk, random-read count: walk stream) runs at the batches' own priority.  Rounds 3-5 put it below them ("fills the
+    // thinning tail of every launch instead of taking slots"): its fifteen small kernels then ran one after the other in the gap between two k_simulate launches --
+    // 0.07 of the 0.46 ms of an E. coli-sized step.  At equal priority they slip in as slots fall free while the big kernel runs and are done when it ends: E. coli-sized
+    // 1 146-1 159 against 980-1 060 M pairs/s, chr20-sized / whole genome / N-rank weak lines unchanged (profiles/r06_bench_lines_final.txt 15).
+    int prio_least = 0, prio_greatest = 0;
+    HIPC(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    // (DWGSIM_HIP_WALK_PRIO=low|mid|above: analysis -- the walk stream below the batches (rounds 3-5), between the two, or the batches below the walk)
+    int prio_walk = prio_greatest, prio_batch = prio_greatest;
+    if (const char *e = getenv("DWGSIM_HIP_WALK_PRIO")) {
+        prio_walk = !strcmp(e, "high") || !strcmp(e, "above") ? prio_greatest : !strcmp(e, "mid") ? (prio_least + prio_greatest) / 2 : prio_least;
+        if (!strcmp(e, "above")) prio_batch = prio_least;
+    }
+    HIPC(c, c->stream.create(prio_batch));
+    HIPC(c, c->copy_stream.create(prio_greatest));
+    HIPC(c, c->walk_stream.create(prio_walk));
+    HIPC(c, c->count_stream.create(prio_walk));
+    HIPC(c, c->ev_up.create()); HIPC(c, c->ev_cnt0.create()); HIPC(c, c->ev_cnt1.create());
+    return 0;
+}
+
+// The counter blocks of the context and of each slot, the chain words (zeroed), and each slot's events
+static int reserve_counter_blocks(dwgsim_hip_ctx *c)
+{
+    const size_t cnt_bytes = N_COUNTERS * sizeof(uint64_t);
+    auto counters = [&](Counters &k) -> int { HIPC(c, reserve(c, k.d, cnt_bytes, cnt_bytes)); HIPC(c, k.h.reserve(cnt_bytes, cnt_bytes)); return 0; };
+    if (int rc = counters(c->counters)) return rc;
+    HIPC(c, reserve(c, c->d_wcounters, sizeof(WalkCounters), sizeof(WalkCounters)));
+    if (int rc = counters(c->pcounters)) return rc;
+    HIPC(c, reserve(c, c->d_chain, 4 * sizeof(uint64_t), 4 * sizeof(uint64_t)));
+    HIPC(c, hipMemset(c->d_chain.get(), 0, 4 * sizeof(uint64_t)));
+    for (Slot &sl : c->slot) {
+        if (int rc = counters(sl.counters)) return rc;
+        HIPC(c, reserve(c, sl.d_rerun_chain, 2 * sizeof(uint64_t), 2 * sizeof(uint64_t)));
+        HIPC(c, sl.ev_k0.create()); HIPC(c, sl.ev_k1.create()); HIPC(c, sl.ev_end.create()); HIPC(c, sl.ev_done.create()); HIPC(c, sl.ev_fetched.create());
+    }
+    return 0;
+}
+
+// The flow order (64 bytes) and, behind it, the log2 table the flow model's gap draws interpolate in (dw_kernels.hpp flow_log2_table)
+static int upload_flow_order(dwgsim_hip_ctx *c)
+{
+    std::vector<uint8_t> fl(64 + sizeof(uint32_t) * FLOW_LG_ENTRIES, 4); for (size_t i = 0; i < c->tab.flow.size() && i < 64; ++i) fl[i] = c->tab.flow[i];
+    flow_log2_table(reinterpret_cast<uint32_t *>(fl.data() + 64));
+    return upload(c, c->tab.d_flow, fl.data(), fl.size());
+}
+
+struct CalibRun { int mult; bool outgrown; int32_t n_err, counts; };      // the room the reads needed (times flow_read_capacity), whether one still outgrew it; int32 accumulators as in the reference
+
+// -B, the buffer mechanics: the 10^6 random reads of read end i at flow error rate e, run with room doubled until no read outgrows its buffers
+static int calibrate_end(dwgsim_hip_ctx *c, int i, double e, CalibRun *r)
+{
+    const int len = c->prm.length[i];
+    CalibArgs ca;
+    ca.seed = (uint32_t)c->prm.seed; ca.end = i; ca.len = len; ca.n_reads = 1000000;       // ERROR_RATE_NUM_RANDOM_READS, dwgsim_opt.h:5
+    ca.thr = !(e > 0) ? 0 : e >= 1.0 ? 0x100000000ull : (uint64_t)ceil(e * 4294967296.0);
+    flow_gap_params(ca.thr, &ca.gap_r, &ca.gap_s);
+    ca.flow = c->tab.d_flow.get(); ca.flow_len = (int32_t)c->tab.flow.size();
+    // a read that outgrows its buffers: once more with twice the room (the reference doubles its buffers, dwgsim.c:296-311) -- by the rule of
+    // dwgsim_hip_wait: up to FLOW_CAP_MAX bases per read.  The scratch holds a CHUNK of the 10^6 reads (at most ~2 GiB), so the room a read
+    // may take does not depend on how many reads there are (round 5 stopped at 16 x: -B then refused flow orders the simulate path handles)
+    const int64_t base_cap = flow_read_capacity(len, e, c->tab.flow);
+    int mult = 1;
+    for (;; mult *= 2) {
+        ca.lds_words = (int32_t)((base_cap * mult + 15) / 16);       // the flow model's one buffer per lane: 16 bases per word
+        ca.stack_words = std::min(FLOW_STACK_WORDS * mult, FLOW_STACK_WORDS_MAX);
+        const size_t per_block = (size_t)ca.lds_words * PAIRS_PER_BLOCK * sizeof(uint32_t);
+        const size_t nblk_all = (size_t)((ca.n_reads + PAIRS_PER_BLOCK - 1) / PAIRS_PER_BLOCK);
+        const size_t nblk = std::max<size_t>(1, std::min(nblk_all, ((size_t)2 << 30) / per_block));
+        ca.chunk_reads = (uint64_t)nblk * PAIRS_PER_BLOCK;
+        if (int rc = ensure(c, c->flow_scratch, per_block * nblk)) return rc;
+        ca.scratch = c->flow_scratch.get<uint32_t>(); ca.counters = c->counters.dev();
+        HIPC(c, hipMemsetAsync(c->counters.dev(), 0, N_COUNTERS * sizeof(uint64_t), c->stream.get()));
+        for (ca.first_read = 0; ca.first_read < ca.n_reads; ca.first_read += ca.chunk_reads) launch_calibrate(c->stream.get(), ca);
+        HIPC(c, hipMemcpyAsync(c->counters.host(), c->counters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream.get()));
+        HIPC(c, hipStreamSynchronize(c->stream.get()));
+        if (!c->counters.host()[2] || base_cap * (int64_t)mult * 2 > (int64_t)FLOW_CAP_MAX) break;
+    }
+    r->mult = mult; r->outgrown = c->counters.host()[2] != 0; r->n_err = (int32_t)c->counters.host()[8]; r->counts = (int32_t)c->counters.host()[9];
+    return 0;
+}
+
+// -B (dwgsim_opt.c:415-457): rescale the flow error so that the per-base error rate of 10^6 random reads matches -e.  Reads that outgrow their buffers
+// are reported as DWGSIM_HIP_ERR_FAILED: an option set, not the device.
+static int calibrate_base_error(dwgsim_hip_ctx *c)
+{
+    if (c->prm.data_type != 2 || !c->prm.use_base_error) return 0;
+    double sf = 0.0;
+    for (int i = 0; i < 2; ++i) {
+        const int len = c->prm.length[i];
+        if (len <= 0) continue;
+        fprintf(stderr, "[dwgsim_core] Updating error rate for end %d\n", i + 1);
+        if (0 < i && len == c->prm.length[1 - i]) {
+            c->prm.e_start[i] = c->prm.e_start[1 - i]; c->prm.e_end[i] = c->prm.e_end[1 - i];
+            fprintf(stderr, "[dwgsim_core] Using scaling factor from previous end\n[dwgsim_core] Updated with scaling factor %.5lf\n", sf);
+            continue;
+        }
+        const double e = c->prm.e_start[i];
+        CalibRun r;
+        if (int rc = calibrate_end(c, i, e, &r)) return rc;
+        // the job's reads will need the room the calibration's needed: start there instead of running the first overflowing batch twice
+        if (r.mult > c->flow_cap_mult) c->flow_cap_mult = r.mult;
+        if (r.outgrown) { c->err = "-B calibration: a read outgrew its flow-space buffer (the flow model's growth at this error rate and flow order: INTEGRATION.md)"; return DWGSIM_HIP_ERR_FAILED; }
+        sf = e / (r.n_err / (1.0 * r.counts));
+        c->prm.e_end[i] *= sf; c->prm.e_start[i] = c->prm.e_end[i];
+        fprintf(stderr, "[dwgsim_core] Updated with scaling factor %.5lf!\n", sf);
+    }
+    return 0;
+}
+
+// Read end j's per-position error thresholds and base qualities (dwgsim_opt.c:459-460, dwgsim.c:237, :906-910)
+static int upload_error_tables(dwgsim_hip_ctx *c, int j)
+{
+    auto &T = c->tab;
+    const int n = c->prm.length[j];
+    if (n <= 0) return 0;
+    T.e_by[j] = (c->prm.e_end[j] - c->prm.e_start[j]) / n;
+    std::vector<uint64_t> thr((size_t)n); std::vector<int8_t> qb((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const double ei = c->prm.e_start[j] + T.e_by[j] * i;
+        thr[(size_t)i] = !(ei > 0) ? 0 : ei >= 1.0 ? 0x100000000ull : (uint64_t)ceil(ei * 4294967296.0);   // u = w * 2^-32 < ei  <=>  w < ceil(ei * 2^32) (exact: scaling by 2^32 is exact)
+        char q;
+        if (ei > 0) q = (char)((int)(-10.0 * log(ei) / log(10.0) + 0.499) + '!'); else q = 40 + '!';
+        qb[(size_t)i] = (int8_t)q;
+    }
+    if (int rc = upload(c, T.d_thr[j], thr.data(), sizeof(uint64_t) * (size_t)n)) return rc;
+    // packed table: n entries, then the last one repeated (>= 8 copies), the same word count for both read ends
+    const int lmax = c->prm.length[0] > c->prm.length[1] ? c->prm.length[0] : c->prm.length[1];
+    T.qb_words = (lmax + 4 + 3) / 4 + 2;      // (a block of the quality stream looks at eight positions: three words from any position <= lmax)
+    std::vector<int8_t> padded((size_t)T.qb_words * 4, qb[(size_t)n - 1]);
+    memcpy(padded.data(), qb.data(), (size_t)n);
+    if (int rc = upload(c, T.d_qbase[j], padded.data(), padded.size())) return rc;
+    std::vector<uint32_t> t32(((size_t)n + 7) / 8 * 8, 0u);
+    for (int i = 0; i < n; ++i) {
+        if (thr[(size_t)i] >= 0x100000000ull) { t32[(size_t)i] = 0xFFFFFFFFu; T.e_full = 1; }
+        else t32[(size_t)i] = (uint32_t)thr[(size_t)i];
+    }
+    if (T.e_full) for (int i = 0; i < n; ++i) if (thr[(size_t)i] == 0xFFFFFFFFull) { c->err = "an error rate within 2^-32 of (but not equal to) 1 next to one equal to 1 is not representable"; return DWGSIM_HIP_ERR_DEVICE; }
+    return upload(c, T.d_thr32[j], t32.data(), sizeof(uint32_t) * t32.size());
+}
+
+// '@' + "[prefix_]rand", zero padded to >= 256 + 16 bytes (the kernel stages 128 bytes in LDS)
+static int upload_rand_name(dwgsim_hip_ctx *c)
+{
+    std::string rf = c->read_prefix.empty() ? std::string("rand") : c->read_prefix + "_rand";
+    c->tab.rand_fixed_len = (int32_t)rf.size();
+    std::string rbuf = "@" + rf; rbuf.resize(rbuf.size() < 256 ? 272 : rbuf.size() + 16, '\0');
+    return upload(c, c->tab.d_rand_fixed, rbuf.data(), rbuf.size());
+}
 
 dwgsim_hip_ctx_t *dwgsim_hip_create(const dwgsim_hip_params_t *p, int device, int *err)
 {
@@ -527,132 +709,17 @@ dwgsim_hip_ctx_t *dwgsim_hip_create(const dwgsim_hip_params_t *p, int device, in
     dwgsim_hip_ctx *c = new dwgsim_hip_ctx();
     c->prm = *p;
     if (p->read_prefix) c->read_prefix = p->read_prefix;
-    if (p->data_type == 2) for (const char *q = p->flow_order; *q; ++q) c->flow.push_back(nt4((unsigned char)*q));
+    if (p->data_type == 2) for (const char *q = p->flow_order; *q; ++q) c->tab.flow.push_back(nt4((unsigned char)*q));
     c->prm.read_prefix = nullptr; c->prm.flow_order = nullptr;
     c->device = device;
     { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess) c->n_cu = pr.multiProcessorCount; if (c->n_cu <= 0) c->n_cu = 256; }
-    int fail_code = DWGSIM_HIP_ERR_DEVICE;       // (the -B calibration reports reads that outgrow their buffers as DWGSIM_HIP_ERR_FAILED: an option set, not the device)
-    auto fail = [&](const char *what) { fprintf(stderr, "dwgsim-hip: %s: %s\n", what, c->err.c_str()); set_err(err, fail_code); dwgsim_hip_destroy(c); return (dwgsim_hip_ctx *)nullptr; };
-    auto init = [&]() -> int {
-        HIPC(c, hipSetDevice(device));
-        // What prepares the NEXT group (upload, walk, random-read count: walk stream) runs at the batches' own priority.  Rounds 3-5 put it below them ("fills the
-        // thinning tail of every launch instead of taking slots"): its fifteen small kernels then ran one after the other in the gap between two k_simulate launches --
-        // 0.07 of the 0.46 ms of an E. coli-sized step.  At equal priority they slip in as slots fall free while the big kernel runs and are done when it ends: E. coli-sized
-        // 1 146-1 159 against 980-1 060 M pairs/s, chr20-sized / whole genome / N-rank weak lines unchanged (profiles/r06_bench_lines_final.txt 15).
-        int prio_least = 0, prio_greatest = 0;
-        HIPC(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-        // (DWGSIM_HIP_WALK_PRIO=low|mid|above: analysis -- the walk stream below the batches (rounds 3-5), between the two, or the batches below the walk)
-        int prio_walk = prio_greatest, prio_batch = prio_greatest;
-        if (const char *e = getenv("DWGSIM_HIP_WALK_PRIO")) {
-            prio_walk = !strcmp(e, "high") || !strcmp(e, "above") ? prio_greatest : !strcmp(e, "mid") ? (prio_least + prio_greatest) / 2 : prio_least;
-            if (!strcmp(e, "above")) prio_batch = prio_least;
-        }
-        HIPC(c, hipStreamCreateWithPriority(&c->stream, hipStreamDefault, prio_batch));
-        HIPC(c, hipStreamCreateWithPriority(&c->copy_stream, hipStreamDefault, prio_greatest));
-        HIPC(c, hipStreamCreateWithPriority(&c->walk_stream, hipStreamDefault, prio_walk));
-        HIPC(c, hipStreamCreateWithPriority(&c->count_stream, hipStreamDefault, prio_walk));
-        HIPC(c, hipEventCreate(&c->ev_up)); HIPC(c, hipEventCreate(&c->ev_cnt0)); HIPC(c, hipEventCreate(&c->ev_cnt1));
-        const size_t cnt_bytes = N_COUNTERS * sizeof(uint64_t);
-        auto counters = [&](Counters &k) -> int { HIPC(c, reserve(c, k.d, cnt_bytes, cnt_bytes)); HIPC(c, k.h.reserve(cnt_bytes, cnt_bytes)); return 0; };
-        if (counters(c->counters)) return -1;
-        HIPC(c, reserve(c, c->d_wcounters, sizeof(WalkCounters), sizeof(WalkCounters)));
-        if (counters(c->pcounters)) return -1;
-        HIPC(c, reserve(c, c->d_chain, 4 * sizeof(uint64_t), 4 * sizeof(uint64_t)));
-        HIPC(c, hipMemset(c->d_chain.get(), 0, 4 * sizeof(uint64_t)));
-        for (Slot &sl : c->slot) {
-            if (counters(sl.counters)) return -1;
-            HIPC(c, reserve(c, sl.d_rerun_chain, 2 * sizeof(uint64_t), 2 * sizeof(uint64_t)));
-            HIPC(c, hipEventCreate(&sl.ev_k0)); HIPC(c, hipEventCreate(&sl.ev_k1)); HIPC(c, hipEventCreate(&sl.ev_end)); HIPC(c, hipEventCreate(&sl.ev_done)); HIPC(c, hipEventCreate(&sl.ev_fetched));
-        }
-        {   // the flow order (64 bytes) and, behind it, the log2 table the flow model's gap draws interpolate in (dw_kernels.hpp flow_log2_table)
-            std::vector<uint8_t> fl(64 + sizeof(uint32_t) * FLOW_LG_ENTRIES, 4); for (size_t i = 0; i < c->flow.size() && i < 64; ++i) fl[i] = c->flow[i];
-            flow_log2_table(reinterpret_cast<uint32_t *>(fl.data() + 64));
-            if (upload(c, c->d_flow, fl.data(), fl.size())) return -1;
-        }
-        // -B (dwgsim_opt.c:415-457): rescale the flow error so that the per-base error rate of 10^6 random reads matches -e
-        if (c->prm.data_type == 2 && c->prm.use_base_error) {
-            double sf = 0.0;
-            for (int i = 0; i < 2; ++i) {
-                const int len = c->prm.length[i];
-                if (len <= 0) continue;
-                fprintf(stderr, "[dwgsim_core] Updating error rate for end %d\n", i + 1);
-                if (0 < i && len == c->prm.length[1 - i]) {
-                    c->prm.e_start[i] = c->prm.e_start[1 - i]; c->prm.e_end[i] = c->prm.e_end[1 - i];
-                    fprintf(stderr, "[dwgsim_core] Using scaling factor from previous end\n[dwgsim_core] Updated with scaling factor %.5lf\n", sf);
-                    continue;
-                }
-                const double e = c->prm.e_start[i];
-                CalibArgs ca;
-                ca.seed = (uint32_t)c->prm.seed; ca.end = i; ca.len = len; ca.n_reads = 1000000;       // ERROR_RATE_NUM_RANDOM_READS, dwgsim_opt.h:5
-                ca.thr = !(e > 0) ? 0 : e >= 1.0 ? 0x100000000ull : (uint64_t)ceil(e * 4294967296.0);
-                flow_gap_params(ca.thr, &ca.gap_r, &ca.gap_s);
-                ca.flow = c->d_flow.get(); ca.flow_len = (int32_t)c->flow.size();
-                // a read that outgrows its buffers: once more with twice the room (the reference doubles its buffers, dwgsim.c:296-311) -- by the rule of
-                // dwgsim_hip_wait: up to FLOW_CAP_MAX bases per read.  The scratch holds a CHUNK of the 10^6 reads (at most ~2 GiB), so the room a read
-                // may take does not depend on how many reads there are (round 5 stopped at 16 x: -B then refused flow orders the simulate path handles)
-                const int64_t base_cap = flow_read_capacity(len, e, c->flow);
-                int mult = 1;
-                for (;; mult *= 2) {
-                    ca.lds_words = (int32_t)((base_cap * mult + 15) / 16);       // the flow model's one buffer per lane: 16 bases per word
-                    ca.stack_words = std::min(FLOW_STACK_WORDS * mult, FLOW_STACK_WORDS_MAX);
-                    const size_t per_block = (size_t)ca.lds_words * PAIRS_PER_BLOCK * sizeof(uint32_t);
-                    const size_t nblk_all = (size_t)((ca.n_reads + PAIRS_PER_BLOCK - 1) / PAIRS_PER_BLOCK);
-                    const size_t nblk = std::max<size_t>(1, std::min(nblk_all, ((size_t)2 << 30) / per_block));
-                    ca.chunk_reads = (uint64_t)nblk * PAIRS_PER_BLOCK;
-                    if (ensure(c, c->flow_scratch, per_block * nblk)) return -1;
-                    ca.scratch = c->flow_scratch.get<uint32_t>(); ca.counters = c->counters.dev();
-                    HIPC(c, hipMemsetAsync(c->counters.dev(), 0, N_COUNTERS * sizeof(uint64_t), c->stream));
-                    for (ca.first_read = 0; ca.first_read < ca.n_reads; ca.first_read += ca.chunk_reads) launch_calibrate(c->stream, ca);
-                    HIPC(c, hipMemcpyAsync(c->counters.host(), c->counters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-                    HIPC(c, hipStreamSynchronize(c->stream));
-                    if (!c->counters.host()[2] || base_cap * (int64_t)mult * 2 > (int64_t)FLOW_CAP_MAX) break;
-                }
-                // the job's reads will need the room the calibration's needed: start there instead of running the first overflowing batch twice
-                if (mult > c->flow_cap_mult) c->flow_cap_mult = mult;
-                if (c->counters.host()[2]) { c->err = "-B calibration: a read outgrew its flow-space buffer (the flow model's growth at this error rate and flow order: INTEGRATION.md)"; fail_code = DWGSIM_HIP_ERR_FAILED; return -1; }
-                const int32_t n_err = (int32_t)c->counters.host()[8], counts = (int32_t)c->counters.host()[9];       // int32 accumulators as in the reference
-                sf = e / (n_err / (1.0 * counts));
-                c->prm.e_end[i] *= sf; c->prm.e_start[i] = c->prm.e_end[i];
-                fprintf(stderr, "[dwgsim_core] Updated with scaling factor %.5lf!\n", sf);
-            }
-        }
-        // per-position error thresholds and base qualities (dwgsim_opt.c:459-460, dwgsim.c:237, :906-910)
-        for (int j = 0; j < 2; ++j) {
-            const int n = c->prm.length[j];
-            if (n <= 0) continue;
-            c->e_by[j] = (c->prm.e_end[j] - c->prm.e_start[j]) / n;
-            std::vector<uint64_t> thr((size_t)n); std::vector<int8_t> qb((size_t)n);
-            for (int i = 0; i < n; ++i) {
-                const double ei = c->prm.e_start[j] + c->e_by[j] * i;
-                thr[(size_t)i] = !(ei > 0) ? 0 : ei >= 1.0 ? 0x100000000ull : (uint64_t)ceil(ei * 4294967296.0);   // u = w * 2^-32 < ei  <=>  w < ceil(ei * 2^32) (exact: scaling by 2^32 is exact)
-                char q;
-                if (ei > 0) q = (char)((int)(-10.0 * log(ei) / log(10.0) + 0.499) + '!'); else q = 40 + '!';
-                qb[(size_t)i] = (int8_t)q;
-            }
-            if (upload(c, c->d_thr[j], thr.data(), sizeof(uint64_t) * (size_t)n)) return -1;
-            {   // packed table: n entries, then the last one repeated (>= 8 copies), the same word count for both read ends
-                const int lmax = c->prm.length[0] > c->prm.length[1] ? c->prm.length[0] : c->prm.length[1];
-                c->qb_words = (lmax + 4 + 3) / 4 + 2;      // (a block of the quality stream looks at eight positions: three words from any position <= lmax)
-                std::vector<int8_t> padded((size_t)c->qb_words * 4, qb[(size_t)n - 1]);
-                memcpy(padded.data(), qb.data(), (size_t)n);
-                if (upload(c, c->d_qbase[j], padded.data(), padded.size())) return -1;
-            }
-            std::vector<uint32_t> t32(((size_t)n + 7) / 8 * 8, 0u);
-            for (int i = 0; i < n; ++i) {
-                if (thr[(size_t)i] >= 0x100000000ull) { t32[(size_t)i] = 0xFFFFFFFFu; c->e_full = 1; }
-                else t32[(size_t)i] = (uint32_t)thr[(size_t)i];
-            }
-            if (c->e_full) for (int i = 0; i < n; ++i) if (thr[(size_t)i] == 0xFFFFFFFFull) { c->err = "an error rate within 2^-32 of (but not equal to) 1 next to one equal to 1 is not representable"; return -1; }
-            if (upload(c, c->d_thr32[j], t32.data(), sizeof(uint32_t) * t32.size())) return -1;
-        }
-        // device copy: '@' + "[prefix_]rand", zero padded to >= 256 + 16 bytes (the kernel stages 128 bytes in LDS)
-        std::string rf = c->read_prefix.empty() ? std::string("rand") : c->read_prefix + "_rand";
-        c->rand_fixed_len = (int32_t)rf.size();
-        std::string rbuf = "@" + rf; rbuf.resize(rbuf.size() < 256 ? 272 : rbuf.size() + 16, '\0');
-        if (upload(c, c->d_rand_fixed, rbuf.data(), rbuf.size())) return -1;
-        return 0;
-    };
-    if (init() != 0) return fail("context initialisation failed");
+    auto fail = [&](int code) { fprintf(stderr, "dwgsim-hip: context initialisation failed: %s\n", c->err.c_str()); set_err(err, code); dwgsim_hip_destroy(c); return (dwgsim_hip_ctx *)nullptr; };
+    if ((rc = open_streams(c))) return fail(rc);
+    if ((rc = reserve_counter_blocks(c))) return fail(rc);
+    if ((rc = upload_flow_order(c))) return fail(rc);
+    if ((rc = calibrate_base_error(c))) return fail(rc);
+    for (int j = 0; j < 2; ++j) if ((rc = upload_error_tables(c, j))) return fail(rc);
+    if ((rc = upload_rand_name(c))) return fail(rc);
     set_err(err, DWGSIM_HIP_OK);
     return c;
 }
@@ -662,26 +729,14 @@ dwgsim_hip_ctx_t *dwgsim_hip_create(const dwgsim_hip_params_t *p, int device, in
 // out[0..2] = bitwise differences (division, sqrt, log), out[3] = comparisons made.
 extern "C" int dwgsim_hip_selftest_fp64(int device, uint32_t seed, uint64_t n, uint64_t *out)
 {
-    if (!out || hipSetDevice(device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    DevMem d;
-    if (d.reserve(4 * sizeof(uint64_t), 4 * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
-    hipMemset(d.get(), 0, 4 * sizeof(uint64_t));
-    launch_selftest_fp64(nullptr, seed, n, d.get<uint64_t>());
-    const hipError_t e = hipMemcpy(out, d.get(), 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
+    return selftest_words(device, 4, out, [&](uint64_t *d) { launch_selftest_fp64(nullptr, seed, n, d); return 0; });
 }
 
 // Not part of the drop-in ABI either: the number formatters of the name line (dw_read.hpp put_dec / put_hex) against one division per digit, on the
 // values first + i * stride, i < n (dw_simulate.hip k_selftest_text).  out[0] / out[1] = decimal / hexadecimal texts that differ, out[2] = values compared.
 extern "C" int dwgsim_hip_selftest_text(int device, uint64_t first, uint64_t n, uint64_t stride, uint64_t *out)
 {
-    if (!out || hipSetDevice(device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    DevMem d;
-    if (d.reserve(4 * sizeof(uint64_t), 4 * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
-    hipMemset(d.get(), 0, 4 * sizeof(uint64_t));
-    launch_selftest_text(nullptr, first, n, stride, d.get<uint64_t>());
-    const hipError_t e = hipMemcpy(out, d.get(), 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
+    return selftest_words(device, 4, out, [&](uint64_t *d) { launch_selftest_text(nullptr, first, n, stride, d); return 0; });
 }
 
 // Not part of the drop-in ABI either: the gap draw geom_gap at threshold thr (0 < thr < 2^32) on the words [first, first + n), with the R, s and log2 table
@@ -691,22 +746,21 @@ extern "C" int dwgsim_hip_selftest_text(int device, uint64_t first, uint64_t n, 
 extern "C" int dwgsim_hip_selftest_gap(int device, uint64_t thr, uint32_t first, uint64_t n, uint32_t g_lo, uint32_t g_cnt, uint32_t *chg, uint64_t *out)
 {
     if (!out || (g_cnt && !chg) || thr == 0 || thr >= 0x100000000ull || n == 0 || (uint64_t)first + n > 0x100000000ull) return DWGSIM_HIP_ERR_ARG;
-    if (hipSetDevice(device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
     uint32_t lg[FLOW_LG_ENTRIES];
     flow_log2_table(lg);
     uint64_t R; int32_t sR;
     flow_gap_params(thr, &R, &sR);
-    DevMem d, d_lg, d_chg;
+    DevMem d_lg, d_chg;
     const size_t chg_bytes = (size_t)g_cnt * sizeof(uint32_t), chg_alloc = chg_bytes ? chg_bytes : 4;
-    if (d.reserve(4 * sizeof(uint64_t), 4 * sizeof(uint64_t)) != hipSuccess || d_lg.reserve(sizeof lg, sizeof lg) != hipSuccess ||
-        d_chg.reserve(chg_alloc, chg_alloc) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
-    hipMemset(d.get(), 0, 4 * sizeof(uint64_t));
-    hipMemset(d_chg.get(), 0, chg_alloc);
-    hipMemcpy(d_lg.get(), lg, sizeof lg, hipMemcpyHostToDevice);
-    launch_selftest_gap(nullptr, d_lg.get<uint32_t>(), R, sR, first, n, g_lo, g_cnt, d_chg.get<uint32_t>(), d.get<uint64_t>());
-    hipError_t e = hipMemcpy(out, d.get(), 4 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && chg_bytes) e = hipMemcpy(chg, d_chg.get(), chg_bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
+    const int rc = selftest_words(device, 4, out, [&](uint64_t *d) {
+        if (d_lg.reserve(sizeof lg, sizeof lg) != hipSuccess || d_chg.reserve(chg_alloc, chg_alloc) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
+        hipMemset(d_chg.get(), 0, chg_alloc);
+        hipMemcpy(d_lg.get(), lg, sizeof lg, hipMemcpyHostToDevice);
+        launch_selftest_gap(nullptr, d_lg.get<uint32_t>(), R, sR, first, n, g_lo, g_cnt, d_chg.get<uint32_t>(), d);
+        return DWGSIM_HIP_OK;
+    });
+    if (rc != DWGSIM_HIP_OK || !chg_bytes) return rc;
+    return hipMemcpy(chg, d_chg.get(), chg_bytes, hipMemcpyDeviceToHost) == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
 }
 
 // Not part of the drop-in ABI either: self-test of the lazy quality normals (dw_simulate.hip k_selftest_lazy).  out[0..4] = counters of the
@@ -715,40 +769,25 @@ extern "C" int dwgsim_hip_selftest_gap(int device, uint64_t thr, uint32_t first,
 // the bounds the error budget assumes (doubles).
 extern "C" int dwgsim_hip_selftest_lazy(int device, uint32_t first, uint64_t n, double sigma, int exhaustive, uint64_t *out)
 {
-    if (!out || hipSetDevice(device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    DevMem dm;
-    if (dm.reserve(12 * sizeof(uint64_t), 12 * sizeof(uint64_t)) != hipSuccess) return DWGSIM_HIP_ERR_NOMEM;
-    uint64_t *d = dm.get<uint64_t>();
-    hipMemset(d, 0, 12 * sizeof(uint64_t));
     float qk, qeps, qlmin; int32_t qnear1;
     lazy_quality_params(sigma, &qk, &qeps, &qlmin, &qnear1);
-    launch_selftest_lazy(nullptr, 0, first, n, sigma, qk, qeps, qlmin, qnear1, d);
-    if (exhaustive) {
-        launch_selftest_lazy(nullptr, 1, 0, 0x3F800000u - 0x30800000u, 0, 0, 0, 0, 0, d);           // [2^-30, 1)
-        launch_selftest_lazy(nullptr, 2, 0, 0x4E800000u - 0x3F800000u + 1u, 0, 0, 0, 0, 0, d);      // [1, 2^30]
-        launch_selftest_lazy(nullptr, 3, 0, 0x42000000u - 0x2B000000u, 0, 0, 0, 0, 0, d);           // [2^-41, 2^5)
-    }
-    const hipError_t e = hipMemcpy(out, d, 12 * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
+    return selftest_words(device, 12, out, [&](uint64_t *d) {
+        launch_selftest_lazy(nullptr, 0, first, n, sigma, qk, qeps, qlmin, qnear1, d);
+        if (exhaustive) {
+            launch_selftest_lazy(nullptr, 1, 0, 0x3F800000u - 0x30800000u, 0, 0, 0, 0, 0, d);           // [2^-30, 1)
+            launch_selftest_lazy(nullptr, 2, 0, 0x4E800000u - 0x3F800000u + 1u, 0, 0, 0, 0, 0, d);      // [1, 2^30]
+            launch_selftest_lazy(nullptr, 3, 0, 0x42000000u - 0x2B000000u, 0, 0, 0, 0, 0, d);           // [2^-41, 2^5)
+        }
+        return 0;
+    });
 }
 
+// The streams that exist are waited for here, by name: the members' destructors (dwgsim_hip_ctx) only give handles and memory back
 void dwgsim_hip_destroy(dwgsim_hip_ctx_t *c)
 {
     if (!c) return;
     hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
-    if (c->walk_stream) hipStreamSynchronize(c->walk_stream);
-    if (c->count_stream) hipStreamSynchronize(c->count_stream);
-    if (c->hap_stream) { hipStreamSynchronize(c->hap_stream); hipStreamDestroy(c->hap_stream); }
-    if (c->ev_up) hipEventDestroy(c->ev_up);
-    if (c->ev_cnt0) hipEventDestroy(c->ev_cnt0);
-    if (c->ev_cnt1) hipEventDestroy(c->ev_cnt1);
-    for (Slot &sl : c->slot) for (hipEvent_t e : {sl.ev_k0, sl.ev_k1, sl.ev_end, sl.ev_done, sl.ev_fetched}) if (e) hipEventDestroy(e);
-    if (c->copy_stream) hipStreamDestroy(c->copy_stream);
-    if (c->walk_stream) hipStreamDestroy(c->walk_stream);
-    if (c->count_stream) hipStreamDestroy(c->count_stream);
-    if (c->stream) hipStreamDestroy(c->stream);
+    for (const DevStream *s : {&c->stream, &c->copy_stream, &c->walk_stream, &c->count_stream, &c->hap_stream}) if (*s) hipStreamSynchronize(s->get());
     delete c;
 }
 
@@ -820,14 +859,14 @@ static int upload_sequence(dwgsim_hip_ctx_t *c, int n, const uint8_t *const *asc
     bool laid_out = true;
     for (int k = 0; k < n && laid_out; ++k) if (lens[k] > 0 && ascii[k] != ascii[0] + starts[k]) laid_out = false;
     if (laid_out && n > 0 && ascii[0] && is_page_locked(ascii[0])) {
-        HIPC(c, hipMemcpyAsync(d_ascii, ascii[0], (size_t)total, hipMemcpyHostToDevice, c->walk_stream));
-        HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream));
+        HIPC(c, hipMemcpyAsync(d_ascii, ascii[0], (size_t)total, hipMemcpyHostToDevice, c->walk_stream.get()));
+        HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream.get()));
         must_wait = false;
     } else if (n <= 8) {
-        HIPC(c, hipMemsetAsync(d_ascii, 0, padded, c->walk_stream));
-        for (int k = 0; k < n; ++k) if (lens[k] > 0) HIPC(c, hipMemcpyAsync(d_ascii + starts[k], ascii[k], (size_t)lens[k], hipMemcpyHostToDevice, c->walk_stream));
+        HIPC(c, hipMemsetAsync(d_ascii, 0, padded, c->walk_stream.get()));
+        for (int k = 0; k < n; ++k) if (lens[k] > 0) HIPC(c, hipMemcpyAsync(d_ascii + starts[k], ascii[k], (size_t)lens[k], hipMemcpyHostToDevice, c->walk_stream.get()));
     } else {
-        if (c->up_in_flight) { HIPC(c, hipEventSynchronize(c->ev_up)); c->up_in_flight = false; }
+        if (c->up_in_flight) { HIPC(c, hipEventSynchronize(c->ev_up.get())); c->up_in_flight = false; }
         HIPC(c, c->h_up.reserve((size_t)total, (size_t)total + (size_t)total / 4 + 4096));
         uint8_t *h_up = c->h_up.get();
         for (int k = 0; k < n; ++k) {
@@ -835,9 +874,9 @@ static int upload_sequence(dwgsim_hip_ctx_t *c, int n, const uint8_t *const *asc
             if (lens[k] > 0) memcpy(h_up + starts[k], ascii[k], (size_t)lens[k]);
             memset(h_up + end, 0, (size_t)(next - end));
         }
-        HIPC(c, hipMemcpyAsync(d_ascii, h_up, (size_t)total, hipMemcpyHostToDevice, c->walk_stream));
-        HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream));
-        HIPC(c, hipEventRecord(c->ev_up, c->walk_stream)); c->up_in_flight = true;
+        HIPC(c, hipMemcpyAsync(d_ascii, h_up, (size_t)total, hipMemcpyHostToDevice, c->walk_stream.get()));
+        HIPC(c, hipMemsetAsync(d_ascii + total, 0, padded - (size_t)total, c->walk_stream.get()));
+        HIPC(c, hipEventRecord(c->ev_up.get(), c->walk_stream.get())); c->up_in_flight = true;
     }
     return 0;
 }
@@ -849,10 +888,10 @@ static int make_pristine(dwgsim_hip_ctx_t *c, const Group &g)
     const GroupMem &M = g.mem;
     const int64_t n_cells = (int64_t)padded_cells(g) & ~(int64_t)15;
     uint8_t *ref = M.d_ref.get();
-    launch_pack(c->walk_stream, c->up_ascii.get(), ref, M.d_cells[0].get(), M.d_cells[1].get(), n_cells);
-    launch_make_view(c->walk_stream, ref, ref, n_cells, g.total, M.d_refview.get(), M.d_view[0].get(), M.d_refsumm.get<uint16_t>(), M.d_summ[0].get<uint16_t>(), M.d_refsumm2.get<uint16_t>(), M.d_summ2[0].get<uint16_t>());
-    if (const int rc = restore_pristine(c, g, 1, R_VIEW | R_SUMM | R_SUMM2, c->walk_stream)) return rc;
-    if (const int rc = clear_dirty(c, g, c->walk_stream)) return rc;
+    launch_pack(c->walk_stream.get(), c->up_ascii.get(), ref, M.d_cells[0].get(), M.d_cells[1].get(), n_cells);
+    launch_make_view(c->walk_stream.get(), ref, ref, n_cells, g.total, M.d_refview.get(), M.d_view[0].get(), M.d_refsumm.get<uint16_t>(), M.d_summ[0].get<uint16_t>(), M.d_refsumm2.get<uint16_t>(), M.d_summ2[0].get<uint16_t>());
+    if (const int rc = restore_pristine(c, g, 1, R_VIEW | R_SUMM | R_SUMM2, c->walk_stream.get())) return rc;
+    if (const int rc = clear_dirty(c, g, c->walk_stream.get())) return rc;
     HIPC(c, hipGetLastError());
     return 0;
 }
@@ -900,7 +939,7 @@ static int build_group(dwgsim_hip_ctx_t *c, Group &g, const uint8_t *const *asci
     if (const int rc = upload_group_tables(c, g)) return rc;
     // -m / -b / -v: the file's entries for these contigs are resolved now, while the sequence is at hand (mut.c:644-745)
     if (c->has_mutin) for (int k = 0; k < n; ++k) resolve_mutation_input(c->mutin, g.m[(size_t)k].contig_index, ascii[k], lens[k], (uint32_t)c->prm.seed, c->prm.is_hap != 0, g.m[(size_t)k].rc);
-    if (must_wait) HIPC(c, hipStreamSynchronize(c->walk_stream));
+    if (must_wait) HIPC(c, hipStreamSynchronize(c->walk_stream.get()));
     return 0;
 }
 
@@ -918,7 +957,7 @@ int dwgsim_hip_add_contigs(dwgsim_hip_ctx_t *c, int n, const char *const *names,
     g.m.resize((size_t)n);
     for (int k = 0; k < n; ++k) { Member &m = g.m[(size_t)k]; m.name = names[k]; m.l = m.l_place = lens[k]; m.contig_index = contig_index[k]; m.start = (int32_t)starts[(size_t)k]; }
     const int rc = build_group(c, g, ascii, lens, starts.data());
-    if (rc != 0) { (void)hipStreamSynchronize(c->walk_stream); g = Group(); return rc; }      // no half-built group stays behind a failed call
+    if (rc != 0) { (void)hipStreamSynchronize(c->walk_stream.get()); g = Group(); return rc; }      // no half-built group stays behind a failed call
     for (int k = 0; k < n; ++k) c->handles.push_back(HandleRef{gid, k});
     return g.first_handle;
 }
@@ -948,7 +987,7 @@ int dwgsim_hip_drop_contig(dwgsim_hip_ctx_t *c, int contig)
     c->pool.push_back(std::move(g->mem));
     *g = Group();
     if (c->pool.size() > 3) {
-        hipStreamSynchronize(c->walk_stream);
+        hipStreamSynchronize(c->walk_stream.get());
         c->pool.erase(c->pool.begin());
     }
     return DWGSIM_HIP_OK;
@@ -1055,7 +1094,7 @@ static void dirty_chunks(hipStream_t st, bool restore, const Group &g)
 // left-justification of the events of a walk: the cluster-parallel form or ("justify_seq", the cross-check) one thread for the whole group
 static void justify(dwgsim_hip_ctx_t *c, hipStream_t st, const Event *ev, Count n, const ContigDev &cd)
 {
-    if (c->seq_justify) launch_justify_seq(st, ev, n, cd);
+    if (c->dbg.seq_justify) launch_justify_seq(st, ev, n, cd);
     else launch_justify(st, ev, n, cd, c->w_lo.get<int32_t>(), c->w_sufmin.get<int32_t>(), c->w_bound.get<uint8_t>());
 }
 
@@ -1069,14 +1108,14 @@ static int64_t pack_walk_form(int attempt, bool file_driven, bool slots, int res
 // GPU scatters them into the cells and left-justifies the indels; the views are made from every cell.  mut_debug runs before and after the justification.
 static int walk_file_driven(dwgsim_hip_ctx_t *c, Group &g)
 {
-    hipStream_t st = c->walk_stream;
+    hipStream_t st = c->walk_stream.get();
     const GroupMem &M = g.mem;
     WalkCounters *wc = c->d_wcounters.get<WalkCounters>();
     const uint32_t np = g.n_patch, nev = g.n_patch_ev;
     const size_t nev1 = nev ? nev : 1;
     if (np && (ensure(c, c->w_ppos, sizeof(int32_t) * np) || ensure(c, c->w_pcells, sizeof(uint16_t) * np) || ensure(c, c->w_ev, sizeof(Event) * nev1) ||
                ensure(c, c->w_lo, sizeof(int32_t) * nev1) || ensure(c, c->w_sufmin, sizeof(int32_t) * (nev1 + 64)) || ensure(c, c->w_bound, nev1))) return DWGSIM_HIP_ERR_DEVICE;      // (+ 64: segment minima of k_sufmin)
-    c->walk_form = pack_walk_form(g.walk_attempt, true, false, g.walk_reset ? 2 : 0, true);
+    c->dbg.walk_form = pack_walk_form(g.walk_attempt, true, false, g.walk_reset ? 2 : 0, true);
     HIPC(c, hipEventRecord(M.ev_walk0.get(), st));
     if (g.walk_reset) for (int h = 0; h < 2; ++h) if (const int rc = restore_pristine(c, g, h, R_CELLS, st)) return rc;
     HIPC(c, wc_fill(c, WC_FILE, 0xff, st));
@@ -1118,13 +1157,13 @@ static WalkPlan walk_plan(const dwgsim_hip_ctx_t *c, const Group &g)
     P.nbs = site_scan_blocks(g.total);
     const double m = (double)site_scan_block_positions() * (c->prm.mut_rate > 0 ? c->prm.mut_rate : 0.0);
     P.slot_cap = (uint32_t)std::min<double>((double)site_scan_block_positions(), m + 8.0 * sqrt(m + 1.0) + 32.0);
-    if (c->site_slot_cap >= 0) P.slot_cap = (uint32_t)std::max<int64_t>(1, c->site_slot_cap);
+    if (c->dbg.site_slot_cap >= 0) P.slot_cap = (uint32_t)std::max<int64_t>(1, c->dbg.site_slot_cap);
     P.slot_bytes = (size_t)P.nbs * P.slot_cap * sizeof(int32_t);
-    P.use_slots = g.walk_attempt == 0 && c->site_slots != 0 && P.nbs > 0 && (c->site_slots > 0 || P.slot_bytes <= std::max<size_t>((size_t)64 << 20, P.ncap * 16));
+    P.use_slots = g.walk_attempt == 0 && c->dbg.site_slots != 0 && P.nbs > 0 && (c->dbg.site_slots > 0 || P.slot_bytes <= std::max<size_t>((size_t)64 << 20, P.ncap * 16));
     // where the group stands: fresh from the upload, or with the chunks the previous walk wrote -- those go back to the pristine copies --, or (a
     // capacity re-run, a walk that kept no bitmap) all of it
     P.restore = g.walk_attempt > 0 || g.dirty_all ? Restore::All : g.dirty_any ? Restore::Chunks : Restore::None;
-    P.dense = c->seq_justify || c->dense_view;
+    P.dense = c->dbg.seq_justify || c->dbg.dense_view;
     return P;
 }
 
@@ -1144,7 +1183,7 @@ static int walk_reserve(dwgsim_hip_ctx_t *c, Group &g, const WalkPlan &P)
 // The kernels of the planned attempt: candidate sites, events, the cells, left-justification, the views of what was written
 static int walk_launch(dwgsim_hip_ctx_t *c, Group &g, const WalkPlan &P)
 {
-    hipStream_t st = c->walk_stream;
+    hipStream_t st = c->walk_stream.get();
     const WalkParams wp = walk_params(c);
     const SegTab seg = seg_tab(g);
     const GroupMem &M = g.mem;
@@ -1193,8 +1232,8 @@ static int walk_random(dwgsim_hip_ctx_t *c, Group &g)
 {
     const WalkPlan P = walk_plan(c, g);
     if (const int rc = walk_reserve(c, g, P)) return rc;
-    c->walk_form = pack_walk_form(g.walk_attempt, false, P.use_slots, (int)P.restore, P.dense);
-    hipStream_t st = c->walk_stream;
+    c->dbg.walk_form = pack_walk_form(g.walk_attempt, false, P.use_slots, (int)P.restore, P.dense);
+    hipStream_t st = c->walk_stream.get();
     HIPC(c, hipEventRecord(g.mem.ev_walk0.get(), st));
     if (P.restore == Restore::All) { for (int h = 0; h < 2; ++h) if (const int rc = restore_pristine(c, g, h, R_ALL, st)) return rc; }
     else if (P.restore == Restore::Chunks) dirty_chunks(st, true, g);
@@ -1242,7 +1281,7 @@ static void initial_walk_caps(const dwgsim_hip_ctx_t *c, Group &g)
     for (const Member &m : g.m) mean += (double)m.l * c->prm.mut_rate;
     g.walk_cap = (uint32_t)std::min<double>((double)g.total, mean + 8.0 * sqrt(mean + 1.0) + 256.0);
     g.walk_cap_bases = (size_t)g.walk_cap * 8 + 4096;
-    if (c->walk_cap >= 0) { g.walk_cap = (uint32_t)c->walk_cap; g.walk_cap_bases = 1; }
+    if (c->dbg.walk_cap >= 0) { g.walk_cap = (uint32_t)c->dbg.walk_cap; g.walk_cap_bases = 1; }
 }
 
 int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
@@ -1262,12 +1301,12 @@ int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
     g.walk_attempt = 0;
     if (g.total == 0) return DWGSIM_HIP_OK;
     if (c->has_mutin) {
-        HIPC(c, hipStreamSynchronize(c->walk_stream));      // (an earlier group's walk may still be copying from the host lists)
+        HIPC(c, hipStreamSynchronize(c->walk_stream.get()));      // (an earlier group's walk may still be copying from the host lists)
         HostIns hi[2];
         collect_file_mutations(c, g, hi);
         g.n_patch = (uint32_t)c->h_ppos.size(); g.n_patch_ev = (uint32_t)c->h_pev.size();
         g.n_cand = g.n_patch_ev;
-        HIPC(c, hipStreamSynchronize(c->walk_stream));      // (the tables are copied from short-lived host vectors)
+        HIPC(c, hipStreamSynchronize(c->walk_stream.get()));      // (the tables are copied from short-lived host vectors)
         if (const int rc = upload_ins_tables(c, g, hi)) return rc;
     } else initial_walk_caps(c, g);
     if (const int rc = c->has_mutin ? walk_file_driven(c, g) : walk_random(c, g)) return rc;
@@ -1298,7 +1337,7 @@ int dwgsim_hip_mutate_wait(dwgsim_hip_ctx_t *c, int contig)
     const WalkCounters &w = *g.mem.h_wc.get<WalkCounters>();
     for (;;) {      // wait, verdict, grow, enqueue again
         HIPC(c, hipEventSynchronize(g.mem.ev_walk.get()));
-        { float ms = 0; if (hipEventElapsedTime(&ms, g.mem.ev_walk0.get(), g.mem.ev_walk.get()) == hipSuccess) c->walk_us += 1e3 * ms; else (void)hipGetLastError(); }      // (analysis: dwgsim_hip_debug_get "walk_us")
+        { float ms = 0; if (hipEventElapsedTime(&ms, g.mem.ev_walk0.get(), g.mem.ev_walk.get()) == hipSuccess) c->dbg.walk_us += 1e3 * ms; else (void)hipGetLastError(); }      // (analysis: dwgsim_hip_debug_get "walk_us")
         if (c->has_mutin) {
             g.walk_pending = false;
             return g.n_patch ? mut_debug_verdict(c, g, w.mut_debug[0], w.mut_debug[1]) : DWGSIM_HIP_OK;
@@ -1439,7 +1478,7 @@ int fetch_mutated_list(dwgsim_hip_ctx_t *c, Group &g)
     if (g.list_valid) return DWGSIM_HIP_OK;
     g.pos.clear(); g.cells.clear();
     for (int h = 0; h < 2; ++h) g.ins[h] = HostIns();
-    hipStream_t st = c->walk_stream;
+    hipStream_t st = c->walk_stream.get();
     if (g.total > 0 && g.n_cand > 0) {
         const uint32_t nblk = (uint32_t)((g.total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
         if (ensure(c, c->scratch_mask, (size_t)nblk * SCAN_THREADS * sizeof(uint16_t))) return DWGSIM_HIP_ERR_DEVICE;
@@ -1548,7 +1587,7 @@ int dwgsim_hip_haplotype_fasta(dwgsim_hip_ctx_t *c, int contig, int hap, int wid
         // (the scan of the blocks is a 32-bit one: cells and inserted bases of a group stay below 2^32 together; the TEXT offsets are 64-bit)
         if ((uint64_t)g.total + g.n_ins_bases[hap] > 0xFFFFFFFFull) { c->err = "haplotype_fasta: more than 2^32 bases in one group"; return DWGSIM_HIP_ERR_UNSUP; }
         GroupMem &M = g.mem;
-        hipStream_t st = c->walk_stream;
+        hipStream_t st = c->walk_stream.get();
         const size_t n = g.m.size();
         const uint32_t nblk = (uint32_t)((g.total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
         if (ensure(c, c->scratch_cnt, ((size_t)nblk + 1) * sizeof(uint32_t))) return DWGSIM_HIP_ERR_DEVICE;
@@ -1587,7 +1626,7 @@ int dwgsim_hip_haplotype_fasta(dwgsim_hip_ctx_t *c, int contig, int hap, int wid
         HIPC(c, hipEventRecord(c->hap_ev[3].get(), st));
         HIPC(c, hipGetLastError());
         DevMem yard;      // "hap_yardstick" (measurement only): a device-to-device copy of as many bytes as the text, behind it on the same stream (the second of two is timed)
-        if (c->hap_yardstick && at) {
+        if (c->dbg.hap_yardstick && at) {
             HIPC(c, reserve(c, yard, (size_t)at, (size_t)at));
             HIPC(c, hipMemcpyAsync(yard.get(), M.d_hap_text[hap].get(), (size_t)at, hipMemcpyDeviceToDevice, st));
             HIPC(c, hipEventRecord(c->hap_ev[4].get(), st));
@@ -1597,9 +1636,9 @@ int dwgsim_hip_haplotype_fasta(dwgsim_hip_ctx_t *c, int contig, int hap, int wid
         HIPC(c, hipStreamSynchronize(st));      // (the records and header lines go up from vectors of this call)
         {   // (analysis: dwgsim_hip_debug_get "hap_len_us" / "hap_write_us" / "hap_copy_us", of the text built last)
             float ms = 0;
-            c->hap_len_us = nblk && hipEventElapsedTime(&ms, c->hap_ev[0].get(), c->hap_ev[1].get()) == hipSuccess ? 1e3 * ms : 0;
-            c->hap_write_us = hipEventElapsedTime(&ms, c->hap_ev[2].get(), c->hap_ev[3].get()) == hipSuccess ? 1e3 * ms : 0;
-            c->hap_copy_us = yard && hipEventElapsedTime(&ms, c->hap_ev[4].get(), c->hap_ev[5].get()) == hipSuccess ? 1e3 * ms : 0;
+            c->dbg.hap_len_us = nblk && hipEventElapsedTime(&ms, c->hap_ev[0].get(), c->hap_ev[1].get()) == hipSuccess ? 1e3 * ms : 0;
+            c->dbg.hap_write_us = hipEventElapsedTime(&ms, c->hap_ev[2].get(), c->hap_ev[3].get()) == hipSuccess ? 1e3 * ms : 0;
+            c->dbg.hap_copy_us = yard && hipEventElapsedTime(&ms, c->hap_ev[4].get(), c->hap_ev[5].get()) == hipSuccess ? 1e3 * ms : 0;
             (void)hipGetLastError();
         }
         T.width = width; T.bytes = at; T.valid = true;
@@ -1634,11 +1673,11 @@ int dwgsim_hip_haplotype_fetch(dwgsim_hip_ctx_t *c, int hap, uint64_t offset, vo
     if (offset > total || (uint64_t)n > total - offset) { c->err = "haplotype_fetch: past the end of the text"; return DWGSIM_HIP_ERR_ARG; }
     if (n == 0) return DWGSIM_HIP_OK;
     HIPC(c, hipSetDevice(c->device));
-    if (!c->hap_stream) HIPC(c, hipStreamCreate(&c->hap_stream));
+    HIPC(c, c->hap_stream.create());
     const uint8_t *src = g.mem.d_hap_text[hap].get<uint8_t>() + offset;
     if (is_page_locked(host_dst)) {
-        HIPC(c, hipMemcpyAsync(host_dst, src, n, hipMemcpyDeviceToHost, c->hap_stream));
-        HIPC(c, hipStreamSynchronize(c->hap_stream));
+        HIPC(c, hipMemcpyAsync(host_dst, src, n, hipMemcpyDeviceToHost, c->hap_stream.get()));
+        HIPC(c, hipStreamSynchronize(c->hap_stream.get()));
         return DWGSIM_HIP_OK;
     }
     // double-buffered page-locked staging, as dwgsim_hip_fetch: the copy of chunk k+1 overlaps the host copy of chunk k
@@ -1647,11 +1686,11 @@ int dwgsim_hip_haplotype_fetch(dwgsim_hip_ctx_t *c, int hap, uint64_t offset, vo
     uint8_t *stage[2] = {c->h_stage.get<uint8_t>(), c->h_stage.get<uint8_t>() + CH};
     size_t done = 0; int b = 0;
     size_t cur = n < CH ? n : CH;
-    HIPC(c, hipMemcpyAsync(stage[0], src, cur, hipMemcpyDeviceToHost, c->hap_stream));
+    HIPC(c, hipMemcpyAsync(stage[0], src, cur, hipMemcpyDeviceToHost, c->hap_stream.get()));
     while (done < n) {
-        HIPC(c, hipStreamSynchronize(c->hap_stream));
+        HIPC(c, hipStreamSynchronize(c->hap_stream.get()));
         const size_t next_off = done + cur, next = next_off < n ? ((n - next_off) < CH ? (n - next_off) : CH) : 0;
-        if (next) HIPC(c, hipMemcpyAsync(stage[b ^ 1], src + next_off, next, hipMemcpyDeviceToHost, c->hap_stream));
+        if (next) HIPC(c, hipMemcpyAsync(stage[b ^ 1], src + next_off, next, hipMemcpyDeviceToHost, c->hap_stream.get()));
         memcpy((uint8_t *)host_dst + done, stage[b], cur);
         done += cur; cur = next; b ^= 1;
     }
@@ -1710,7 +1749,7 @@ static int build_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n,
 static int sim_form(dwgsim_hip_ctx_t *c, SimForm &f)
 {
     const dwgsim_hip_params_t &p = c->prm;
-    const size_t qb = (size_t)c->qb_words;
+    const size_t qb = (size_t)c->tab.qb_words;
     const int lmax = p.length[0] > p.length[1] ? p.length[0] : p.length[1];
     f = SimForm();
     f.lpp = p.length[1] > 0 ? 2 : 1;
@@ -1728,12 +1767,12 @@ static int sim_form(dwgsim_hip_ctx_t *c, SimForm &f)
         const int b_fifo = sim_blocks_per_cu(sim_lds_bytes((size_t)f.lds_words, SIM_THREADS, qb, true), cap_fifo), b_reg = sim_blocks_per_cu(sim_lds_bytes((size_t)f.lds_words, SIM_THREADS, qb, false), cap_reg);
         // (-o 0: one assembly for both families outweighs a resident block: 2 x 250 bp 7.72 ms with three blocks per CU against 8.13 ms with four, profiles/r05_o0.txt)
         if (b_fifo < b_reg && !(p.reads_output_type == 0 && b_fifo >= 3)) fifo = false;
-        if (c->writer >= 0) fifo = c->writer != 0;
+        if (c->dbg.writer >= 0) fifo = c->dbg.writer != 0;
     }
     const size_t need = sim_lds_bytes((size_t)f.lds_words, SIM_THREADS, qb, fifo);     // staged bases + the two base-quality tables + the text FIFOs
     // (from where LDS staging leaves room for ONE 256-lane block per CU -- reads of ~650 bases on -- the one-wave blocks are the faster form: 800 / 1 000 /
     // 2 000 bases 13.1 / 13.0 / 22.7 ms in LDS against 7.8 / 8.0 / 8.6 ms staged in scratch slots, 600 bases 7.4 against 7.9: profiles/r04_long_reads.txt)
-    if (p.data_type != 2 && (need > SIM_LDS_BUDGET || ((sim_blocks_per_cu(need, 8) < 2 || c->force_threads == SIM_THREADS_LONG) && c->force_threads != SIM_THREADS))) {
+    if (p.data_type != 2 && (need > SIM_LDS_BUDGET || ((sim_blocks_per_cu(need, 8) < 2 || c->dbg.force_threads == SIM_THREADS_LONG) && c->dbg.force_threads != SIM_THREADS))) {
         // reads too long to stage in LDS: one-wave blocks whose reads are staged in scratch slots (global memory, dw_simulate.hip GS); what is left in LDS
         // is the two base-quality tables (2 bytes per base) and the FIFOs, which bounds a read at ~70 000 bases (the reference has no bound, dwgsim.c:75-153)
         f.nthr = SIM_THREADS_LONG; fifo = true;
@@ -1751,7 +1790,7 @@ static int sim_form(dwgsim_hip_ctx_t *c, SimForm &f)
         f.stack_words = std::min(FLOW_STACK_WORDS * c->flow_cap_mult, FLOW_STACK_WORDS_MAX);
         const size_t per_lane = (size_t)(f.lds_words + f.stack_words);
         const size_t need256 = sim_lds_bytes(per_lane, SIM_THREADS, qb, true), need64 = sim_lds_bytes(per_lane, ION_THREADS_SMALL, qb, true);
-        int mode = c->ion_lds;
+        int mode = c->dbg.ion_lds;
         if (mode < 0) mode = (need256 <= SIM_LDS_BUDGET && sim_blocks_per_cu(need256, 8) >= 2) ? 1 : (need64 <= SIM_LDS_BUDGET && sim_blocks_per_cu(need64, 32) >= 4) ? 2 : 0;
         if ((mode == 1 && need256 > SIM_LDS_BUDGET) || (mode == 2 && need64 > SIM_LDS_BUDGET)) mode = 0;
         f.dt = mode != 0 ? 3 : 2; f.nthr = mode == 2 ? ION_THREADS_SMALL : SIM_THREADS;
@@ -1762,11 +1801,11 @@ static int sim_form(dwgsim_hip_ctx_t *c, SimForm &f)
     // two kernels, 2 x 50 +0.8 %, 2 x 75 -3 %, 2 x 100 -10 %, 100 bp single-end -9 %, 2 x 150 -12 %.  "split" = 0 / 1 forces either.
     // (The cut at 100 bases of rounds 4-5 and their rule for small launches: DESIGN.md §4, k_simulate.)
     const bool split_wins = lmax <= 50;
-    f.split = (p.data_type == 0 && f.nthr == SIM_THREADS && (c->split < 0 ? split_wins : c->split != 0)) ? 1 : 0;
+    f.split = (p.data_type == 0 && f.nthr == SIM_THREADS && (c->dbg.split < 0 ? split_wins : c->dbg.split != 0)) ? 1 : 0;
     // Ion Torrent with its buffers in LDS: as two kernels as well (the flow model | qualities + text).  The first half holds no text FIFOs, so a fourth
     // block fits a CU, and no block waits for the record sizes of the blocks in front of it ("split" = 0 forces the single kernel)
-    if (f.dt == 3 && f.nthr == SIM_THREADS && f.cap < 32768 && c->split != 0) f.split = 1;
-    if (f.split && c->writer < 0) fifo = true;      // (its LDS holds no bases: the FIFO writer always fits)
+    if (f.dt == 3 && f.nthr == SIM_THREADS && f.cap < 32768 && c->dbg.split != 0) f.split = 1;
+    if (f.split && c->dbg.writer < 0) fifo = true;      // (its LDS holds no bases: the FIFO writer always fits)
     // dynamic LDS: the staged bases (Ion Torrent: the read buffers when LDS holds them + the pass-2 run stack; the scratch slots hold the rest, and the
     // reads of the one-wave blocks) + the base-quality tables + the text FIFOs.  Two kernels: the first half stages the bases only, the second half
     // (no staged bases) the tables and its FIFOs of 64-byte bursts
@@ -1791,25 +1830,25 @@ static void fill_sim_args(const dwgsim_hip_ctx_t *c, const Group &g, const SimFo
     fill_haps(g, a.hap);
     a.chain = c->d_chain.get<uint64_t>();
     a.have_regions = c->has_regions ? 1 : 0; a.reg = g.mem.d_reg.get<int32_t>();
-    for (int j = 0; j < 2; ++j) { a.e_thr[j] = c->d_thr[j].get<uint64_t>(); a.e_thr32[j] = c->d_thr32[j].get<uint32_t>(); a.qbase[j] = c->d_qbase[j].get<uint32_t>() ? c->d_qbase[j].get<uint32_t>() : c->d_qbase[0].get<uint32_t>(); }
-    a.qb_words = c->qb_words;
-    a.e_full = c->e_full;
+    for (int j = 0; j < 2; ++j) { a.e_thr[j] = c->tab.d_thr[j].get<uint64_t>(); a.e_thr32[j] = c->tab.d_thr32[j].get<uint32_t>(); a.qbase[j] = c->tab.d_qbase[j].get<uint32_t>() ? c->tab.d_qbase[j].get<uint32_t>() : c->tab.d_qbase[0].get<uint32_t>(); }
+    a.qb_words = c->tab.qb_words;
+    a.e_full = c->tab.e_full;
     a.names = g.mem.d_names.get();
     a.summ[0] = g.mem.d_summ[0].get<uint16_t>(); a.summ[1] = g.mem.d_summ[1].get<uint16_t>(); a.summ2[0] = g.mem.d_summ2[0].get<uint16_t>(); a.summ2[1] = g.mem.d_summ2[1].get<uint16_t>();
     // k_place decides most pairs without their insert size: |normal| <= sqrt(-2 ln 2^-104) < 12.01 for the polar method on 53-bit uniforms (dw_simulate.hip pair_surely_accepted)
     a.place_fast = (!c->has_regions && !p.amplicons && p.std_dev * 12.1 + 2.0 < 1e9) ? 1 : 0;
     a.place_k = a.place_fast ? (int32_t)ceil(p.std_dev * 12.1) + 2 : 0;
-    a.rand_fixed = c->d_rand_fixed.get(); a.rand_fixed_len = c->rand_fixed_len;
+    a.rand_fixed = c->tab.d_rand_fixed.get(); a.rand_fixed_len = c->tab.rand_fixed_len;
     a.sim_threads = f.nthr; a.fifo = f.wr != 0; a.split = f.split; a.ion_lds = f.dt == 3;
     a.cap = f.cap; a.lds_words = f.lds_words; a.flow_stack_words = f.stack_words;
     // the quality line in the staging rows: the instances that write the sequence line in lockstep units (dw_simulate.hip SEQ_LOCKSTEP), from 72 bytes per lane on
-    a.qrows = (c->qrows != 0 && f.dt == 0 && f.split == 0 && f.wr == 1 && f.nthr == SIM_THREADS && f.out != 3 && f.lds_words >= 18) ? 1 : 0;
-    a.flow = c->d_flow.get(); a.flow_len = (int32_t)c->flow.size();
+    a.qrows = (c->dbg.qrows != 0 && f.dt == 0 && f.split == 0 && f.wr == 1 && f.nthr == SIM_THREADS && f.out != 3 && f.lds_words >= 18) ? 1 : 0;
+    a.flow = c->tab.d_flow.get(); a.flow_len = (int32_t)c->tab.flow.size();
     for (int j = 0; j < 2; ++j) {      // Illumina / SOLiD: the gap chain of a read end's error sites runs at the largest threshold of its ramp (dw_simulate.hip; thresholds as dwgsim_hip_create made them)
         const int n = c->prm.length[j];
         uint64_t tmax = 0, tmin = ~0ull;
         for (int i = 0; i < n; ++i) {
-            const double ei = c->prm.e_start[j] + c->e_by[j] * i;
+            const double ei = c->prm.e_start[j] + c->tab.e_by[j] * i;
             const uint64_t t = !(ei > 0) ? 0 : ei >= 1.0 ? 0x100000000ull : (uint64_t)ceil(ei * 4294967296.0);
             tmax = std::max(tmax, t); tmin = std::min(tmin, t);
         }
@@ -1847,7 +1886,7 @@ int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t
     if (n_pairs == 0) return DWGSIM_HIP_OK;
     Group &g = *L.g;
     HIPC(c, hipSetDevice(c->device));
-    hipStream_t st = c->count_stream;     // (the count of one group can run while batches of another -- or of this one -- are being simulated)
+    hipStream_t st = c->count_stream.get();     // (the count of one group can run while batches of another -- or of this one -- are being simulated)
     // (the haplotype summaries k_place reads -- per 64 and per 1024 cells -- were written with the read views at the end of the walk: the count follows
     // its group's walk by that walk's event, whatever else has been put on the walk stream since)
     if (g.walk_pending) { if (const int rc = dwgsim_hip_mutate_wait(c, g.first_handle)) return rc; }      // (a walk that exceeded a capacity is run again inside the wait: only then are the summaries final)
@@ -1869,27 +1908,27 @@ int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t
     const uint64_t waves = (uint64_t)n_blocks * (PLACE_PAIRS / 64);
     const uint32_t cap_full = (uint32_t)((waves + PLACE_LISTS - 1) / PLACE_LISTS) * 64u;
     uint32_t cap = (uint32_t)std::min<uint64_t>(cap_full, 1024 + n_pairs / PLACE_LISTS / 8);
-    if (c->place_cap >= 0 && (uint64_t)c->place_cap < cap) cap = (uint32_t)c->place_cap;      // dwgsim_hip_debug_option("place_cap"): start too small, exercise the second run
+    if (c->dbg.place_cap >= 0 && (uint64_t)c->dbg.place_cap < cap) cap = (uint32_t)c->dbg.place_cap;      // dwgsim_hip_debug_option("place_cap"): start too small, exercise the second run
     for (int attempt = 0;; ++attempt) {
         if (ensure(c, c->place_list, sizeof(uint32_t) * (size_t)cap * PLACE_LISTS)) return DWGSIM_HIP_ERR_DEVICE;
         a.place_list = c->place_list.get<uint32_t>(); a.place_list_cap = cap;
         a.place_list_n = c->place_aux.get<uint32_t>(); a.range_rand = reinterpret_cast<uint64_t *>(c->place_aux.get<uint8_t>() + PLACE_LISTS * 16 * sizeof(uint32_t));
         HIPC(c, hipMemsetAsync(c->pcounters.dev(), 0, N_COUNTERS * sizeof(uint64_t), st));
         HIPC(c, hipMemsetAsync(c->place_aux.get(), 0, PLACE_LISTS * 16 * sizeof(uint32_t) + sizeof(uint64_t) * ns, st));
-        HIPC(c, hipEventRecord(c->ev_cnt0, st));
+        HIPC(c, hipEventRecord(c->ev_cnt0.get(), st));
         launch_place(st, a);
-        HIPC(c, hipEventRecord(c->ev_cnt1, st));
+        HIPC(c, hipEventRecord(c->ev_cnt1.get(), st));
         HIPC(c, hipGetLastError());
         HIPC(c, hipMemcpyAsync(c->pcounters.host(), c->pcounters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIPC(c, hipMemcpyAsync(c->h_range_rand.get(), a.range_rand, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
         HIPC(c, hipStreamSynchronize(st));
-        { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_cnt0, c->ev_cnt1) == hipSuccess) c->count_us += 1e3 * ms; else (void)hipGetLastError(); }
+        { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_cnt0.get(), c->ev_cnt1.get()) == hipSuccess) c->dbg.count_us += 1e3 * ms; else (void)hipGetLastError(); }
         if (!(c->pcounters.host()[2] & 16) || attempt > 0) break;
         cap = cap_full;
     }
     if (c->pcounters.host()[2] & 16) { c->err = "count_random: the list of undecided pairs overflowed twice"; return DWGSIM_HIP_ERR_FAILED; }
     if (c->pcounters.host()[2]) { char b[128]; snprintf(b, sizeof b, "\r[dwgsim_core] failed to generate a read after %d trials\n", MAX_ATTEMPTS + 1); c->err = b; return DWGSIM_HIP_ERR_FAILED; }
-    c->place_open = c->pcounters.host()[5];
+    c->dbg.place_open = c->pcounters.host()[5];
     uint64_t total = 0;
     for (int q = 0, si = 0; q < n; ++q) if (r[q].n_pairs) { total += h_range_rand[si]; if (per_range) per_range[q] = h_range_rand[si]; ++si; }
     if (n_random) *n_random = total;
@@ -1916,7 +1955,7 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
     const uint64_t n_pairs = L.n_pairs; const size_t nblk = L.nblk;
     SimPlan P{};
     // upper bound of one FASTQ record (name tail: 2 positions <= 10 digits, 6 counters, 16 hex digits)
-    const int fixed_max = std::max(L.fixed_max, c->rand_fixed_len);
+    const int fixed_max = std::max(L.fixed_max, c->tab.rand_fixed_len);
     for (int j = 0; j < 2; ++j) if (p.length[j] > 0) P.cap[j] = (size_t)n_pairs * (size_t)(1 + fixed_max + 120 + 3 + 2 * (p.data_type == 2 ? f.cap : p.length[j]) + 4);
     // the one look-back word of the single Illumina kernel: 62 bits for the random reads and the bytes of stream 1 in front of a block
     int bw_bytes = 0, bw_pairs = 0;
@@ -1938,7 +1977,7 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
         const int cu_per_xcd = (c->n_cu >= 64 && c->n_cu % 8 == 0) ? c->n_cu / 8 : c->n_cu;
         const bool ion = p.data_type == 2;
         const int per_cu = sim_blocks_per_cu(f.lds, ion ? 8 : 32);       // (one-wave blocks: up to eight per SIMD)
-        P.flow_slots = c->flow_slots > 0 ? c->flow_slots : cu_per_xcd * per_cu;
+        P.flow_slots = c->dbg.flow_slots > 0 ? c->dbg.flow_slots : cu_per_xcd * per_cu;
         if ((uint64_t)P.flow_slots > (uint64_t)nblk) P.flow_slots = (int32_t)nblk;
         if (ion) {      // reads that have grown far beyond their estimate (capacity re-runs): fewer slots, at most 4 GB of them (blocks wait for a slot, they never fail for want of one)
             const size_t slot_bytes = (size_t)flow_words_per_lane(f.lds_words) * (size_t)SIM_THREADS * sizeof(uint32_t);
@@ -1961,7 +2000,7 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
 static int sim_reserve(dwgsim_hip_ctx_t *c, int slot, const SimPlan &P)
 {
     Slot &sl = c->slot[slot]; DevMem *out = c->out[slot];
-    if (sl.fetch_in_flight) { HIPC(c, hipStreamWaitEvent(c->stream, sl.ev_fetched, 0)); bool grows = false; for (int t = 0; t < 3; ++t) if (P.cap[t] + 64 > out[t].cap()) grows = true; if (grows) HIPC(c, hipEventSynchronize(sl.ev_fetched)); sl.fetch_in_flight = false; }
+    if (sl.fetch_in_flight) { HIPC(c, hipStreamWaitEvent(c->stream.get(), sl.ev_fetched.get(), 0)); bool grows = false; for (int t = 0; t < 3; ++t) if (P.cap[t] + 64 > out[t].cap()) grows = true; if (grows) HIPC(c, hipEventSynchronize(sl.ev_fetched.get())); sl.fetch_in_flight = false; }
     for (int t = 0; t < 3; ++t) if (ensure(c, out[t], P.cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE;
     if (ensure(c, c->block_rand, P.block_rand) || ensure(c, c->status_all, P.status) ||
         ensure(c, c->split_state, P.split_state) || ensure(c, c->split_hand, P.split_hand) || ensure(c, c->split_agg, P.split_agg) || ensure(c, c->split_pre, P.split_pre) || ensure(c, c->split_chunk, P.split_chunk) ||
@@ -1994,10 +2033,10 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
     const uint64_t n_pairs = L.n_pairs; const uint32_t nblk = L.nblk;
     for (int t = 0; t < 3; ++t) sl.out_bytes[t] = sl.gz_bytes[t] = 0;
     sl.n_pairs = n_pairs; sl.empty = n_pairs == 0;
-    if (n_pairs == 0) { if (ch.set_rand || ch.set_carry) launch_chain_set(c->stream, ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry); return DWGSIM_HIP_OK; }
+    if (n_pairs == 0) { if (ch.set_rand || ch.set_carry) launch_chain_set(c->stream.get(), ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry); return DWGSIM_HIP_OK; }
     uint32_t opens = 0; for (const SimSeg &s : L.segs) opens |= s.contig_start;      // (ranges that begin their contig)
     memcpy(sl.h_segs.get(), L.segs.data(), P.segs);
-    HIPC(c, hipMemcpyAsync(sl.segs.get(), sl.h_segs.get(), P.segs, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(sl.segs.get(), sl.h_segs.get(), P.segs, hipMemcpyHostToDevice, c->stream.get()));
     a.segs = sl.segs.get<SimSeg>(); a.n_seg = (int32_t)L.segs.size(); a.n_blocks = nblk; a.n_pairs = n_pairs; a.chain = ch.words; a.lb_shift = P.lb_shift;
     a.meta = c->meta.get<uint32_t>(); a.block_rand = c->block_rand.get<uint32_t>(); a.counters = sl.counters.dev();
     for (int t = 0; t < 3; ++t) a.out[t] = c->out[slot][t].get<uint8_t>();
@@ -2006,28 +2045,28 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
     if (P.scratch) { a.flow_scratch = c->flow_scratch.get<uint32_t>(); a.flow_free = c->flow_free.get<uint64_t>(); a.flow_slots = P.flow_slots; }
     sl.group = c->handles[(size_t)L.g->first_handle].group;
     // one operation in front of the kernel: counters, look-back words (the four arrays are contiguous), the scratch slots' free lists, the running values
-    launch_init(c->stream, sl.counters.dev(), (uint32_t)N_COUNTERS, a.status[0], f.split ? 0 : 4 * (uint64_t)nblk, a.flow_free, a.flow_free ? 256 + 8 * (uint64_t)nblk : 0,
+    launch_init(c->stream.get(), sl.counters.dev(), (uint32_t)N_COUNTERS, a.status[0], f.split ? 0 : 4 * (uint64_t)nblk, a.flow_free, a.flow_free ? 256 + 8 * (uint64_t)nblk : 0,
                 ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry);
-    HIPC(c, hipEventRecord(sl.ev_k0, c->stream));
-    c->sim_form = (int64_t)f.nthr << 20 | f.lpp << 16 | f.out << 12 | f.dt << 8 | f.wr << 4 | f.split;
-    if (!launch_simulate(c->stream, a, f)) { c->err = "simulate: no k_simulate instance for this form"; return DWGSIM_HIP_ERR_FAILED; }
-    HIPC(c, hipEventRecord(sl.ev_k1, c->stream));
+    HIPC(c, hipEventRecord(sl.ev_k0.get(), c->stream.get()));
+    c->dbg.sim_form = (int64_t)f.nthr << 20 | f.lpp << 16 | f.out << 12 | f.dt << 8 | f.wr << 4 | f.split;
+    if (!launch_simulate(c->stream.get(), a, f)) { c->err = "simulate: no k_simulate instance for this form"; return DWGSIM_HIP_ERR_FAILED; }
+    HIPC(c, hipEventRecord(sl.ev_k1.get(), c->stream.get()));
     sl.cap_mult = c->flow_cap_mult;
-    if (!rerun) launch_failrule(c->stream, a.meta, n_pairs, opens, c->fail_summ.get<uint64_t>(), sl.counters.dev(), c->d_chain.get<uint64_t>());
+    if (!rerun) launch_failrule(c->stream.get(), a.meta, n_pairs, opens, c->fail_summ.get<uint64_t>(), sl.counters.dev(), c->d_chain.get<uint64_t>());
     if (c->gzip_on) {      // the .gz form of every stream, enqueued behind the text (lengths are read on the device: counters[4 + t])
-        HIPC(c, hipMemsetAsync(sl.gz_status.get(), 0, P.gz_status, c->stream));
+        HIPC(c, hipMemsetAsync(sl.gz_status.get(), 0, P.gz_status, c->stream.get()));
         size_t off = 0;
         for (int t = 0; t < 3; ++t) {
             if (P.cap[t] == 0) continue;
-            launch_gzip(c->stream, a.out[t], &sl.counters.dev()[4 + t], P.cap[t], sl.gz_out[t].get<uint8_t>(), P.gz_cap[t], sl.gz_status.get<uint64_t>() + off, &sl.counters.dev()[28 + t], &sl.counters.dev()[24 + t], &sl.counters.dev()[2],
+            launch_gzip(c->stream.get(), a.out[t], &sl.counters.dev()[4 + t], P.cap[t], sl.gz_out[t].get<uint8_t>(), P.gz_cap[t], sl.gz_status.get<uint64_t>() + off, &sl.counters.dev()[28 + t], &sl.counters.dev()[24 + t], &sl.counters.dev()[2],
                         c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
             off += P.gz_chunks[t];
         }
     }
-    HIPC(c, hipEventRecord(sl.ev_end, c->stream));
+    HIPC(c, hipEventRecord(sl.ev_end.get(), c->stream.get()));
     HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(sl.counters.host(), sl.counters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipEventRecord(sl.ev_done, c->stream));
+    HIPC(c, hipMemcpyAsync(sl.counters.host(), sl.counters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPC(c, hipEventRecord(sl.ev_done.get(), c->stream.get()));
     sl.pending = true;
     return DWGSIM_HIP_OK;
 }
@@ -2067,7 +2106,7 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
     if (sl.empty) { sl.pending = false; return DWGSIM_HIP_OK; }
     if (!sl.pending) { c->err = "wait: no batch was enqueued on this slot"; return DWGSIM_HIP_ERR_STATE; }
     HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipEventSynchronize(sl.ev_done));
+    HIPC(c, hipEventSynchronize(sl.ev_done.get()));
     sl.pending = false;
     uint64_t *h = sl.counters.host();
     if ((h[2] & 2) && !(h[2] & ~(2ull | 8ull)) && c->prm.data_type == 2) {
@@ -2084,7 +2123,7 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
                 c->flow_cap_mult *= 2;
             }
             if (const int rc = sim_enqueue(c, sl.ranges.data(), (int)sl.ranges.size(), base, slot, true)) return rc;
-            HIPC(c, hipEventSynchronize(sl.ev_done));
+            HIPC(c, hipEventSynchronize(sl.ev_done.get()));
             sl.pending = false;
         }
         for (int q = 0; q < 6; ++q) h[16 + q] = keep[q];
@@ -2096,7 +2135,7 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
     }
     if (h[2] & 8) { c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
     for (int t = 0; t < 3; ++t) { sl.out_bytes[t] = h[4 + t]; sl.gz_bytes[t] = h[24 + t]; }
-    if (c->phases) {   // only meaningful with the -DDW_PHASE_TIMING build (tools/phase_profile.sh)
+    if (c->dbg.phases) {   // only meaningful with the -DDW_PHASE_TIMING build (tools/phase_profile.sh)
         uint64_t tot = 0; for (int k = 0; k < 8; ++k) tot += h[8 + k];
         fprintf(stderr, "[phases]");
         for (int k = 0; k < 8; ++k) fprintf(stderr, " p%d=%.1f%%", k, tot ? 100.0 * h[8 + k] / tot : 0.0);
@@ -2108,8 +2147,8 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
         for (int t = 0; t < 3; ++t) out->gz_bytes[t] = sl.gz_bytes[t];
         for (int t = 0; t < 4; ++t) out->fail_seg[t] = h[16 + t];
         out->fail_carry = h[21];
-        HIPC(c, hipEventElapsedTime(&out->sim_kernel_ms, sl.ev_k0, sl.ev_k1));
-        HIPC(c, hipEventElapsedTime(&out->kernel_ms, sl.ev_k0, sl.ev_end));       // ... with the abort-rule epilogue and the gzip kernels
+        HIPC(c, hipEventElapsedTime(&out->sim_kernel_ms, sl.ev_k0.get(), sl.ev_k1.get()));
+        HIPC(c, hipEventElapsedTime(&out->kernel_ms, sl.ev_k0.get(), sl.ev_end.get()));       // ... with the abort-rule epilogue and the gzip kernels
     }
     return DWGSIM_HIP_OK;
 }
@@ -2185,8 +2224,8 @@ static int fetch_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst
     const size_t n = (size_t)(gz ? sl.gz_bytes[stream] : sl.out_bytes[stream]);
     if (n > cap) { c->err = "fetch: destination too small"; return DWGSIM_HIP_ERR_ARG; }
     if (n == 0) return DWGSIM_HIP_OK;
-    HIPC(c, hipMemcpyAsync(host_dst, gz ? sl.gz_out[stream].get() : c->out[slot][stream].get(), n, hipMemcpyDeviceToHost, c->copy_stream));
-    HIPC(c, hipEventRecord(sl.ev_fetched, c->copy_stream));
+    HIPC(c, hipMemcpyAsync(host_dst, gz ? sl.gz_out[stream].get() : c->out[slot][stream].get(), n, hipMemcpyDeviceToHost, c->copy_stream.get()));
+    HIPC(c, hipEventRecord(sl.ev_fetched.get(), c->copy_stream.get()));
     sl.fetch_in_flight = true;
     return DWGSIM_HIP_OK;
 }
@@ -2213,7 +2252,7 @@ int dwgsim_hip_fetch_wait(dwgsim_hip_ctx_t *c, int slot)
     Slot &sl = c->slot[slot];
     if (!sl.fetch_in_flight) return DWGSIM_HIP_OK;
     HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipEventSynchronize(sl.ev_fetched));
+    HIPC(c, hipEventSynchronize(sl.ev_fetched.get()));
     sl.fetch_in_flight = false;
     return DWGSIM_HIP_OK;
 }
@@ -2228,8 +2267,8 @@ int dwgsim_hip_fetch(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, 
     if (n > cap) { c->err = "fetch: destination too small"; return DWGSIM_HIP_ERR_ARG; }
     if (n == 0) return DWGSIM_HIP_OK;
     if (is_page_locked(host_dst)) {   // a pinned (page-locked / registered) destination takes one direct copy at link speed
-        HIPC(c, hipMemcpyAsync(host_dst, c->out[slot][stream].get(), n, hipMemcpyDeviceToHost, c->copy_stream));
-        HIPC(c, hipStreamSynchronize(c->copy_stream));
+        HIPC(c, hipMemcpyAsync(host_dst, c->out[slot][stream].get(), n, hipMemcpyDeviceToHost, c->copy_stream.get()));
+        HIPC(c, hipStreamSynchronize(c->copy_stream.get()));
         return DWGSIM_HIP_OK;
     }
     // double-buffered pinned staging: D2H of chunk k+1 overlaps the host copy of chunk k
@@ -2239,11 +2278,11 @@ int dwgsim_hip_fetch(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, 
     uint8_t *stage[2] = {c->h_stage.get<uint8_t>(), c->h_stage.get<uint8_t>() + CH};
     size_t done = 0; int b = 0;
     size_t cur = n < CH ? n : CH;
-    HIPC(c, hipMemcpyAsync(stage[0], src, cur, hipMemcpyDeviceToHost, c->copy_stream));
+    HIPC(c, hipMemcpyAsync(stage[0], src, cur, hipMemcpyDeviceToHost, c->copy_stream.get()));
     while (done < n) {
-        HIPC(c, hipStreamSynchronize(c->copy_stream));
+        HIPC(c, hipStreamSynchronize(c->copy_stream.get()));
         const size_t next_off = done + cur, next = next_off < n ? ((n - next_off) < CH ? (n - next_off) : CH) : 0;
-        if (next) HIPC(c, hipMemcpyAsync(stage[b ^ 1], src + next_off, next, hipMemcpyDeviceToHost, c->copy_stream));
+        if (next) HIPC(c, hipMemcpyAsync(stage[b ^ 1], src + next_off, next, hipMemcpyDeviceToHost, c->copy_stream.get()));
         memcpy((uint8_t *)host_dst + done, stage[b], cur);
         done += cur; cur = next; b ^= 1;
     }
@@ -2257,10 +2296,10 @@ int dwgsim_hip_debug_count_byte(dwgsim_hip_ctx_t *c, int slot, int stream, int b
     HIPC(c, hipSetDevice(c->device));
     Slot &sl = c->slot[slot];
     if (sl.pending) { c->err = "count_byte: wait for the batch first"; return DWGSIM_HIP_ERR_STATE; }
-    HIPC(c, hipMemsetAsync(&c->counters.dev()[15], 0, sizeof(uint64_t), c->stream));
-    if (sl.out_bytes[stream]) launch_count_byte(c->stream, c->out[slot][stream].get<uint8_t>(), sl.out_bytes[stream], (uint32_t)(byte & 0xff), &c->counters.dev()[15]);
-    HIPC(c, hipMemcpyAsync(&c->counters.host()[15], &c->counters.dev()[15], sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, hipMemsetAsync(&c->counters.dev()[15], 0, sizeof(uint64_t), c->stream.get()));
+    if (sl.out_bytes[stream]) launch_count_byte(c->stream.get(), c->out[slot][stream].get<uint8_t>(), sl.out_bytes[stream], (uint32_t)(byte & 0xff), &c->counters.dev()[15]);
+    HIPC(c, hipMemcpyAsync(&c->counters.host()[15], &c->counters.dev()[15], sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPC(c, hipStreamSynchronize(c->stream.get()));
     *count = c->counters.host()[15];
     return DWGSIM_HIP_OK;
 }
@@ -2280,12 +2319,12 @@ int dwgsim_hip_debug_gzip(dwgsim_hip_ctx_t *c, const void *text, size_t n, void 
     if (reserve(c, text_m, n + 64, n + 64) != hipSuccess || reserve(c, out_m, gcap + 64, gcap + 64) != hipSuccess || reserve(c, aux_m, sizeof(uint64_t) * (4 + nch), sizeof(uint64_t) * (4 + nch)) != hipSuccess) { c->err = "out of device memory"; return DWGSIM_HIP_ERR_DEVICE; }
     uint8_t *d_text = text_m.get(), *d_out = out_m.get(); uint64_t *d_aux = aux_m.get<uint64_t>();       // aux: [0] length, [1] ticket, [2] total, [3] flags, [4..] look-back words
     const uint64_t n64 = n;
-    bool ok = hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c->stream) == hipSuccess && hipMemsetAsync(d_aux, 0, sizeof(uint64_t) * (4 + nch), c->stream) == hipSuccess &&
-              hipMemcpyAsync(d_aux, &n64, sizeof n64, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+    bool ok = hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c->stream.get()) == hipSuccess && hipMemsetAsync(d_aux, 0, sizeof(uint64_t) * (4 + nch), c->stream.get()) == hipSuccess &&
+              hipMemcpyAsync(d_aux, &n64, sizeof n64, hipMemcpyHostToDevice, c->stream.get()) == hipSuccess;
     if (ok) {
-        launch_gzip(c->stream, d_text, &d_aux[0], n, d_out, gcap, &d_aux[4], &d_aux[1], &d_aux[2], &d_aux[3], c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
+        launch_gzip(c->stream.get(), d_text, &d_aux[0], n, d_out, gcap, &d_aux[4], &d_aux[1], &d_aux[2], &d_aux[3], c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
         uint64_t res[4] = {0, 0, 0, 0};
-        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(res, d_aux, sizeof res, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(res, d_aux, sizeof res, hipMemcpyDeviceToHost, c->stream.get()) == hipSuccess && hipStreamSynchronize(c->stream.get()) == hipSuccess;
         if (ok && (res[3] & 8)) { c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
         if (ok && res[2] > cap) { c->err = "debug_gzip: destination too small"; return DWGSIM_HIP_ERR_ARG; }
         if (ok) { ok = hipMemcpy(out, d_out, (size_t)res[2], hipMemcpyDeviceToHost) == hipSuccess; *out_n = (size_t)res[2]; }
@@ -2307,22 +2346,22 @@ int dwgsim_hip_debug_gzip(dwgsim_hip_ctx_t *c, const void *text, size_t n, void 
 int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *c, const char *key, int64_t value)
 {
     if (!c || !key) return DWGSIM_HIP_ERR_ARG;
-    if (!strcmp(key, "justify_seq")) c->seq_justify = value != 0;
-    else if (!strcmp(key, "dense_view")) c->dense_view = value != 0;
-    else if (!strcmp(key, "walk_cap")) c->walk_cap = value;
-    else if (!strcmp(key, "site_slots")) c->site_slots = (int)value;
-    else if (!strcmp(key, "site_slot_cap")) c->site_slot_cap = value;
-    else if (!strcmp(key, "phases")) c->phases = value != 0;
-    else if (!strcmp(key, "writer")) c->writer = (int)value;
-    else if (!strcmp(key, "sim_threads")) c->force_threads = (int)value;
+    if (!strcmp(key, "justify_seq")) c->dbg.seq_justify = value != 0;
+    else if (!strcmp(key, "dense_view")) c->dbg.dense_view = value != 0;
+    else if (!strcmp(key, "walk_cap")) c->dbg.walk_cap = value;
+    else if (!strcmp(key, "site_slots")) c->dbg.site_slots = (int)value;
+    else if (!strcmp(key, "site_slot_cap")) c->dbg.site_slot_cap = value;
+    else if (!strcmp(key, "phases")) c->dbg.phases = value != 0;
+    else if (!strcmp(key, "writer")) c->dbg.writer = (int)value;
+    else if (!strcmp(key, "sim_threads")) c->dbg.force_threads = (int)value;
     else if (!strcmp(key, "walk_seg_min")) walk_debug_seg_min((uint32_t)value);      // (process-wide)
-    else if (!strcmp(key, "place_cap")) c->place_cap = value;
-    else if (!strcmp(key, "split")) c->split = (int)value;
-    else if (!strcmp(key, "qrows")) c->qrows = (int)value;
-    else if (!strcmp(key, "flow_slots")) c->flow_slots = (int)value;
-    else if (!strcmp(key, "ion_lds")) c->ion_lds = (int)value;
-    else if (!strcmp(key, "flow_cap")) c->flow_cap_forced = (int)value;
-    else if (!strcmp(key, "hap_yardstick")) c->hap_yardstick = value != 0;      // dwgsim_hip_haplotype_fasta also times a device-to-device copy of the text's size ("hap_copy_us")
+    else if (!strcmp(key, "place_cap")) c->dbg.place_cap = value;
+    else if (!strcmp(key, "split")) c->dbg.split = (int)value;
+    else if (!strcmp(key, "qrows")) c->dbg.qrows = (int)value;
+    else if (!strcmp(key, "flow_slots")) c->dbg.flow_slots = (int)value;
+    else if (!strcmp(key, "ion_lds")) c->dbg.ion_lds = (int)value;
+    else if (!strcmp(key, "flow_cap")) c->dbg.flow_cap_forced = (int)value;
+    else if (!strcmp(key, "hap_yardstick")) c->dbg.hap_yardstick = value != 0;      // dwgsim_hip_haplotype_fasta also times a device-to-device copy of the text's size ("hap_copy_us")
     else { c->err = "unknown debug option"; return DWGSIM_HIP_ERR_ARG; }
     return DWGSIM_HIP_OK;
 }
@@ -2338,15 +2377,15 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *c, const char *key, int64_t value)
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
 {
     if (!c || !key || !value) return DWGSIM_HIP_ERR_ARG;
-    if (!strcmp(key, "place_open")) *value = (int64_t)c->place_open;
+    if (!strcmp(key, "place_open")) *value = (int64_t)c->dbg.place_open;
     else if (!strcmp(key, "flow_cap_mult")) *value = (int64_t)c->flow_cap_mult;
-    else if (!strcmp(key, "walk_us")) *value = (int64_t)c->walk_us;           // HIP-event time of the walk chains waited for so far (start of the chain to its end, on the walk stream)
-    else if (!strcmp(key, "count_us")) *value = (int64_t)c->count_us;         // ... of the random-read counts (k_place .. k_range_counts)
-    else if (!strcmp(key, "sim_form")) *value = c->sim_form;                  // k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> of the last launch, packed
-    else if (!strcmp(key, "hap_len_us")) *value = (int64_t)c->hap_len_us;     // the haplotype text built last: HIP-event time of its length pass + scan,
-    else if (!strcmp(key, "hap_write_us")) *value = (int64_t)c->hap_write_us; // ... of its header and write kernels,
-    else if (!strcmp(key, "hap_copy_us")) *value = (int64_t)c->hap_copy_us;   // ... and ("hap_yardstick") of a device-to-device copy of its size
-    else if (!strcmp(key, "walk_form")) *value = c->walk_form;                // attempt, file-driven / random, site-scan form, restore, views of the last walk, packed
+    else if (!strcmp(key, "walk_us")) *value = (int64_t)c->dbg.walk_us;           // HIP-event time of the walk chains waited for so far (start of the chain to its end, on the walk stream)
+    else if (!strcmp(key, "count_us")) *value = (int64_t)c->dbg.count_us;         // ... of the random-read counts (k_place .. k_range_counts)
+    else if (!strcmp(key, "sim_form")) *value = c->dbg.sim_form;                  // k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> of the last launch, packed
+    else if (!strcmp(key, "hap_len_us")) *value = (int64_t)c->dbg.hap_len_us;     // the haplotype text built last: HIP-event time of its length pass + scan,
+    else if (!strcmp(key, "hap_write_us")) *value = (int64_t)c->dbg.hap_write_us; // ... of its header and write kernels,
+    else if (!strcmp(key, "hap_copy_us")) *value = (int64_t)c->dbg.hap_copy_us;   // ... and ("hap_yardstick") of a device-to-device copy of its size
+    else if (!strcmp(key, "walk_form")) *value = c->dbg.walk_form;                // attempt, file-driven / random, site-scan form, restore, views of the last walk, packed
     else { c->err = "unknown debug value"; return DWGSIM_HIP_ERR_ARG; }
     return DWGSIM_HIP_OK;
 }

@@ -1,9 +1,11 @@
-// dw_mem.hpp -- owners of device and page-locked host memory for the host code (dw_host.cpp, dw_eval.cpp; no kernel includes it).
+// dw_mem.hpp -- owners of device and page-locked host memory, events and streams for the host code (dw_host.cpp, dw_eval.cpp; no kernel includes it).
 //
 // DevMem / HostMem own one hipMalloc / hipHostMalloc allocation each: move-only, freed by the destructor.  reserve(need, want) keeps the
 // allocation when it holds `need` bytes, else frees it and allocates `want` bytes -- every site keeps its own growth rule and exact sizes --
 // and records the new capacity only once the allocation succeeded.  An allocation function may be passed (dw_host.cpp: dev_malloc, which
-// retries when the device is out of memory).  DevEvent owns a hipEvent_t the same way.
+// retries when the device is out of memory).  DevEvent and DevStream own a hipEvent_t / hipStream_t the same way: create() makes the handle once, the
+// destructor gives it back.  Destroying a stream does not wait for its work: whoever owns one synchronises it before the owner goes.  These are the
+// only places in the host code that create or destroy an event or a stream.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -85,6 +87,33 @@ public:
 
 private:
     hipEvent_t e_ = nullptr;
+};
+
+class DevStream {
+public:
+    DevStream() = default;
+    DevStream(const DevStream &) = delete;
+    DevStream &operator=(const DevStream &) = delete;
+    DevStream(DevStream &&o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+    DevStream &operator=(DevStream &&o) noexcept
+    {
+        if (this != &o) { reset(); s_ = o.s_; o.s_ = nullptr; }
+        return *this;
+    }
+    ~DevStream() { reset(); }
+
+    hipError_t create() { return s_ ? hipSuccess : hipStreamCreate(&s_); }      // (once: a stream that exists is kept, whatever its priority)
+    hipError_t create(int priority) { return s_ ? hipSuccess : hipStreamCreateWithPriority(&s_, hipStreamDefault, priority); }
+    void reset()
+    {
+        if (s_) (void)hipStreamDestroy(s_);
+        s_ = nullptr;
+    }
+    hipStream_t get() const { return s_; }
+    explicit operator bool() const { return s_ != nullptr; }
+
+private:
+    hipStream_t s_ = nullptr;
 };
 
 } // namespace dw

@@ -137,14 +137,16 @@ static inline hipError_t hipMemset(void *d, int v, size_t n) { memset(d, v, n); 
 enum hipMemoryType { hipMemoryTypeUnregistered = 0, hipMemoryTypeHost = 1, hipMemoryTypeDevice = 2 };
 struct hipPointerAttribute_t { hipMemoryType type; };
 static inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t *a, const void *) { a->type = hipMemoryTypeUnregistered; return 1; }
-static inline hipError_t hipStreamCreate(hipStream_t *s) { *s = (hipStream_t)malloc(1); return 0; }
+// Streams and events are counted like allocations (hip_emu.cpp: hipemu_live_handles)
+namespace hipemu { void *handle_make(size_t n); void handle_free(void *h); }
+static inline hipError_t hipStreamCreate(hipStream_t *s) { *s = (hipStream_t)hipemu::handle_make(1); return 0; }
 #define hipStreamDefault 0
 static inline hipError_t hipDeviceGetStreamPriorityRange(int *least, int *greatest) { *least = 0; *greatest = 0; return 0; }
 static inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { return hipStreamCreate(s); }
-static inline hipError_t hipStreamDestroy(hipStream_t s) { free(s); return 0; }
+static inline hipError_t hipStreamDestroy(hipStream_t s) { hipemu::handle_free(s); return 0; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
-static inline hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)calloc(1, sizeof(hipemu_event)); return 0; }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { free(e); return 0; }
+static inline hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)hipemu::handle_make(sizeof(hipemu_event)); return 0; }
+static inline hipError_t hipEventDestroy(hipEvent_t e) { hipemu::handle_free(e); return 0; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); e->t = ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; return 0; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 static inline hipError_t hipEventQuery(hipEvent_t) { return 0; }

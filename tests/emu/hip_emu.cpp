@@ -242,7 +242,7 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()> &fn
 // device and page-locked memory (hipMalloc / hipHostMalloc): live allocations are counted, and the k-th allocation from a given moment can be
 // made to fail with hipErrorOutOfMemory -- tests/test_emu_memory.py checks that every allocation is freed and that a failed one leaves sound state
 namespace {
-std::atomic<long> g_live{0}, g_fail_in{0};
+std::atomic<long> g_live{0}, g_fail_in{0}, g_live_handles{0};
 }
 namespace hipemu {
 hipError_t mem_alloc(void **p, size_t n)
@@ -259,7 +259,16 @@ void mem_free(void *p)
     --g_live;
     free(p);
 }
+// streams and events (zeroed; never made to fail: the k-th ALLOCATION is what the tests fail)
+void *handle_make(size_t n) { ++g_live_handles; return calloc(1, n); }
+void handle_free(void *h)
+{
+    if (!h) return;
+    --g_live_handles;
+    free(h);
+}
 } // namespace hipemu
 extern "C" long hipemu_live_allocs(void) { return g_live.load(); }
+extern "C" long hipemu_live_handles(void) { return g_live_handles.load(); }      // streams + events created and not destroyed
 // k > 0: the k-th allocation from now fails (once); 0: none.  Returns how many allocations the previous request still had to wait for (0: it fired or there was none).
 extern "C" long hipemu_fail_alloc(long k) { return g_fail_in.exchange(k < 0 ? 0 : k); }

@@ -1,6 +1,7 @@
 """CPU-only check of the host code's memory ownership, on the libraries that tests/emu/build.sh and build_eval.sh build: the emulation shim
-counts live hipMalloc / hipHostMalloc allocations and can make the k-th allocation from a given moment fail (hip_emu.cpp hipemu_live_allocs,
-hipemu_fail_alloc).  Every scenario must give back all it allocated; a call whose allocation fails must return an error, and the same call
+counts live hipMalloc / hipHostMalloc allocations and live streams and events, and can make the k-th allocation from a given moment fail (hip_emu.cpp
+hipemu_live_allocs, hipemu_live_handles, hipemu_fail_alloc).  Every scenario must give back all it allocated and every stream and event it made -- a
+context whose creation dies at its k-th allocation included; a call whose allocation fails must return an error, and the same call
 repeated without the failure must then succeed and give what an undisturbed run gives.  The scenarios run in a child process: a call that
 went on with a missing table crashes it.  The job level (dw_job.cpp) gets the same treatment one level up: the k-th allocation of a whole job
 fails, a sink refuses its n-th call, a job is destroyed unfinished -- each must return in time with an error or the right output, and with nothing
@@ -20,6 +21,7 @@ import eval_sam
 
 def hooks(lib):
     lib.hipemu_live_allocs.restype = C.c_long
+    lib.hipemu_live_handles.restype = C.c_long
     lib.hipemu_fail_alloc.restype = C.c_long
     lib.hipemu_fail_alloc.argtypes = [C.c_long]
     return lib
@@ -33,10 +35,11 @@ contigs = [("c%d" % k, synth.random_contig(3000 + 700 * k, 11 + k)) for k in ran
 
 DRIVER = PRELUDE + r'''
 def leak_free(name, lib, fn):
-    base = lib.hipemu_live_allocs()
+    base, base_h = lib.hipemu_live_allocs(), lib.hipemu_live_handles()
     fn()
-    left = lib.hipemu_live_allocs() - base
+    left, left_h = lib.hipemu_live_allocs() - base, lib.hipemu_live_handles() - base_h
     assert left == 0, "%s: %d allocations left behind" % (name, left)
+    assert left_h == 0, "%s: %d streams and events left behind" % (name, left_h)
 
 def context_scenario():
     ctx = api.Context(params, lib=lib)
@@ -69,9 +72,41 @@ def eval_scenario():
 def job_scenario():
     api.run_job_api(params, contigs[:3], devices=[0, 0, 0], batch_pairs=64, lib=lib)
 
+def create_destroy(lib, create, destroy, k=0):
+    """create(err) with its k-th allocation failing (0: none), then destroy -> (whether a context came back, the error code, whether the failure fired)"""
+    err = C.c_int(0)
+    lib.hipemu_fail_alloc(k)
+    h = create(C.byref(err))
+    fired = lib.hipemu_fail_alloc(0) == 0 and k > 0
+    if h:
+        destroy(h)
+    return bool(h), err.value, fired
+
+def failed_creates(name, lib, create, destroy):
+    """a plain create / destroy, then one whose k-th allocation fails, for every k up to the allocations a create makes: an error comes back, nothing is left"""
+    got = []
+    leak_free(name + " create", lib, lambda: got.append(create_destroy(lib, create, destroy)))
+    assert got[-1] == (True, 0, False), (name, got[-1])
+    k = 1
+    while True:
+        leak_free("%s create, allocation %d fails" % (name, k), lib, lambda: got.append(create_destroy(lib, create, destroy, k)))
+        made, code, fired = got[-1]
+        if not fired:
+            break
+        assert not made and code < 0, "%s create: allocation %d failed, a context came back or the error code is %d" % (name, k, code)
+        k += 1
+    assert made and code == 0 and k > 4, (name, k, got[-1])
+    print(name, "create makes", k - 1, "allocations", flush=True)
+
+EVAL_OPTS = api.EvalOpts()
+elib.dwgsim_hip_eval_opts_default(C.byref(EVAL_OPTS))
+EVAL_OPTS.chunk_bytes = 4096
+
 leak_free("context", lib, context_scenario)
 leak_free("eval", elib, eval_scenario)
 leak_free("job", lib, job_scenario)
+failed_creates("context", lib, lambda err: lib.dwgsim_hip_create(C.byref(params), 0, err), lib.dwgsim_hip_destroy)
+failed_creates("eval", elib, lambda err: elib.dwgsim_hip_eval_create(C.byref(EVAL_OPTS), 0, err), elib.dwgsim_hip_eval_destroy)
 print("no leaks", flush=True)
 
 # ---- a failed allocation in add_contigs, mutate_async or set_gzip(1), then the same call again ----
@@ -86,7 +121,7 @@ STAGES = ["add_contigs", "mutate_async", "set_gzip"]
 
 def pipeline(stage=None, k=0):
     """the calls in order; at `stage` the k-th allocation fails.  Returns (outputs, whether the failure fired)"""
-    base = lib.hipemu_live_allocs()
+    base, base_h = lib.hipemu_live_allocs(), lib.hipemu_live_handles()
     ctx = api.Context(params, lib=lib)
     h = ctx.h
     fired = False
@@ -117,6 +152,8 @@ def pipeline(stage=None, k=0):
     ctx.close()
     left = lib.hipemu_live_allocs() - base
     assert left == 0, "%s, allocation %d: %d allocations left behind" % (stage, k, left)
+    left_h = lib.hipemu_live_handles() - base_h
+    assert left_h == 0, "%s, allocation %d: %d streams and events left behind" % (stage, k, left_h)
     return out, fired
 
 want, _ = pipeline()
@@ -180,7 +217,7 @@ def run(devices, offset_sink, fail_alloc=0, refuse=None, destroy_after=None, job
     err = C.c_int(0)
     devs = (C.c_int * len(devices))(*devices)
     faulthandler.dump_traceback_later(RUN_TIMEOUT, exit=True)
-    base = lib.hipemu_live_allocs()
+    base, base_h = lib.hipemu_live_allocs(), lib.hipemu_live_handles()
     lib.hipemu_fail_alloc(fail_alloc)
     where, code, text = None, 0, ""
     h = lib.dwgsim_hip_job_create(C.byref(params), devs, len(devices), C.byref(sink), C.byref(opt), C.byref(err))
@@ -213,6 +250,8 @@ def run(devices, offset_sink, fail_alloc=0, refuse=None, destroy_after=None, job
     faulthandler.cancel_dump_traceback_later()
     left = lib.hipemu_live_allocs() - base
     assert left == 0, "devices %s, allocation %d, %s: %d allocations left behind (ended at %s)" % (devices, fail_alloc, refuse.which, left, where)
+    left_h = lib.hipemu_live_handles() - base_h
+    assert left_h == 0, "devices %s, allocation %d, %s: %d streams and events left behind (ended at %s)" % (devices, fail_alloc, refuse.which, left_h, where)
     out = None
     if where is None:
         streams = []
