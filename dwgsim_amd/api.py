@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DWGSIM_HIP_LIB") or os.path.join(_HERE, "libdwgsim_hip.so")   # env override: analysis builds only
 
 STREAM_BWA1, STREAM_BWA2, STREAM_BFAST = 0, 1, 2
+STREAM_SAM = 3      # DWGSIM_HIP_STREAM_SAM: the truth SAM (Context.set_truth_sam)
 STREAM_NAMES = {0: "bwa.read1.fastq", 1: "bwa.read2.fastq", 2: "bfast.fastq"}
 
 
@@ -34,7 +35,8 @@ class Params(C.Structure):
 class Batch(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("n_random", C.c_uint64), ("n_retries", C.c_uint64), ("bytes", C.c_uint64 * 3),
                 ("dev_ptr", C.c_void_p * 3), ("kernel_ms", C.c_float), ("sim_kernel_ms", C.c_float),
-                ("fail_seg", C.c_uint64 * 4), ("fail_carry", C.c_uint64), ("gz_bytes", C.c_uint64 * 3)]
+                ("fail_seg", C.c_uint64 * 4), ("fail_carry", C.c_uint64), ("gz_bytes", C.c_uint64 * 3),
+                ("sam_bytes", C.c_uint64), ("sam_gz_bytes", C.c_uint64), ("sam_dev_ptr", C.c_void_p)]      # (ABI 8) the truth SAM
 
 
 class Range(C.Structure):
@@ -87,6 +89,7 @@ EXPORTS = [
     "dwgsim_hip_eval_set_breakdown", "dwgsim_hip_eval_breakdown_text",
     "dwgsim_hip_haplotype_fasta", "dwgsim_hip_haplotype_layout", "dwgsim_hip_haplotype_fetch", "dwgsim_hip_job_set_haplotype_sink",
     "dwgsim_hip_debug_sim_instances",
+    "dwgsim_hip_set_truth_sam", "dwgsim_hip_truth_sam_header", "dwgsim_hip_job_set_truth_sam",
 ]
 
 _lib = None
@@ -178,6 +181,10 @@ def load(path: str | None = None):
     lib.dwgsim_hip_haplotype_fetch.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
     lib.dwgsim_hip_job_set_haplotype_sink.argtypes = [C.c_void_p, HAP_CB, C.c_void_p, C.c_int]
     lib.dwgsim_hip_debug_sim_instances.argtypes = [P(C.c_int64), C.c_int]
+    lib.dwgsim_hip_set_truth_sam.argtypes = [C.c_void_p, C.c_int]
+    lib.dwgsim_hip_truth_sam_header.restype = C.c_int64
+    lib.dwgsim_hip_truth_sam_header.argtypes = [P(C.c_char_p), P(C.c_int64), C.c_int, C.c_char_p, C.c_size_t]
+    lib.dwgsim_hip_job_set_truth_sam.argtypes = [C.c_void_p, C.c_int]
     if hasattr(lib, "dwgsim_hip_eval_create"):
         _bind_eval(lib)
     if path is None:
@@ -317,6 +324,7 @@ class JobResult:
     flow_cap_mult: int = 1                           # Ion Torrent: by how much the read capacity had grown at the end of the job (run_job)
     haplotypes: dict = field(default_factory=dict)   # haplotypes=True: {0: bytes, 1: bytes}, the two mutated haplotypes as FASTA
     sim_forms: set = field(default_factory=set)      # debug_get("sim_form") after every simulate call of the job (run_job): the k_simulate forms it ran
+    truth_sam: bytes = b""                           # truth_sam=True: the records of the truth SAM (no header: truth_sam_header)
 
 
 VCF_HEADER_POST = (
@@ -503,6 +511,10 @@ class Context:
     def set_gzip(self, on: bool = True):
         self._chk(self.lib.dwgsim_hip_set_gzip(self.h, 1 if on else 0))
 
+    def set_truth_sam(self, on: bool = True):
+        """Every simulate call also leaves stream STREAM_SAM: the true alignment of every read end as SAM records (Illumina reads only)."""
+        self._chk(self.lib.dwgsim_hip_set_truth_sam(self.h, 1 if on else 0))
+
     def fetch_gz(self, slot: int, stream: int, nbytes: int) -> bytes:
         """The .gz form of a finished stream (GPU gzip), through a page-locked bounce buffer."""
         if not nbytes:
@@ -539,6 +551,20 @@ class Context:
         buf = C.create_string_buffer(int(nbytes) if nbytes else 1)
         self._chk(self.lib.dwgsim_hip_fetch(self.h, slot, stream, buf, nbytes))
         return buf.raw[:nbytes]
+
+
+def truth_sam_header(contigs, lib=None) -> bytes:
+    """The header of a truth SAM for the contig table `contigs` ((name, sequence or length) pairs, FASTA order)."""
+    lib = lib or load()
+    n = len(contigs)
+    names = (C.c_char_p * n)(*[nm.encode() for nm, _ in contigs])
+    lens = (C.c_int64 * n)(*[a if isinstance(a, int) else len(a) for _, a in contigs])
+    size = lib.dwgsim_hip_truth_sam_header(names, lens, n, None, 0)
+    if size < 0:
+        raise DwgsimError(f"dwgsim_hip_truth_sam_header: error {size}")
+    buf = C.create_string_buffer(size + 1)
+    lib.dwgsim_hip_truth_sam_header(names, lens, n, buf, size)
+    return buf.raw[:size]
 
 
 def pairs_for_contig(params: Params, l: int, tot_len: int, is_last: bool, n_sim: int, lib=None) -> int:
@@ -597,7 +623,7 @@ def split_ranges(ranges, batch_pairs):
 
 
 def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22, fetch: bool = True, lib=None, debug_options=None, group_bp: int = 0, check_list_form: bool = False,
-            haplotypes: bool = False, hap_width: int = 60) -> JobResult:
+            haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False) -> JobResult:
     """dwgsim_core (dwgsim.c:419-1121) over the C-ABI: header pass, then schedule -> mutate -> mutations text -> simulate in
     read-index batches.  group_bp = 0: contig after contig, as the reference walks them.  group_bp > 0: consecutive contigs are resident
     together in groups of up to group_bp bases (dwgsim_hip_add_contigs): one walk per group, batches that run across contig boundaries."""
@@ -608,6 +634,7 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
     vcf = bytearray()
     txt = bytearray()
     haps = {0: bytearray(), 1: bytearray()}
+    sam = bytearray()
     if want_mut:
         vcf += b"##fileformat=VCFv4.1\n"
         for name, arr in contigs:
@@ -618,6 +645,8 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
     with Context(params, device, lib) as ctx:
         for k, v in (debug_options or {}).items():
             ctx.debug_option(k, v)
+        if truth_sam:
+            ctx.set_truth_sam(True)
         if getattr(params, "_mut_input", None):
             ctx.set_mutation_input(params._mut_input[0], params._mut_input[1], contigs)
         have_regions = bool(getattr(params, "_regions", None))
@@ -659,6 +688,8 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
                     for s in range(3):
                         if b.bytes[s]:
                             res.streams[s] += ctx.fetch(0, s, b.bytes[s])
+                    if b.sam_bytes:
+                        sam += ctx.fetch(0, STREAM_SAM, b.sam_bytes)
                 rand_ii += b.n_random
                 n_sim += b.n_pairs
             ctx.drop_contig(h0)
@@ -670,11 +701,12 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
     res.streams = {k: bytes(v) for k, v in res.streams.items()}
     if haplotypes:
         res.haplotypes = {k: bytes(v) for k, v in haps.items()}
+    res.truth_sam = bytes(sam)
     return res
 
 
 def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True, batch_pairs: int = 0, group_bp: int = 0, min_share: int = 0,
-                lib=None, keep_output: bool = True, offset_sink: bool = False, haplotypes: bool = False, hap_width: int = 60) -> JobResult:
+                lib=None, keep_output: bool = True, offset_sink: bool = False, haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False) -> JobResult:
     """The same job through the JOB level of the C-ABI (dwgsim_hip_job_*): the library schedules, groups, shards over `devices`
     (default: all) and delivers in file order; the sink below only collects.  Streams are returned as text (gzip members are
     decompressed here)."""
@@ -682,14 +714,14 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
     import numpy as np
     lib = lib or load()
     res = JobResult(streams={0: bytearray(), 1: bytearray(), 2: bytearray()})
-    raw = {0: [], 1: [], 2: []}
+    raw = {0: [], 1: [], 2: [], STREAM_SAM: []}      # (stream 3: the truth SAM, delivered like a FASTQ stream)
     txt, vcf = bytearray(), bytearray()
     if params.output_type != 1:
         vcf += b"##fileformat=VCFv4.1\n"
         for name, arr in contigs:
             vcf += f"##contig=<ID={name},length={len(arr)}>\n".encode()
         vcf += VCF_HEADER_POST
-    order = {"mut": [], "text_n": {0: 0, 1: 0, 2: 0}}
+    order = {"mut": [], "text_n": {0: 0, 1: 0, 2: 0, STREAM_SAM: 0}}
 
     def on_mut(user, name, t, tl, v, vl):
         order["mut"].append(name.decode())
@@ -704,7 +736,7 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
         return 0
 
     import threading
-    at_lock = threading.Lock(); at_pieces = {0: [], 1: [], 2: []}; at_threads = set()
+    at_lock = threading.Lock(); at_pieces = {0: [], 1: [], 2: [], STREAM_SAM: []}; at_threads = set()
 
     def on_reads_at(user, stream, offset, data, n, text_n, gz):      # (called from several threads of the job: one per device and stream)
         blob = C.string_at(data, n) if keep_output else b""
@@ -738,6 +770,8 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
         chk(lib.dwgsim_hip_job_set_contig_table(job, names, lens, n))
         if haplotypes:
             chk(lib.dwgsim_hip_job_set_haplotype_sink(job, hap_cb, None, hap_width))
+        if truth_sam:
+            chk(lib.dwgsim_hip_job_set_truth_sam(job, 1))
         if getattr(params, "_regions", None):
             chk(lib.dwgsim_hip_job_set_regions(job, params._regions.encode()))
         if getattr(params, "_mut_input", None):
@@ -754,7 +788,7 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
     finally:
         lib.dwgsim_hip_job_destroy(job)
     if offset_sink:      # the pieces must tile [0, total) of every stream, each exactly once; put in order they are the stream
-        for s_ in range(3):
+        for s_ in range(4):
             at = 0
             for off, n, gz, blob, text_n in sorted(at_pieces[s_]):
                 if off != at:
@@ -762,14 +796,19 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
                 at += n
                 raw[s_].append((gz, blob, text_n))
         res.delivery_threads = len(at_threads)
-    for s_ in range(3):
+    sam = bytearray()
+    for s_ in range(4):
         for gz, blob, text_n in raw[s_]:
             piece = _gz.decompress(blob) if gz else blob
             assert len(piece) == text_n
-            res.streams[s_] += piece
+            if s_ == STREAM_SAM:
+                sam += piece
+            else:
+                res.streams[s_] += piece
+    res.truth_sam = bytes(sam)
     res.mutations_txt, res.mutations_vcf = bytes(txt), bytes(vcf)
     res.streams = {k: bytes(v) for k, v in res.streams.items()}
-    res.delivered_text_bytes = dict(order["text_n"])
+    res.delivered_text_bytes = {k: v for k, v in order["text_n"].items() if k != STREAM_SAM or truth_sam}
     if haplotypes:
         res.haplotypes = {h: b"".join(p for q, p in hap_pieces if q == h) for h in (0, 1)}
         res.haplotype_pieces = [(q, len(p)) for q, p in hap_pieces]

@@ -113,6 +113,9 @@ struct Group {
 struct HandleRef { int group = -1, k = 0; };
 
 constexpr int N_COUNTERS = 32;      // u64 words of a counter block (SimArgs::counters)
+constexpr int N_STREAMS = 4;        // output streams of a batch: the three FASTQ streams and the truth SAM (DWGSIM_HIP_STREAM_SAM)
+// where a stream's text length stands in a slot's counters (its gzip total is [24 + t], its gzip ticket [28 + t])
+constexpr int text_len_counter(int t) { return t < 3 ? 4 + t : 7; }
 
 struct Counters {                   // a device counter block and its page-locked mirror
     DevMem d; HostMem h;
@@ -123,10 +126,11 @@ struct Counters {                   // a device counter block and its page-locke
 struct Slot {                       // one of the two batches a context can have in flight
     Counters counters;
     DevEvent ev_k0, ev_k1, ev_end, ev_done, ev_fetched;
+    DevEvent ev_t0, ev_t1;          // around the truth step (made by dwgsim_hip_set_truth_sam: a context that never switches it on has none)
     bool pending = false, empty = true, fetch_in_flight = false;
     int group = -1;                 // the group the batch in flight reads
-    uint64_t n_pairs = 0, out_bytes[3] = {0, 0, 0}, gz_bytes[3] = {0, 0, 0};
-    DevMem gz_out[3], gz_status, segs;        // GPU gzip: the members of each stream, look-back words; the range table of the launch
+    uint64_t n_pairs = 0, out_bytes[N_STREAMS] = {0, 0, 0, 0}, gz_bytes[N_STREAMS] = {0, 0, 0, 0};
+    DevMem gz_out[N_STREAMS], gz_status, segs;        // GPU gzip: the members of each stream, look-back words; the range table of the launch
     HostMem h_segs;                           // ... and its page-locked source
     std::vector<dwgsim_hip_range_t> ranges;      // what the batch in flight covers (it is enqueued again, with larger read buffers, when an Ion Torrent read outgrew them)
     DevMem d_rerun_chain;                        // [2]: the chain words such a second run starts from
@@ -163,7 +167,7 @@ struct dwgsim_hip_ctx {
         uint64_t place_open = 0; double walk_us = 0, count_us = 0;      // "place_open", "walk_us", "count_us": read back
         int64_t sim_form = 0;                  // dwgsim_hip_debug_get("sim_form"): the k_simulate form of the last launch
         int64_t walk_form = 0;                 // dwgsim_hip_debug_get("walk_form"): what the last walk enqueued was made of
-        double hap_len_us = 0, hap_write_us = 0, hap_copy_us = 0; bool hap_yardstick = false;      // "hap_len_us" / "hap_write_us" / "hap_copy_us", "hap_yardstick" (dwgsim_hip_debug_get / _option)
+        double hap_len_us = 0, hap_write_us = 0, hap_copy_us = 0, truth_us = 0, truth_copy_us = 0; bool hap_yardstick = false;      // "hap_len_us" / "hap_write_us" / "hap_copy_us", "hap_yardstick" (dwgsim_hip_debug_get / _option)
     } dbg;
     int device = 0;
     DevStream stream;            // simulate: kernels of the batches
@@ -177,7 +181,7 @@ struct dwgsim_hip_ctx {
                                              // job of many groups pays its hipMalloc / hipFree (each a device-wide synchronisation) once, not at every group end
     std::vector<HandleRef> handles;          // contig handle -> (group, member); handles are never reused
     // simulate() working set
-    DevMem meta, fail_summ, block_rand, status_all, out[DWGSIM_HIP_SLOTS][3], split_state, split_hand, split_agg, split_pre, split_chunk;
+    DevMem meta, fail_summ, block_rand, status_all, out[DWGSIM_HIP_SLOTS][N_STREAMS], split_state, split_hand, split_agg, split_pre, split_chunk;
     // walk-stream working set (grow-only)
     DevMem w_slots, w_slot_aux;      // the site scan's per-block slots (dw_walk.hip k_site_scan_slots) and their counts / bases
     DevMem scratch_mask, scratch_cnt, scratch_status, w_cand, w_ev, w_flags, w_lo, w_sufmin, w_bound, w_ppos, w_pcells, up_ascii, l_pos, l_cells, place_segs, place_rand, place_list, place_aux;
@@ -198,6 +202,8 @@ struct dwgsim_hip_ctx {
     int n_cu = 0;                          // compute units of the device
     DevEvent ev_cnt0, ev_cnt1;
     bool gzip_on = false; DevMem d_crc_table, d_crc_shift;      // dwgsim_hip_set_gzip (u32; d_crc_shift is uploaded last)
+    bool truth_on = false;                 // dwgsim_hip_set_truth_sam: every batch also leaves stream DWGSIM_HIP_STREAM_SAM
+    DevMem t_nl[2], t_rec[2], t_ends, t_len, t_blk;      // ... its working set (dw_truth.hpp TruthArgs): newline counts and record starts of the source streams, the read ends, the line lengths per end and per block
     HostMem h_stage;                       // pinned staging for fetch
     DevStream hap_stream;                  // dwgsim_hip_haplotype_fetch: copies of its own (made at the first call), not behind the batches' copy-outs
     DevEvent hap_ev[6];                    // dwgsim_hip_haplotype_fasta: the ends of its passes (dbg.hap_*_us)
@@ -1703,11 +1709,12 @@ namespace {
 struct Launch { SimForm f; SimArgs a; Group *g = nullptr; std::vector<SimSeg> segs; uint64_t n_pairs = 0; uint32_t nblk = 0; int fixed_max = 0; };
 // The sizes of one k_simulate launch besides its arguments (sim_plan), in bytes -- 0: the launch does not use that buffer -- and what follows from them
 struct SimPlan {
-    size_t cap[3];                        // record capacity of each stream (0: not written); its text buffer holds 64 bytes more
+    size_t cap[N_STREAMS];                // record capacity of each stream (0: not written); its text buffer holds 64 bytes more
+    size_t t_nl[2], t_rec[2], t_ends, t_len, t_blk; int32_t t_qname_max;      // the truth step's working set (0: off)
     int32_t lb_shift; bool too_many;      // SimArgs::lb_shift; the launch's sums would not fit the look-back word of the single Illumina / SOLiD kernel
     size_t block_rand, status, meta, fail_summ, split_state, split_hand, split_agg, split_pre, split_chunk;      // (split_*: what the first half of the two-kernel form hands to the second)
     bool scratch; int32_t flow_slots; size_t flow_scratch, flow_free;      // scratch slots: in use, per XCD, the slots, their free lists
-    size_t segs, gz_chunks[3], gz_cap[3], gz_status;      // the range table; GPU gzip: chunks and member capacity of each stream, the look-back words of all
+    size_t segs, gz_chunks[N_STREAMS], gz_cap[N_STREAMS], gz_status;      // the range table; GPU gzip: chunks and member capacity of each stream, the look-back words of all
 };
 struct ChainSet { uint64_t *words; int set_rand, set_carry; uint64_t carry; };      // where a launch's running values come from (launch_init / launch_chain_set)
 }
@@ -1965,6 +1972,25 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
     P.cap[2] = P.cap[0] + P.cap[1];
     if (!L.a.p.has_bwa) P.cap[0] = P.cap[1] = 0;
     if (!L.a.p.has_bfast) P.cap[2] = 0;
+    if (c->truth_on) {
+        // The truth SAM (dw_truth.hpp), sized here so that no length crosses to the host.  A line of a read end of s bases is at most
+        //   QNAME (the FASTQ name without '@': below fixed_max + 120, the bound the FASTQ buffers are sized with) + FLAG (3) + RNAME (fixed_max) + POS (10) + MAPQ (2)
+        //   + CIGAR + RNEXT (1) + PNEXT (10) + TLEN (11) + SEQ (s) + QUAL (s) + "HP:i:1" (6) + 11 tabs + the newline.
+        // CIGAR: the runs that hold read bases (M, I) have counts of at least one each that add up to s -- at most s runs, and a count has no more digits than
+        // its value: 2 s characters at most.  A D run stands between two read bases (never first or last) and neighbouring ones merge: at most s - 1 of them, each
+        // a count below 2^31 (10 digits) and its letter.  Together at most 2 s + 11 (s - 1) < 13 s.  (1M1D1M1D... takes 4 s - 2.)
+        P.t_qname_max = fixed_max + 120;
+        size_t ends = 0, bytes = 0;
+        for (int j = 0; j < 2; ++j) if (p.length[j] > 0) { ends += n_pairs; bytes += (size_t)n_pairs * (size_t)(P.t_qname_max + fixed_max + 3 + 10 + 2 + 1 + 10 + 11 + 6 + 11 + 1 + 15 * (size_t)p.length[j]); }
+        P.cap[3] = bytes;
+        const bool bfast_src = !L.a.p.has_bwa;
+        for (int q = 0; q < (bfast_src ? 1 : f.lpp); ++q) {
+            const size_t src_cap = P.cap[bfast_src ? 2 : q];
+            P.t_nl[q] = sizeof(uint32_t) * ((src_cap + 4095) / 4096 + 1); P.t_rec[q] = sizeof(uint32_t) * ((bfast_src ? ends : (size_t)n_pairs) + 2);
+        }
+        P.t_ends = sizeof(TruthEnd) * ends; P.t_len = sizeof(uint32_t) * (ends + 1); P.t_blk = sizeof(uint32_t) * (nblk + 1);
+        for (int t = 0; t < N_STREAMS; ++t) if ((uint64_t)P.cap[t] >> 32) P.too_many = true;      // (record starts and line starts are 32-bit words)
+    }
     P.block_rand = sizeof(uint32_t) * nblk;
     if (!f.split) P.status = 4 * sizeof(uint64_t) * nblk;      // the four look-back arrays, contiguous: one memset per batch
     else { P.split_state = sizeof(uint32_t) * (size_t)f.lds_words * SIM_THREADS * nblk; P.split_hand = 16 * (size_t)SIM_THREADS * nblk; P.split_agg = 16 * nblk; P.split_pre = 32 * nblk; P.split_chunk = 32 * (nblk / 1024 + 1); }
@@ -1990,7 +2016,7 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
     P.segs = sizeof(SimSeg) * L.segs.size();
     if (c->gzip_on) {
         size_t chunks = 0;
-        for (int t = 0; t < 3; ++t) { P.gz_chunks[t] = (size_t)gz_chunks(P.cap[t]); chunks += P.gz_chunks[t]; if (P.cap[t]) P.gz_cap[t] = (size_t)gz_capacity(P.cap[t]); }
+        for (int t = 0; t < N_STREAMS; ++t) { P.gz_chunks[t] = (size_t)gz_chunks(P.cap[t]); chunks += P.gz_chunks[t]; if (P.cap[t]) P.gz_cap[t] = (size_t)gz_capacity(P.cap[t]); }
         P.gz_status = sizeof(uint64_t) * (chunks ? chunks : 1);
     }
     return P;
@@ -2000,13 +2026,15 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
 static int sim_reserve(dwgsim_hip_ctx_t *c, int slot, const SimPlan &P)
 {
     Slot &sl = c->slot[slot]; DevMem *out = c->out[slot];
-    if (sl.fetch_in_flight) { HIPC(c, hipStreamWaitEvent(c->stream.get(), sl.ev_fetched.get(), 0)); bool grows = false; for (int t = 0; t < 3; ++t) if (P.cap[t] + 64 > out[t].cap()) grows = true; if (grows) HIPC(c, hipEventSynchronize(sl.ev_fetched.get())); sl.fetch_in_flight = false; }
+    if (sl.fetch_in_flight) { HIPC(c, hipStreamWaitEvent(c->stream.get(), sl.ev_fetched.get(), 0)); bool grows = false; for (int t = 0; t < N_STREAMS; ++t) if (P.cap[t] + 64 > out[t].cap() && (t < 3 || P.cap[t])) grows = true; if (grows) HIPC(c, hipEventSynchronize(sl.ev_fetched.get())); sl.fetch_in_flight = false; }
     for (int t = 0; t < 3; ++t) if (ensure(c, out[t], P.cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE;
+    if (P.cap[3] && (ensure(c, out[3], P.cap[3] + 64) || ensure(c, c->t_nl[0], P.t_nl[0]) || ensure(c, c->t_nl[1], P.t_nl[1]) || ensure(c, c->t_rec[0], P.t_rec[0]) || ensure(c, c->t_rec[1], P.t_rec[1]) ||
+                     ensure(c, c->t_ends, P.t_ends) || ensure(c, c->t_len, P.t_len) || ensure(c, c->t_blk, P.t_blk))) return DWGSIM_HIP_ERR_DEVICE;
     if (ensure(c, c->block_rand, P.block_rand) || ensure(c, c->status_all, P.status) ||
         ensure(c, c->split_state, P.split_state) || ensure(c, c->split_hand, P.split_hand) || ensure(c, c->split_agg, P.split_agg) || ensure(c, c->split_pre, P.split_pre) || ensure(c, c->split_chunk, P.split_chunk) ||
         ensure(c, c->meta, P.meta) || ensure(c, c->fail_summ, P.fail_summ) || ensure(c, c->flow_scratch, P.flow_scratch) || ensure(c, c->flow_free, P.flow_free) || ensure(c, sl.segs, P.segs)) return DWGSIM_HIP_ERR_DEVICE;
     HIPC(c, sl.h_segs.reserve(P.segs, P.segs + 64 * sizeof(SimSeg)));      // (+ 64 entries; the slot is not pending: no copy reads the old one)
-    for (int t = 0; t < 3; ++t) if (P.gz_cap[t] && ensure(c, sl.gz_out[t], P.gz_cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE;
+    for (int t = 0; t < N_STREAMS; ++t) if (P.gz_cap[t] && ensure(c, sl.gz_out[t], P.gz_cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE;
     return ensure(c, sl.gz_status, P.gz_status);
 }
 
@@ -2031,7 +2059,7 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
 {
     Slot &sl = c->slot[slot]; SimArgs &a = L.a; const SimForm &f = L.f;
     const uint64_t n_pairs = L.n_pairs; const uint32_t nblk = L.nblk;
-    for (int t = 0; t < 3; ++t) sl.out_bytes[t] = sl.gz_bytes[t] = 0;
+    for (int t = 0; t < N_STREAMS; ++t) sl.out_bytes[t] = sl.gz_bytes[t] = 0;
     sl.n_pairs = n_pairs; sl.empty = n_pairs == 0;
     if (n_pairs == 0) { if (ch.set_rand || ch.set_carry) launch_chain_set(c->stream.get(), ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry); return DWGSIM_HIP_OK; }
     uint32_t opens = 0; for (const SimSeg &s : L.segs) opens |= s.contig_start;      // (ranges that begin their contig)
@@ -2053,12 +2081,29 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
     HIPC(c, hipEventRecord(sl.ev_k1.get(), c->stream.get()));
     sl.cap_mult = c->flow_cap_mult;
     if (!rerun) launch_failrule(c->stream.get(), a.meta, n_pairs, opens, c->fail_summ.get<uint64_t>(), sl.counters.dev(), c->d_chain.get<uint64_t>());
-    if (c->gzip_on) {      // the .gz form of every stream, enqueued behind the text (lengths are read on the device: counters[4 + t])
+    if (P.cap[3]) {
+        // The truth step (dw_truth.hpp): this batch's alignments as SAM text, replayed from what the launch left.  It reads meta, which belongs to the CONTEXT, not
+        // to the slot -- the next batch's k_simulate overwrites it -- and the slot's FASTQ text and counters: all of it is safe because the step runs on the
+        // stream of the launches, behind this batch's kernels and in front of the next batch's (and of the gzip kernels below, which take the SAM as a fourth stream).
+        TruthArgs t; memset(&t, 0, sizeof t);
+        HIPC(c, hipEventRecord(sl.ev_t0.get(), c->stream.get()));
+        t.lpp = f.lpp; t.bfast = a.p.has_bwa ? 0 : 1; t.prefix_len = c->read_prefix.empty() ? 0 : (int32_t)c->read_prefix.size() + 1; t.qname_max = P.t_qname_max;
+        for (int q = 0; q < (t.bfast ? 1 : f.lpp); ++q) {
+            const int st = t.bfast ? 2 : q;
+            t.src[q] = a.out[st]; t.src_bytes[q] = &sl.counters.dev()[text_len_counter(st)]; t.src_cap[q] = P.cap[st];
+            t.nl_count[q] = c->t_nl[q].get<uint32_t>(); t.rec[q] = c->t_rec[q].get<uint32_t>(); t.n_rec[q] = t.bfast ? n_pairs * (uint64_t)f.lpp : n_pairs;
+        }
+        t.ends = c->t_ends.get<TruthEnd>(); t.line_len = c->t_len.get<uint32_t>(); t.blk = c->t_blk.get<uint32_t>();
+        t.out = c->out[slot][3].get<uint8_t>(); t.cap = P.cap[3]; t.total = &sl.counters.dev()[text_len_counter(3)];
+        launch_truth(c->stream.get(), a, t);
+        HIPC(c, hipEventRecord(sl.ev_t1.get(), c->stream.get()));
+    }
+    if (c->gzip_on) {      // the .gz form of every stream, enqueued behind the text (lengths are read on the device: counters[4 + t], the SAM's [7])
         HIPC(c, hipMemsetAsync(sl.gz_status.get(), 0, P.gz_status, c->stream.get()));
         size_t off = 0;
-        for (int t = 0; t < 3; ++t) {
+        for (int t = 0; t < N_STREAMS; ++t) {
             if (P.cap[t] == 0) continue;
-            launch_gzip(c->stream.get(), a.out[t], &sl.counters.dev()[4 + t], P.cap[t], sl.gz_out[t].get<uint8_t>(), P.gz_cap[t], sl.gz_status.get<uint64_t>() + off, &sl.counters.dev()[28 + t], &sl.counters.dev()[24 + t], &sl.counters.dev()[2],
+            launch_gzip(c->stream.get(), c->out[slot][t].get<uint8_t>(), &sl.counters.dev()[text_len_counter(t)], P.cap[t], sl.gz_out[t].get<uint8_t>(), P.gz_cap[t], sl.gz_status.get<uint64_t>() + off, &sl.counters.dev()[28 + t], &sl.counters.dev()[24 + t], &sl.counters.dev()[2],
                         c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
             off += P.gz_chunks[t];
         }
@@ -2130,11 +2175,13 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
     }
     if (h[2] & 4) { c->err = "dwgsim-hip: no fragment placement satisfied the target regions (-x) after 2^20 tries (the reference would not terminate)\n"; return DWGSIM_HIP_ERR_FAILED; }
     if (h[2] & 2) { c->err = "dwgsim-hip: a read outgrew its buffer (or degenerated) in the flow-error model\n"; return DWGSIM_HIP_ERR_FAILED; }
-    if ((h[2] & ~8ull) || h[20]) {      // one pair used up its 10 001 attempts, or the counter of failed attempts over the pairs of the contig passed the limit (dwgsim.c:635, :833-843)
+    if ((h[2] & ~(8ull | TRUTH_ERR_BIT)) || h[20]) {      // one pair used up its 10 001 attempts, or the counter of failed attempts over the pairs of the contig passed the limit (dwgsim.c:635, :833-843)
         char b[128]; snprintf(b, sizeof b, "\r[dwgsim_core] failed to generate a read after %d trials\n", MAX_ATTEMPTS + 1); c->err = b; return DWGSIM_HIP_ERR_FAILED;
     }
     if (h[2] & 8) { c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
-    for (int t = 0; t < 3; ++t) { sl.out_bytes[t] = h[4 + t]; sl.gz_bytes[t] = h[24 + t]; }
+    if (h[2] & TRUTH_ERR_BIT) { c->err = "dwgsim-hip: the truth SAM could not be made (a read's record or alignment could not be replayed)\n"; return DWGSIM_HIP_ERR_FAILED; }
+    for (int t = 0; t < N_STREAMS; ++t) { sl.out_bytes[t] = h[text_len_counter(t)]; sl.gz_bytes[t] = h[24 + t]; }
+    if (!c->truth_on) sl.out_bytes[3] = sl.gz_bytes[3] = 0;
     if (c->dbg.phases) {   // only meaningful with the -DDW_PHASE_TIMING build (tools/phase_profile.sh)
         uint64_t tot = 0; for (int k = 0; k < 8; ++k) tot += h[8 + k];
         fprintf(stderr, "[phases]");
@@ -2145,6 +2192,8 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
         out->n_pairs = sl.n_pairs; out->n_random = h[3]; out->n_retries = h[1];
         for (int t = 0; t < 3; ++t) { out->bytes[t] = sl.out_bytes[t]; out->dev_ptr[t] = c->out[slot][t].get(); }
         for (int t = 0; t < 3; ++t) out->gz_bytes[t] = sl.gz_bytes[t];
+        if (sl.out_bytes[3]) { float ms = 0; HIPC(c, hipEventElapsedTime(&ms, sl.ev_t0.get(), sl.ev_t1.get())); c->dbg.truth_us = 1e3 * ms; }
+        out->sam_bytes = sl.out_bytes[3]; out->sam_gz_bytes = sl.gz_bytes[3]; out->sam_dev_ptr = sl.out_bytes[3] ? c->out[slot][3].get() : nullptr;
         for (int t = 0; t < 4; ++t) out->fail_seg[t] = h[16 + t];
         out->fail_carry = h[21];
         HIPC(c, hipEventElapsedTime(&out->sim_kernel_ms, sl.ev_k0.get(), sl.ev_k1.get()));
@@ -2217,7 +2266,7 @@ void dwgsim_hip_host_free(void *p)
 // stream's gzip members instead of its text.
 static int fetch_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap, bool gz)
 {
-    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream > 2 || (!host_dst && cap)) { if (c) c->err = "bad fetch arguments"; return DWGSIM_HIP_ERR_ARG; }
+    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream >= N_STREAMS || (stream == DWGSIM_HIP_STREAM_SAM && !c->truth_on) || (!host_dst && cap)) { if (c) c->err = "bad fetch arguments"; return DWGSIM_HIP_ERR_ARG; }
     Slot &sl = c->slot[slot];
     if (sl.pending) { c->err = "fetch: wait for the batch first (its sizes are not known yet)"; return DWGSIM_HIP_ERR_STATE; }
     HIPC(c, hipSetDevice(c->device));
@@ -2246,6 +2295,33 @@ int dwgsim_hip_set_gzip(dwgsim_hip_ctx_t *c, int on)
 
 int dwgsim_hip_fetch_gz_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap) { return fetch_async(c, slot, stream, host_dst, cap, true); }
 
+// The truth SAM (DESIGN.md "6e").  Switched on, every simulate call also leaves stream DWGSIM_HIP_STREAM_SAM; switched off nothing of it is launched or allocated.
+int dwgsim_hip_set_truth_sam(dwgsim_hip_ctx_t *c, int on)
+{
+    if (!c) return DWGSIM_HIP_ERR_ARG;
+    for (const Slot &sl : c->slot) if (sl.pending) { c->err = "set_truth_sam: a batch is in flight (wait for every slot first)"; return DWGSIM_HIP_ERR_STATE; }
+    if (on && c->prm.data_type != 0) {
+        c->err = c->prm.data_type == 1 ? "dwgsim-hip: no truth SAM for SOLiD reads (-c 1): colour space has no base-space SEQ\n"
+                                       : "dwgsim-hip: no truth SAM for Ion Torrent reads (-c 2): the flow model adds indels of its own that a haplotype CIGAR would not show\n";
+        return DWGSIM_HIP_ERR_UNSUP;
+    }
+    if (on) { HIPC(c, hipSetDevice(c->device)); for (Slot &sl : c->slot) { HIPC(c, sl.ev_t0.create()); HIPC(c, sl.ev_t1.create()); } }
+    c->truth_on = on != 0;
+    return DWGSIM_HIP_OK;
+}
+
+// The header of a truth SAM: host text, the same bytes for every caller.  One @SQ per contig of the table, in its order.  Returns the bytes the header has
+// (whatever cap is); at most cap of them are written to buf (may be NULL with cap 0: the size alone).
+int64_t dwgsim_hip_truth_sam_header(const char *const *names, const int64_t *lens, int n, char *buf, size_t cap)
+{
+    if (n < 0 || (n > 0 && (!names || !lens)) || (!buf && cap)) return DWGSIM_HIP_ERR_ARG;
+    std::string h = "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
+    for (int k = 0; k < n; ++k) { if (!names[k]) return DWGSIM_HIP_ERR_ARG; h += "@SQ\tSN:"; h += names[k]; h += "\tLN:" + std::to_string((long long)lens[k]) + "\n"; }
+    h += "@PG\tID:dwgsim-hip\tPN:dwgsim-hip\tDS:true alignments of the simulated reads\n";
+    if (buf) memcpy(buf, h.data(), h.size() < cap ? h.size() : cap);
+    return (int64_t)h.size();
+}
+
 int dwgsim_hip_fetch_wait(dwgsim_hip_ctx_t *c, int slot)
 {
     if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS) { if (c) c->err = "bad slot"; return DWGSIM_HIP_ERR_ARG; }
@@ -2259,7 +2335,7 @@ int dwgsim_hip_fetch_wait(dwgsim_hip_ctx_t *c, int slot)
 
 int dwgsim_hip_fetch(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap)
 {
-    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream > 2 || (!host_dst && cap)) return DWGSIM_HIP_ERR_ARG;
+    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream >= N_STREAMS || (stream == DWGSIM_HIP_STREAM_SAM && !c->truth_on) || (!host_dst && cap)) return DWGSIM_HIP_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
     Slot &sl = c->slot[slot];
     if (sl.pending) { c->err = "fetch: wait for the batch first (its sizes are not known yet)"; return DWGSIM_HIP_ERR_STATE; }
@@ -2292,7 +2368,7 @@ int dwgsim_hip_fetch(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, 
 // Test / analysis hook (not part of the drop-in surface): occurrences of `byte` in one finished stream of a waited-for slot, counted on the device.
 int dwgsim_hip_debug_count_byte(dwgsim_hip_ctx_t *c, int slot, int stream, int byte, uint64_t *count)
 {
-    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream > 2 || !count) return DWGSIM_HIP_ERR_ARG;
+    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream >= N_STREAMS || (stream == DWGSIM_HIP_STREAM_SAM && !c->truth_on) || !count) return DWGSIM_HIP_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
     Slot &sl = c->slot[slot];
     if (sl.pending) { c->err = "count_byte: wait for the batch first"; return DWGSIM_HIP_ERR_STATE; }
@@ -2362,6 +2438,19 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *c, const char *key, int64_t value)
     else if (!strcmp(key, "ion_lds")) c->dbg.ion_lds = (int)value;
     else if (!strcmp(key, "flow_cap")) c->dbg.flow_cap_forced = (int)value;
     else if (!strcmp(key, "hap_yardstick")) c->dbg.hap_yardstick = value != 0;      // dwgsim_hip_haplotype_fasta also times a device-to-device copy of the text's size ("hap_copy_us")
+    else if (!strcmp(key, "truth_yardstick")) {      // a device-to-device copy of `value` bytes of slot 0's truth SAM, timed at once on the compute stream: debug_get("truth_copy_us")
+        Slot &sl = c->slot[0];
+        if (!c->truth_on || sl.pending || value <= 0 || (uint64_t)value > sl.out_bytes[3]) { c->err = "truth_yardstick: slot 0 holds no truth SAM of that size"; return DWGSIM_HIP_ERR_ARG; }
+        HIPC(c, hipSetDevice(c->device));
+        DevMem tmp;
+        HIPC(c, reserve(c, tmp, (size_t)value, (size_t)value));
+        HIPC(c, hipEventRecord(sl.ev_t0.get(), c->stream.get()));
+        HIPC(c, hipMemcpyAsync(tmp.get(), c->out[0][3].get(), (size_t)value, hipMemcpyDeviceToDevice, c->stream.get()));
+        HIPC(c, hipEventRecord(sl.ev_t1.get(), c->stream.get()));
+        HIPC(c, hipStreamSynchronize(c->stream.get()));
+        float ms = 0; HIPC(c, hipEventElapsedTime(&ms, sl.ev_t0.get(), sl.ev_t1.get()));
+        c->dbg.truth_copy_us = 1e3 * ms;
+    }
     else { c->err = "unknown debug option"; return DWGSIM_HIP_ERR_ARG; }
     return DWGSIM_HIP_OK;
 }
@@ -2385,6 +2474,8 @@ int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
     else if (!strcmp(key, "hap_len_us")) *value = (int64_t)c->dbg.hap_len_us;     // the haplotype text built last: HIP-event time of its length pass + scan,
     else if (!strcmp(key, "hap_write_us")) *value = (int64_t)c->dbg.hap_write_us; // ... of its header and write kernels,
     else if (!strcmp(key, "hap_copy_us")) *value = (int64_t)c->dbg.hap_copy_us;   // ... and ("hap_yardstick") of a device-to-device copy of its size
+    else if (!strcmp(key, "truth_us")) *value = (int64_t)c->dbg.truth_us;         // HIP-event time (microseconds) of the truth step of the batch waited for last (dwgsim_hip_set_truth_sam)
+    else if (!strcmp(key, "truth_copy_us")) *value = (int64_t)c->dbg.truth_copy_us;      // ... and of the copy the option "truth_yardstick" made
     else if (!strcmp(key, "walk_form")) *value = c->dbg.walk_form;                // attempt, file-driven / random, site-scan form, restore, views of the last walk, packed
     else { c->err = "unknown debug value"; return DWGSIM_HIP_ERR_ARG; }
     return DWGSIM_HIP_OK;

@@ -81,7 +81,8 @@ struct HostMem {
         return true;
     }
 };
-struct PinBuf { HostMem s[3]; };      // the output of one batch, a block per stream
+constexpr int JOB_STREAMS = 4;         // output streams of a batch: the three FASTQ streams and, with dwgsim_hip_job_set_truth_sam, DWGSIM_HIP_STREAM_SAM
+struct PinBuf { HostMem s[JOB_STREAMS]; };      // the output of one batch, a block per stream
 
 struct CtxDestroy { void operator()(dwgsim_hip_ctx_t *x) const { dwgsim_hip_destroy(x); } };
 struct MutlistFree { void operator()(dwgsim_hip_mutlist_t *l) const { dwgsim_hip_mutlist_free(l); } };
@@ -96,11 +97,11 @@ struct Batch {
     // the output, known when the batch's kernels are done (stage A): page-locked buffer (lent by device `lane`), bytes per stream as delivered and
     // as text, streams that still have to deliver it; ready = the copy-out has landed and the fields above are in (stage B)
     PinBuf *buf = nullptr; int lane = -1;
-    uint64_t n[3] = {0, 0, 0}, text_n[3] = {0, 0, 0};
+    uint64_t n[JOB_STREAMS] = {0, 0, 0, 0}, text_n[JOB_STREAMS] = {0, 0, 0, 0};
     int left = 0; bool ready = false;
     // reads_at (pieces with their place in the stream, delivered by several threads): sized = n[] is in; placed = so is n[] of every batch in
     // front of it, in file order across groups, and off[] is where its pieces go (assign_offsets)
-    uint64_t off[3] = {0, 0, 0}; bool sized = false, placed = false;
+    uint64_t off[JOB_STREAMS] = {0, 0, 0, 0}; bool sized = false, placed = false;
 };
 
 struct GroupJob {
@@ -169,6 +170,7 @@ struct dwgsim_hip_job {
         size_t stage_want = 0;        // room for the largest group, so that a staging buffer is page-locked once
         std::string regions_path, mutin_path; int mutin_type = -1;
         dwgsim_hip_job_haplotype_fn hap_fn = nullptr; void *hap_user = nullptr; int hap_width = 60;      // dwgsim_hip_job_set_haplotype_sink
+        bool truth_sam = false;       // dwgsim_hip_job_set_truth_sam: every batch also delivers stream DWGSIM_HIP_STREAM_SAM
     } cfg;
 
     // CALLER: touched only by the thread that calls the job_ functions (the ABI allows one at a time).  The workers see the staging through
@@ -193,7 +195,7 @@ struct dwgsim_hip_job {
         int n_dispatched = 0; bool no_more = false;
         std::vector<int> next_group;                       // per device: id of the group it takes next
         bool stage_busy[Caller::N_STAGE] = {false, false};
-        uint64_t next_off[3] = {0, 0, 0}; int off_gid = 0, off_b = 0;      // reads_at: the next piece's offsets; the batch (group id, index) they belong to
+        uint64_t next_off[JOB_STREAMS] = {0, 0, 0, 0}; int off_gid = 0, off_b = 0;      // reads_at: the next piece's offsets; the batch (group id, index) they belong to
         uint64_t delivered_pairs = 0;
         uint64_t total_rand = 0;                           // random reads up to the end of the last group that was totalled (advance_rand_base, its only writer)
         std::vector<std::vector<std::unique_ptr<PinBuf>>> bufs; std::vector<std::vector<PinBuf *>> free_bufs;      // page-locked output buffers per device: all / not lent
@@ -253,7 +255,7 @@ void assign_offsets(dwgsim_hip_job *j)
         const int nb = (int)g->batch.size();
         for (; sh.off_b < nb && g->batch[(size_t)sh.off_b].sized; ++sh.off_b) {
             Batch &B = g->batch[(size_t)sh.off_b];
-            for (int s = 0; s < 3; ++s) { B.off[s] = sh.next_off[s]; sh.next_off[s] += B.n[s]; }
+            for (int s = 0; s < JOB_STREAMS; ++s) { B.off[s] = sh.next_off[s]; sh.next_off[s] += B.n[s]; }
             B.placed = true;
         }
         if (sh.off_b < nb) break;
@@ -467,7 +469,7 @@ struct Worker {
         return true;
     }
 
-    PinBuf *acquire(const uint64_t need[3])
+    PinBuf *acquire(const uint64_t need[JOB_STREAMS])
     {
         PinBuf *b = nullptr;
         {
@@ -478,7 +480,7 @@ struct Worker {
             if (!fr.empty()) { b = fr.back(); fr.pop_back(); }
             else { all.push_back(std::make_unique<PinBuf>()); b = all.back().get(); }
         }
-        for (int s = 0; s < 3; ++s)
+        for (int s = 0; s < JOB_STREAMS; ++s)
             if (need[s] > b->s[s].cap && !b->s[s].grow((size_t)need[s] + (size_t)need[s] / 8 + 4096, 0)) { job_fail(j, "dwgsim-hip: cannot allocate page-locked host memory for the output"); return nullptr; }
         return b;
     }
@@ -489,12 +491,14 @@ struct Worker {
         if (pb.a_done) return true;
         if (dwgsim_hip_wait(x, pb.slot, &pb.bt) < 0) { fail_ctx(); return false; }
         pb.a_done = true;
-        const uint64_t *n = j->cfg.gzip ? pb.bt.gz_bytes : pb.bt.bytes;
+        uint64_t n[JOB_STREAMS], text_n[JOB_STREAMS];      // bytes per stream as delivered / as text (the truth SAM: 0 unless switched on)
+        for (int s = 0; s < 3; ++s) { n[s] = j->cfg.gzip ? pb.bt.gz_bytes[s] : pb.bt.bytes[s]; text_n[s] = pb.bt.bytes[s]; }
+        n[DWGSIM_HIP_STREAM_SAM] = j->cfg.gzip ? pb.bt.sam_gz_bytes : pb.bt.sam_bytes; text_n[DWGSIM_HIP_STREAM_SAM] = pb.bt.sam_bytes;
         if (j->cfg.has_sink()) {
             PinBuf *tb = acquire(n);
             if (!tb) return false;
             int left = 0;
-            for (int s = 0; s < 3; ++s) if (n[s]) {
+            for (int s = 0; s < JOB_STREAMS; ++s) if (n[s]) {
                 char *to = (char *)tb->s[s].p; const size_t cap = tb->s[s].cap;
                 if ((j->cfg.gzip ? dwgsim_hip_fetch_gz_async(x, pb.slot, s, to, cap) : dwgsim_hip_fetch_async(x, pb.slot, s, to, cap)) < 0) { fail_ctx(); return false; }
                 ++left;
@@ -502,10 +506,10 @@ struct Worker {
             std::lock_guard<std::mutex> lk(j->m);
             Batch &B = pb.g->batch[(size_t)pb.b];
             B.buf = tb; B.lane = d; B.left = left;
-            for (int s = 0; s < 3; ++s) { B.n[s] = n[s]; B.text_n[s] = pb.bt.bytes[s]; }
+            for (int s = 0; s < JOB_STREAMS; ++s) { B.n[s] = n[s]; B.text_n[s] = text_n[s]; }
             if (j->cfg.sink.reads_at) { B.sized = true; assign_offsets(j); j->cv.notify_all(); }      // this batch's offsets, and those of any batch behind it that was only waiting for its sizes
         }
-        if (pb.b < 2 * j->cfg.VD) trace(j, "dev %d group %d: batch %d kernels done, copy issued (%.1f MB)", d, pb.g->id, pb.b, j->cfg.has_sink() ? (n[0] + n[1] + n[2]) / 1e6 : 0.0);
+        if (pb.b < 2 * j->cfg.VD) trace(j, "dev %d group %d: batch %d kernels done, copy issued (%.1f MB)", d, pb.g->id, pb.b, j->cfg.has_sink() ? (n[0] + n[1] + n[2] + n[3]) / 1e6 : 0.0);
         if (pb.last_of_group && !flush_haplotypes(pb.h)) return false;
         if (pb.last_of_group && dwgsim_hip_drop_contig(x, pb.h) < 0) { fail_ctx(); return false; }      // (the kernels of the group's last batch are done: nothing reads it any more)
         return true;
@@ -823,11 +827,12 @@ int start_threads(dwgsim_hip_job *j)
         if (c.mutin_type >= 0 &&            // dwgsim.c:494-497
             dwgsim_hip_set_mutation_input(x, c.mutin_type, c.mutin_path.c_str(), nm.data(), c.tab_lens.data(), (int)nm.size()) < 0) { job_fail(j, dwgsim_hip_last_error(x)); return DWGSIM_HIP_ERR_ARG; }
         if (c.gzip && c.want_reads && c.has_sink() && dwgsim_hip_set_gzip(x, 1) < 0) { job_fail(j, dwgsim_hip_last_error(x)); return DWGSIM_HIP_ERR_DEVICE; }
+        if (c.truth_sam && c.want_reads) { const int rc = dwgsim_hip_set_truth_sam(x, 1); if (rc < 0) { job_fail(j, dwgsim_hip_last_error(x)); return rc; } }      // (-M 2: no reads, no SAM)
     }
     for (int d = 0; d < c.ND; ++d) j->me.workers.emplace_back([j, d]() { Worker w{j, d, j->cfg.ctx[(size_t)d].get()}; w.run(); });
     if (c.want_reads && c.has_sink())      // reads_at: a thread per device and stream; reads: one per stream
         for (int dev = c.sink.reads_at ? 0 : -1; dev < (c.sink.reads_at ? c.ND : 0); ++dev)
-            for (int s = 0; s < 3; ++s) j->me.deliverers.emplace_back([j, dev, s]() { deliver_loop(j, dev, s); });
+            for (int s = 0; s < (c.truth_sam ? JOB_STREAMS : 3); ++s) j->me.deliverers.emplace_back([j, dev, s]() { deliver_loop(j, dev, s); });      // (the truth SAM: a thread of its own, like a FASTQ stream)
     return DWGSIM_HIP_OK;
 }
 
@@ -968,6 +973,15 @@ int dwgsim_hip_job_set_haplotype_sink(dwgsim_hip_job_t *j, dwgsim_hip_job_haplot
     if (!j || width < 0) return arg_error(j, DWGSIM_HIP_ERR_ARG, "job: the haplotype line width must not be negative");
     if (j->me.started) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: the haplotype sink must be set before the first contig");
     j->cfg.hap_fn = fn; j->cfg.hap_user = user; j->cfg.hap_width = width;
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_job_set_truth_sam(dwgsim_hip_job_t *j, int on)
+{
+    if (!j) return DWGSIM_HIP_ERR_ARG;
+    if (j->me.started) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: the truth SAM must be switched on before prepare / the first contig");
+    if (on && j->cfg.prm.data_type != 0) return arg_error(j, DWGSIM_HIP_ERR_UNSUP, "dwgsim-hip: the truth SAM is made for Illumina reads only (-c 0)\n");
+    j->cfg.truth_sam = on != 0;
     return DWGSIM_HIP_OK;
 }
 

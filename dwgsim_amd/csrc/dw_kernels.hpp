@@ -226,4 +226,19 @@ struct SimArgs {
     int32_t qrows;                 // 1: the quality line of the lockstep instances runs in the wave's staging rows (dw_simulate.hip QROWS: lds_words >= 18; "qrows" = 0 switches it off)
 };
 
+// ---- the truth step (dw_truth.hpp): the true alignment of every read end of a launch as SAM text ----
+// One read end between the length pass and the write pass: the cells lo .. hi of its contig that it is aligned to (both give a base of their own), the
+// inserted bases in front of lo's / behind hi's base where the read stopped inside an insertion, the characters of its CIGAR
+constexpr uint32_t TRUTH_F_RAND = 1, TRUTH_F_REV = 2, TRUTH_F_HAP2 = 4, TRUTH_F_BAD = 8;      // a random read; the reverse strand; haplotype 2; no line (the replay or the record index failed)
+constexpr uint64_t TRUTH_ERR_BIT = 32;                // SimArgs::counters[2]: a line could not be made
+struct TruthEnd { int32_t lo, hi; uint32_t lead, tail, flags, cigar, pad_[2]; };
+struct TruthArgs {
+    int32_t lpp, bfast;             // read ends per pair; 1: the names and reads come from the one interleaved BFAST stream (-o 2), 0: from the BWA stream of each end
+    int32_t prefix_len, qname_max;  // bytes of "prefix_" in front of a contig's name in the name pool; the longest QNAME the FASTQ buffers were sized for
+    const uint8_t *src[2]; const uint64_t *src_bytes[2]; uint64_t src_cap[2];      // the source streams: text, its length (a device counter), the capacity the grid covers
+    uint32_t *nl_count[2], *rec[2]; uint64_t n_rec[2];      // newlines per block of 4096 bytes (then their scan); rec[r] = start of record r, n_rec + 1 entries
+    TruthEnd *ends; uint32_t *line_len, *blk;      // per read end (pair * lpp + end): the alignment; the bytes of its block's lines in front of its own.  Per block: the bytes of its lines, then their scan
+    uint8_t *out; uint64_t cap; uint64_t *total;      // the SAM text, its capacity, its length (a device counter)
+};
+
 } // namespace dw

@@ -8,6 +8,7 @@
 //     k_calibrate     -B: per-base calibration of the Ion Torrent flow error (dwgsim_opt.c:415-457)
 //     k_selftest_fp64 device self-test of the range-restricted fp64 forms (dw_common.hpp)
 //     k_selftest_gap  device self-test of the gap draw geom_gap (dw_common.hpp) on every word of a range
+//     k_truth_*       (dw_truth.hpp, on request only) the true alignment of every read end of a launch as SAM text, replayed behind it
 //
 // Byte/integer work plus fp64 for the normals: no MFMA.  fp64 expressions mirror the reference's evaluation order; compile
 // with -ffp-contract=off.
@@ -24,6 +25,9 @@
 #define DW_PART -1
 #endif
 #define DW_HAS(part) (DW_PART == -1 || DW_PART == (part))
+#if DW_HAS(0)
+#include "dw_truth.hpp"      // the truth step (dwgsim_hip_set_truth_sam): kernels of its own behind a launch, built on dw_read.hpp; nothing of k_simulate
+#endif
 #ifndef DW_SIM_WAVES
 #define DW_SIM_WAVES 5       // minimum waves per SIMD requested for the Illumina variants (one less when both output families are written):
                              // the kernel sits 1-2 VGPRs above these occupancy steps without the hint; measured +4 % at 5 vs 4 waves, 6 spills (so do the SOLiD variants with any hint)

@@ -25,6 +25,8 @@
 //     DWGSIM_HIP_HAPLOTYPES  anything but empty or "0": also write the two mutated haplotypes the reads are drawn from, <prefix>.hap1.fa and <prefix>.hap2.fa
 //                          (plain text, assembled on the GPU; a record per simulated contig, the contig's plain name; removed again if the job fails)
 //     DWGSIM_HIP_HAPLOTYPES_WIDTH  bases per line of those files (default 60; 0: the whole sequence on one line)
+//     DWGSIM_HIP_TRUTH_SAM   anything but empty or "0": also write <prefix>.truth.sam.gz, the true alignment of every read end (Illumina reads):
+//                          the header, then the job's stream 3, in the gzip mode of the FASTQ files.  -M 2 writes none
 //     DWGSIM_HIP_SOLO      "r/W": measurement aid (dw_job.cpp) -- this process's one device does what device r of a W-device job does, nothing else
 #include <stdio.h>
 #include <stdlib.h>
@@ -437,10 +439,10 @@ static double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return
 
 // what the job delivers, written as the reference writes it (dwgsim.c:919-981 -> the three .gz files, mut.c:781-893 -> the two mutation files)
 struct FileSink {
-    FILE *fp_txt = nullptr, *fp_vcf = nullptr, *fgz[3] = {nullptr, nullptr, nullptr};
+    FILE *fp_txt = nullptr, *fp_vcf = nullptr, *fgz[4] = {nullptr, nullptr, nullptr, nullptr};      // fgz[3]: DWGSIM_HIP_TRUTH_SAM, <prefix>.truth.sam.gz (stream DWGSIM_HIP_STREAM_SAM)
     DeflatePool *pool = nullptr; bool null_sink = false, memcpy_sink = false;
-    std::atomic<uint64_t> bytes_in{0}, bytes_out{0}, sink_ns[3] = {{0}, {0}, {0}}, sink_bytes[3] = {{0}, {0}, {0}};
-    std::vector<char> scratch[3];
+    std::atomic<uint64_t> bytes_in{0}, bytes_out{0}, sink_ns[4] = {{0}, {0}, {0}, {0}}, sink_bytes[4] = {{0}, {0}, {0}, {0}};
+    std::vector<char> scratch[4];
     static int mutations(void *u, const char *, const char *txt, size_t tl, const char *vcf, size_t vl)
     {
         FileSink *s = (FileSink *)u;
@@ -454,7 +456,8 @@ struct FileSink {
         FileSink *s = (FileSink *)u;
         return s->fp_hap[hap] && fwrite(data, 1, len, s->fp_hap[hap]) == len ? 0 : 1;
     }
-    std::atomic<uint64_t> written[3] = {{0}, {0}, {0}};      // bytes that went to file `stream` through reads_at
+    std::atomic<uint64_t> written[4] = {{0}, {0}, {0}, {0}};      // bytes that went to file `stream` through reads_at
+    uint64_t base_off[4] = {0, 0, 0, 0};      // ... behind what main wrote into the file first (the truth SAM's header)
     // pieces with their place (dwgsim_hip_job_sink_t::reads_at): several threads per file, pwrite
     static int reads_at(void *u, int stream, uint64_t offset, const void *data, size_t len, size_t text_len, int)
     {
@@ -472,7 +475,7 @@ struct FileSink {
             s->sink_ns[stream] += (uint64_t)((b.tv_sec - a.tv_sec) * 1000000000ll + (b.tv_nsec - a.tv_nsec)); s->sink_bytes[stream] += len;
             return 0;
         }
-        const char *p = (const char *)data; size_t left = len; off_t at = (off_t)offset;
+        const char *p = (const char *)data; size_t left = len; off_t at = (off_t)(offset + s->base_off[stream]);
         while (left) { const ssize_t w = pwrite(fileno(f), p, left, at); if (w <= 0) return 1; p += w; left -= (size_t)w; at += w; }
         s->written[stream] += len;
         return 0;
@@ -670,6 +673,23 @@ int main(int argc, char **argv)
     }
     std::unique_ptr<DeflatePool> pool;
     if (!gpu_gzip && want_reads) { pool = std::make_unique<DeflatePool>(nthreads, gz_level); fs.pool = pool.get(); }
+    // the truth SAM: the header (one exported function: the same bytes as every other caller's) as the first piece, then the job's stream 3, in the job's gzip mode
+    const char *sam_env = getenv("DWGSIM_HIP_TRUTH_SAM");
+    const bool want_sam = want_reads && sam_env && sam_env[0] && strcmp(sam_env, "0");
+    if (want_sam) {
+        std::vector<const char *> nm; for (auto &s : tab_names) nm.push_back(s.c_str());
+        const int64_t hn = dwgsim_hip_truth_sam_header(nm.data(), tab_lens.data(), (int)nm.size(), nullptr, 0);
+        std::vector<char> hdr((size_t)(hn > 0 ? hn : 0));
+        if (hn > 0) (void)dwgsim_hip_truth_sam_header(nm.data(), tab_lens.data(), (int)nm.size(), hdr.data(), hdr.size());
+        fs.fgz[3] = fopen((p + ".truth.sam.gz").c_str(), "wb");
+        bool ok = fs.fgz[3] != nullptr && hn > 0;
+        if (ok) {
+            setvbuf(fs.fgz[3], nullptr, _IONBF, 0);
+            if (gpu_gzip) { std::vector<unsigned char> m; ok = deflate_member(hdr.data(), hdr.size(), gz_level, m) && fwrite(m.data(), 1, m.size(), fs.fgz[3]) == m.size(); fs.base_off[3] = m.size(); }
+            else ok = pool->write(fs.fgz[3], hdr.data(), hdr.size());
+        }
+        if (!ok) { fprintf(stderr, "dwgsim-hip: fail to write the truth SAM for '%s'\n", out_prefix); return give_up(1); }
+    }
 
     dwgsim_hip_job_t *job = job_made.get();
     if (!job) { fprintf(stderr, "dwgsim-hip: cannot set the job up (error %d)\n", job_err); if (want_hap) { (void)unlink((p + ".hap1.fa").c_str()); (void)unlink((p + ".hap2.fa").c_str()); } return 1; }
@@ -681,6 +701,7 @@ int main(int argc, char **argv)
         if (rc == 0 && !regions_fn.empty() && dwgsim_hip_job_set_regions(job, regions_fn.c_str()) < 0) job_error();             // dwgsim.c:499-506
         if (rc == 0 && muts_type >= 0 && dwgsim_hip_job_set_mutation_input(job, muts_type, muts_fn.c_str()) < 0) job_error();   // dwgsim.c:494-497
         if (rc == 0 && want_hap && dwgsim_hip_job_set_haplotype_sink(job, FileSink::haplotype, &fs, hap_width) < 0) job_error();
+        if (rc == 0 && want_sam && dwgsim_hip_job_set_truth_sam(job, 1) < 0) job_error();
         if (rc == 0 && dwgsim_hip_job_prepare(job, nullptr) < 0) job_error();
     }
     const double t_ctx = now_s();
@@ -729,7 +750,8 @@ int main(int argc, char **argv)
         if (fclose(fs.fp_hap[h]) != 0 && rc == 0) { fprintf(stderr, "dwgsim-hip: writing the haplotype files failed\n"); rc = 1; }
         if (rc != 0) (void)unlink((p + (h ? ".hap2.fa" : ".hap1.fa")).c_str());
     }
-    for (int s = 0; s < 3; ++s) close_gz(fs.fgz[s], gz_level, fs.written[s].load());
+    for (int s = 0; s < 4; ++s) close_gz(fs.fgz[s], gz_level, fs.written[s].load());
+    if (want_sam && rc != 0) (void)unlink((p + ".truth.sam.gz").c_str());      // (a failed job leaves no partial truth SAM)
     if (getenv("DWGSIM_HIP_TEARDOWN")) { dwgsim_hip_job_destroy(job); return rc; }
     // everything has been delivered and the files are closed: the process ends here.  Handing back device memory, page-locked buffers and the
     // runtime piece by piece costs 0.2 s after a chromosome-sized job; the driver reclaims them with the process.

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define DWGSIM_HIP_ABI_VERSION 7
+#define DWGSIM_HIP_ABI_VERSION 8
 
 /* error codes (negative) */
 #define DWGSIM_HIP_OK            0
@@ -82,7 +82,8 @@ typedef struct dwgsim_hip_params {
 typedef struct dwgsim_hip_ctx dwgsim_hip_ctx_t;
 
 /* output streams of one simulate() batch */
-enum { DWGSIM_HIP_STREAM_BWA1 = 0, DWGSIM_HIP_STREAM_BWA2 = 1, DWGSIM_HIP_STREAM_BFAST = 2 };
+enum { DWGSIM_HIP_STREAM_BWA1 = 0, DWGSIM_HIP_STREAM_BWA2 = 1, DWGSIM_HIP_STREAM_BFAST = 2,
+       DWGSIM_HIP_STREAM_SAM = 3 /* (ABI 8) the truth SAM: only with dwgsim_hip_set_truth_sam(ctx, 1) */ };
 
 typedef struct dwgsim_hip_batch {
     uint64_t n_pairs;          /* pairs generated (== requested) */
@@ -99,6 +100,9 @@ typedef struct dwgsim_hip_batch {
     uint64_t fail_seg[4];
     uint64_t fail_carry;       /* the counter after this batch, given the carry it started from */
     uint64_t gz_bytes[3];      /* with dwgsim_hip_set_gzip(ctx, 1): bytes of the .gz form of each stream (a sequence of complete gzip members) */
+    /* (ABI 8) with dwgsim_hip_set_truth_sam(ctx, 1): stream DWGSIM_HIP_STREAM_SAM -- its text bytes, the bytes of its .gz form, its device address (else 0, 0, NULL) */
+    uint64_t sam_bytes, sam_gz_bytes;
+    const void *sam_dev_ptr;
 } dwgsim_hip_batch_t;
 
 /* rand_base value meaning "continue the running count after the previous batch of this context" (kept on the device, so successive
@@ -275,6 +279,23 @@ int dwgsim_hip_fetch_wait(dwgsim_hip_ctx_t *ctx, int slot);
 int dwgsim_hip_set_gzip(dwgsim_hip_ctx_t *ctx, int on);
 int dwgsim_hip_fetch_gz_async(dwgsim_hip_ctx_t *ctx, int slot, int stream, void *host_dst, size_t cap);
 
+/* (ABI 8) The truth SAM: the true alignment of every simulated read end, made on the device behind the batch's kernels (no counterpart in the reference;
+ * DESIGN.md "6e").  Once switched on, every simulate call also leaves stream DWGSIM_HIP_STREAM_SAM in HBM: one SAM record per read end, in pair order (end 1,
+ * then end 2), without a header.  fetch, fetch_async, fetch_gz_async (with dwgsim_hip_set_gzip: members like the other streams') and debug_count_byte take
+ * the stream; while the feature is off they answer DWGSIM_HIP_ERR_ARG for it.  Illumina reads only: DWGSIM_HIP_ERR_UNSUP for -c 1 / -c 2.
+ * DWGSIM_HIP_ERR_STATE while a batch is in flight.  Off (the default): nothing is launched or allocated, every byte is as before.
+ * A record: QNAME = the FASTQ name without '@' and "/1" / "/2"; FLAG = 0x1 | 0x2 | 0x40 / 0x80 | 0x10 (the end's strand) | 0x20 (the mate's), single-end
+ * 0 / 0x10; RNAME = the contig's plain name; POS = the leftmost reference cell that gives an M, 1-based; MAPQ 60; CIGAR: M an unmutated or substituted cell,
+ * D a deleted cell, I inserted bases, equal neighbours merged -- it never starts or ends with D and always holds an M, and it starts or ends with I where
+ * the read stops inside an insertion; RNEXT "=", PNEXT the mate's POS, TLEN rightmost end - leftmost start + 1, positive for the leftmost end (end 1 on
+ * a tie); SEQ / QUAL the FASTQ's, reverse-complemented / reversed under 0x10; HP:i:1 or HP:i:2, the haplotype the read was drawn from.  A random read:
+ * FLAG 0x4 (pairs: 0x1 | 0x4 | 0x8 | 0x40 / 0x80), RNAME *, POS 0, MAPQ 0, CIGAR *, RNEXT *, PNEXT 0, TLEN 0, no HP. */
+int dwgsim_hip_set_truth_sam(dwgsim_hip_ctx_t *ctx, int on);
+/* The header that goes in front of the records: @HD VN:1.6 SO:unsorted GO:query, one @SQ per contig of the table (every contig of the FASTA, in its
+ * order, skipped ones included), one @PG.  Needs no context.  Returns the header's size; at most cap bytes of it are written to buf (NULL with cap 0: the
+ * size alone). */
+int64_t dwgsim_hip_truth_sam_header(const char *const *names, const int64_t *lens, int n, char *buf, size_t cap);
+
 /* Copy one finished stream of a slot to host memory.  A page-locked destination (hipHostMalloc / hipHostRegister) takes one direct
  * hipMemcpyAsync at link speed; pageable memory goes through double-buffered pinned staging inside. */
 int dwgsim_hip_fetch(dwgsim_hip_ctx_t *ctx, int slot, int stream, void *host_dst, size_t cap);
@@ -341,6 +362,11 @@ int dwgsim_hip_job_set_contig_table(dwgsim_hip_job_t *job, const char *const *na
 int dwgsim_hip_job_set_regions(dwgsim_hip_job_t *job, const char *path);
 int dwgsim_hip_job_set_mutation_input(dwgsim_hip_job_t *job, int type, const char *path);
 int dwgsim_hip_job_set_haplotype_sink(dwgsim_hip_job_t *job, dwgsim_hip_job_haplotype_fn fn, void *user, int width);
+/* (ABI 8) The truth SAM (dwgsim_hip_set_truth_sam) through the job: once switched on, the records arrive through the sink's reads / reads_at callbacks as
+ * stream DWGSIM_HIP_STREAM_SAM, exactly like a FASTQ stream -- a delivery thread of its own, pieces in file order (or with their offsets), gzip members or text as the
+ * job's gzip option says.  The header is not part of the stream (dwgsim_hip_truth_sam_header).  -M 2 makes no reads and no SAM.  To be called before
+ * dwgsim_hip_job_prepare / the first contig: DWGSIM_HIP_ERR_STATE later; DWGSIM_HIP_ERR_UNSUP for -c 1 / -c 2. */
+int dwgsim_hip_job_set_truth_sam(dwgsim_hip_job_t *job, int on);
 /* optional: parse the files above and start the device threads now (errors of -x / -m / -b / -v surface here instead of at the first contig) */
 int dwgsim_hip_job_prepare(dwgsim_hip_job_t *job, uint64_t *total_len);
 /* The body of the contig loop (dwgsim.c:519-625 and everything below it) for the next contig of the FASTA.  Returns the pairs scheduled for
@@ -466,7 +492,9 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *ctx, const char *key, int64_t valu
  * (ATTEMPT 1, 2: the exact re-runs; FILE 1: the file-driven walk of -m / -b / -v; SLOTS 1 / 0: the slot / look-back form of the site scan; RESTORE: what
  * went back to the pristine copies first -- 0 nothing, 1 the dirty chunks, 2 whole buffers; DENSE 1 / 0: views made from every cell / from the dirty bitmap);
  * "hap_len_us" / "hap_write_us": HIP-event time (microseconds) of the length pass + scan / of the header and write kernels of the haplotype text built
- * last (dwgsim_hip_haplotype_fasta); "hap_copy_us": with the option "hap_yardstick" = 1, of a device-to-device copy of that text's size behind it */
+ * last (dwgsim_hip_haplotype_fasta); "hap_copy_us": with the option "hap_yardstick" = 1, of a device-to-device copy of that text's size behind it;
+ * "truth_us": HIP-event time (microseconds) of the truth step of the batch waited for last (dwgsim_hip_set_truth_sam); "truth_copy_us": of the device-to-device copy
+ * of n bytes of slot 0's truth SAM that the option "truth_yardstick" = n makes at once */
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *ctx, const char *key, int64_t *value);
 /* (ABI 7) the k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> instances the library was built with, from the list that instantiates them and in which a
  * launch looks its form up: returns their number and writes at most `cap` of them to `out` (may be NULL), each packed as "sim_form" above with SPLIT

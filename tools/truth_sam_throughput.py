@@ -1,0 +1,64 @@
+"""Cost of the truth step (dwgsim_hip_set_truth_sam; DESIGN.md "6e"; not part of bench.py), on one device.
+One batch of --pairs pairs (default 2^18) of the chr20-sized contig of bench.py's workload at 2 x 150, bench.py's flags:
+  truth_us      the truth step's kernels -- record index, length passes, scan, write pass -- between two HIP events (dwgsim_hip_debug_get "truth_us")
+  simulate_us   the same batch's k_simulate (dwgsim_hip_batch_t.sim_kernel_ms)
+  copy_us       a device-to-device copy of the SAM's bytes on the same stream (dwgsim_hip_debug_option "truth_yardstick" / "truth_copy_us"): the yardstick;
+                truth_GBps / copy_GBps = bytes over the two times
+  plain_*       the same batch with the feature off: its k_simulate and kernel times (nothing of the step runs)
+Each is the best of --reps batches (the first one allocates: not counted).  Prints one JSON line.
+Usage: python tools/truth_sam_throughput.py [--reps 5] [--pairs 262144]"""
+import argparse, json, os, sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from dwgsim_amd import api, synth  # noqa: E402
+
+FLAGS = "-z 13 -1 150 -2 150 -C 30 -o 1"      # bench.py's
+
+
+def batches(ctx, h, pairs, reps):
+    best = {}
+    last = None
+    for r in range(reps + 1):
+        b = ctx.simulate(h, r * pairs, pairs, 0, 0)
+        if r:
+            for k, v in (("simulate_us", 1e3 * b.sim_kernel_ms), ("kernels_us", 1e3 * b.kernel_ms), ("truth_us", ctx.debug_get("truth_us") if b.sam_bytes else 0)):
+                best[k] = v if k not in best else min(best[k], v)
+        last = b
+    return best, last
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--pairs", type=int, default=1 << 18)
+    args = ap.parse_args()
+    lib = api.load()
+    if lib.dwgsim_hip_device_count() < 1:
+        raise SystemExit("no HIP device: nothing is measured without one")
+    out = {"flags": FLAGS, "pairs": args.pairs, "reps": args.reps}
+    contigs = synth.workload_contigs("chr20")
+    with api.Context(api.parse_flags(FLAGS, lib), 0, lib) as ctx:
+        h = ctx.add_contigs(contigs)
+        ctx.mutate(h)
+        plain, _ = batches(ctx, h, args.pairs, args.reps)
+        out.update({"plain_simulate_us": plain["simulate_us"], "plain_kernels_us": plain["kernels_us"]})
+        ctx.set_truth_sam(True)
+        on, b = batches(ctx, h, args.pairs, args.reps)
+        out.update(on)
+        out["sam_bytes"] = int(b.sam_bytes); out["fastq_bytes"] = int(b.bytes[0] + b.bytes[1])
+        best = None
+        for _ in range(args.reps + 1):
+            ctx.debug_option("truth_yardstick", int(b.sam_bytes))
+            us = ctx.debug_get("truth_copy_us")
+            best = us if best is None else min(best, us)
+        out["copy_us"] = best
+        out["truth_GBps"] = b.sam_bytes / max(on["truth_us"], 1) / 1e3
+        out["copy_GBps"] = b.sam_bytes / max(best, 1) / 1e3
+        out["truth_over_simulate"] = on["truth_us"] / max(on["simulate_us"], 1)
+        ctx.drop_contig(h)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
