@@ -90,6 +90,7 @@ EXPORTS = [
     "dwgsim_hip_haplotype_fasta", "dwgsim_hip_haplotype_layout", "dwgsim_hip_haplotype_fetch", "dwgsim_hip_job_set_haplotype_sink",
     "dwgsim_hip_debug_sim_instances",
     "dwgsim_hip_set_truth_sam", "dwgsim_hip_truth_sam_header", "dwgsim_hip_job_set_truth_sam",
+    "dwgsim_hip_set_truth_md", "dwgsim_hip_job_set_truth_md", "dwgsim_hip_job_debug_option", "dwgsim_hip_job_debug_get",
 ]
 
 _lib = None
@@ -185,6 +186,10 @@ def load(path: str | None = None):
     lib.dwgsim_hip_truth_sam_header.restype = C.c_int64
     lib.dwgsim_hip_truth_sam_header.argtypes = [P(C.c_char_p), P(C.c_int64), C.c_int, C.c_char_p, C.c_size_t]
     lib.dwgsim_hip_job_set_truth_sam.argtypes = [C.c_void_p, C.c_int]
+    lib.dwgsim_hip_set_truth_md.argtypes = [C.c_void_p, C.c_int]
+    lib.dwgsim_hip_job_set_truth_md.argtypes = [C.c_void_p, C.c_int]
+    lib.dwgsim_hip_job_debug_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+    lib.dwgsim_hip_job_debug_get.argtypes = [C.c_void_p, C.c_char_p, P(C.c_int64)]
     if hasattr(lib, "dwgsim_hip_eval_create"):
         _bind_eval(lib)
     if path is None:
@@ -325,6 +330,7 @@ class JobResult:
     haplotypes: dict = field(default_factory=dict)   # haplotypes=True: {0: bytes, 1: bytes}, the two mutated haplotypes as FASTA
     sim_forms: set = field(default_factory=set)      # debug_get("sim_form") after every simulate call of the job (run_job): the k_simulate forms it ran
     truth_sam: bytes = b""                           # truth_sam=True: the records of the truth SAM (no header: truth_sam_header)
+    truth_reruns: int = 0                            # batches that ran a second time because their tagged truth SAM (truth_md=True) needed more room than planned (run_job)
 
 
 VCF_HEADER_POST = (
@@ -515,6 +521,10 @@ class Context:
         """Every simulate call also leaves stream STREAM_SAM: the true alignment of every read end as SAM records (Illumina reads only)."""
         self._chk(self.lib.dwgsim_hip_set_truth_sam(self.h, 1 if on else 0))
 
+    def set_truth_md(self, on: bool = True):
+        """(ABI 9) On top of set_truth_sam: every mapped record of the truth SAM also carries NM:i: and MD:Z:.  While the truth SAM is off it does nothing."""
+        self._chk(self.lib.dwgsim_hip_set_truth_md(self.h, 1 if on else 0))
+
     def fetch_gz(self, slot: int, stream: int, nbytes: int) -> bytes:
         """The .gz form of a finished stream (GPU gzip), through a page-locked bounce buffer."""
         if not nbytes:
@@ -623,7 +633,7 @@ def split_ranges(ranges, batch_pairs):
 
 
 def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22, fetch: bool = True, lib=None, debug_options=None, group_bp: int = 0, check_list_form: bool = False,
-            haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False) -> JobResult:
+            haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False, truth_md: bool = False) -> JobResult:
     """dwgsim_core (dwgsim.c:419-1121) over the C-ABI: header pass, then schedule -> mutate -> mutations text -> simulate in
     read-index batches.  group_bp = 0: contig after contig, as the reference walks them.  group_bp > 0: consecutive contigs are resident
     together in groups of up to group_bp bases (dwgsim_hip_add_contigs): one walk per group, batches that run across contig boundaries."""
@@ -647,6 +657,8 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
             ctx.debug_option(k, v)
         if truth_sam:
             ctx.set_truth_sam(True)
+        if truth_md:
+            ctx.set_truth_md(True)
         if getattr(params, "_mut_input", None):
             ctx.set_mutation_input(params._mut_input[0], params._mut_input[1], contigs)
         have_regions = bool(getattr(params, "_regions", None))
@@ -694,6 +706,7 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
                 n_sim += b.n_pairs
             ctx.drop_contig(h0)
         res.flow_cap_mult = ctx.debug_get("flow_cap_mult")
+        res.truth_reruns = ctx.debug_get("truth_reruns")
     res.n_pairs = n_sim
     res.n_random = rand_ii
     res.mutations_txt = bytes(txt)
@@ -706,7 +719,8 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
 
 
 def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True, batch_pairs: int = 0, group_bp: int = 0, min_share: int = 0,
-                lib=None, keep_output: bool = True, offset_sink: bool = False, haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False) -> JobResult:
+                lib=None, keep_output: bool = True, offset_sink: bool = False, haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False,
+                truth_md: bool = False, debug_options=None) -> JobResult:
     """The same job through the JOB level of the C-ABI (dwgsim_hip_job_*): the library schedules, groups, shards over `devices`
     (default: all) and delivers in file order; the sink below only collects.  Streams are returned as text (gzip members are
     decompressed here)."""
@@ -772,6 +786,10 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
             chk(lib.dwgsim_hip_job_set_haplotype_sink(job, hap_cb, None, hap_width))
         if truth_sam:
             chk(lib.dwgsim_hip_job_set_truth_sam(job, 1))
+        if truth_md:
+            chk(lib.dwgsim_hip_job_set_truth_md(job, 1))
+        for k, v in (debug_options or {}).items():
+            chk(lib.dwgsim_hip_job_debug_option(job, k.encode(), v))
         if getattr(params, "_regions", None):
             chk(lib.dwgsim_hip_job_set_regions(job, params._regions.encode()))
         if getattr(params, "_mut_input", None):
@@ -785,6 +803,9 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
             if r > 0:
                 res.n_pairs += r
         chk(lib.dwgsim_hip_job_finish(job))
+        reruns = C.c_int64(0)
+        chk(lib.dwgsim_hip_job_debug_get(job, b"truth_reruns", C.byref(reruns)))
+        res.truth_reruns = reruns.value
     finally:
         lib.dwgsim_hip_job_destroy(job)
     if offset_sink:      # the pieces must tile [0, total) of every stream, each exactly once; put in order they are the stream

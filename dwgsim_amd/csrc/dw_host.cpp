@@ -116,6 +116,7 @@ constexpr int N_COUNTERS = 32;      // u64 words of a counter block (SimArgs::co
 constexpr int N_STREAMS = 4;        // output streams of a batch: the three FASTQ streams and the truth SAM (DWGSIM_HIP_STREAM_SAM)
 // where a stream's text length stands in a slot's counters (its gzip total is [24 + t], its gzip ticket [28 + t])
 constexpr int text_len_counter(int t) { return t < 3 ? 4 + t : 7; }
+constexpr int TRUTH_FIT_COUNTER = 23;      // the bytes of a tagged truth SAM that its gzip may read (TruthArgs::fit)
 
 struct Counters {                   // a device counter block and its page-locked mirror
     DevMem d; HostMem h;
@@ -162,6 +163,7 @@ struct dwgsim_hip_ctx {
         int flow_cap_forced = 0;               // "flow_cap" (tests): the capacity a job starts from, instead of flow_read_capacity()
         int ion_lds = -1;                      // "ion_lds" (tests): where the Ion Torrent read buffers live (fill_sim_args)
         int flow_slots = 0;                    // "flow_slots": scratch slots per XCD forced by the tests (0: as many as an XCD can hold blocks)
+        int64_t truth_cap = -1, truth_reruns = 0;      // "truth_cap": the capacity (bytes) a batch's truth SAM is planned with at first (-1: the product's own); "truth_reruns": second runs that found the room (dwgsim_hip_set_truth_md)
         int64_t walk_cap = -1, place_cap = -1; bool phases = false;      // "walk_cap", "place_cap": capacities to start too small from (-1: the product's own); "phases": print the phase split of the -DDW_PHASE_TIMING build
         int writer = -1, force_threads = 0, split = -1, qrows = 1;      // "writer", "sim_threads", "split", "qrows": the k_simulate form forced (choose_sim_form)
         uint64_t place_open = 0; double walk_us = 0, count_us = 0;      // "place_open", "walk_us", "count_us": read back
@@ -203,6 +205,8 @@ struct dwgsim_hip_ctx {
     DevEvent ev_cnt0, ev_cnt1;
     bool gzip_on = false; DevMem d_crc_table, d_crc_shift;      // dwgsim_hip_set_gzip (u32; d_crc_shift is uploaded last)
     bool truth_on = false;                 // dwgsim_hip_set_truth_sam: every batch also leaves stream DWGSIM_HIP_STREAM_SAM
+    bool truth_md = false;                 // dwgsim_hip_set_truth_md: ... with NM:i: and MD:Z: on every mapped record (nothing while truth_on is off)
+    uint64_t truth_need = 0;               // inside dwgsim_hip_wait: the bytes the first run of the batch asked for (0: plan as usual)
     DevMem t_nl[2], t_rec[2], t_ends, t_len, t_blk;      // ... its working set (dw_truth.hpp TruthArgs): newline counts and record starts of the source streams, the read ends, the line lengths per end and per block
     HostMem h_stage;                       // pinned staging for fetch
     DevStream hap_stream;                  // dwgsim_hip_haplotype_fetch: copies of its own (made at the first call), not behind the batches' copy-outs
@@ -1982,6 +1986,13 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
         P.t_qname_max = fixed_max + 120;
         size_t ends = 0, bytes = 0;
         for (int j = 0; j < 2; ++j) if (p.length[j] > 0) { ends += n_pairs; bytes += (size_t)n_pairs * (size_t)(P.t_qname_max + fixed_max + 3 + 10 + 2 + 1 + 10 + 11 + 6 + 11 + 1 + 15 * (size_t)p.length[j]); }
+        // NM and MD (dwgsim_hip_set_truth_md): the part that IS bounded -- two tabs, "NM:i:" and "MD:Z:" (12), NM's digits (10), and for the M cells, at most s of
+        // them, a count and a letter each and the last count: 2 s + 1.  MD also spells out every deleted base, and a -m file may delete kilobases between two
+        // read bases: no bound in s exists.  The lines pack contiguously, so those bases normally come out of the slack of the 15 s above; where they do not, the
+        // write pass says so and dwgsim_hip_wait runs the batch again with the exact size (truth_need).
+        if (c->truth_md) for (int j = 0; j < 2; ++j) if (p.length[j] > 0) bytes += (size_t)n_pairs * (size_t)(12 + 10 + 2 * (size_t)p.length[j] + 1);
+        if (c->truth_need) bytes = (size_t)c->truth_need;
+        else if (c->dbg.truth_cap >= 0 && c->truth_md) bytes = (size_t)std::max<int64_t>(c->dbg.truth_cap, 64);      // dwgsim_hip_debug_option("truth_cap"): start too small, exercise the second run
         P.cap[3] = bytes;
         const bool bfast_src = !L.a.p.has_bwa;
         for (int q = 0; q < (bfast_src ? 1 : f.lpp); ++q) {
@@ -2095,6 +2106,7 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
         }
         t.ends = c->t_ends.get<TruthEnd>(); t.line_len = c->t_len.get<uint32_t>(); t.blk = c->t_blk.get<uint32_t>();
         t.out = c->out[slot][3].get<uint8_t>(); t.cap = P.cap[3]; t.total = &sl.counters.dev()[text_len_counter(3)];
+        t.md = c->truth_md ? 1 : 0; t.ref = L.g->mem.d_ref.get(); t.fit = &sl.counters.dev()[TRUTH_FIT_COUNTER];
         launch_truth(c->stream.get(), a, t);
         HIPC(c, hipEventRecord(sl.ev_t1.get(), c->stream.get()));
     }
@@ -2103,7 +2115,8 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
         size_t off = 0;
         for (int t = 0; t < N_STREAMS; ++t) {
             if (P.cap[t] == 0) continue;
-            launch_gzip(c->stream.get(), c->out[slot][t].get<uint8_t>(), &sl.counters.dev()[text_len_counter(t)], P.cap[t], sl.gz_out[t].get<uint8_t>(), P.gz_cap[t], sl.gz_status.get<uint64_t>() + off, &sl.counters.dev()[28 + t], &sl.counters.dev()[24 + t], &sl.counters.dev()[2],
+            // (the tagged SAM may not have fitted its buffer: its gzip takes the length k_truth_scan vouches for, 0 then -- dwgsim_hip_wait runs the batch again)
+            launch_gzip(c->stream.get(), c->out[slot][t].get<uint8_t>(), &sl.counters.dev()[t == 3 && c->truth_md ? TRUTH_FIT_COUNTER : text_len_counter(t)], P.cap[t], sl.gz_out[t].get<uint8_t>(), P.gz_cap[t], sl.gz_status.get<uint64_t>() + off, &sl.counters.dev()[28 + t], &sl.counters.dev()[24 + t], &sl.counters.dev()[2],
                         c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
             off += P.gz_chunks[t];
         }
@@ -2173,13 +2186,32 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
         }
         for (int q = 0; q < 6; ++q) h[16 + q] = keep[q];
     }
+    if ((h[2] & TRUTH_ROOM_BIT) && !(h[2] & ~TRUTH_ROOM_BIT) && !h[20]) {      // (nothing else went wrong: the first run's gzip took none of the SAM, TruthArgs::fit)
+        // The tagged truth SAM did not fit its planned buffer (sim_plan: MD has no bound in the read length).  The scan left the exact size in its counter, so the
+        // batch runs once more with that much room, the way an Ion Torrent batch does above: nothing of the chain moves, and the abort rule's words of the first
+        // run stand.  Record and line offsets are 32-bit words: a batch whose SAM would pass 4 GiB is refused.
+        const uint64_t need = h[text_len_counter(3)];
+        if (need + 64 >= (1ull << 32)) { c->err = "dwgsim-hip: the truth SAM of one batch would pass 4 GiB with its MD strings (deletions are spelled out): use smaller batches\n"; return DWGSIM_HIP_ERR_UNSUP; }
+        uint64_t keep[6]; for (int q = 0; q < 6; ++q) keep[q] = h[16 + q];
+        const uint64_t base = h[22];
+        c->truth_need = need;
+        const int rc = sim_enqueue(c, sl.ranges.data(), (int)sl.ranges.size(), base, slot, true);
+        c->truth_need = 0;
+        if (rc) return rc;
+        HIPC(c, hipEventSynchronize(sl.ev_done.get()));
+        sl.pending = false;
+        ++c->dbg.truth_reruns;
+        for (int q = 0; q < 6; ++q) h[16 + q] = keep[q];
+        if (h[2] & TRUTH_ROOM_BIT) { c->err = "dwgsim-hip: the truth SAM did not fit the room its own scan asked for\n"; return DWGSIM_HIP_ERR_FAILED; }
+    }
     if (h[2] & 4) { c->err = "dwgsim-hip: no fragment placement satisfied the target regions (-x) after 2^20 tries (the reference would not terminate)\n"; return DWGSIM_HIP_ERR_FAILED; }
     if (h[2] & 2) { c->err = "dwgsim-hip: a read outgrew its buffer (or degenerated) in the flow-error model\n"; return DWGSIM_HIP_ERR_FAILED; }
-    if ((h[2] & ~(8ull | TRUTH_ERR_BIT)) || h[20]) {      // one pair used up its 10 001 attempts, or the counter of failed attempts over the pairs of the contig passed the limit (dwgsim.c:635, :833-843)
+    if ((h[2] & ~(8ull | TRUTH_ERR_BIT | TRUTH_ROOM_BIT)) || h[20]) {      // one pair used up its 10 001 attempts, or the counter of failed attempts over the pairs of the contig passed the limit (dwgsim.c:635, :833-843)
         char b[128]; snprintf(b, sizeof b, "\r[dwgsim_core] failed to generate a read after %d trials\n", MAX_ATTEMPTS + 1); c->err = b; return DWGSIM_HIP_ERR_FAILED;
     }
     if (h[2] & 8) { c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
     if (h[2] & TRUTH_ERR_BIT) { c->err = "dwgsim-hip: the truth SAM could not be made (a read's record or alignment could not be replayed)\n"; return DWGSIM_HIP_ERR_FAILED; }
+    if (h[2] & TRUTH_ROOM_BIT) { c->err = "dwgsim-hip: the truth SAM did not fit its buffer\n"; return DWGSIM_HIP_ERR_FAILED; }
     for (int t = 0; t < N_STREAMS; ++t) { sl.out_bytes[t] = h[text_len_counter(t)]; sl.gz_bytes[t] = h[24 + t]; }
     if (!c->truth_on) sl.out_bytes[3] = sl.gz_bytes[3] = 0;
     if (c->dbg.phases) {   // only meaningful with the -DDW_PHASE_TIMING build (tools/phase_profile.sh)
@@ -2309,6 +2341,15 @@ int dwgsim_hip_set_truth_sam(dwgsim_hip_ctx_t *c, int on)
     c->truth_on = on != 0;
     return DWGSIM_HIP_OK;
 }
+// ... with NM:i: and MD:Z: on every mapped record (DESIGN.md "6e", the law: dw_truth.hpp).  A switch on top of the truth SAM: while that is off it does nothing.
+int dwgsim_hip_set_truth_md(dwgsim_hip_ctx_t *c, int on)
+{
+    if (!c) return DWGSIM_HIP_ERR_ARG;
+    for (const Slot &sl : c->slot) if (sl.pending) { c->err = "set_truth_md: a batch is in flight (wait for every slot first)"; return DWGSIM_HIP_ERR_STATE; }
+    if (on && c->prm.data_type != 0) { c->err = "dwgsim-hip: no truth SAM, and so no NM / MD tags, for SOLiD and Ion Torrent reads (-c 1, -c 2)\n"; return DWGSIM_HIP_ERR_UNSUP; }
+    c->truth_md = on != 0;
+    return DWGSIM_HIP_OK;
+}
 
 // The header of a truth SAM: host text, the same bytes for every caller.  One @SQ per contig of the table, in its order.  Returns the bytes the header has
 // (whatever cap is); at most cap of them are written to buf (may be NULL with cap 0: the size alone).
@@ -2432,6 +2473,7 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *c, const char *key, int64_t value)
     else if (!strcmp(key, "sim_threads")) c->dbg.force_threads = (int)value;
     else if (!strcmp(key, "walk_seg_min")) walk_debug_seg_min((uint32_t)value);      // (process-wide)
     else if (!strcmp(key, "place_cap")) c->dbg.place_cap = value;
+    else if (!strcmp(key, "truth_cap")) c->dbg.truth_cap = value;      // the bytes a batch's tagged truth SAM is planned with at first (tests: exercises the second run; -1: the product's plan)
     else if (!strcmp(key, "split")) c->dbg.split = (int)value;
     else if (!strcmp(key, "qrows")) c->dbg.qrows = (int)value;
     else if (!strcmp(key, "flow_slots")) c->dbg.flow_slots = (int)value;
@@ -2475,6 +2517,7 @@ int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
     else if (!strcmp(key, "hap_write_us")) *value = (int64_t)c->dbg.hap_write_us; // ... of its header and write kernels,
     else if (!strcmp(key, "hap_copy_us")) *value = (int64_t)c->dbg.hap_copy_us;   // ... and ("hap_yardstick") of a device-to-device copy of its size
     else if (!strcmp(key, "truth_us")) *value = (int64_t)c->dbg.truth_us;         // HIP-event time (microseconds) of the truth step of the batch waited for last (dwgsim_hip_set_truth_sam)
+    else if (!strcmp(key, "truth_reruns")) *value = c->dbg.truth_reruns;         // batches of this context that ran a second time because their tagged truth SAM needed room (dwgsim_hip_set_truth_md)
     else if (!strcmp(key, "truth_copy_us")) *value = (int64_t)c->dbg.truth_copy_us;      // ... and of the copy the option "truth_yardstick" made
     else if (!strcmp(key, "walk_form")) *value = c->dbg.walk_form;                // attempt, file-driven / random, site-scan form, restore, views of the last walk, packed
     else { c->err = "unknown debug value"; return DWGSIM_HIP_ERR_ARG; }

@@ -171,6 +171,7 @@ struct dwgsim_hip_job {
         std::string regions_path, mutin_path; int mutin_type = -1;
         dwgsim_hip_job_haplotype_fn hap_fn = nullptr; void *hap_user = nullptr; int hap_width = 60;      // dwgsim_hip_job_set_haplotype_sink
         bool truth_sam = false;       // dwgsim_hip_job_set_truth_sam: every batch also delivers stream DWGSIM_HIP_STREAM_SAM
+        bool truth_md = false;        // dwgsim_hip_job_set_truth_md: ... its mapped records with NM:i: and MD:Z:
     } cfg;
 
     // CALLER: touched only by the thread that calls the job_ functions (the ABI allows one at a time).  The workers see the staging through
@@ -827,7 +828,7 @@ int start_threads(dwgsim_hip_job *j)
         if (c.mutin_type >= 0 &&            // dwgsim.c:494-497
             dwgsim_hip_set_mutation_input(x, c.mutin_type, c.mutin_path.c_str(), nm.data(), c.tab_lens.data(), (int)nm.size()) < 0) { job_fail(j, dwgsim_hip_last_error(x)); return DWGSIM_HIP_ERR_ARG; }
         if (c.gzip && c.want_reads && c.has_sink() && dwgsim_hip_set_gzip(x, 1) < 0) { job_fail(j, dwgsim_hip_last_error(x)); return DWGSIM_HIP_ERR_DEVICE; }
-        if (c.truth_sam && c.want_reads) { const int rc = dwgsim_hip_set_truth_sam(x, 1); if (rc < 0) { job_fail(j, dwgsim_hip_last_error(x)); return rc; } }      // (-M 2: no reads, no SAM)
+        if (c.truth_sam && c.want_reads) { int rc = dwgsim_hip_set_truth_sam(x, 1); if (rc >= 0 && c.truth_md) rc = dwgsim_hip_set_truth_md(x, 1); if (rc < 0) { job_fail(j, dwgsim_hip_last_error(x)); return rc; } }      // (-M 2: no reads, no SAM)
     }
     for (int d = 0; d < c.ND; ++d) j->me.workers.emplace_back([j, d]() { Worker w{j, d, j->cfg.ctx[(size_t)d].get()}; w.run(); });
     if (c.want_reads && c.has_sink())      // reads_at: a thread per device and stream; reads: one per stream
@@ -982,6 +983,32 @@ int dwgsim_hip_job_set_truth_sam(dwgsim_hip_job_t *j, int on)
     if (j->me.started) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: the truth SAM must be switched on before prepare / the first contig");
     if (on && j->cfg.prm.data_type != 0) return arg_error(j, DWGSIM_HIP_ERR_UNSUP, "dwgsim-hip: the truth SAM is made for Illumina reads only (-c 0)\n");
     j->cfg.truth_sam = on != 0;
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_job_set_truth_md(dwgsim_hip_job_t *j, int on)
+{
+    if (!j) return DWGSIM_HIP_ERR_ARG;
+    if (j->me.started) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: the NM / MD tags of the truth SAM must be switched on before prepare / the first contig");
+    if (on && j->cfg.prm.data_type != 0) return arg_error(j, DWGSIM_HIP_ERR_UNSUP, "dwgsim-hip: the truth SAM and its NM / MD tags are made for Illumina reads only (-c 0)\n");
+    j->cfg.truth_md = on != 0;
+    return DWGSIM_HIP_OK;
+}
+
+// test / analysis hooks: dwgsim_hip_debug_option on every context of the job (before the first contig), dwgsim_hip_debug_get summed over them (after finish)
+int dwgsim_hip_job_debug_option(dwgsim_hip_job_t *j, const char *key, int64_t value)
+{
+    if (!j || !key) return DWGSIM_HIP_ERR_ARG;
+    if (j->me.started) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: debug options must be set before prepare / the first contig");
+    for (auto &x : j->cfg.ctx) { const int rc = dwgsim_hip_debug_option(x.get(), key, value); if (rc < 0) return arg_error(j, rc, dwgsim_hip_last_error(x.get())); }
+    return DWGSIM_HIP_OK;
+}
+int dwgsim_hip_job_debug_get(dwgsim_hip_job_t *j, const char *key, int64_t *value)
+{
+    if (!j || !key || !value) return DWGSIM_HIP_ERR_ARG;
+    if (j->me.started && !j->me.finished) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: debug values are read before the first contig or after finish");
+    *value = 0;
+    for (auto &x : j->cfg.ctx) { int64_t v = 0; const int rc = dwgsim_hip_debug_get(x.get(), key, &v); if (rc < 0) return arg_error(j, rc, dwgsim_hip_last_error(x.get())); *value += v; }
     return DWGSIM_HIP_OK;
 }
 

@@ -231,7 +231,8 @@ struct SimArgs {
 // inserted bases in front of lo's / behind hi's base where the read stopped inside an insertion, the characters of its CIGAR
 constexpr uint32_t TRUTH_F_RAND = 1, TRUTH_F_REV = 2, TRUTH_F_HAP2 = 4, TRUTH_F_BAD = 8;      // a random read; the reverse strand; haplotype 2; no line (the replay or the record index failed)
 constexpr uint64_t TRUTH_ERR_BIT = 32;                // SimArgs::counters[2]: a line could not be made
-struct TruthEnd { int32_t lo, hi; uint32_t lead, tail, flags, cigar, pad_[2]; };
+constexpr uint64_t TRUTH_ROOM_BIT = 64;               // SimArgs::counters[2], tagged lines only: a line would end behind the buffer (the batch runs again with the room the scan asked for)
+struct TruthEnd { int32_t lo, hi; uint32_t lead, tail, flags, cigar, nm, md; };      // nm, md (dwgsim_hip_set_truth_md, else 0): the value of NM and the characters of the MD string
 struct TruthArgs {
     int32_t lpp, bfast;             // read ends per pair; 1: the names and reads come from the one interleaved BFAST stream (-o 2), 0: from the BWA stream of each end
     int32_t prefix_len, qname_max;  // bytes of "prefix_" in front of a contig's name in the name pool; the longest QNAME the FASTQ buffers were sized for
@@ -239,6 +240,9 @@ struct TruthArgs {
     uint32_t *nl_count[2], *rec[2]; uint64_t n_rec[2];      // newlines per block of 4096 bytes (then their scan); rec[r] = start of record r, n_rec + 1 entries
     TruthEnd *ends; uint32_t *line_len, *blk;      // per read end (pair * lpp + end): the alignment; the bytes of its block's lines in front of its own.  Per block: the bytes of its lines, then their scan
     uint8_t *out; uint64_t cap; uint64_t *total;      // the SAM text, its capacity, its length (a device counter)
+    const uint8_t *ref; int32_t md;      // dwgsim_hip_set_truth_md: the group's reference codes (at group coordinate 0); 1: every mapped line carries NM:i: and MD:Z:
+    uint64_t *fit;                       // ... and the length the gzip kernel takes for the SAM (a device word of its own): the total where the text fits cap, else 0 -- the grid of
+                                         // k_gzip covers cap, and a chunk reads up to the length it is given
 };
 
 } // namespace dw

@@ -9,6 +9,8 @@
 //   k_truth_len, k_truth_len2                               one lane per read end: the replay and the travel walk; then, with the mate's record in reach, the bytes of its line
 //   k_scan_excl                                            over the blocks' bytes: with the scan k_truth_len2 makes inside each block, where each line starts
 //   k_truth_write                                           one lane per read end: the line, its CIGAR from a second walk over the cells (no CIGAR is ever stored)
+// With dwgsim_hip_set_truth_md the three kernels run as their <true> instances (the <false> ones are the step as it was, to the instruction): the length pass also
+// takes NM and the characters of MD (truth_tags), the sums are taken in 64 bits (k_truth_scan), the write pass spells MD out with a second truth_tags walk.
 //
 // The alignment of a read end.  gen_read starts at the first cell in travel order that is unmutated or substituted and stops once s bases have been
 // produced; a deleted cell produces nothing, a cell with an insertion its own base and the inserted bases -- a forward read the base first, a reverse
@@ -138,6 +140,92 @@ DW_DEV void truth_put_dec(O &o, uint32_t v)
     for (; p; p /= 10u) o.put((uint32_t)'0' + (v / p) % 10u);
 }
 
+// ---- NM:i: and MD:Z: (dwgsim_hip_set_truth_md) ----
+// The law (samtools calmd's convention, restated).  Walk the CIGAR in reference order from POS.  r = the reference letter of a cell: A C G T for the codes
+// 0-3, N for every other code, always upper case.  b = the base of SEQ as the line prints it (reverse-complemented under 0x10); a leading I run takes the
+// first `lead` bases of SEQ.
+//   M cell     a match if and only if b == r and r is one of ACGT (N against N is a mismatch).  A match adds one to the running count; a mismatch emits the
+//              count, then r, sets the count to 0 and adds 1 to NM
+//   I run, n   NM += n; MD is not touched and the count runs on
+//   D run, n   the count, '^', the n reference letters; the count is 0 again; NM += n
+//   the end    the count, also when it is 0
+// so MD matches [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)* and a mismatch directly behind a deletion gets its 0 (^AC0T).
+// Nothing of it is instrumented: SEQ (the finished FASTQ text, errors included) against the reference codes along the replayed alignment is the answer.
+DW_DEV uint32_t truth_ref_letter(uint32_t code) { return code < 4u ? (0x54474341u >> (8u * code)) & 0xffu : (uint32_t)'N'; }
+// eight base codes 0 .. 3, one per byte, as their letters: 'A' + 2 (bit 0) + 6 (bit 1) + 11 (both)
+DW_DEV uint64_t truth_letters8(uint64_t c)
+{
+    const uint64_t one = 0x0101010101010101ull, b0 = c & one, b1 = (c >> 1) & one;
+    return 0x41ull * one + 2ull * b0 + 6ull * b1 + 11ull * (b0 & b1);
+}
+DW_DEV uint32_t truth_comp(uint32_t b) { return b == 'A' ? (uint32_t)'T' : b == 'T' ? (uint32_t)'A' : b == 'C' ? (uint32_t)'G' : b == 'G' ? (uint32_t)'C' : b; }
+// The walk of the tags: the cells lo .. hi in reference order with the reference and the read beside them.  ref: the codes of the contig (its cell 0); seq: the s
+// bases of the FASTQ record; rev: the line prints them reverse-complemented.  num(n): a count of the MD string, ch(c): one character of it.  Returns NM.
+// Sixteen cells per step from wherever the walk stands -- the record's bases lie at the record's own phase anyway, and gfx950 takes 16-byte loads at any address
+// -- of which the ones in front of the first INSERT or DELETE cell (and inside lo .. hi) count: their reference codes as letters (a reverse read: of the
+// complement) against as many bases of the record as they stand.  The common case is sixteen matches that only add to the count; a cell that differs, or holds no
+// ACGT, is taken out of the difference one at a time.  The INSERT or DELETE cell that ended the step is taken singly, a run of DELETE cells out of the same load.
+// (The loads run up to fifteen bytes past what counts: cells and reference codes are padded by CELL_PAD behind the group, the text buffers by 64 bytes; a reverse
+// read's last step reads in front of its bases, into its own name line: the caller vouches for TRUTH_MD_QNAME_MIN characters of QNAME -- a read name has 26 at least.)
+constexpr uint32_t TRUTH_MD_QNAME_MIN = 14;      // '@' + QNAME + '\n' in front of the bases: sixteen bytes at least (a record that has fewer gets no line: k_truth_len<true>)
+template <class N, class C>
+DW_DEV uint32_t truth_tags(const HapDev &h, const uint8_t *ref, const TruthEnd &t, const uint8_t *seq, uint32_t s, bool rev, N &&num, C &&ch)
+{
+    uint32_t nm = t.lead, q = t.lead, run = 0; bool del = false;
+    const uint64_t turn = rev ? 0x0303030303030303ull : 0ull, other = 0xfcfcfcfcfcfcfcfcull;
+    auto byte_of = [](uint64_t lo, uint64_t hi, uint32_t k) -> uint32_t { return (uint32_t)((k < 8u ? lo : hi) >> (8u * (k & 7u))) & 0xffu; };
+    auto m_cell = [&](uint32_t code) {      // one M cell against the next base of SEQ
+        const uint32_t b = rev ? truth_comp(seq[s - 1u - q]) : (uint32_t)seq[q];
+        ++q; del = false;
+        const bool same = code < 4u && b == truth_ref_letter(code);
+        if (!same) { num(run); ch(truth_ref_letter(code)); }
+        run = same ? run + 1u : 0u; nm += same ? 0u : 1u;      // (as selects: an increment of either one behind a branch was merged into one through memory)
+    };
+    int32_t c = t.lo;
+    while (c <= t.hi) {
+        const uint32_t left = (uint32_t)(t.hi - c) + 1u, lim = left < 16u ? left : 16u;
+        const uint64_t m0 = reinterpret_cast<const Unal16 *>(h.cells + c)->a, m1 = reinterpret_cast<const Unal16 *>(h.cells + c)->b;
+        const uint64_t r0 = reinterpret_cast<const Unal16 *>(ref + c)->a, r1 = reinterpret_cast<const Unal16 *>(ref + c)->b;
+        const uint64_t i0 = m0 & 0x1010101010101010ull, i1 = m1 & 0x1010101010101010ull;
+        uint32_t n = i0 ? (uint32_t)__builtin_ctzll(i0) >> 3 : i1 ? 8u + ((uint32_t)__builtin_ctzll(i1) >> 3) : 16u;      // cells in front of the first INSERT / DELETE cell
+        if (n > lim) n = lim;
+        if (n) {
+            uint64_t e0, e1;      // the bases at positions q .. q + 15 of the printed SEQ, uncomplemented
+            if (rev) { const uint8_t *p = seq + (s - q); e0 = __builtin_bswap64(reinterpret_cast<const Unal8 *>(p - 8)->v); e1 = __builtin_bswap64(reinterpret_cast<const Unal8 *>(p - 16)->v); }
+            else { e0 = reinterpret_cast<const Unal16 *>(seq + q)->a; e1 = reinterpret_cast<const Unal16 *>(seq + q)->b; }
+            uint64_t d0 = (truth_letters8((r0 ^ turn) & ~other) ^ e0) | (r0 & other), d1 = (truth_letters8((r1 ^ turn) & ~other) ^ e1) | (r1 & other);
+            if (n < 8u) { d0 &= (1ull << (8u * n)) - 1ull; d1 = 0; }
+            else if (n < 16u) d1 &= (1ull << (8u * (n - 8u))) - 1ull;      // (n = 8: nothing of d1)
+            if ((d0 | d1) == 0) run += n;
+            else {
+                uint32_t prev = 0;
+                auto differ = [&](uint64_t d, uint64_t r, uint32_t first) {      // the cells of one half that differ, in order
+                    while (d) {
+                        const uint32_t k = (uint32_t)__builtin_ctzll(d) >> 3, at = first + k;
+                        d &= ~(0xffull << (8u * k));
+                        num(run + (at - prev)); ch(truth_ref_letter((uint32_t)(r >> (8u * k)) & 0xffu)); run = 0; prev = at + 1u; ++nm;
+                    }
+                };
+                differ(d0, r0, 0u); differ(d1, r1, 8u);
+                run += n - prev;
+            }
+            q += n; c += (int32_t)n; del = false;
+        }
+        if (n == lim) continue;      // no INSERT or DELETE cell among them
+        if ((byte_of(m0, m1, n) & TMASK) == T_DEL) {
+            if (!del) { num(run); ch('^'); run = 0; del = true; }
+            for (uint32_t k = n; k < lim && (byte_of(m0, m1, k) & TMASK) == T_DEL; ++k, ++c) { ch(truth_ref_letter(byte_of(r0, r1, k))); ++nm; }
+        } else {      // an INSERT cell: its own base is an M, the inserted bases follow it
+            m_cell(byte_of(r0, r1, n));
+            const uint32_t ins = c == t.hi ? t.tail : truth_ins_len(h, c);
+            nm += ins; q += ins; ++c;
+        }
+    }
+    num(run);
+    return nm;
+}
+DW_DEV uint32_t truth_sat32(uint64_t v) { return v > 0xffffffffull ? 0xffffffffu : (uint32_t)v; }
+
 // what the length pass and the write pass both derive for a lane: its range of the launch, its pair and read end, where its FASTQ record lies
 struct TruthLane {
     SegPtr sg; bool valid; int j; uint64_t pair_in, pair, e;
@@ -185,6 +273,7 @@ DW_DEV int32_t truth_tlen(const TruthEnd &me, const TruthEnd &mate, int j)
 
 // The length pass.  Reads meta, which belongs to the context and is overwritten by the next batch's k_simulate: the step runs on the stream of the
 // launches, behind this batch's and in front of the next one's.
+template <bool MD>
 __global__ void __launch_bounds__(SIM_THREADS) k_truth_len(SimArgs a, TruthArgs t)
 {
     const TruthLane L = truth_lane(a, t);
@@ -193,7 +282,9 @@ __global__ void __launch_bounds__(SIM_THREADS) k_truth_len(SimArgs a, TruthArgs 
     const uint32_t m = a.meta[L.pair];
     const int s = L.j ? a.p.len[1] : a.p.len[0];
     TruthEnd E; E.lo = E.hi = 0; E.lead = E.tail = 0; E.flags = 0; E.cigar = 0;
+    if constexpr (MD) E.nm = E.md = 0;
     bool ok = L.rec_ok;
+    if constexpr (MD) if (L.qn < TRUTH_MD_QNAME_MIN) ok = false;      // (truth_tags reads up to fifteen bytes in front of the bases)
     if (m & 0x80000000u) E.flags = TRUTH_F_RAND;
     else {
         const RngKey key{a.p.seed, L.sg->contig_index};
@@ -207,12 +298,18 @@ __global__ void __launch_bounds__(SIM_THREADS) k_truth_len(SimArgs a, TruthArgs 
             uint32_t chars = 0;
             truth_cigar(h, E, [&](uint32_t n, uint32_t) { chars += truth_ndigits(n) + 1u; });
             E.cigar = chars;
+            if constexpr (MD) if (ok) {
+                uint32_t md = 0;
+                E.nm = truth_tags(h, t.ref + sc.start, E, L.text + L.rs + 1u + L.qn + (t.bfast ? 0u : 2u) + 1u, (uint32_t)s, step < 0, [&](uint32_t n) { md += truth_ndigits(n); }, [&](uint32_t) { ++md; });
+                E.md = md;
+            }
         }
     }
     if (!ok) { E.flags |= TRUTH_F_BAD; atomicOr((unsigned long long *)&a.counters[2], (unsigned long long)TRUTH_ERR_BIT); }
     t.ends[L.e] = E;
 }
 // The bytes of a line.  FLAG, PNEXT and TLEN need the mate's record, so the lengths are taken by a pass of their own behind k_truth_len: one lane per read end again
+template <bool MD>
 DW_DEV uint32_t truth_line_bytes(const SimArgs &a, const TruthArgs &t, const TruthLane &L, const TruthEnd &me, const TruthEnd &mate)
 {
     const uint32_t s = (uint32_t)(L.j ? a.p.len[1] : a.p.len[0]);
@@ -226,10 +323,14 @@ DW_DEV uint32_t truth_line_bytes(const SimArgs &a, const TruthArgs &t, const Tru
     }
     n += s + 1u + s;
     if (!(me.flags & TRUTH_F_RAND)) n += 7u;                                      // \t HP:i:1
+    if constexpr (MD) if (!(me.flags & TRUTH_F_RAND)) n += 6u + truth_ndigits(me.nm) + 6u + me.md;      // \t NM:i: n \t MD:Z: string
     return n + 1u;
 }
 // ... scanned inside the block at once (the lanes of a block are consecutive read ends): line_len[e] = the bytes of the block's lines in front of line e,
 // blk[block] = the block's bytes; k_scan_excl over the blocks does the rest (one block scanning every line of a 2^18-pair batch took as long as two k_simulate)
+// <true>: a tagged line spells out every deleted base, so no bound in the read length holds for it: the block's sums are taken in 64 bits (two scans of 16 bits
+// each) and stored saturated -- 0xffffffff lies behind every buffer the host can make
+template <bool MD>
 __global__ void __launch_bounds__(SIM_THREADS) k_truth_len2(SimArgs a, TruthArgs t)
 {
     __shared__ uint32_t sm[17];
@@ -237,12 +338,34 @@ __global__ void __launch_bounds__(SIM_THREADS) k_truth_len2(SimArgs a, TruthArgs
     uint32_t len = 0;
     if (L.valid) {
         const TruthEnd me = t.ends[L.e], mate = t.lpp == 2 ? t.ends[L.e ^ 1ull] : me;
-        if (!((me.flags | mate.flags) & TRUTH_F_BAD)) len = truth_line_bytes(a, t, L, me, mate);      // (a pair's lines stand or fall together)
+        if (!((me.flags | mate.flags) & TRUTH_F_BAD)) len = truth_line_bytes<MD>(a, t, L, me, mate);      // (a pair's lines stand or fall together)
     }
-    uint32_t total;
-    const uint32_t before = block_excl_scan(len, sm, &total);      // (every lane of the block takes part)
-    if (L.valid) t.line_len[L.e] = before;
-    if (threadIdx.x == 0) t.blk[blockIdx.x] = total;
+    if constexpr (!MD) {
+        uint32_t total;
+        const uint32_t before = block_excl_scan(len, sm, &total);      // (every lane of the block takes part)
+        if (L.valid) t.line_len[L.e] = before;
+        if (threadIdx.x == 0) t.blk[blockIdx.x] = total;
+    } else {
+        uint32_t tl, th;
+        const uint32_t bl = block_excl_scan(len & 0xffffu, sm, &tl), bh = block_excl_scan(len >> 16, sm, &th);
+        if (L.valid) t.line_len[L.e] = truth_sat32((uint64_t)bl + ((uint64_t)bh << 16));
+        if (threadIdx.x == 0) t.blk[blockIdx.x] = truth_sat32((uint64_t)tl + ((uint64_t)th << 16));
+    }
+}
+// k_scan_excl for the blocks' bytes of tagged lines: the running sum in 64 bits, the prefixes stored saturated.  *total_out is exact unless a block's own sum
+// was saturated -- and then it is 2^32 - 1 at least, which the host refuses.  *fit_out: what the gzip kernel may read of the text, nothing where it did not fit
+__global__ void __launch_bounds__(1024) k_truth_scan(uint32_t *data, uint32_t n, uint64_t *total_out, uint64_t cap, uint64_t *fit_out)
+{
+    __shared__ uint32_t sm[17];
+    uint64_t grand = 0;
+    for (uint32_t base = 0; base < n; base += 1024u) {
+        const uint32_t i = base + threadIdx.x, v = i < n ? data[i] : 0u;
+        uint32_t tl, th;
+        const uint32_t bl = block_excl_scan(v & 0xffffu, sm, &tl), bh = block_excl_scan(v >> 16, sm, &th);
+        if (i < n) data[i] = truth_sat32(grand + (uint64_t)bl + ((uint64_t)bh << 16));
+        grand += (uint64_t)tl + ((uint64_t)th << 16);
+    }
+    if (threadIdx.x == 0) { *total_out = grand; *fit_out = grand <= cap ? grand : 0ull; }
 }
 
 // `n` bytes from src, in order or -- turn -- last byte first, each through the complement where comp is set
@@ -263,16 +386,18 @@ DW_DEV void truth_copy(O &o, const uint8_t *src, uint32_t n, bool turn, bool com
     for (; k < n; ++k) o.put(cb(turn ? src[n - 1 - k] : src[k]));
 }
 // The write pass: a line starts at blk[block] (scanned) + line_len[e]; the text's length stands in *t.total.  A line is written only if it ends inside the buffer (the host
-// sized it from a proven bound: a belt to its braces).
+// sized it from a proven bound: a belt to its braces).  <true>: no such bound (a deletion's bases are spelled out), so a line that would end behind the buffer is
+// left out under a status bit of its own, TRUTH_ROOM_BIT: the host runs the batch again with the room *t.total asks for.
+template <bool MD>
 __global__ void __launch_bounds__(SIM_THREADS) k_truth_write(SimArgs a, TruthArgs t)
 {
     const TruthLane L = truth_lane(a, t);
     if (!L.valid) return;
     const TruthEnd me = t.ends[L.e], mate = t.lpp == 2 ? t.ends[L.e ^ 1ull] : me;
     if ((me.flags | mate.flags) & TRUTH_F_BAD) return;
-    const uint32_t len = truth_line_bytes(a, t, L, me, mate);
+    const uint32_t len = truth_line_bytes<MD>(a, t, L, me, mate);
     const uint64_t off = (uint64_t)t.blk[blockIdx.x] + t.line_len[L.e];
-    if (off + len > t.cap) { atomicOr((unsigned long long *)&a.counters[2], (unsigned long long)TRUTH_ERR_BIT); return; }
+    if (off + len > t.cap) { atomicOr((unsigned long long *)&a.counters[2], (unsigned long long)(MD ? TRUTH_ROOM_BIT : TRUTH_ERR_BIT)); return; }
     const uint32_t s = (uint32_t)(L.j ? a.p.len[1] : a.p.len[0]);
     const bool rnd = (me.flags & TRUTH_F_RAND) != 0, rev = !rnd && (me.flags & TRUTH_F_REV);
     Writer o; o.init(t.out + off);
@@ -299,6 +424,12 @@ __global__ void __launch_bounds__(SIM_THREADS) k_truth_write(SimArgs a, TruthArg
     o.put('\t');
     truth_copy(o, seq + s + 3u, s, rev, false);
     if (!rnd) { truth_lit(o, "\tHP:i:"); o.put((me.flags & TRUTH_F_HAP2) ? '2' : '1'); }
+    if constexpr (MD) if (!rnd) {      // the second walk of the tags: no MD string is ever stored between the passes
+        const SegCtx sc = seg_ctx(a, L.sg);
+        const HapDev h = sel_hap(a, sc, (me.flags & TRUTH_F_HAP2) ? 1 : 0);
+        truth_lit(o, "\tNM:i:"); truth_put_dec(o, me.nm); truth_lit(o, "\tMD:Z:");
+        (void)truth_tags(h, t.ref + sc.start, me, seq, s, rev, [&](uint32_t n) { truth_put_dec(o, n); }, [&](uint32_t c) { o.put(c); });
+    }
     o.put('\n');
     o.flush();
 }
@@ -314,10 +445,17 @@ void launch_truth(hipStream_t st, const SimArgs &a, const TruthArgs &t)
         launch_scan_excl(st, t.nl_count[q], nb, nullptr);
         hipLaunchKernelGGL(k_truth_nl_index, dim3(nb), dim3(TRUTH_NL_THREADS), 0, st, t.src[q], t.src_bytes[q], t.nl_count[q], t.rec[q], t.n_rec[q]);
     }
-    hipLaunchKernelGGL(k_truth_len, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
-    hipLaunchKernelGGL(k_truth_len2, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+    if (t.md) {
+        hipLaunchKernelGGL(k_truth_len<true>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+        hipLaunchKernelGGL(k_truth_len2<true>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+        hipLaunchKernelGGL(k_truth_scan, dim3(1), dim3(1024), 0, st, t.blk, a.n_blocks, t.total, t.cap, t.fit);
+        hipLaunchKernelGGL(k_truth_write<true>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+        return;
+    }
+    hipLaunchKernelGGL(k_truth_len<false>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+    hipLaunchKernelGGL(k_truth_len2<false>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
     launch_scan_excl(st, t.blk, a.n_blocks, t.total);
-    hipLaunchKernelGGL(k_truth_write, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+    hipLaunchKernelGGL(k_truth_write<false>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
 }
 
 } // namespace dw

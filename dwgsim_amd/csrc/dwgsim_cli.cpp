@@ -27,6 +27,9 @@
 //     DWGSIM_HIP_HAPLOTYPES_WIDTH  bases per line of those files (default 60; 0: the whole sequence on one line)
 //     DWGSIM_HIP_TRUTH_SAM   anything but empty or "0": also write <prefix>.truth.sam.gz, the true alignment of every read end (Illumina reads):
 //                          the header, then the job's stream 3, in the gzip mode of the FASTQ files.  -M 2 writes none
+//     DWGSIM_HIP_TRUTH_MD    anything but empty or "0", together with DWGSIM_HIP_TRUTH_SAM: every mapped record of that file also carries NM:i: and MD:Z:
+//                          (samtools calmd's convention; SEQ with its errors against the reference).  Without DWGSIM_HIP_TRUTH_SAM it does nothing
+//     DWGSIM_HIP_DEBUG     "key=value,...": test / analysis only -- dwgsim_hip_job_debug_option for each pair, and a line "[dwgsim-hip-debug] truth_reruns=<n>" on stderr at the end
 //     DWGSIM_HIP_SOLO      "r/W": measurement aid (dw_job.cpp) -- this process's one device does what device r of a W-device job does, nothing else
 #include <stdio.h>
 #include <stdlib.h>
@@ -676,6 +679,8 @@ int main(int argc, char **argv)
     // the truth SAM: the header (one exported function: the same bytes as every other caller's) as the first piece, then the job's stream 3, in the job's gzip mode
     const char *sam_env = getenv("DWGSIM_HIP_TRUTH_SAM");
     const bool want_sam = want_reads && sam_env && sam_env[0] && strcmp(sam_env, "0");
+    const char *md_env = getenv("DWGSIM_HIP_TRUTH_MD");
+    const bool want_md = want_sam && md_env && md_env[0] && strcmp(md_env, "0");
     if (want_sam) {
         std::vector<const char *> nm; for (auto &s : tab_names) nm.push_back(s.c_str());
         const int64_t hn = dwgsim_hip_truth_sam_header(nm.data(), tab_lens.data(), (int)nm.size(), nullptr, 0);
@@ -702,6 +707,14 @@ int main(int argc, char **argv)
         if (rc == 0 && muts_type >= 0 && dwgsim_hip_job_set_mutation_input(job, muts_type, muts_fn.c_str()) < 0) job_error();   // dwgsim.c:494-497
         if (rc == 0 && want_hap && dwgsim_hip_job_set_haplotype_sink(job, FileSink::haplotype, &fs, hap_width) < 0) job_error();
         if (rc == 0 && want_sam && dwgsim_hip_job_set_truth_sam(job, 1) < 0) job_error();
+        if (rc == 0 && want_md && dwgsim_hip_job_set_truth_md(job, 1) < 0) job_error();
+        if (const char *e = getenv("DWGSIM_HIP_DEBUG")) {
+            for (std::string rest = e; rc == 0 && !rest.empty();) {
+                const size_t comma = rest.find(','); const std::string kv = rest.substr(0, comma); rest = comma == std::string::npos ? "" : rest.substr(comma + 1);
+                const size_t eq = kv.find('=');
+                if (eq != std::string::npos && dwgsim_hip_job_debug_option(job, kv.substr(0, eq).c_str(), atoll(kv.c_str() + eq + 1)) < 0) job_error();
+            }
+        }
         if (rc == 0 && dwgsim_hip_job_prepare(job, nullptr) < 0) job_error();
     }
     const double t_ctx = now_s();
@@ -735,6 +748,7 @@ int main(int argc, char **argv)
     if (dwgsim_hip_job_finish(job) < 0) job_error();
     const double t_out_done = now_s();
     if (rc == 0) fprintf(stderr, "\n[dwgsim_core] Complete!\n");
+    if (getenv("DWGSIM_HIP_DEBUG")) { int64_t v = 0; if (dwgsim_hip_job_debug_get(job, "truth_reruns", &v) == 0) fprintf(stderr, "[dwgsim-hip-debug] truth_reruns=%lld\n", (long long)v); }
     if (timing) fprintf(stderr, "[dwgsim-hip] contig table%s %.2f s | contexts, files, inputs %.2f s | %scontigs handed to the GPUs %.2f s | remaining simulate + copy + write %.2f s | "
                                 "total %.2f s; text %.2f GB -> gz %.2f GB, %s\n",
                         streaming ? " (.fai)" : " (FASTA read into memory)", t_fasta - t_start, t_ctx - t_fasta, streaming ? "FASTA read, " : "", t_fed - t_ctx, t_out_done - t_fed, t_out_done - t_start,

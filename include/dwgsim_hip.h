@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define DWGSIM_HIP_ABI_VERSION 8
+#define DWGSIM_HIP_ABI_VERSION 9
 
 /* error codes (negative) */
 #define DWGSIM_HIP_OK            0
@@ -291,6 +291,19 @@ int dwgsim_hip_fetch_gz_async(dwgsim_hip_ctx_t *ctx, int slot, int stream, void 
  * a tie); SEQ / QUAL the FASTQ's, reverse-complemented / reversed under 0x10; HP:i:1 or HP:i:2, the haplotype the read was drawn from.  A random read:
  * FLAG 0x4 (pairs: 0x1 | 0x4 | 0x8 | 0x40 / 0x80), RNAME *, POS 0, MAPQ 0, CIGAR *, RNEXT *, PNEXT 0, TLEN 0, no HP. */
 int dwgsim_hip_set_truth_sam(dwgsim_hip_ctx_t *ctx, int on);
+/* (ABI 9) NM and MD on top of the truth SAM: with it, every mapped record carries NM:i:<n> and MD:Z:<string> behind HP:i:, in that order; unmapped (random-read)
+ * records get no tags.  It takes effect only while the truth SAM is on and on its own produces no stream; off (the default), every byte of every output is as
+ * before and no kernel launch is added.  DWGSIM_HIP_ERR_STATE while a batch is in flight, DWGSIM_HIP_ERR_UNSUP for -c 1 / -c 2.
+ * The law (samtools calmd's convention, restated).  Walk the record's CIGAR in reference order from POS.  r = the reference letter of a cell: A C G T for the
+ * codes 0-3, N for everything else, always upper case.  b = the base of SEQ as the line prints it (reverse-complemented under 0x10); a leading I run takes the
+ * first bases of SEQ.  An M cell matches if and only if b == r and r is one of ACGT (N against N is a mismatch): a match adds one to the running count; a
+ * mismatch emits the count, then r, sets the count to 0 and adds 1 to NM.  An I run of n bases: NM += n, MD untouched, the count runs on.  A D run of n cells:
+ * the count, '^', the n reference letters; the count is 0 again; NM += n.  At the end the count, also when it is 0.  So MD matches
+ * [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)* and a mismatch directly behind a deletion gets its 0 (^AC0T).  SEQ holds the sequencing errors, so the tags show them too.
+ * MD spells out every deleted base, so a line has no bound in the read length: a batch whose text outgrows its planned buffer is run a second time inside
+ * dwgsim_hip_wait with the exact room (nothing is lost, nothing of the job's random numbers moves); a batch whose SAM would pass 4 GiB is refused with
+ * DWGSIM_HIP_ERR_UNSUP (use smaller batches). */
+int dwgsim_hip_set_truth_md(dwgsim_hip_ctx_t *ctx, int on);
 /* The header that goes in front of the records: @HD VN:1.6 SO:unsorted GO:query, one @SQ per contig of the table (every contig of the FASTA, in its
  * order, skipped ones included), one @PG.  Needs no context.  Returns the header's size; at most cap bytes of it are written to buf (NULL with cap 0: the
  * size alone). */
@@ -367,6 +380,9 @@ int dwgsim_hip_job_set_haplotype_sink(dwgsim_hip_job_t *job, dwgsim_hip_job_hapl
  * job's gzip option says.  The header is not part of the stream (dwgsim_hip_truth_sam_header).  -M 2 makes no reads and no SAM.  To be called before
  * dwgsim_hip_job_prepare / the first contig: DWGSIM_HIP_ERR_STATE later; DWGSIM_HIP_ERR_UNSUP for -c 1 / -c 2. */
 int dwgsim_hip_job_set_truth_sam(dwgsim_hip_job_t *job, int on);
+/* (ABI 9) ... with NM:i: and MD:Z: on its mapped records (dwgsim_hip_set_truth_md).  Before dwgsim_hip_job_prepare / the first contig, like the call above; without
+ * it, it does nothing. */
+int dwgsim_hip_job_set_truth_md(dwgsim_hip_job_t *job, int on);
 /* optional: parse the files above and start the device threads now (errors of -x / -m / -b / -v surface here instead of at the first contig) */
 int dwgsim_hip_job_prepare(dwgsim_hip_job_t *job, uint64_t *total_len);
 /* The body of the contig loop (dwgsim.c:519-625 and everything below it) for the next contig of the FASTA.  Returns the pairs scheduled for
@@ -481,7 +497,8 @@ int dwgsim_hip_eval_debug_inflate(const void *bam, size_t len, int threads, int 
  * the single Illumina kernel stays on the per-lane FIFO where it would run in the wave's staging rows (reads of 137 bases on); "flow_slots" = n:
  * n scratch slots per XCD for the Ion Torrent read buffers / the long reads of the one-wave blocks (blocks wait for slots); "flow_cap" = n: the Ion Torrent
  * read capacity a job starts from (a read that outgrows it makes the batch run again with twice the room); "phases" = 1: print the phase
- * split of the -DDW_PHASE_TIMING analysis build. */
+ * split of the -DDW_PHASE_TIMING analysis build; "truth_cap" = n: the bytes a batch's tagged truth SAM (dwgsim_hip_set_truth_md) is planned with at first
+ * (exercises the second run that finds the room). */
 int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *ctx, const char *key, int64_t value);
 /* "place_open": pairs the last dwgsim_hip_count_random* call could not settle from the coarse haplotype summaries; "flow_cap_mult": how often (as a
  * power of two) the Ion Torrent read capacity has been doubled so far; "walk_us" / "count_us":
@@ -494,8 +511,14 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *ctx, const char *key, int64_t valu
  * "hap_len_us" / "hap_write_us": HIP-event time (microseconds) of the length pass + scan / of the header and write kernels of the haplotype text built
  * last (dwgsim_hip_haplotype_fasta); "hap_copy_us": with the option "hap_yardstick" = 1, of a device-to-device copy of that text's size behind it;
  * "truth_us": HIP-event time (microseconds) of the truth step of the batch waited for last (dwgsim_hip_set_truth_sam); "truth_copy_us": of the device-to-device copy
- * of n bytes of slot 0's truth SAM that the option "truth_yardstick" = n makes at once */
+ * of n bytes of slot 0's truth SAM that the option "truth_yardstick" = n makes at once; "truth_reruns": batches of the context that ran a second time because
+ * their tagged truth SAM needed more room than planned */
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *ctx, const char *key, int64_t *value);
+/* (ABI 9) the two calls above through a job: the option goes to every context of the job (before dwgsim_hip_job_prepare / the first contig: DWGSIM_HIP_ERR_STATE
+ * later); the value is the sum over the job's contexts (before the first contig or after dwgsim_hip_job_finish).  dwgsim-hip: DWGSIM_HIP_DEBUG="key=value,..."
+ * sets the options and makes the program report "truth_reruns" on stderr. */
+int dwgsim_hip_job_debug_option(dwgsim_hip_job_t *job, const char *key, int64_t value);
+int dwgsim_hip_job_debug_get(dwgsim_hip_job_t *job, const char *key, int64_t *value);
 /* (ABI 7) the k_simulate<LPP, OUT, DT, NTHR, WR, SPLIT> instances the library was built with, from the list that instantiates them and in which a
  * launch looks its form up: returns their number and writes at most `cap` of them to `out` (may be NULL), each packed as "sim_form" above with SPLIT
  * the template parameter -- 0: the single kernel, 1 / 2: the first / second half of the two-kernel form.  A form with SPLIT 1 that "sim_form" reports,

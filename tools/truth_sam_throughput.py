@@ -5,8 +5,10 @@ One batch of --pairs pairs (default 2^18) of the chr20-sized contig of bench.py'
   copy_us       a device-to-device copy of the SAM's bytes on the same stream (dwgsim_hip_debug_option "truth_yardstick" / "truth_copy_us"): the yardstick;
                 truth_GBps / copy_GBps = bytes over the two times
   plain_*       the same batch with the feature off: its k_simulate and kernel times (nothing of the step runs)
+--md: the same with dwgsim_hip_set_truth_md on top (NM:i: and MD:Z: on every mapped record); the line then also holds "md": true and "truth_reruns" (second
+runs for want of room: 0 on this workload).
 Each is the best of --reps batches (the first one allocates: not counted).  Prints one JSON line.
-Usage: python tools/truth_sam_throughput.py [--reps 5] [--pairs 262144]"""
+Usage: python tools/truth_sam_throughput.py [--reps 5] [--pairs 262144] [--md]"""
 import argparse, json, os, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,11 +34,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=1 << 18)
+    ap.add_argument("--md", action="store_true", help="with NM:i: and MD:Z: (dwgsim_hip_set_truth_md)")
     args = ap.parse_args()
     lib = api.load()
     if lib.dwgsim_hip_device_count() < 1:
         raise SystemExit("no HIP device: nothing is measured without one")
-    out = {"flags": FLAGS, "pairs": args.pairs, "reps": args.reps}
+    out = {"flags": FLAGS, "pairs": args.pairs, "reps": args.reps, "md": bool(args.md)}
     contigs = synth.workload_contigs("chr20")
     with api.Context(api.parse_flags(FLAGS, lib), 0, lib) as ctx:
         h = ctx.add_contigs(contigs)
@@ -44,6 +47,8 @@ def main():
         plain, _ = batches(ctx, h, args.pairs, args.reps)
         out.update({"plain_simulate_us": plain["simulate_us"], "plain_kernels_us": plain["kernels_us"]})
         ctx.set_truth_sam(True)
+        if args.md:
+            ctx.set_truth_md(True)
         on, b = batches(ctx, h, args.pairs, args.reps)
         out.update(on)
         out["sam_bytes"] = int(b.sam_bytes); out["fastq_bytes"] = int(b.bytes[0] + b.bytes[1])
@@ -56,6 +61,8 @@ def main():
         out["truth_GBps"] = b.sam_bytes / max(on["truth_us"], 1) / 1e3
         out["copy_GBps"] = b.sam_bytes / max(best, 1) / 1e3
         out["truth_over_simulate"] = on["truth_us"] / max(on["simulate_us"], 1)
+        if args.md:
+            out["truth_reruns"] = ctx.debug_get("truth_reruns")
         ctx.drop_contig(h)
     print(json.dumps(out))
 
