@@ -184,7 +184,7 @@ template <class Front> __device__ __forceinline__ void eval_records_body(const E
 
 __global__ __launch_bounds__(EV_THREADS) void k_eval_records(EvalRecArgs A)
 {
-    __shared__ uint32_t h[5 * (EVAL_WIN + 1)];
+    __shared__ uint32_t h[(EVAL_WIN + 1) * 5];
     eval_records_body<SamFront>(A, h);
 }
 
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_records(EvalRecArgs A)
 // A.res->n_lines their number; no newline kernels run
 __global__ __launch_bounds__(EV_THREADS) void k_eval_bam_records(EvalRecArgs A)
 {
-    __shared__ uint32_t h[5 * (EVAL_WIN + 1)];
+    __shared__ uint32_t h[(EVAL_WIN + 1) * 5];
     eval_records_body<BamFront>(A, h);
 }
 

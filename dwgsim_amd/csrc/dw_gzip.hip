@@ -43,7 +43,7 @@ constexpr int GZ_MIN_MATCH = 3;
 struct GzArgs {
     const uint8_t *text; const uint64_t *n_dev;   // the stream; its length is still on the device when the kernel is enqueued
     uint32_t *out; uint64_t cap;            // output (4-byte aligned), cap bytes
-    uint64_t *flags;                        // |= 8 when a member would not fit
+    uint64_t *flags;                        // the status word of the batch's counter block (dw_kernels.hpp): GZIP_ROOM_BIT when a member would not fit
     uint64_t *status;                       // look-back words, one per chunk (zeroed)
     uint64_t *ticket;                       // zeroed
     uint64_t *total;                        // out: compressed bytes of the stream (written by the last chunk)
@@ -556,7 +556,7 @@ __global__ void __launch_bounds__(GZ_THREADS, 3) k_gzip(GzArgs a)
     const uint32_t hdr_bytes = 10u + pad + 1u, member_bytes = hdr_bytes + body_bytes + 8u;
     if (wave == 0) { const uint64_t g = lookback_excl(a.status, t, member_bytes, 0); if (lane == 0) { s_base = g; if (c0 + clen >= n_text) *a.total = g + member_bytes; } }
     __syncthreads();
-    if (s_base + member_bytes > a.cap) { if (tid == 0) atomicOr((unsigned long long *)a.flags, 8ull); return; }      // (cannot happen: gz_capacity covers stored members)
+    if (s_base + member_bytes > a.cap) { if (tid == 0) atomicOr((unsigned long long *)a.flags, GZIP_ROOM_BIT); return; }      // (cannot happen: gz_capacity covers stored members)
 
     if (probe::off(1 << 24)) return;      // ... + header tokens, bit counts, look-back
     // CRC-32 of the chunk: the spans' registers joined by a tree; the right half of a node is shifted in by its true length (the last chunk of

@@ -112,13 +112,7 @@ struct Group {
 
 struct HandleRef { int group = -1, k = 0; };
 
-constexpr int N_COUNTERS = 32;      // u64 words of a counter block (SimArgs::counters)
-constexpr int N_STREAMS = 4;        // output streams of a batch: the three FASTQ streams and the truth SAM (DWGSIM_HIP_STREAM_SAM)
-// where a stream's text length stands in a slot's counters (its gzip total is [24 + t], its gzip ticket [28 + t])
-constexpr int text_len_counter(int t) { return t < 3 ? 4 + t : 7; }
-constexpr int TRUTH_FIT_COUNTER = 23;      // the bytes of a tagged truth SAM that its gzip may read (TruthArgs::fit)
-
-struct Counters {                   // a device counter block and its page-locked mirror
+struct Counters {                   // a device counter block (its layout: dw_kernels.hpp) and its page-locked mirror
     DevMem d; HostMem h;
     uint64_t *dev() const { return d.get<uint64_t>(); }
     uint64_t *host() const { return h.get<uint64_t>(); }
@@ -206,7 +200,6 @@ struct dwgsim_hip_ctx {
     bool gzip_on = false; DevMem d_crc_table, d_crc_shift;      // dwgsim_hip_set_gzip (u32; d_crc_shift is uploaded last)
     bool truth_on = false;                 // dwgsim_hip_set_truth_sam: every batch also leaves stream DWGSIM_HIP_STREAM_SAM
     bool truth_md = false;                 // dwgsim_hip_set_truth_md: ... with NM:i: and MD:Z: on every mapped record (nothing while truth_on is off)
-    uint64_t truth_need = 0;               // inside dwgsim_hip_wait: the bytes the first run of the batch asked for (0: plan as usual)
     DevMem t_nl[2], t_rec[2], t_ends, t_len, t_blk;      // ... its working set (dw_truth.hpp TruthArgs): newline counts and record starts of the source streams, the read ends, the line lengths per end and per block
     HostMem h_stage;                       // pinned staging for fetch
     DevStream hap_stream;                  // dwgsim_hip_haplotype_fetch: copies of its own (made at the first call), not behind the batches' copy-outs
@@ -632,9 +625,9 @@ static int calibrate_end(dwgsim_hip_ctx *c, int i, double e, CalibRun *r)
         for (ca.first_read = 0; ca.first_read < ca.n_reads; ca.first_read += ca.chunk_reads) launch_calibrate(c->stream.get(), ca);
         HIPC(c, hipMemcpyAsync(c->counters.host(), c->counters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream.get()));
         HIPC(c, hipStreamSynchronize(c->stream.get()));
-        if (!c->counters.host()[2] || base_cap * (int64_t)mult * 2 > (int64_t)FLOW_CAP_MAX) break;
+        if (!(c->counters.host()[STATUS_COUNTER] & FLOW_ROOM_BIT) || base_cap * (int64_t)mult * 2 > (int64_t)FLOW_CAP_MAX) break;
     }
-    r->mult = mult; r->outgrown = c->counters.host()[2] != 0; r->n_err = (int32_t)c->counters.host()[8]; r->counts = (int32_t)c->counters.host()[9];
+    r->mult = mult; r->outgrown = (c->counters.host()[STATUS_COUNTER] & FLOW_ROOM_BIT) != 0; r->n_err = (int32_t)c->counters.host()[CALIB_ERR_COUNTER]; r->counts = (int32_t)c->counters.host()[CALIB_LEN_COUNTER];
     return 0;
 }
 
@@ -1884,6 +1877,8 @@ static int sim_resolve(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, 
     return DWGSIM_HIP_OK;
 }
 
+// the reference's own last words (dwgsim.c:833-843): one pair used up its 10 001 attempts, or the counter of failed attempts over the pairs of a contig passed the limit (dwgsim.c:635)
+static int fail_attempts(dwgsim_hip_ctx_t *c) { char b[128]; snprintf(b, sizeof b, "\r[dwgsim_core] failed to generate a read after %d trials\n", MAX_ATTEMPTS + 1); c->err = b; return DWGSIM_HIP_ERR_FAILED; }
 int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t *n_random, uint64_t *per_range)
 {
     if (!c) return DWGSIM_HIP_ERR_ARG;
@@ -1934,12 +1929,12 @@ int dwgsim_hip_count_random_ranges(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t
         HIPC(c, hipMemcpyAsync(c->h_range_rand.get(), a.range_rand, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, st));
         HIPC(c, hipStreamSynchronize(st));
         { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_cnt0.get(), c->ev_cnt1.get()) == hipSuccess) c->dbg.count_us += 1e3 * ms; else (void)hipGetLastError(); }
-        if (!(c->pcounters.host()[2] & 16) || attempt > 0) break;
+        if (!(c->pcounters.host()[STATUS_COUNTER] & PLACE_ROOM_BIT) || attempt > 0) break;
         cap = cap_full;
     }
-    if (c->pcounters.host()[2] & 16) { c->err = "count_random: the list of undecided pairs overflowed twice"; return DWGSIM_HIP_ERR_FAILED; }
-    if (c->pcounters.host()[2]) { char b[128]; snprintf(b, sizeof b, "\r[dwgsim_core] failed to generate a read after %d trials\n", MAX_ATTEMPTS + 1); c->err = b; return DWGSIM_HIP_ERR_FAILED; }
-    c->dbg.place_open = c->pcounters.host()[5];
+    if (c->pcounters.host()[STATUS_COUNTER] & PLACE_ROOM_BIT) { c->err = "count_random: the list of undecided pairs overflowed twice"; return DWGSIM_HIP_ERR_FAILED; }
+    if (c->pcounters.host()[STATUS_COUNTER]) return fail_attempts(c);
+    c->dbg.place_open = c->pcounters.host()[PLACE_OPEN_COUNTER];
     uint64_t total = 0;
     for (int q = 0, si = 0; q < n; ++q) if (r[q].n_pairs) { total += h_range_rand[si]; if (per_range) per_range[q] = h_range_rand[si]; ++si; }
     if (n_random) *n_random = total;
@@ -1959,8 +1954,13 @@ int dwgsim_hip_set_fail_carry(dwgsim_hip_ctx_t *c, uint64_t carry)
     return DWGSIM_HIP_OK;
 }
 
+// How a batch is run: where its random-read index starts (DWGSIM_HIP_RAND_CHAIN: where the last batch ended).  again: the batch of this slot once more (sim_rerun), with
+// truth_bytes of room for its truth SAM (0: the planned bound).  Nothing of the chain moves then: the random reads and the failed attempts of a batch depend on no buffer's size,
+// so the first run's epilogue stands; the kernels start from the chain word the first run started from (rand_base = its CHAIN_BASE_COUNTER).
+struct SimRun { uint64_t rand_base; bool again; uint64_t truth_bytes; };
+
 // The plan step: every size the launch needs, from its form, arguments and ranges.  No side effects.
-static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
+static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L, const SimRun &run)
 {
     const dwgsim_hip_params_t &p = c->prm; const SimForm &f = L.f;
     const uint64_t n_pairs = L.n_pairs; const size_t nblk = L.nblk;
@@ -1989,9 +1989,9 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L)
         // NM and MD (dwgsim_hip_set_truth_md): the part that IS bounded -- two tabs, "NM:i:" and "MD:Z:" (12), NM's digits (10), and for the M cells, at most s of
         // them, a count and a letter each and the last count: 2 s + 1.  MD also spells out every deleted base, and a -m file may delete kilobases between two
         // read bases: no bound in s exists.  The lines pack contiguously, so those bases normally come out of the slack of the 15 s above; where they do not, the
-        // write pass says so and dwgsim_hip_wait runs the batch again with the exact size (truth_need).
+        // write pass says so and dwgsim_hip_wait runs the batch again with the exact size (SimRun::truth_bytes).
         if (c->truth_md) for (int j = 0; j < 2; ++j) if (p.length[j] > 0) bytes += (size_t)n_pairs * (size_t)(12 + 10 + 2 * (size_t)p.length[j] + 1);
-        if (c->truth_need) bytes = (size_t)c->truth_need;
+        if (run.truth_bytes) bytes = (size_t)run.truth_bytes;
         else if (c->dbg.truth_cap >= 0 && c->truth_md) bytes = (size_t)std::max<int64_t>(c->dbg.truth_cap, 64);      // dwgsim_hip_debug_option("truth_cap"): start too small, exercise the second run
         P.cap[3] = bytes;
         const bool bfast_src = !L.a.p.has_bwa;
@@ -2050,26 +2050,26 @@ static int sim_reserve(dwgsim_hip_ctx_t *c, int slot, const SimPlan &P)
 }
 
 // The chain step: the running values the batch starts from; the context's chain moves on to its end (a re-run moves nothing)
-static ChainSet sim_chain(dwgsim_hip_ctx_t *c, Slot &sl, const dwgsim_hip_range_t *r, int n, bool set_rand, bool rerun)
+static ChainSet sim_chain(dwgsim_hip_ctx_t *c, Slot &sl, const dwgsim_hip_range_t *r, int n, const SimRun &run)
 {
-    if (rerun) return ChainSet{sl.d_rerun_chain.get<uint64_t>(), 1, 1, 0};
+    if (run.again) return ChainSet{sl.d_rerun_chain.get<uint64_t>(), 1, 1, 0};
     // the reference's failure counter (dwgsim.c:635) runs over the pairs of ONE contig in index order: it is carried from the previous
     // batch only when this one continues it; any other range starts from zero unless the caller supplied the carry (sharded jobs)
     const dwgsim_hip_range_t *r_first = nullptr, *r_last = nullptr;
     for (int q = 0; q < n; ++q) if (r[q].n_pairs) { if (!r_first) r_first = &r[q]; r_last = &r[q]; }
     if (!r_first) { r_first = &r[0]; r_last = &r[n - 1]; }
     const bool continues = c->chain_contig == r_first->contig && c->chain_next_ii == r_first->first_ii && r_first->first_ii != 0;
-    const ChainSet ch{c->d_chain.get<uint64_t>(), set_rand ? 1 : 0, (c->has_carry_override || !continues) ? 1 : 0, c->has_carry_override ? c->carry_override : 0};
+    const ChainSet ch{c->d_chain.get<uint64_t>(), run.rand_base != DWGSIM_HIP_RAND_CHAIN ? 1 : 0, (c->has_carry_override || !continues) ? 1 : 0, c->has_carry_override ? c->carry_override : 0};
     c->has_carry_override = false; c->chain_contig = r_last->contig; c->chain_next_ii = r_last->first_ii + r_last->n_pairs;
     if (sl.ranges.data() != r) sl.ranges.assign(r, r + n);
     return ch;
 }
 
 // The enqueue step: [chain set] -> launch_init -> k_simulate -> abort-rule epilogue -> [k_gzip] -> counters to the slot's pinned mirror -> event
-static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P, const ChainSet &ch, uint64_t rand_base, bool rerun)
+static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P, const ChainSet &ch, const SimRun &run)
 {
-    Slot &sl = c->slot[slot]; SimArgs &a = L.a; const SimForm &f = L.f;
-    const uint64_t n_pairs = L.n_pairs; const uint32_t nblk = L.nblk;
+    Slot &sl = c->slot[slot]; SimArgs &a = L.a; const SimForm &f = L.f; uint64_t *cnt = sl.counters.dev();
+    const uint64_t n_pairs = L.n_pairs, rand_base = run.rand_base; const uint32_t nblk = L.nblk;
     for (int t = 0; t < N_STREAMS; ++t) sl.out_bytes[t] = sl.gz_bytes[t] = 0;
     sl.n_pairs = n_pairs; sl.empty = n_pairs == 0;
     if (n_pairs == 0) { if (ch.set_rand || ch.set_carry) launch_chain_set(c->stream.get(), ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry); return DWGSIM_HIP_OK; }
@@ -2077,21 +2077,21 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
     memcpy(sl.h_segs.get(), L.segs.data(), P.segs);
     HIPC(c, hipMemcpyAsync(sl.segs.get(), sl.h_segs.get(), P.segs, hipMemcpyHostToDevice, c->stream.get()));
     a.segs = sl.segs.get<SimSeg>(); a.n_seg = (int32_t)L.segs.size(); a.n_blocks = nblk; a.n_pairs = n_pairs; a.chain = ch.words; a.lb_shift = P.lb_shift;
-    a.meta = c->meta.get<uint32_t>(); a.block_rand = c->block_rand.get<uint32_t>(); a.counters = sl.counters.dev();
+    a.meta = c->meta.get<uint32_t>(); a.block_rand = c->block_rand.get<uint32_t>(); a.counters = cnt;
     for (int t = 0; t < 3; ++t) a.out[t] = c->out[slot][t].get<uint8_t>();
     for (int j = 0; j < 4; ++j) a.status[j] = f.split ? nullptr : c->status_all.get<uint64_t>() + (size_t)j * (size_t)nblk;
     if (f.split) { a.split_state = c->split_state.get<uint32_t>(); a.split_hand = c->split_hand.get<uint32_t>(); a.split_agg = c->split_agg.get<uint32_t>(); a.split_pre = c->split_pre.get<uint64_t>(); a.split_chunk = c->split_chunk.get<uint64_t>(); }
     if (P.scratch) { a.flow_scratch = c->flow_scratch.get<uint32_t>(); a.flow_free = c->flow_free.get<uint64_t>(); a.flow_slots = P.flow_slots; }
     sl.group = c->handles[(size_t)L.g->first_handle].group;
     // one operation in front of the kernel: counters, look-back words (the four arrays are contiguous), the scratch slots' free lists, the running values
-    launch_init(c->stream.get(), sl.counters.dev(), (uint32_t)N_COUNTERS, a.status[0], f.split ? 0 : 4 * (uint64_t)nblk, a.flow_free, a.flow_free ? 256 + 8 * (uint64_t)nblk : 0,
+    launch_init(c->stream.get(), cnt, (uint32_t)N_COUNTERS, a.status[0], f.split ? 0 : 4 * (uint64_t)nblk, a.flow_free, a.flow_free ? 256 + 8 * (uint64_t)nblk : 0,
                 ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry);
     HIPC(c, hipEventRecord(sl.ev_k0.get(), c->stream.get()));
     c->dbg.sim_form = (int64_t)f.nthr << 20 | f.lpp << 16 | f.out << 12 | f.dt << 8 | f.wr << 4 | f.split;
     if (!launch_simulate(c->stream.get(), a, f)) { c->err = "simulate: no k_simulate instance for this form"; return DWGSIM_HIP_ERR_FAILED; }
     HIPC(c, hipEventRecord(sl.ev_k1.get(), c->stream.get()));
     sl.cap_mult = c->flow_cap_mult;
-    if (!rerun) launch_failrule(c->stream.get(), a.meta, n_pairs, opens, c->fail_summ.get<uint64_t>(), sl.counters.dev(), c->d_chain.get<uint64_t>());
+    if (!run.again) launch_failrule(c->stream.get(), a.meta, n_pairs, opens, c->fail_summ.get<uint64_t>(), cnt, c->d_chain.get<uint64_t>());
     if (P.cap[3]) {
         // The truth step (dw_truth.hpp): this batch's alignments as SAM text, replayed from what the launch left.  It reads meta, which belongs to the CONTEXT, not
         // to the slot -- the next batch's k_simulate overwrites it -- and the slot's FASTQ text and counters: all of it is safe because the step runs on the
@@ -2101,29 +2101,28 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
         t.lpp = f.lpp; t.bfast = a.p.has_bwa ? 0 : 1; t.prefix_len = c->read_prefix.empty() ? 0 : (int32_t)c->read_prefix.size() + 1; t.qname_max = P.t_qname_max;
         for (int q = 0; q < (t.bfast ? 1 : f.lpp); ++q) {
             const int st = t.bfast ? 2 : q;
-            t.src[q] = a.out[st]; t.src_bytes[q] = &sl.counters.dev()[text_len_counter(st)]; t.src_cap[q] = P.cap[st];
+            t.src[q] = a.out[st]; t.src_bytes[q] = &cnt[text_len_counter(st)]; t.src_cap[q] = P.cap[st];
             t.nl_count[q] = c->t_nl[q].get<uint32_t>(); t.rec[q] = c->t_rec[q].get<uint32_t>(); t.n_rec[q] = t.bfast ? n_pairs * (uint64_t)f.lpp : n_pairs;
         }
         t.ends = c->t_ends.get<TruthEnd>(); t.line_len = c->t_len.get<uint32_t>(); t.blk = c->t_blk.get<uint32_t>();
-        t.out = c->out[slot][3].get<uint8_t>(); t.cap = P.cap[3]; t.total = &sl.counters.dev()[text_len_counter(3)];
-        t.md = c->truth_md ? 1 : 0; t.ref = L.g->mem.d_ref.get(); t.fit = &sl.counters.dev()[TRUTH_FIT_COUNTER];
+        t.out = c->out[slot][3].get<uint8_t>(); t.cap = P.cap[3]; t.total = &cnt[text_len_counter(3)];
+        t.md = c->truth_md ? 1 : 0; t.ref = L.g->mem.d_ref.get(); t.fit = &cnt[TRUTH_FIT_COUNTER];
         launch_truth(c->stream.get(), a, t);
         HIPC(c, hipEventRecord(sl.ev_t1.get(), c->stream.get()));
     }
-    if (c->gzip_on) {      // the .gz form of every stream, enqueued behind the text (lengths are read on the device: counters[4 + t], the SAM's [7])
+    if (c->gzip_on) {      // the .gz form of every stream, enqueued behind the text (lengths are read on the device: gz_src_len_counter)
         HIPC(c, hipMemsetAsync(sl.gz_status.get(), 0, P.gz_status, c->stream.get()));
         size_t off = 0;
         for (int t = 0; t < N_STREAMS; ++t) {
             if (P.cap[t] == 0) continue;
-            // (the tagged SAM may not have fitted its buffer: its gzip takes the length k_truth_scan vouches for, 0 then -- dwgsim_hip_wait runs the batch again)
-            launch_gzip(c->stream.get(), c->out[slot][t].get<uint8_t>(), &sl.counters.dev()[t == 3 && c->truth_md ? TRUTH_FIT_COUNTER : text_len_counter(t)], P.cap[t], sl.gz_out[t].get<uint8_t>(), P.gz_cap[t], sl.gz_status.get<uint64_t>() + off, &sl.counters.dev()[28 + t], &sl.counters.dev()[24 + t], &sl.counters.dev()[2],
-                        c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
+            launch_gzip(c->stream.get(), c->out[slot][t].get<uint8_t>(), &cnt[gz_src_len_counter(t, c->truth_md)], P.cap[t], sl.gz_out[t].get<uint8_t>(), P.gz_cap[t], sl.gz_status.get<uint64_t>() + off,
+                        &cnt[gz_ticket_counter(t)], &cnt[gz_len_counter(t)], &cnt[STATUS_COUNTER], c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
             off += P.gz_chunks[t];
         }
     }
     HIPC(c, hipEventRecord(sl.ev_end.get(), c->stream.get()));
     HIPC(c, hipGetLastError());
-    HIPC(c, hipMemcpyAsync(sl.counters.host(), sl.counters.dev(), N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPC(c, hipMemcpyAsync(sl.counters.host(), cnt, N_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream.get()));
     HIPC(c, hipEventRecord(sl.ev_done.get(), c->stream.get()));
     sl.pending = true;
     return DWGSIM_HIP_OK;
@@ -2131,29 +2130,52 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
 
 // Enqueue one batch on the compute stream: resolve -> plan -> reserve -> chain -> enqueue.  Every buffer the batch needs is in place before anything
 // is enqueued or the chain state moves, so a failing call leaves the context as it found it.
-// rerun: the batch of this slot once more with larger Ion Torrent read buffers (dwgsim_hip_wait).  Nothing of the chain moves: the random reads and
-// the failed attempts of a batch do not depend on the flow model, so the first run's epilogue stands; the kernels start from the chain words the
-// first run started from (rand_base = its counters[22]).
-static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t rand_base, int slot, bool rerun)
+static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, int slot, const SimRun &run)
 {
     if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS) { if (c) c->err = "bad simulate arguments"; return DWGSIM_HIP_ERR_ARG; }
     if (c->slot[slot].pending) { c->err = "simulate: the slot still holds a batch that was not waited for"; return DWGSIM_HIP_ERR_STATE; }
     Launch L;
     if (const int rc = sim_resolve(c, r, n, L)) return rc;
     HIPC(c, hipSetDevice(c->device));
-    const SimPlan P = sim_plan(c, L);
+    const SimPlan P = sim_plan(c, L, run);
     if (P.too_many) { c->err = "too many pairs in one call"; return DWGSIM_HIP_ERR_ARG; }
     if (L.n_pairs) { if (const int rc = sim_reserve(c, slot, P)) return rc; }
     // ---- nothing below fails for want of memory ----
-    return sim_launch(c, slot, L, P, sim_chain(c, c->slot[slot], r, n, rand_base != DWGSIM_HIP_RAND_CHAIN, rerun), rand_base, rerun);
+    return sim_launch(c, slot, L, P, sim_chain(c, c->slot[slot], r, n, run), run);
 }
 
-int dwgsim_hip_simulate_ranges_async(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t rand_base, int slot) { return sim_enqueue(c, r, n, rand_base, slot, false); }
+int dwgsim_hip_simulate_ranges_async(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, uint64_t rand_base, int slot) { return sim_enqueue(c, r, n, slot, SimRun{rand_base, false, 0}); }
 
 int dwgsim_hip_simulate_async(dwgsim_hip_ctx_t *c, int contig, uint64_t first_ii, uint64_t n_pairs, uint64_t rand_base, int slot)
 {
     dwgsim_hip_range_t r; memset(&r, 0, sizeof r); r.contig = contig; r.first_ii = first_ii; r.n_pairs = n_pairs;
     return dwgsim_hip_simulate_ranges_async(c, &r, 1, rand_base, slot);
+}
+
+// The waited-for batch of a slot once more, and the wait for it (dwgsim_hip_wait: larger flow buffers, or truth_bytes of room for the truth SAM).  The abort
+// rule's epilogue does not run again, so what it left in the block is kept across the run: its segment, verdict and carry, and the chain base the run starts from.
+static int sim_rerun(dwgsim_hip_ctx_t *c, int slot, uint64_t truth_bytes)
+{
+    static const int kept[7] = {fail_seg_counter(0), fail_seg_counter(1), fail_seg_counter(2), fail_seg_counter(3), ABORT_COUNTER, CARRY_COUNTER, CHAIN_BASE_COUNTER};
+    Slot &sl = c->slot[slot]; uint64_t *h = sl.counters.host();
+    uint64_t keep[7]; for (int q = 0; q < 7; ++q) keep[q] = h[kept[q]];
+    if (const int rc = sim_enqueue(c, sl.ranges.data(), (int)sl.ranges.size(), slot, SimRun{h[CHAIN_BASE_COUNTER], true, truth_bytes})) return rc;
+    HIPC(c, hipEventSynchronize(sl.ev_done.get())); sl.pending = false;
+    for (int q = 0; q < 7; ++q) h[kept[q]] = keep[q];
+    return DWGSIM_HIP_OK;
+}
+
+// What the counter block of a finished batch says: DWGSIM_HIP_OK, or the error and its message.  Blame goes in this order; a bit that is none of the later rungs' counts as used-up attempts.
+static int batch_verdict(dwgsim_hip_ctx_t *c, const uint64_t *h)
+{
+    const uint64_t st = h[STATUS_COUNTER];
+    if (st & REGIONS_BIT) { c->err = "dwgsim-hip: no fragment placement satisfied the target regions (-x) after 2^20 tries (the reference would not terminate)\n"; return DWGSIM_HIP_ERR_FAILED; }
+    if (st & FLOW_ROOM_BIT) { c->err = "dwgsim-hip: a read outgrew its buffer (or degenerated) in the flow-error model\n"; return DWGSIM_HIP_ERR_FAILED; }
+    if ((st & ~(GZIP_ROOM_BIT | TRUTH_ERR_BIT | TRUTH_ROOM_BIT)) || h[ABORT_COUNTER]) return fail_attempts(c);
+    if (st & GZIP_ROOM_BIT) { c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
+    if (st & TRUTH_ERR_BIT) { c->err = "dwgsim-hip: the truth SAM could not be made (a read's record or alignment could not be replayed)\n"; return DWGSIM_HIP_ERR_FAILED; }
+    if (st & TRUTH_ROOM_BIT) { c->err = "dwgsim-hip: the truth SAM did not fit its buffer\n"; return DWGSIM_HIP_ERR_FAILED; }
+    return DWGSIM_HIP_OK;
 }
 
 int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
@@ -2166,68 +2188,44 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipEventSynchronize(sl.ev_done.get()));
     sl.pending = false;
-    uint64_t *h = sl.counters.host();
-    if ((h[2] & 2) && !(h[2] & ~(2ull | 8ull)) && c->prm.data_type == 2) {
-        // a read outgrew its flow-space buffers: the reference doubles them and goes on (dwgsim.c:296-311); here the batch runs again with twice the
-        // capacity (kept for the rest of the job).  Its random reads and failed attempts are settled before the flow model runs, so the chain words
-        // the epilogue of the first run has already moved on stand; the second run starts from the ones the first started from (counters[22]).
-        uint64_t keep[8]; for (int q = 0; q < 6; ++q) keep[q] = h[16 + q];
-        const uint64_t base = h[22];
-        while (h[2] & 2) {
+    const uint64_t *h = sl.counters.host();
+    if ((h[STATUS_COUNTER] & FLOW_ROOM_BIT) && !(h[STATUS_COUNTER] & ~(FLOW_ROOM_BIT | GZIP_ROOM_BIT)) && c->prm.data_type == 2) {
+        // a read outgrew its flow-space buffers: the reference doubles them and goes on, without end (dwgsim.c:296-311); here the batch runs again with twice
+        // the capacity (kept for the rest of the job), up to FLOW_CAP_MAX bases per read -- two thousand times a 400-base read, in scratch slots whose number
+        // shrinks as they grow (sim_plan; the retired 16 x limit: DESIGN.md §4, Ion Torrent)
+        while (h[STATUS_COUNTER] & FLOW_ROOM_BIT) {
             if (sl.cap_mult >= c->flow_cap_mult) {      // (another batch may have doubled it already)
-                // the reference doubles without end (dwgsim.c:296-311); here up to FLOW_CAP_MAX bases per read -- two thousand times a 400-base read, in
-                // scratch slots whose number shrinks as they grow (sim_plan; the retired 16 x limit: DESIGN.md §4, Ion Torrent)
                 if ((int64_t)flow_base_capacity(c) * (int64_t)c->flow_cap_mult * 2 > (int64_t)FLOW_CAP_MAX) break;
                 c->flow_cap_mult *= 2;
             }
-            if (const int rc = sim_enqueue(c, sl.ranges.data(), (int)sl.ranges.size(), base, slot, true)) return rc;
-            HIPC(c, hipEventSynchronize(sl.ev_done.get()));
-            sl.pending = false;
+            if (const int rc = sim_rerun(c, slot, 0)) return rc;
         }
-        for (int q = 0; q < 6; ++q) h[16 + q] = keep[q];
     }
-    if ((h[2] & TRUTH_ROOM_BIT) && !(h[2] & ~TRUTH_ROOM_BIT) && !h[20]) {      // (nothing else went wrong: the first run's gzip took none of the SAM, TruthArgs::fit)
+    if (h[STATUS_COUNTER] == TRUTH_ROOM_BIT && !h[ABORT_COUNTER]) {      // (nothing else went wrong: the first run's gzip took none of the SAM, TruthArgs::fit)
         // The tagged truth SAM did not fit its planned buffer (sim_plan: MD has no bound in the read length).  The scan left the exact size in its counter, so the
-        // batch runs once more with that much room, the way an Ion Torrent batch does above: nothing of the chain moves, and the abort rule's words of the first
-        // run stand.  Record and line offsets are 32-bit words: a batch whose SAM would pass 4 GiB is refused.
+        // batch runs once more with that much room.  Record and line offsets are 32-bit words: a batch whose SAM would pass 4 GiB is refused.
         const uint64_t need = h[text_len_counter(3)];
         if (need + 64 >= (1ull << 32)) { c->err = "dwgsim-hip: the truth SAM of one batch would pass 4 GiB with its MD strings (deletions are spelled out): use smaller batches\n"; return DWGSIM_HIP_ERR_UNSUP; }
-        uint64_t keep[6]; for (int q = 0; q < 6; ++q) keep[q] = h[16 + q];
-        const uint64_t base = h[22];
-        c->truth_need = need;
-        const int rc = sim_enqueue(c, sl.ranges.data(), (int)sl.ranges.size(), base, slot, true);
-        c->truth_need = 0;
-        if (rc) return rc;
-        HIPC(c, hipEventSynchronize(sl.ev_done.get()));
-        sl.pending = false;
+        if (const int rc = sim_rerun(c, slot, need)) return rc;
         ++c->dbg.truth_reruns;
-        for (int q = 0; q < 6; ++q) h[16 + q] = keep[q];
-        if (h[2] & TRUTH_ROOM_BIT) { c->err = "dwgsim-hip: the truth SAM did not fit the room its own scan asked for\n"; return DWGSIM_HIP_ERR_FAILED; }
+        if (h[STATUS_COUNTER] & TRUTH_ROOM_BIT) { c->err = "dwgsim-hip: the truth SAM did not fit the room its own scan asked for\n"; return DWGSIM_HIP_ERR_FAILED; }
     }
-    if (h[2] & 4) { c->err = "dwgsim-hip: no fragment placement satisfied the target regions (-x) after 2^20 tries (the reference would not terminate)\n"; return DWGSIM_HIP_ERR_FAILED; }
-    if (h[2] & 2) { c->err = "dwgsim-hip: a read outgrew its buffer (or degenerated) in the flow-error model\n"; return DWGSIM_HIP_ERR_FAILED; }
-    if ((h[2] & ~(8ull | TRUTH_ERR_BIT | TRUTH_ROOM_BIT)) || h[20]) {      // one pair used up its 10 001 attempts, or the counter of failed attempts over the pairs of the contig passed the limit (dwgsim.c:635, :833-843)
-        char b[128]; snprintf(b, sizeof b, "\r[dwgsim_core] failed to generate a read after %d trials\n", MAX_ATTEMPTS + 1); c->err = b; return DWGSIM_HIP_ERR_FAILED;
-    }
-    if (h[2] & 8) { c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
-    if (h[2] & TRUTH_ERR_BIT) { c->err = "dwgsim-hip: the truth SAM could not be made (a read's record or alignment could not be replayed)\n"; return DWGSIM_HIP_ERR_FAILED; }
-    if (h[2] & TRUTH_ROOM_BIT) { c->err = "dwgsim-hip: the truth SAM did not fit its buffer\n"; return DWGSIM_HIP_ERR_FAILED; }
-    for (int t = 0; t < N_STREAMS; ++t) { sl.out_bytes[t] = h[text_len_counter(t)]; sl.gz_bytes[t] = h[24 + t]; }
+    if (const int rc = batch_verdict(c, h)) return rc;
+    for (int t = 0; t < N_STREAMS; ++t) { sl.out_bytes[t] = h[text_len_counter(t)]; sl.gz_bytes[t] = h[gz_len_counter(t)]; }
     if (!c->truth_on) sl.out_bytes[3] = sl.gz_bytes[3] = 0;
     if (c->dbg.phases) {   // only meaningful with the -DDW_PHASE_TIMING build (tools/phase_profile.sh)
-        uint64_t tot = 0; for (int k = 0; k < 8; ++k) tot += h[8 + k];
+        uint64_t tot = 0; for (int k = 0; k < N_PHASES; ++k) tot += h[phase_counter(k)];
         fprintf(stderr, "[phases]");
-        for (int k = 0; k < 8; ++k) fprintf(stderr, " p%d=%.1f%%", k, tot ? 100.0 * h[8 + k] / tot : 0.0);
+        for (int k = 0; k < N_PHASES; ++k) fprintf(stderr, " p%d=%.1f%%", k, tot ? 100.0 * h[phase_counter(k)] / tot : 0.0);
         fprintf(stderr, " (ticks %llu)\n", (unsigned long long)tot);
     }
     if (out) {
-        out->n_pairs = sl.n_pairs; out->n_random = h[3]; out->n_retries = h[1];
-        for (int t = 0; t < 3; ++t) { out->bytes[t] = sl.out_bytes[t]; out->dev_ptr[t] = c->out[slot][t].get(); }
-        for (int t = 0; t < 3; ++t) out->gz_bytes[t] = sl.gz_bytes[t];
+        out->n_pairs = sl.n_pairs; out->n_random = h[RANDOM_COUNTER]; out->n_retries = h[RETRY_COUNTER];
+        for (int t = 0; t < 3; ++t) { out->bytes[t] = sl.out_bytes[t]; out->gz_bytes[t] = sl.gz_bytes[t]; out->dev_ptr[t] = c->out[slot][t].get(); }
         if (sl.out_bytes[3]) { float ms = 0; HIPC(c, hipEventElapsedTime(&ms, sl.ev_t0.get(), sl.ev_t1.get())); c->dbg.truth_us = 1e3 * ms; }
         out->sam_bytes = sl.out_bytes[3]; out->sam_gz_bytes = sl.gz_bytes[3]; out->sam_dev_ptr = sl.out_bytes[3] ? c->out[slot][3].get() : nullptr;
-        for (int t = 0; t < 4; ++t) out->fail_seg[t] = h[16 + t];
-        out->fail_carry = h[21];
+        for (int t = 0; t < 4; ++t) out->fail_seg[t] = h[fail_seg_counter(t)];
+        out->fail_carry = h[CARRY_COUNTER];
         HIPC(c, hipEventElapsedTime(&out->sim_kernel_ms, sl.ev_k0.get(), sl.ev_k1.get()));
         HIPC(c, hipEventElapsedTime(&out->kernel_ms, sl.ev_k0.get(), sl.ev_end.get()));       // ... with the abort-rule epilogue and the gzip kernels
     }
@@ -2294,11 +2292,12 @@ void dwgsim_hip_host_free(void *p)
     munmap(r.base, r.len);
 }
 
+static bool is_slot_stream(const dwgsim_hip_ctx_t *c, int slot, int stream) { return c && slot >= 0 && slot < DWGSIM_HIP_SLOTS && stream >= 0 && stream < N_STREAMS && (stream != DWGSIM_HIP_STREAM_SAM || c->truth_on); }      // (no SAM stream while the truth SAM is off)
 // Copies on the context's second stream: a batch that is being copied out of one slot overlaps with the kernels filling the other.  gz: the
 // stream's gzip members instead of its text.
 static int fetch_async(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap, bool gz)
 {
-    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream >= N_STREAMS || (stream == DWGSIM_HIP_STREAM_SAM && !c->truth_on) || (!host_dst && cap)) { if (c) c->err = "bad fetch arguments"; return DWGSIM_HIP_ERR_ARG; }
+    if (!is_slot_stream(c, slot, stream) || (!host_dst && cap)) { if (c) c->err = "bad fetch arguments"; return DWGSIM_HIP_ERR_ARG; }
     Slot &sl = c->slot[slot];
     if (sl.pending) { c->err = "fetch: wait for the batch first (its sizes are not known yet)"; return DWGSIM_HIP_ERR_STATE; }
     HIPC(c, hipSetDevice(c->device));
@@ -2376,7 +2375,7 @@ int dwgsim_hip_fetch_wait(dwgsim_hip_ctx_t *c, int slot)
 
 int dwgsim_hip_fetch(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, size_t cap)
 {
-    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream >= N_STREAMS || (stream == DWGSIM_HIP_STREAM_SAM && !c->truth_on) || (!host_dst && cap)) return DWGSIM_HIP_ERR_ARG;
+    if (!is_slot_stream(c, slot, stream) || (!host_dst && cap)) return DWGSIM_HIP_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
     Slot &sl = c->slot[slot];
     if (sl.pending) { c->err = "fetch: wait for the batch first (its sizes are not known yet)"; return DWGSIM_HIP_ERR_STATE; }
@@ -2409,15 +2408,15 @@ int dwgsim_hip_fetch(dwgsim_hip_ctx_t *c, int slot, int stream, void *host_dst, 
 // Test / analysis hook (not part of the drop-in surface): occurrences of `byte` in one finished stream of a waited-for slot, counted on the device.
 int dwgsim_hip_debug_count_byte(dwgsim_hip_ctx_t *c, int slot, int stream, int byte, uint64_t *count)
 {
-    if (!c || slot < 0 || slot >= DWGSIM_HIP_SLOTS || stream < 0 || stream >= N_STREAMS || (stream == DWGSIM_HIP_STREAM_SAM && !c->truth_on) || !count) return DWGSIM_HIP_ERR_ARG;
+    if (!is_slot_stream(c, slot, stream) || !count) return DWGSIM_HIP_ERR_ARG;
     HIPC(c, hipSetDevice(c->device));
     Slot &sl = c->slot[slot];
     if (sl.pending) { c->err = "count_byte: wait for the batch first"; return DWGSIM_HIP_ERR_STATE; }
-    HIPC(c, hipMemsetAsync(&c->counters.dev()[15], 0, sizeof(uint64_t), c->stream.get()));
-    if (sl.out_bytes[stream]) launch_count_byte(c->stream.get(), c->out[slot][stream].get<uint8_t>(), sl.out_bytes[stream], (uint32_t)(byte & 0xff), &c->counters.dev()[15]);
-    HIPC(c, hipMemcpyAsync(&c->counters.host()[15], &c->counters.dev()[15], sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream.get()));
+    HIPC(c, hipMemsetAsync(&c->counters.dev()[COUNT_BYTE_COUNTER], 0, sizeof(uint64_t), c->stream.get()));
+    if (sl.out_bytes[stream]) launch_count_byte(c->stream.get(), c->out[slot][stream].get<uint8_t>(), sl.out_bytes[stream], (uint32_t)(byte & 0xff), &c->counters.dev()[COUNT_BYTE_COUNTER]);
+    HIPC(c, hipMemcpyAsync(&c->counters.host()[COUNT_BYTE_COUNTER], &c->counters.dev()[COUNT_BYTE_COUNTER], sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream.get()));
     HIPC(c, hipStreamSynchronize(c->stream.get()));
-    *count = c->counters.host()[15];
+    *count = c->counters.host()[COUNT_BYTE_COUNTER];
     return DWGSIM_HIP_OK;
 }
 
@@ -2442,7 +2441,7 @@ int dwgsim_hip_debug_gzip(dwgsim_hip_ctx_t *c, const void *text, size_t n, void 
         launch_gzip(c->stream.get(), d_text, &d_aux[0], n, d_out, gcap, &d_aux[4], &d_aux[1], &d_aux[2], &d_aux[3], c->d_crc_table.get<uint32_t>(), c->d_crc_shift.get<uint32_t>());
         uint64_t res[4] = {0, 0, 0, 0};
         ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(res, d_aux, sizeof res, hipMemcpyDeviceToHost, c->stream.get()) == hipSuccess && hipStreamSynchronize(c->stream.get()) == hipSuccess;
-        if (ok && (res[3] & 8)) { c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
+        if (ok && (res[3] & GZIP_ROOM_BIT)) { c->err = "dwgsim-hip: the gzip output buffer is too small for this text\n"; return DWGSIM_HIP_ERR_FAILED; }
         if (ok && res[2] > cap) { c->err = "debug_gzip: destination too small"; return DWGSIM_HIP_ERR_ARG; }
         if (ok) { ok = hipMemcpy(out, d_out, (size_t)res[2], hipMemcpyDeviceToHost) == hipSuccess; *out_n = (size_t)res[2]; }
     }

@@ -155,7 +155,7 @@ struct CalibArgs {
     uint64_t gap_r; int32_t gap_s;  // ... and what the gaps between scoring first draws are computed with (flow_gap_params)
     const uint8_t *flow; int32_t flow_len, lds_words, stack_words;       // flow: 64 bytes of flow order + the log2 table (flow_log2_table)       // lds_words: words per lane of the read buffer (16 bases each)
     uint32_t *scratch;              // per block [lds_words][PAIRS_PER_BLOCK] words
-    uint64_t *counters;             // [8] += errors, [9] += read lengths after errors, [2] |= 2 on a buffer overflow
+    uint64_t *counters;             // the context's counter block (the layout in front of SimArgs): CALIB_ERR_COUNTER, CALIB_LEN_COUNTER, FLOW_ROOM_BIT
 };
 
 constexpr int SUMM_CELLS = 64;          // cells per haplotype-summary word (k_summarize / k_place)
@@ -179,6 +179,61 @@ struct SimSeg {
     uint32_t pad_;
 };
 
+// ---- The counter block: N_COUNTERS u64 words through which kernels report to the host (SimArgs::counters, CalibArgs::counters). ----
+// Three blocks exist, and a word's meaning depends on which one holds it:
+//   slot     one per batch in flight (dw_host.cpp Slot::counters): k_simulate, the abort-rule epilogue, the truth step, k_gzip
+//   place    dwgsim_hip_ctx::pcounters: k_place, k_place_rest, k_range_counts (dwgsim_hip_count_random_ranges)
+//   context  dwgsim_hip_ctx::counters: k_calibrate and dwgsim_hip_debug_count_byte
+// Every block is zeroed in front of the kernels that write it and copied whole to its page-locked mirror behind them.
+constexpr int N_COUNTERS = 32;
+constexpr int N_STREAMS = 4;        // output streams of a batch: the three FASTQ streams and the truth SAM (DWGSIM_HIP_STREAM_SAM)
+constexpr int N_PHASES = 8;         // phase clocks of the analysis build (tools/probe/dw_probe.hpp)
+constexpr int STATUS_COUNTER = 2;            // every block: the *_BIT values below, OR-ed in
+constexpr int TICKET_COUNTER = 0;            // slot: block ticket of the single kernel
+constexpr int RETRY_COUNTER = 1;             // slot, place: failed attempts
+constexpr int RANDOM_COUNTER = 3;            // slot, place: random reads of the launch
+constexpr int text_len_counter(int t) { return t < 3 ? 4 + t : 7; }      // slot: text bytes of stream t (the truth SAM had to take the word behind the FASTQ streams')
+constexpr int phase_counter(int k) { return 8 + k; }                     // slot, analysis build only: shader-clock ticks of phase k < N_PHASES
+constexpr int fail_seg_counter(int q) { return 16 + q; }                 // slot: the abort rule's segment of this batch, q = 0..3: P, S, R, bad (dw_simulate.hip FailSeg)
+constexpr int ABORT_COUNTER = 20;            // slot: the abort rule's verdict
+constexpr int CARRY_COUNTER = 21;            // slot: the abort rule's carry out
+constexpr int CHAIN_BASE_COUNTER = 22;       // slot: SimArgs::chain[0] as the batch found it (a second run of the batch starts from it: dw_host.cpp sim_rerun)
+constexpr int TRUTH_FIT_COUNTER = 23;        // slot: the bytes of a tagged truth SAM that its gzip may read (TruthArgs::fit)
+constexpr int gz_len_counter(int t) { return 24 + t; }                   // slot: gzip bytes of stream t
+constexpr int gz_ticket_counter(int t) { return 28 + t; }                // slot: chunk ticket of stream t's gzip
+// where the gzip of stream t reads the length of its text: the tagged SAM may not have fitted its buffer, so its gzip takes what k_truth_scan vouches for
+constexpr int gz_src_len_counter(int t, bool truth_md) { return t == 3 && truth_md ? TRUTH_FIT_COUNTER : text_len_counter(t); }
+// Aliases, on purpose: the same numbers as slot words above, in blocks that never hold those.
+constexpr int PLACE_OPEN_COUNTER = 5;        // place: pairs k_place left to k_place_rest (= text_len_counter(1): k_place writes no text)
+constexpr int CALIB_ERR_COUNTER = 8;         // context: k_calibrate's errors (= phase_counter(0): the phase clocks are k_simulate's, which never gets this block)
+constexpr int CALIB_LEN_COUNTER = 9;         // context: ... and its read lengths after errors (= phase_counter(1): likewise)
+constexpr int COUNT_BYTE_COUNTER = 15;       // context: dwgsim_hip_debug_count_byte's result (= phase_counter(7): likewise; it zeroes and fetches this word alone, so a calibration's words stand)
+// The bits of STATUS_COUNTER (unsigned long long: what atomicOr takes)
+constexpr unsigned long long ATTEMPTS_BIT = 1;        // slot, place: a pair used up its MAX_ATTEMPTS
+constexpr unsigned long long FLOW_ROOM_BIT = 2;       // slot, context: a read of the flow model outgrew its buffer (the batch runs again with twice the capacity)
+constexpr unsigned long long REGIONS_BIT = 4;         // slot, place: no placement inside the target regions (-x) after 2^20 tries
+constexpr unsigned long long GZIP_ROOM_BIT = 8;       // slot: a gzip member did not fit (GzArgs::flags)
+constexpr unsigned long long PLACE_ROOM_BIT = 16;     // place: a list of k_place overflowed (the count runs again with room for every pair)
+constexpr unsigned long long TRUTH_ERR_BIT = 32;      // slot: a line of the truth SAM could not be made
+constexpr unsigned long long TRUTH_ROOM_BIT = 64;     // slot, tagged lines only: a line would end behind the buffer (the batch runs again with the room the scan asked for)
+// no two words of a block are the same, none lies behind the block (so the per-stream families overlap neither each other nor 16 .. 23)
+constexpr bool counter_claim(uint32_t &seen, int w) { if (w < 0 || w >= N_COUNTERS || (seen >> w & 1u)) return false; seen |= 1u << w; return true; }
+constexpr bool slot_counters_ok()
+{
+    uint32_t seen = 0;
+    bool ok = counter_claim(seen, TICKET_COUNTER) && counter_claim(seen, RETRY_COUNTER) && counter_claim(seen, STATUS_COUNTER) && counter_claim(seen, RANDOM_COUNTER) && counter_claim(seen, ABORT_COUNTER) &&
+              counter_claim(seen, CARRY_COUNTER) && counter_claim(seen, CHAIN_BASE_COUNTER) && counter_claim(seen, TRUTH_FIT_COUNTER);
+    for (int k = 0; k < N_PHASES; ++k) ok = ok && counter_claim(seen, phase_counter(k));
+    for (int q = 0; q < 4; ++q) ok = ok && counter_claim(seen, fail_seg_counter(q));
+    for (int t = 0; t < N_STREAMS; ++t) ok = ok && counter_claim(seen, text_len_counter(t)) && counter_claim(seen, gz_len_counter(t)) && counter_claim(seen, gz_ticket_counter(t));
+    return ok;
+}
+constexpr bool place_counters_ok() { uint32_t seen = 0; return counter_claim(seen, RETRY_COUNTER) && counter_claim(seen, STATUS_COUNTER) && counter_claim(seen, RANDOM_COUNTER) && counter_claim(seen, PLACE_OPEN_COUNTER); }
+constexpr bool context_counters_ok() { uint32_t seen = 0; return counter_claim(seen, STATUS_COUNTER) && counter_claim(seen, CALIB_ERR_COUNTER) && counter_claim(seen, CALIB_LEN_COUNTER) && counter_claim(seen, COUNT_BYTE_COUNTER); }
+static_assert(slot_counters_ok(), "slot block: two words collide or one lies behind N_COUNTERS");
+static_assert(place_counters_ok(), "place block: two words collide or one lies behind N_COUNTERS");
+static_assert(context_counters_ok(), "context block: two words collide or one lies behind N_COUNTERS");
+
 struct SimArgs {
     SimParams p;
     HapDev hap[2];                 // the group (pointers at group coordinate 0)
@@ -200,7 +255,7 @@ struct SimArgs {
     const uint8_t *rand_fixed; int32_t rand_fixed_len;   // "[prefix_]rand"
     uint32_t *meta;                // per pair: failed attempts | contig start << 30 | random read << 31 (input of the abort rule, k_failrule)
     uint32_t *block_rand;          // per 128-pair block: random pairs (k_place), then exclusive prefix (k_scan)
-    uint64_t *counters;            // this batch's slot: [0] ticket, [1] retries, [2] fail flags, [3] total random, [4..6] stream bytes, [16..19] abort-rule segment of the batch, [20] abort, [21] carry out
+    uint64_t *counters;            // the counter block above: this batch's slot (k_simulate) or the place block (k_place)
     uint64_t *status[4];           // look-back words: record bytes of stream BWA1 / BWA2, random-read count, (SOLiD) BFAST bytes
     uint8_t *out[3];               // packed FASTQ text: bwa read1, bwa read2, bfast
     int32_t lds_words;             // uint32 words of packed bases per lane: 8 bases per word; Ion Torrent: 16 per word, the flow model's one in-place buffer
@@ -230,8 +285,6 @@ struct SimArgs {
 // One read end between the length pass and the write pass: the cells lo .. hi of its contig that it is aligned to (both give a base of their own), the
 // inserted bases in front of lo's / behind hi's base where the read stopped inside an insertion, the characters of its CIGAR
 constexpr uint32_t TRUTH_F_RAND = 1, TRUTH_F_REV = 2, TRUTH_F_HAP2 = 4, TRUTH_F_BAD = 8;      // a random read; the reverse strand; haplotype 2; no line (the replay or the record index failed)
-constexpr uint64_t TRUTH_ERR_BIT = 32;                // SimArgs::counters[2]: a line could not be made
-constexpr uint64_t TRUTH_ROOM_BIT = 64;               // SimArgs::counters[2], tagged lines only: a line would end behind the buffer (the batch runs again with the room the scan asked for)
 struct TruthEnd { int32_t lo, hi; uint32_t lead, tail, flags, cigar, nm, md; };      // nm, md (dwgsim_hip_set_truth_md, else 0): the value of NM and the characters of the MD string
 struct TruthArgs {
     int32_t lpp, bfast;             // read ends per pair; 1: the names and reads come from the one interleaved BFAST stream (-o 2), 0: from the BWA stream of each end

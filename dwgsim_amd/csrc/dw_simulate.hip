@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(PLACE_PAIRS) k_place(SimArgs a)
         const uint32_t at = base + (uint32_t)__popcll(om & ((1ull << lane) - 1ull));
         if (open) {
             if (at < a.place_list_cap) a.place_list[(size_t)li * a.place_list_cap + at] = blockIdx.x * (uint32_t)PLACE_PAIRS + (uint32_t)tid;
-            else atomicOr((unsigned long long *)&a.counters[2], 16ull);                             // (a list overflowed: the host runs the count again with room for every pair)
+            else atomicOr((unsigned long long *)&a.counters[STATUS_COUNTER], PLACE_ROOM_BIT);                             // (a list overflowed: the host runs the count again with room for every pair)
         }
     }
     __syncthreads();
@@ -192,25 +192,25 @@ __global__ void __launch_bounds__(128) k_place_rest(SimArgs a)
                 bool is_rand, failed; uint32_t att;
                 place_pair_exact(a, sc, key, sg->first_ii + pair, is_rand, failed, att);
                 if (is_rand) atomicAdd((unsigned long long *)&a.range_rand[s], 1ull);
-                if (failed) atomicOr((unsigned long long *)&a.counters[2], 1ull);
+                if (failed) atomicOr((unsigned long long *)&a.counters[STATUS_COUNTER], ATTEMPTS_BIT);
                 retries = att;
                 todo = false;
             }
         }
         const uint32_t rs = wave_sum_u32(retries);
-        if (lane == 0 && rs) atomicAdd((unsigned long long *)&a.counters[1], (unsigned long long)rs);
+        if (lane == 0 && rs) atomicAdd((unsigned long long *)&a.counters[RETRY_COUNTER], (unsigned long long)rs);
     }
 }
 
-// random reads per range: what k_place counted per block (block_rand, scanned: exclusive prefix; total in counters[3]) + what k_place_rest added
+// random reads per range: what k_place counted per block (block_rand, scanned: exclusive prefix; total in RANDOM_COUNTER) + what k_place_rest added
 __global__ void __launch_bounds__(256) k_range_counts(SimArgs a)
 {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     if (q >= (uint32_t)a.n_seg) return;
     const SegPtr sg = as_constant(a.segs);
-    const uint64_t lo = a.block_rand[sg[q].first_block], hi = q + 1 < (uint32_t)a.n_seg ? (uint64_t)a.block_rand[sg[q + 1].first_block] : a.counters[3];
+    const uint64_t lo = a.block_rand[sg[q].first_block], hi = q + 1 < (uint32_t)a.n_seg ? (uint64_t)a.block_rand[sg[q + 1].first_block] : a.counters[RANDOM_COUNTER];
     a.range_rand[q] += hi - lo;
-    if (q == 0) { uint64_t open = 0; for (int li = 0; li < PLACE_LISTS; ++li) open += a.place_list_n[16 * li]; a.counters[5] = open; }      // (how many pairs took the long path: analysis)
+    if (q == 0) { uint64_t open = 0; for (int li = 0; li < PLACE_LISTS; ++li) open += a.place_list_n[16 * li]; a.counters[PLACE_OPEN_COUNTER] = open; }      // (how many pairs took the long path: analysis)
 }
 #endif // DW_HAS(0): k_place
 
@@ -491,7 +491,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
     const int wave = tid >> 6, lane = tid & 63;
     DW_PROBE_INIT();
     if (GS && tid == 0) { s_slot = scratch_slot_take(a.flow_free, (uint32_t)a.flow_slots, a.n_blocks); asm volatile("" ::: "memory"); }      // (before the ticket: see scratch_slot_take)
-    if (SPLIT == 0 && tid == 0) s_ticket = (uint32_t)atomicAdd((unsigned long long *)&a.counters[0], 1ull);
+    if (SPLIT == 0 && tid == 0) s_ticket = (uint32_t)atomicAdd((unsigned long long *)&a.counters[TICKET_COUNTER], 1ull);
     if (SPLIT != 1) for (int q = tid; q < 32; q += nthr) s_fixed[1][q] = reinterpret_cast<const uint32_t *>(a.rand_fixed)[q];      // buffers are padded to 256 + 16 bytes
     if (ION && tid < 64) s_ft.flow[tid] = a.flow[tid];
     if (!ION && SPLIT != 2) for (int q = tid; q < FLOW_LG_ENTRIES; q += nthr) s_lg[q] = reinterpret_cast<const uint32_t *>(a.flow + 64)[q];
@@ -571,20 +571,20 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
         if (LPP == 2) { const int other = __shfl_xor((int)ok, 1); ok = ok && (other != 0); }   // every lane shuffles
         if (!done) {
             if (ok) done = true;
-            else if (++att > (uint32_t)MAX_ATTEMPTS) { atomicOr((unsigned long long *)&a.counters[2], 1ull); done = true; }
+            else if (++att > (uint32_t)MAX_ATTEMPTS) { atomicOr((unsigned long long *)&a.counters[STATUS_COUNTER], ATTEMPTS_BIT); done = true; }
         }
     }
     DW_PROBE_MARKF(a, 5);    // (fine) the extraction of the last attempt, leaving the loop
     // failed attempts and outcome of the pair, and whether it opens its contig: input of the abort rule (k_failrule)
     if (valid && j == 0) a.meta[pair] = att | (is_rand ? 0x80000000u : 0u) | ((sg->contig_start && pair_in == 0) ? 0x40000000u : 0u);
-    { const uint32_t retries = wave_sum_u32((valid && j == 0) ? att : 0u); if (lane == 0 && retries) atomicAdd((unsigned long long *)&a.counters[1], (unsigned long long)retries); }
+    { const uint32_t retries = wave_sum_u32((valid && j == 0) ? att : 0u); if (lane == 0 && retries) atomicAdd((unsigned long long *)&a.counters[RETRY_COUNTER], (unsigned long long)retries); }
     // running random-read index (dwgsim.c:1042,1096): look-back over the blocks' random counts + rank inside the block
     if (H == 0 && !ONE_LB) {
     { const uint32_t v[1] = {(is_rand && j == 0) ? 1u : 0u}; uint32_t ex[1], tot[1]; block_excl_scan_n<1>(v, sm_rand, ex, tot); rrank = ex[0]; rtot = tot[0]; }
     DW_PROBE_MARKF(a, 6);    // (fine) the block scan of the random reads
     if (wave == 0) {
         const uint64_t g = probe::off(128) ? (uint64_t)t * 6 : lookback_excl(a.status[2], t, rtot, 0);
-        if (lane == 0) { s_rbase = g; if (t + 1 == a.n_blocks) a.counters[3] = g + rtot; }
+        if (lane == 0) { s_rbase = g; if (t + 1 == a.n_blocks) a.counters[RANDOM_COUNTER] = g + rtot; }
     }
     }
     // (the barrier that publishes s_rbase comes after the error phase, which does not need the index: the look-back's latency
@@ -599,7 +599,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
         const int so = flow_errors(flows, rg, s_ft, a.flow_len, (j ? a.e_thr[1] : a.e_thr[0])[0], j ? a.flow_gap_r[1] : a.flow_gap_r[0], j ? a.flow_gap_s[1] : a.flow_gap_s[0], lds, flow_stk, nthr, 2 * a.flow_stack_words, s, j ? pd.strand1 : pd.strand0, capb, &n_err);
         if (flows) {
             s_out = so;
-            if (s_out < 0) { atomicOr((unsigned long long *)&a.counters[2], 2ull); s_out = 0; }
+            if (s_out < 0) { atomicOr((unsigned long long *)&a.counters[STATUS_COUNTER], FLOW_ROOM_BIT); s_out = 0; }
             flow_reversed = (j ? pd.strand1 : pd.strand0) != 0;     // the read is turned back while it is written (dwgsim.c:408-414)
         }
     }
@@ -695,7 +695,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
     }
     // (Ion Torrent: a read the flow model gave up on emits nothing, which the arithmetic offsets of the two-kernel form do not allow for -- and the batch
     // is run again or fails as a whole (dw_host.cpp dwgsim_hip_wait): nothing is written for it)
-    if (ION && H == 2 && (a.counters[2] & 2ull)) return;
+    if (ION && H == 2 && (a.counters[STATUS_COUNTER] & FLOW_ROOM_BIT)) return;
     if (H == 2) {
         const uint4 hm = reinterpret_cast<const uint4 *>(a.split_hand)[(size_t)t * nthr + tid];
         rr.ext_coor = (int32_t)hm.x; n_err = (int32_t)(hm.y & 0xffffu); rr.n_sub = (int32_t)(hm.y >> 16); rr.n_indel = (int32_t)(hm.z & 0xffffu); rr.n_ins = (int32_t)(hm.z >> 16);
@@ -784,7 +784,7 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
             eb += LPP == 2 ? h1 + h2 : h1; Tb = tot[NS - 1] + (LPP == 2 ? 2u : 1u) * htot;
             Gb_one = s_base[2] + (LPP == 2 ? 2ull : 1ull) * hex_before;
         }
-        if (tid == nthr - 1 && t + 1 == a.n_blocks) a.counters[3] = base_r + rtot;
+        if (tid == nthr - 1 && t + 1 == a.n_blocks) a.counters[RANDOM_COUNTER] = base_r + rtot;
     } else
     if (BF_SCAN) {
         const uint32_t Lbf = !emits ? 0u : DT == 1 ? (1u + fixed_len + tail_len + 1u + 1u + 2u * (uint32_t)s_out + 3u + 1u) : Lbwa - 2u;
@@ -827,9 +827,9 @@ __global__ void __launch_bounds__(NTHR, sim_min_waves(OUT, DT, NTHR, WR, SPLIT))
     if (H == 0 && tid == nthr - 1) {
         if (t + 1 == a.n_blocks) {
             const uint64_t nreads = a.n_pairs * (uint64_t)((a.p.len[1] > 0) ? 2 : 1);
-            a.counters[4] = a.p.has_bwa ? G1 + T1 : 0;
-            a.counters[5] = a.p.has_bwa ? G2 + T2 : 0;
-            a.counters[6] = !a.p.has_bfast ? 0 : BF_SCAN ? (ONE_LB ? Gb_one : s_base[2]) + Tb : G1 + T1 + G2 + T2 - 2 * nreads;
+            a.counters[text_len_counter(0)] = a.p.has_bwa ? G1 + T1 : 0;
+            a.counters[text_len_counter(1)] = a.p.has_bwa ? G2 + T2 : 0;
+            a.counters[text_len_counter(2)] = !a.p.has_bfast ? 0 : BF_SCAN ? (ONE_LB ? Gb_one : s_base[2]) + Tb : G1 + T1 + G2 + T2 - 2 * nreads;
         }
     }
 
@@ -1234,7 +1234,7 @@ void launch_selftest_fp64(hipStream_t st, uint32_t seed, uint64_t n, uint64_t *m
 // Exclusive sums over the logical blocks of {random pairs, bytes of stream 1, bytes of stream 2} (agg, 16 bytes per block: the byte counts
 // without the hexadecimal digits of random reads' names), in two small kernels.  k_split_scan1: a block per 1024 logical blocks -- their sums
 // scanned inside the chunk -> pre[4 t .. 4 t + 2], the chunk's totals -> chunk[4 c ..].  k_split_scan2 (one wave): the chunk totals scanned ->
-// chunk[4 c ..] = sums in front of chunk c, and the launch's totals into counters[3 .. 6] as the single kernel leaves them.  The second half
+// chunk[4 c ..] = sums in front of chunk c, and the launch's totals into RANDOM_COUNTER and text_len_counter(0 .. 2) as the single kernel leaves them.  The second half
 // adds pre + chunk and the digits (split_offsets below).
 __global__ void __launch_bounds__(1024) k_split_scan1(SimArgs a)
 {
@@ -1270,10 +1270,10 @@ __global__ void __launch_bounds__(64) k_split_scan2(SimArgs a, int lpp)
     if (threadIdx.x == 0) {
         const uint64_t H = hex_digits_sum(a.chain[0], run[0]), G1 = run[1] + H, G2 = run[2] + (lpp == 2 ? H : 0ull);
         const uint64_t nreads = a.n_pairs * (uint64_t)((a.p.len[1] > 0) ? 2 : 1);
-        a.counters[3] = run[0];
-        a.counters[4] = a.p.has_bwa ? G1 : 0;
-        a.counters[5] = a.p.has_bwa ? G2 : 0;
-        a.counters[6] = !a.p.has_bfast ? 0 : G1 + G2 - 2 * nreads;
+        a.counters[RANDOM_COUNTER] = run[0];
+        a.counters[text_len_counter(0)] = a.p.has_bwa ? G1 : 0;
+        a.counters[text_len_counter(1)] = a.p.has_bwa ? G2 : 0;
+        a.counters[text_len_counter(2)] = !a.p.has_bfast ? 0 : G1 + G2 - 2 * nreads;
     }
 }
 
@@ -1311,11 +1311,11 @@ DW_DEV FailSeg failseg_wave_join(FailSeg x, int cnt)
 }
 constexpr int FAIL_PAIRS_PER_THREAD = 64;
 // A: thread = 64 consecutive pairs, block = 256 threads; one FailSeg per block into summ[4 * block .. +4).  A batch without a single
-// failed attempt (counters[1] == 0, the usual case) is summarised by B from the counters alone.
+// failed attempt (RETRY_COUNTER == 0, the usual case) is summarised by B from the counters alone.
 __global__ void __launch_bounds__(256) k_failrule_a(const uint32_t *__restrict__ meta, uint64_t n_pairs, const uint64_t *__restrict__ counters, uint64_t *__restrict__ summ)
 {
     __shared__ FailSeg seg[4];
-    if (counters[1] == 0) return;
+    if (counters[RETRY_COUNTER] == 0) return;
     const uint64_t first = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * FAIL_PAIRS_PER_THREAD;
     FailSeg s{0, 0, 0, 0};                                          // the neutral element: nothing failed, no reset (also what a thread past the end holds)
     for (int q4 = 0; q4 < FAIL_PAIRS_PER_THREAD && first + q4 < n_pairs; q4 += 4) {       // 16-byte loads (meta is padded to a multiple of four entries)
@@ -1342,12 +1342,12 @@ __global__ void __launch_bounds__(256) k_failrule_a(const uint32_t *__restrict__
     }
 }
 // B, the batch epilogue (one wave): the block summaries are joined in order (64 lanes stage them through LDS, lane 0 joins) into the
-// segment of this batch alone -> counters[16..19]; behind the carry of the earlier batches (chain[1]) that gives the verdict
-// counters[20] = abort? and the carry out counters[21] = chain[1]; the running random-read count chain[0] moves on by counters[3].
+// segment of this batch alone -> fail_seg_counter(0 .. 3); behind the carry of the earlier batches (chain[1]) that gives the verdict
+// ABORT_COUNTER = abort? and the carry out CARRY_COUNTER = chain[1]; the running random-read count chain[0] moves on by RANDOM_COUNTER.
 __global__ void __launch_bounds__(64) k_failrule_b(const uint64_t *__restrict__ summ, uint32_t n_blocks, uint64_t n_pairs, uint32_t opens_contig, uint64_t *__restrict__ counters, uint64_t *__restrict__ chain)
 {
-    FailSeg t{0, 0, (counters[3] < n_pairs || opens_contig) ? 1u : 0u, 0};          // no failed attempt at all: any genomic read -- or the start of a contig inside the batch -- resets the counter
-    if (counters[1] != 0) {                                       // lane k joins its slice of the block summaries, the wave joins the slices in order
+    FailSeg t{0, 0, (counters[RANDOM_COUNTER] < n_pairs || opens_contig) ? 1u : 0u, 0};          // no failed attempt at all: any genomic read -- or the start of a contig inside the batch -- resets the counter
+    if (counters[RETRY_COUNTER] != 0) {                                       // lane k joins its slice of the block summaries, the wave joins the slices in order
         const uint32_t per = (n_blocks + 63) / 64, b0 = threadIdx.x * per, b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
         FailSeg x{0, 0, 0, 0};
         for (uint32_t b = b0; b < b1; ++b) {
@@ -1359,12 +1359,12 @@ __global__ void __launch_bounds__(64) k_failrule_b(const uint64_t *__restrict__ 
     if (threadIdx.x == 0) {
         const uint64_t carry = chain[1];
         const FailSeg all = failseg_join(FailSeg{carry, carry, 0, 0}, t);
-        counters[16] = t.P; counters[17] = t.S; counters[18] = t.R; counters[19] = t.bad;
-        counters[20] = (all.bad || all.P > (uint64_t)MAX_ATTEMPTS || all.S > (uint64_t)MAX_ATTEMPTS) ? 1 : 0;
-        counters[21] = all.S;
+        counters[fail_seg_counter(0)] = t.P; counters[fail_seg_counter(1)] = t.S; counters[fail_seg_counter(2)] = t.R; counters[fail_seg_counter(3)] = t.bad;
+        counters[ABORT_COUNTER] = (all.bad || all.P > (uint64_t)MAX_ATTEMPTS || all.S > (uint64_t)MAX_ATTEMPTS) ? 1 : 0;
+        counters[CARRY_COUNTER] = all.S;
         chain[1] = all.S;
-        counters[22] = chain[0];      // what this batch's k_simulate started from (a batch is run again when an Ion Torrent read outgrew its buffers: dw_host.cpp)
-        chain[0] += counters[3];
+        counters[CHAIN_BASE_COUNTER] = chain[0];      // what this batch's k_simulate started from (a batch is run again when an Ion Torrent read outgrew its buffers: dw_host.cpp)
+        chain[0] += counters[RANDOM_COUNTER];
     }
 }
 void launch_failrule(hipStream_t st, const uint32_t *meta, uint64_t n_pairs, uint32_t opens_contig, uint64_t *summ, uint64_t *counters, uint64_t *chain)
@@ -1420,13 +1420,13 @@ void launch_count_byte(hipStream_t st, const uint8_t *text, uint64_t n, uint32_t
     hipLaunchKernelGGL(k_count_byte, dim3(4096), dim3(256), 0, st, text, n, byte, out);
 }
 // a.segs / a.n_blocks laid out for PLACE_PAIRS pairs per block; a.block_rand[n_blocks], a.range_rand[n_seg] (zeroed), a.place_list_n (zeroed).
-// Behind it: a.block_rand scanned (exclusive) with its total in a.counters[3], a.range_rand[q] = random reads of range q.
+// Behind it: a.block_rand scanned (exclusive) with its total in RANDOM_COUNTER, a.range_rand[q] = random reads of range q.
 void launch_place(hipStream_t st, const SimArgs &a)
 {
     hipLaunchKernelGGL(k_place, dim3(a.n_blocks), dim3(PLACE_PAIRS), 0, st, a);
     const uint32_t per_list = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, ((uint64_t)a.place_list_cap + 1023) / 1024));      // blocks of 128 lanes per list, sized for a tenth of the capacity in one sweep
     hipLaunchKernelGGL(k_place_rest, dim3(PLACE_LISTS * per_list), dim3(128), 0, st, a);
-    launch_scan_excl(st, a.block_rand, a.n_blocks, &a.counters[3]);
+    launch_scan_excl(st, a.block_rand, a.n_blocks, &a.counters[RANDOM_COUNTER]);
     hipLaunchKernelGGL(k_range_counts, dim3(cdiv((uint64_t)a.n_seg, 256)), dim3(256), 0, st, a);
 }
 void launch_split_scan(hipStream_t st, const SimArgs &a, int lpp)
@@ -1438,7 +1438,7 @@ void launch_split_scan(hipStream_t st, const SimArgs &a, int lpp)
 
 #if DW_HAS(4)      // (k_calibrate stays beside the single-end Ion Torrent instances it has always been compiled with: in another part its code and theirs come out different)
 // -B (dwgsim_opt.c:415-457): lane = one random read of read end a.end pushed through the flow model on the forward strand; the block
-// adds its error and length sums to counters[8], [9].  Draws: bases = narrow words of (D_CALIB + end, read, attempt 0), flow model =
+// adds its error and length sums to CALIB_ERR_COUNTER, CALIB_LEN_COUNTER.  Draws: bases = narrow words of (D_CALIB + end, read, attempt 0), flow model =
 // the streams of (D_CALIB + end, read, attempt 1).  The read buffers (dw_read.hpp flow_errors: a.lds_words words per lane) are in a.scratch.
 __global__ void __launch_bounds__(PAIRS_PER_BLOCK) k_calibrate(CalibArgs a)
 {
@@ -1471,10 +1471,10 @@ __global__ void __launch_bounds__(PAIRS_PER_BLOCK) k_calibrate(CalibArgs a)
     {   // every lane calls (the loops of the model are wave-uniform)
         FlowRng rg; rg.seed = a.seed; rg.contig = 0; rg.dom = dom; rg.att = 1; rg.evt = 0; rg.s = 0; rg.ii = jj; rg.w0 = rg.w1 = rg.w2 = rg.w3 = 0;
         const int so = flow_errors(live, rg, s_ft, a.flow_len, a.thr, a.gap_r, a.gap_s, buf, dyn_lds + tid, nthr, 2 * a.stack_words, a.len, 0, capb, &n_err);
-        if (live) { s_out = so; if (s_out < 0) { atomicOr((unsigned long long *)&a.counters[2], 2ull); s_out = 0; n_err = 0; } }
+        if (live) { s_out = so; if (s_out < 0) { atomicOr((unsigned long long *)&a.counters[STATUS_COUNTER], FLOW_ROOM_BIT); s_out = 0; n_err = 0; } }
     }
     const uint32_t es = wave_sum_u32((uint32_t)n_err), ls = wave_sum_u32((uint32_t)s_out);
-    if ((tid & 63) == 0) { atomicAdd((unsigned long long *)&a.counters[8], (unsigned long long)es); atomicAdd((unsigned long long *)&a.counters[9], (unsigned long long)ls); }
+    if ((tid & 63) == 0) { atomicAdd((unsigned long long *)&a.counters[CALIB_ERR_COUNTER], (unsigned long long)es); atomicAdd((unsigned long long *)&a.counters[CALIB_LEN_COUNTER], (unsigned long long)ls); }
 }
 void launch_calibrate(hipStream_t st, const CalibArgs &a)
 {

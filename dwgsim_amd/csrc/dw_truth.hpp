@@ -305,7 +305,7 @@ __global__ void __launch_bounds__(SIM_THREADS) k_truth_len(SimArgs a, TruthArgs 
             }
         }
     }
-    if (!ok) { E.flags |= TRUTH_F_BAD; atomicOr((unsigned long long *)&a.counters[2], (unsigned long long)TRUTH_ERR_BIT); }
+    if (!ok) { E.flags |= TRUTH_F_BAD; atomicOr((unsigned long long *)&a.counters[STATUS_COUNTER], TRUTH_ERR_BIT); }
     t.ends[L.e] = E;
 }
 // The bytes of a line.  FLAG, PNEXT and TLEN need the mate's record, so the lengths are taken by a pass of their own behind k_truth_len: one lane per read end again
@@ -397,7 +397,7 @@ __global__ void __launch_bounds__(SIM_THREADS) k_truth_write(SimArgs a, TruthArg
     if ((me.flags | mate.flags) & TRUTH_F_BAD) return;
     const uint32_t len = truth_line_bytes<MD>(a, t, L, me, mate);
     const uint64_t off = (uint64_t)t.blk[blockIdx.x] + t.line_len[L.e];
-    if (off + len > t.cap) { atomicOr((unsigned long long *)&a.counters[2], (unsigned long long)(MD ? TRUTH_ROOM_BIT : TRUTH_ERR_BIT)); return; }
+    if (off + len > t.cap) { atomicOr((unsigned long long *)&a.counters[STATUS_COUNTER], MD ? TRUTH_ROOM_BIT : TRUTH_ERR_BIT); return; }
     const uint32_t s = (uint32_t)(L.j ? a.p.len[1] : a.p.len[0]);
     const bool rnd = (me.flags & TRUTH_F_RAND) != 0, rev = !rnd && (me.flags & TRUTH_F_REV);
     Writer o; o.init(t.out + off);

@@ -49,6 +49,10 @@ def test_second_run_forced(emu_lib):
     M.check_second_run_forced(emu_lib)
 
 
+def test_second_run_leaves_no_trace(emu_lib):
+    M.check_second_run_leaves_no_trace(emu_lib)
+
+
 def test_second_run_with_gzip(emu_lib):
     M.check_second_run_gzip(emu_lib)
 

@@ -50,6 +50,10 @@ def test_second_run_forced(lib):
     M.check_second_run_forced(lib)
 
 
+def test_second_run_leaves_no_trace(lib):
+    M.check_second_run_leaves_no_trace(lib)
+
+
 def test_second_run_with_gzip(lib):
     M.check_second_run_gzip(lib)
 

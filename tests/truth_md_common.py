@@ -270,9 +270,9 @@ def check_batch_shapes(lib):
     assert b"".join(g["sam"] for g in got["batches"]) == whole.truth_sam and got["reruns"] == 0
 
 
-def two_slots(lib, force):
-    """two batches in two slots, the second enqueued before the first was waited for, its random-read count chained on the device.  force: None, "both" or "first":
-    which of them are planned with a truth_cap far too small"""
+def two_slots(lib, force, in_turn=False, cap=3000):
+    """two batches in two slots, the second enqueued before the first was waited for (in_turn: only after it, so after its second run where it takes one), its
+    random-read count chained on the device.  force: None, "both" or "first": which of them are planned with a truth_cap far too small"""
     contigs = shape_contigs()
     p = api.parse_flags(SHAPE_FLAGS, lib)
     with api.Context(p, 0, lib) as ctx:
@@ -282,18 +282,20 @@ def two_slots(lib, force):
         ctx.mutate(h0)
         na, nb = sched[0][3], sched[1][3]
         if force:
-            ctx.debug_option("truth_cap", 3000)
+            ctx.debug_option("truth_cap", cap)
         ctx.simulate_ranges_async([(h0, 0, 100)], 0, 1)
+        first = ctx.wait(1) if in_turn else None
+        reruns_first = ctx.debug_get("truth_reruns")
         if force == "first":
             ctx.debug_option("truth_cap", -1)
         ctx.simulate_ranges_async([(h0, 100, na - 100), (h0 + 1, 0, nb)], api.RAND_CHAIN, 2)
         out = []
         for slot in (1, 2):
-            b = ctx.wait(slot)
+            b = first if in_turn and slot == 1 else ctx.wait(slot)
             out.append(dict(n_pairs=b.n_pairs, n_random=b.n_random, n_retries=b.n_retries, fail_seg=tuple(b.fail_seg), fail_carry=b.fail_carry,
                             fastq=[ctx.fetch(slot, s, b.bytes[s]) for s in range(3)], sam=ctx.fetch(slot, api.STREAM_SAM, b.sam_bytes)))
             assert ctx.count_byte(slot, api.STREAM_SAM, 10) == 2 * b.n_pairs
-        return dict(batches=out, reruns=ctx.debug_get("truth_reruns"))
+        return dict(batches=out, reruns=ctx.debug_get("truth_reruns"), reruns_first=reruns_first)
 
 
 # ---- 6. the second run ----
@@ -313,6 +315,18 @@ def check_second_run_forced(lib):
     # the tags off: "truth_cap" forces nothing, and no second run happens
     off = api.run_job(api.parse_flags(SHAPE_FLAGS, lib), contigs, lib=lib, truth_sam=True, group_bp=1 << 30, debug_options={"truth_cap": 4096})
     assert off.truth_reruns == 0 and off.truth_sam == api.run_job(api.parse_flags(SHAPE_FLAGS, lib), contigs, lib=lib, truth_sam=True, group_bp=1 << 30).truth_sam
+
+
+def check_second_run_leaves_no_trace(lib):
+    """a batch that takes the second run, and only then a batch on the other slot of the same context without the forced cap: the room the first one's scan asked
+    for is its own.  The later batch is the larger one, so planned with that room it would run twice as well; planned as usual it runs once, and both batches
+    are those of a context that never ran anything again"""
+    base = two_slots(lib, None, in_turn=True)
+    got = two_slots(lib, "first", in_turn=True, cap=4096)
+    assert base["reruns_first"] == 0 and base["reruns"] == 0
+    assert got["reruns_first"] == 1 and got["reruns"] == 1
+    assert len(got["batches"][1]["sam"]) > len(got["batches"][0]["sam"]) > 4096
+    assert got["batches"] == base["batches"] == two_slots(lib, None)["batches"]
 
 
 def check_second_run_gzip(lib):

@@ -3,7 +3,7 @@
 //                       time means something): 1 no text assembly at all, 2 text assembled but not stored, 4 no error tests, 8 no base
 //                       extraction, 16 no header, 64 producers kept alive but no assembly, 256 no first draws of the flow model, 1024 no
 //                       pass 2 of the flow model, 4096 first draws made but none scores; further bits: tools/knockout_build.sh
-//   -DDW_PHASE_TIMING   per wave, shader-clock ticks spent in each phase of k_simulate are added to counters[8 + phase]
+//   -DDW_PHASE_TIMING   per wave, shader-clock ticks spent in each phase of k_simulate are added to the phase_counter words of the batch (dw_kernels.hpp)
 // Found first by the builds of tools/knockout_build.sh and tools/phase_profile.sh (-Itools/probe); never by the product build or the tests.
 #pragma once
 #ifndef DW_KNOCK
@@ -17,7 +17,7 @@ template <class T, class... R> __device__ __forceinline__ void keep(const T &v, 
 } }
 #ifdef DW_PHASE_TIMING
 #define DW_PROBE_INIT() uint64_t ph_t = __builtin_amdgcn_s_memtime()
-#define DW_PROBE_MARK_(args, k) do { const uint64_t ph_n = __builtin_amdgcn_s_memtime(); if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)&(args).counters[8 + (k)], (unsigned long long)(ph_n - ph_t)); ph_t = ph_n; } while (0)
+#define DW_PROBE_MARK_(args, k) do { const uint64_t ph_n = __builtin_amdgcn_s_memtime(); if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)&(args).counters[dw::phase_counter(k)], (unsigned long long)(ph_n - ph_t)); ph_t = ph_n; } while (0)
 #ifdef DW_PHASE_FINE
 // the fine split of what happens in front of the text: the coarse marks 3 .. 6 (name lengths + look-backs 2-3, header, sequence, quality) are ONE phase (4), mark 2 becomes 3 = the
 // barrier behind the error phase (the wait for wave 0's look-back of the random-read index), and the fine marks take 5 = the last attempt's extraction + leaving the attempt loop,
