@@ -6,6 +6,7 @@ back to a CPU implementation: if the library or a HIP device is missing it raise
 """
 from __future__ import annotations
 import ctypes as C
+import gzip
 import os
 import shlex
 from dataclasses import dataclass, field
@@ -87,6 +88,8 @@ EXPORTS = [
     "dwgsim_hip_eval_debug_time", "dwgsim_hip_eval_debug_device_chunk", "dwgsim_hip_eval_bam_begin", "dwgsim_hip_eval_feed_bam",
     "dwgsim_hip_eval_debug_device_bam_chunk", "dwgsim_hip_eval_debug_inflate",
     "dwgsim_hip_eval_set_breakdown", "dwgsim_hip_eval_breakdown_text",
+    "dwgsim_hip_eval_truth_header", "dwgsim_hip_eval_truth_feed", "dwgsim_hip_eval_truth_commit", "dwgsim_hip_eval_truth_text",
+    "dwgsim_hip_eval_debug_truth_slots",
     "dwgsim_hip_haplotype_fasta", "dwgsim_hip_haplotype_layout", "dwgsim_hip_haplotype_fetch", "dwgsim_hip_job_set_haplotype_sink",
     "dwgsim_hip_debug_sim_instances",
     "dwgsim_hip_set_truth_sam", "dwgsim_hip_truth_sam_header", "dwgsim_hip_job_set_truth_sam",
@@ -879,6 +882,11 @@ def _bind_eval(lib):
     lib.dwgsim_hip_eval_debug_inflate.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(C.c_double), P(C.c_uint64)]
     lib.dwgsim_hip_eval_set_breakdown.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.dwgsim_hip_eval_breakdown_text.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_size_t)]
+    lib.dwgsim_hip_eval_truth_header.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.dwgsim_hip_eval_truth_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.dwgsim_hip_eval_truth_commit.argtypes = [C.c_void_p]
+    lib.dwgsim_hip_eval_truth_text.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_size_t)]
+    lib.dwgsim_hip_eval_debug_truth_slots.argtypes = [C.c_void_p, C.c_int]
 
 
 def load_eval(path: str | None = None):
@@ -900,6 +908,7 @@ class EvalSummaryResult:
     stderr: bytes            # dwgsim_eval's stderr text
     incorrect: bytes = b""   # -p: the first header and the incorrectly mapped records
     breakdown: dict = field(default_factory=dict)     # "snps=0", "errors=8+", "indels=1+", "end=2", ... -> that stratum's table text
+    truth: bytes = b""       # with a truth: the base-level section (dwgsim_hip_eval_truth_text)
 
 
 class EvalContext:
@@ -941,6 +950,49 @@ class EvalContext:
         if r == 0:
             self._breakdown = bool(dims)
         return r
+
+    def truth_header(self, text: bytes) -> int:
+        """dwgsim_hip_eval_truth_header (the truth SAM's '@' lines): its return value, as for the two calls below"""
+        return self.lib.dwgsim_hip_eval_truth_header(self.ctx, text, len(text))
+
+    def truth_feed(self, buf) -> int:
+        """truth record text, split anywhere"""
+        n = len(buf)
+        return self.lib.dwgsim_hip_eval_truth_feed(self.ctx, buf if isinstance(buf, bytes) else (C.c_char * n).from_buffer_copy(buf), n)
+
+    def truth_commit(self) -> int:
+        """builds the index; 0, or a negative DWGSIM_HIP_ERR_* (last_error() says why)"""
+        return self.lib.dwgsim_hip_eval_truth_commit(self.ctx)
+
+    def last_error(self) -> str:
+        return self.lib.dwgsim_hip_eval_last_error(self.ctx).decode(errors="replace")
+
+    def load_truth(self, truth, read_bytes: int = 8 << 20):
+        """a whole truth SAM (a path or a binary file object; gzip when it starts with 1f 8b): header, feed, commit.  Raises DwgsimError."""
+        f = open(truth, "rb") if isinstance(truth, (str, bytes, os.PathLike)) else truth
+        try:
+            lead = f.read(2)
+            rest = _Chained(lead, f)
+            src = gzip.GzipFile(fileobj=rest, mode="rb") if lead == b"\x1f\x8b" else rest
+            head, fed = b"", False
+            while True:
+                blk = src.read(read_bytes)
+                if not blk:
+                    break
+                if not fed:
+                    head += blk
+                    h, blk = split_sam_header(head)
+                    if not blk:
+                        continue
+                    self._check(self.truth_header(h))
+                    fed = True
+                self._check(self.truth_feed(blk))
+            if not fed:
+                self._check(self.truth_header(head))
+            self._check(self.truth_commit())
+        finally:
+            if f is not truth:
+                f.close()
 
     def _check(self, r: int):
         if r < 0:
@@ -984,6 +1036,8 @@ class EvalContext:
         if self._breakdown:
             self._check(self.lib.dwgsim_hip_eval_breakdown_text(self.ctx, C.byref(txt), C.byref(ln)))
             res.breakdown = split_breakdown(C.string_at(txt, ln.value) if ln.value else b"")
+        self._check(self.lib.dwgsim_hip_eval_truth_text(self.ctx, C.byref(txt), C.byref(ln)))
+        res.truth = C.string_at(txt, ln.value) if ln.value else b""
         return table, res
 
     def debug_time_ms(self) -> float:
@@ -1009,6 +1063,22 @@ class EvalContext:
             pass
 
 
+class _Chained:
+    """a binary reader over some bytes already read and the file they came from"""
+
+    def __init__(self, lead: bytes, f):
+        self.lead, self.f = lead, f
+
+    def read(self, n=-1):
+        if not self.lead:
+            return self.f.read(n)
+        if n is None or n < 0:
+            out, self.lead = self.lead + self.f.read(), b""
+            return out
+        out, self.lead = self.lead[:n], self.lead[n:]
+        return out + (self.f.read(n - len(out)) if len(out) < n else b"")
+
+
 def split_breakdown(text: bytes) -> dict:
     """the sections of dwgsim_hip_eval_breakdown_text: {"snps=0": table text, ...} in the text's order"""
     out, key = {}, None
@@ -1030,12 +1100,15 @@ def split_sam_header(data: bytes):
     return data[:i], data[i:]
 
 
-def eval_sam(paths, device: int = 0, lib=None, chunk_bytes: int = 0, read_bytes: int = 8 << 20, **opts):
+def eval_sam(paths, device: int = 0, lib=None, chunk_bytes: int = 0, read_bytes: int = 8 << 20, truth=None, **opts):
     """dwgsim_eval -S over SAM files (paths, or file objects opened in binary mode): (table_text, EvalSummaryResult).
-    The table is empty after a fatal record (summary.status == 1; summary.stderr says why)."""
+    The table is empty after a fatal record (summary.status == 1; summary.stderr says why).  truth: a truth SAM (path or binary file object,
+    plain or gzip), read completely before the first file; summary.truth is then the base-level section."""
     if isinstance(paths, (str, bytes, os.PathLike)):
         paths = [paths]
     with EvalContext(device, lib, chunk_bytes, **opts) as ctx:
+        if truth is not None:
+            ctx.load_truth(truth, read_bytes)
         for p in paths:
             f = open(p, "rb") if isinstance(p, (str, bytes, os.PathLike)) else p
             try:
@@ -1062,12 +1135,15 @@ def eval_sam(paths, device: int = 0, lib=None, chunk_bytes: int = 0, read_bytes:
         return ctx.finish()
 
 
-def eval_bam(paths, device: int = 0, lib=None, chunk_bytes: int = 0, read_bytes: int = 8 << 20, **opts):
+def eval_bam(paths, device: int = 0, lib=None, chunk_bytes: int = 0, read_bytes: int = 8 << 20, truth=None, **opts):
     """dwgsim_eval over BAM files (paths, or file objects opened in binary mode): (table_text, EvalSummaryResult), as eval_sam.
-    A file that is not a readable BAM file raises DwgsimError, unless a fatal record in front of the damage ends the run first."""
+    A file that is not a readable BAM file raises DwgsimError, unless a fatal record in front of the damage ends the run first.
+    truth: as for eval_sam."""
     if isinstance(paths, (str, bytes, os.PathLike)):
         paths = [paths]
     with EvalContext(device, lib, chunk_bytes, **opts) as ctx:
+        if truth is not None:
+            ctx.load_truth(truth, read_bytes)
         for p in paths:
             f = open(p, "rb") if isinstance(p, (str, bytes, os.PathLike)) else p
             try:

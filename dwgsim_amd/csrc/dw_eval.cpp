@@ -16,6 +16,10 @@
 // Breakdown (set_breakdown; dw_eval.hpp BREAKDOWN).  The same chunks go through the breakdown form of the record kernel, which counts into the
 // strata of the selected dimensions (dw_eval_launch.hpp EvalBdArgs) instead of the one histogram.  finish() makes the main table from the sum of
 // the first selected dimension's strata and one section per stratum; tables, sections and the dimension list are dw_eval_table.hpp's.
+// Truth (truth_header / truth_feed / truth_commit; dw_eval.hpp TRUTH).  Before the first file, truth text fills slot 0; every full slot is cut at
+// its last newline and loaded (truth_chunk: newline kernels, count, scan, write -- each step sized by what the one before produced), commit
+// builds the index and checks it.  With a committed truth the chunks go through the truth form of the record kernel, and every header /
+// bam_begin uploads the map from the file's targets to the truth's contigs (map_contigs).  finish() makes the section from the 64-bit counters.
 // A container error (framing, inflate, CRC, ISIZE, magic, header, a file that ends inside something) first evaluates the whole records in
 // front of it: a fatal record there wins; otherwise the call returns DWGSIM_HIP_ERR_FAILED and last_error says what and where.
 #include <hip/hip_runtime.h>
@@ -24,11 +28,13 @@
 #include <stdio.h>
 #include <string.h>
 #include <time.h>
+#include <algorithm>
 #include <array>
 #include <deque>
 #include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 #include "dw_bam.hpp"
 #include "dw_eval_launch.hpp"
@@ -99,6 +105,20 @@ struct dwgsim_hip_eval_ctx {
     std::vector<uint8_t> zbuf;          // compressed bytes not yet consumed: zbuf[zhead] is byte zpos of the file
     size_t zhead = 0;
     uint64_t zpos = 0;
+    // the truth (dw_eval.hpp TRUTH): its contigs, its records, CIGAR pool and index on the device, the 64-bit counters, its text
+    struct Truth {
+        bool begun = false, fed = false, committed = false, bad = false;
+        std::string names;
+        std::vector<uint32_t> off;
+        std::vector<int32_t> hash;
+        DevMem d_names, d_off, d_hash, d_cnt, d_err;       // (the load's own: freed by commit)
+        ev::Targets tg = {};
+        DevMem d_recs, d_pool, d_slots, d_ctrs, d_tmap;     // TruthRec, u32, u64, u64, i32
+        uint64_t n_recs = 0, n_pool = 0;
+        uint32_t mask = 0;
+        int force_log2 = -1;
+        std::string text;
+    } tr;
     bool in_header = false, bam_stop = false, broken = false;
     std::vector<uint8_t> hdr_bytes;     // inflated bytes while the header is incomplete
     bam::Header bh;
@@ -223,15 +243,25 @@ EvalBdArgs bd_args(dwgsim_hip_eval_ctx *c)
 uint32_t bd_grid(uint32_t plain_grid) { return (plain_grid + 1) / 2; }
 
 // the record kernels of a SAM chunk / a BAM chunk, in the form that the run uses
+EvalTruthArgs truth_args(dwgsim_hip_eval_ctx *c)
+{
+    EvalTruthArgs T;
+    T.slots = c->tr.d_slots.get<unsigned long long>(); T.mask = c->tr.mask; T.recs = c->tr.d_recs.get<ev::TruthRec>(); T.pool = c->tr.d_pool.get<uint32_t>();
+    T.tmap = c->tr.d_tmap.get<int32_t>(); T.ctrs = c->tr.d_ctrs.get<unsigned long long>();
+    return T;
+}
+
 void launch_chunk(dwgsim_hip_eval_ctx *c, hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tiles)
 {
     if (c->bd.on) launch_eval_chunk_bd(st, A, bd_args(c), len, tiles, bd_grid(records_grid(len)));
+    else if (c->tr.committed) launch_eval_chunk_tr(st, A, truth_args(c), len, tiles, records_grid(len));
     else launch_eval_chunk(st, A, len, tiles, records_grid(len));
 }
 
 void launch_bam_chunk(dwgsim_hip_eval_ctx *c, hipStream_t st, const EvalRecArgs &A, uint32_t n_rec)
 {
     if (c->bd.on) launch_eval_bam_chunk_bd(st, A, bd_args(c), bd_grid(bam_records_grid(n_rec)));
+    else if (c->tr.committed) launch_eval_bam_chunk_tr(st, A, truth_args(c), bam_records_grid(n_rec));
     else launch_eval_bam_chunk(st, A, bam_records_grid(n_rec));
 }
 
@@ -406,12 +436,11 @@ int end_file(dwgsim_hip_eval_ctx *c)
     return drain(c);
 }
 
-int build_targets(dwgsim_hip_eval_ctx *c);
-
-int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
+// the SN: names of the @SQ lines of a header text: names[off[t] .. off[t + 1])
+void sq_names(const char *text, size_t len, std::string &names, std::vector<uint32_t> &off)
 {
-    c->names.clear();
-    c->off.assign(1, 0);
+    names.clear();
+    off.assign(1, 0);
     for (size_t p = 0; p < len;) {
         const char *nl = (const char *)memchr(text + p, '\n', len - p);
         const size_t e = nl ? (size_t)(nl - text) : len;
@@ -420,8 +449,8 @@ int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
                 const char *tab = (const char *)memchr(text + f, '\t', e - f);
                 const size_t fe = tab ? (size_t)(tab - text) : e;
                 if (f > p && fe - f >= 3 && !memcmp(text + f, "SN:", 3)) {
-                    c->names.append(text + f + 3, fe - f - 3);
-                    c->off.push_back((uint32_t)c->names.size());
+                    names.append(text + f + 3, fe - f - 3);
+                    off.push_back((uint32_t)names.size());
                     break;
                 }
                 f = fe + 1;
@@ -429,31 +458,60 @@ int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
         }
         p = e + 1;
     }
-    return build_targets(c);
+}
+
+// the open-addressing hash of ev::Targets over such names (a repeated name: the first)
+void hash_names(const std::string &names, const std::vector<uint32_t> &off, std::vector<int32_t> &hash)
+{
+    const int32_t nt = (int32_t)off.size() - 1;
+    uint32_t hs = 2;
+    while (hs < 2u * (uint32_t)nt) hs <<= 1;
+    hash.assign(hs, -1);
+    for (int32_t t = 0; t < nt; ++t) {
+        const uint32_t b = off[t], n = off[t + 1] - b;
+        uint32_t h = ev::fnv1a(names.data() + b, n) & (hs - 1);
+        while (hash[h] >= 0) {
+            const int32_t u = hash[h];
+            if (off[u + 1] - off[u] == n && !memcmp(names.data() + off[u], names.data() + b, n)) break;
+            h = (h + 1) & (hs - 1);
+        }
+        if (hash[h] < 0) hash[h] = t;
+    }
+}
+
+// device copies of names, offsets and hash, and the ev::Targets over them
+int upload_names(dwgsim_hip_eval_ctx *c, const std::string &names, const std::vector<uint32_t> &off, const std::vector<int32_t> &hash, DevMem &d_names,
+                 DevMem &d_off, DevMem &d_hash, ev::Targets *tg)
+{
+    if (const int r = upload(c, d_names, names.data(), names.size() + 1)) return r;
+    if (const int r = upload(c, d_off, off.data(), off.size() * sizeof(uint32_t))) return r;
+    if (const int r = upload(c, d_hash, hash.data(), hash.size() * sizeof(int32_t))) return r;
+    tg->names = d_names.get<char>(); tg->off = d_off.get<uint32_t>(); tg->hash = d_hash.get<int32_t>(); tg->n = (int32_t)off.size() - 1; tg->hmask = (uint32_t)hash.size() - 1;
+    return DWGSIM_HIP_OK;
+}
+
+// with a truth: for every target of the current file the truth contig of the same name, or -1
+int map_contigs(dwgsim_hip_eval_ctx *c)
+{
+    if (!c->tr.committed) return DWGSIM_HIP_OK;
+    const ev::Targets T = {c->tr.names.data(), c->tr.off.data(), c->tr.hash.data(), (int32_t)c->tr.off.size() - 1, (uint32_t)c->tr.hash.size() - 1};
+    std::vector<int32_t> map(c->off.size(), -1);        // (one more than the targets: never empty)
+    for (size_t t = 0; t + 1 < c->off.size(); ++t) map[t] = ev::target_find(T, c->names.data() + c->off[t], c->off[t + 1] - c->off[t]);
+    return upload(c, c->tr.d_tmap, map.data(), map.size() * sizeof(int32_t));
 }
 
 // c->names / c->off (the @SQ names of a SAM header, or the reference list of a BAM file): the hash, and the device copies
 int build_targets(dwgsim_hip_eval_ctx *c)
 {
-    const int32_t nt = (int32_t)c->off.size() - 1;
-    uint32_t hs = 2;
-    while (hs < 2u * (uint32_t)nt) hs <<= 1;
-    c->hash.assign(hs, -1);
-    for (int32_t t = 0; t < nt; ++t) {
-        const uint32_t b = c->off[t], n = c->off[t + 1] - b;
-        uint32_t h = ev::fnv1a(c->names.data() + b, n) & (hs - 1);
-        while (c->hash[h] >= 0) {
-            const int32_t u = c->hash[h];
-            if (c->off[u + 1] - c->off[u] == n && !memcmp(c->names.data() + c->off[u], c->names.data() + b, n)) break;      // a repeated name: the first
-            h = (h + 1) & (hs - 1);
-        }
-        if (c->hash[h] < 0) c->hash[h] = t;
-    }
-    if (const int r = upload(c, c->d_names, c->names.data(), c->names.size() + 1)) return r;
-    if (const int r = upload(c, c->d_off, c->off.data(), c->off.size() * sizeof(uint32_t))) return r;
-    if (const int r = upload(c, c->d_hash, c->hash.data(), hs * sizeof(int32_t))) return r;
-    c->tg.names = c->d_names.get<char>(); c->tg.off = c->d_off.get<uint32_t>(); c->tg.hash = c->d_hash.get<int32_t>(); c->tg.n = nt; c->tg.hmask = hs - 1;
-    return DWGSIM_HIP_OK;
+    hash_names(c->names, c->off, c->hash);
+    if (const int r = upload_names(c, c->names, c->off, c->hash, c->d_names, c->d_off, c->d_hash, &c->tg)) return r;
+    return map_contigs(c);
+}
+
+int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
+{
+    sq_names(text, len, c->names, c->off);
+    return build_targets(c);
 }
 
 // ---- BAM stream ----
@@ -654,6 +712,133 @@ void convert_ctx(dwgsim_hip_eval_ctx *c, int fmt)
     }
 }
 
+// ---- the truth (dw_eval.hpp TRUTH): load, index, text ----
+
+int truth_fail(dwgsim_hip_eval_ctx *c, int rc, const std::string &msg)
+{
+    c->err = msg;
+    c->tr.bad = true;
+    return rc;
+}
+
+// room for `total` elements in a buffer that holds `have`: it doubles, and what it holds moves over
+int truth_room(dwgsim_hip_eval_ctx *c, DevMem &buf, uint64_t have, uint64_t total, size_t elem, const char *what)
+{
+    if (total * elem <= buf.cap()) return DWGSIM_HIP_OK;
+    DevMem nb;
+    const uint64_t twice = std::max<uint64_t>(2 * have, 4096);
+    // (while it copies, the old and the new buffer exist side by side: up to three times the bytes held)
+    if (nb.reserve(1, std::max(total, twice) * elem) != hipSuccess) {
+        (void)hipGetLastError();        // the doubled size did not fit: the exact one may
+        if (nb.reserve(1, total * elem) != hipSuccess) {
+            (void)hipGetLastError();
+            nb.reset();
+        }
+    }
+    if (!nb) {
+        return truth_fail(c, DWGSIM_HIP_ERR_NOMEM, std::string("truth: the ") + what + " do not fit in device memory");
+    }
+    if (have) CK(hipMemcpy(nb.get(), buf.get(), have * elem, hipMemcpyDeviceToDevice));
+    buf = std::move(nb);
+    return DWGSIM_HIP_OK;
+}
+
+const char *truth_line_error(int code)
+{
+    switch (code) {
+    case ev::T_E_FIELDS: return "has fewer than 11 fields";
+    case ev::T_E_FORMAT: return "is not a truth record (QNAME, FLAG, POS or the end bits of FLAG)";
+    case ev::T_E_POS: return "is mapped at POS 0";
+    case ev::T_E_RNAME: return "has an RNAME that is not one of the truth's @SQ names";
+    default: return "has a CIGAR that is no sequence of M, I and D runs with a query base";
+    }
+}
+
+// the whole lines h_text[0, cut) of slot 0: newline kernels, then count, scan and write, each sized by what the step before it produced
+int truth_chunk(dwgsim_hip_eval_ctx *c, size_t cut)
+{
+    Slot &S = c->s[0];
+    auto &T = c->tr;
+    hipStream_t st = S.st.get();
+    EvalRes *hres = S.h_res.get<EvalRes>(), *dres = S.d_res.get<EvalRes>();
+    *hres = EvalRes{~0ull, 0, 0, 0};
+    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get(), cut, hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(dres, hres, sizeof(EvalRes), hipMemcpyHostToDevice, st));
+    launch_eval_newlines(st, S.d_text.get(), cut, S.d_tiles.get<uint32_t>(), dres, S.d_ends.get<uint32_t>());
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(hres, dres, sizeof(EvalRes), hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    const uint32_t n = hres->n_lines;
+    if (!n) return DWGSIM_HIP_OK;
+    if (T.n_recs + n > 0xFFFFFFFEull) return truth_fail(c, DWGSIM_HIP_ERR_ARG, "truth: more than 2^32 - 2 records");
+    if (const int r = truth_room(c, T.d_recs, T.n_recs, T.n_recs + n, sizeof(ev::TruthRec), "records")) return r;
+    if (T.d_cnt.reserve((size_t)n * sizeof(uint32_t), (size_t)n * sizeof(uint32_t)) != hipSuccess || T.d_err.reserve(8, 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return truth_fail(c, DWGSIM_HIP_ERR_NOMEM, "truth: the records do not fit in device memory");
+    }
+    EvalTruthLoadArgs L;
+    L.text = S.d_text.get(); L.ends = S.d_ends.get<uint32_t>(); L.n_lines = n; L.cnt = T.d_cnt.get<uint32_t>(); L.tg = T.tg;
+    L.recs = T.d_recs.get<ev::TruthRec>() + T.n_recs; L.pool = nullptr; L.pool_base = (uint32_t)T.n_pool; L.err = T.d_err.get<unsigned long long>();
+    CK(hipMemsetAsync(T.d_err.get(), 0xff, 8, st));
+    launch_truth_load(st, L, dres);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(hres, dres, sizeof(EvalRes), hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    unsigned long long bad = 0;
+    CK(hipMemcpy(&bad, T.d_err.get(), 8, hipMemcpyDeviceToHost));
+    if (bad != ~0ull) {
+        char buf[64];
+        snprintf(buf, sizeof buf, "truth: record line %llu ", (unsigned long long)(T.n_recs + (bad >> 8) + 1));
+        return truth_fail(c, DWGSIM_HIP_ERR_FAILED, std::string(buf) + truth_line_error((int)(bad & 0xff)));
+    }
+    const uint32_t words = hres->n_lines;       // (k_eval_scan leaves its total there)
+    if (T.n_pool + words > 0xFFFFFFFFull) return truth_fail(c, DWGSIM_HIP_ERR_ARG, "truth: more than 2^32 - 1 CIGAR operations outside single M runs");
+    if (const int r = truth_room(c, T.d_pool, T.n_pool, T.n_pool + words, sizeof(uint32_t), "CIGAR operations")) return r;
+    L.pool = T.d_pool.get<uint32_t>();
+    launch_truth_write(st, L);
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(st));
+    T.n_recs += n; T.n_pool += words;
+    return DWGSIM_HIP_OK;
+}
+
+int truth_state(dwgsim_hip_eval_ctx *c)
+{
+    if (!c || c->finished || c->begun || c->tr.committed) return DWGSIM_HIP_ERR_STATE;
+    if (c->tr.bad) return DWGSIM_HIP_ERR_FAILED;
+    if (c->bd.on) {
+        c->err = "a breakdown and a truth in one context are not supported";
+        return DWGSIM_HIP_ERR_ARG;
+    }
+    return hipSetDevice(c->device) == hipSuccess ? DWGSIM_HIP_OK : DWGSIM_HIP_ERR_DEVICE;
+}
+
+// the truth section of the output from the 64-bit counters (dw_eval_launch.hpp)
+std::string truth_text(const std::vector<unsigned long long> &k)
+{
+    std::string s;
+    for (int st = 0; st < 2; ++st) {
+        s += st ? "## truth indel\n" : "## truth all\n";
+        s += "# mapq\tmissing\trandom\tunusable\tcompared\texact\tbases\tright\tclipped\tibases\tiright\n";
+        unsigned long long cum[EVAL_TR_COLS] = {0};
+        bool any = false;
+        auto row = [&](int q) {
+            s += std::to_string(q);
+            for (unsigned long long v : cum) s += '\t' + std::to_string(v);
+            s += '\n';
+        };
+        for (int q = 255; q >= 0; --q) {
+            const unsigned long long *r = &k[(size_t)(st * 256 + q) * EVAL_TR_COLS];
+            if (!(r[TC_MISSING] + r[TC_RANDOM] + r[TC_UNUSABLE] + r[TC_COMPARED])) continue;
+            any = true;
+            for (int j = 0; j < EVAL_TR_COLS; ++j) cum[j] += r[j];
+            row(q);
+        }
+        if (!any) row(0);
+    }
+    return s;
+}
+
 // the main table of a plain run: the spill lists' counts and the window h
 void format_table(dwgsim_hip_eval_ctx *c, const std::vector<unsigned long long> &h)
 {
@@ -723,6 +908,10 @@ dwgsim_hip_eval_ctx_t *dwgsim_hip_eval_create(const dwgsim_hip_eval_opts_t *opts
 int dwgsim_hip_eval_header(dwgsim_hip_eval_ctx_t *c, const char *text, size_t len)
 {
     if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
+    if (c->tr.begun && !c->tr.committed) {
+        c->err = "the truth is not committed";
+        return DWGSIM_HIP_ERR_STATE;
+    }
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
     c->begun = true;
     int r = end_file(c);
@@ -737,6 +926,10 @@ int dwgsim_hip_eval_header(dwgsim_hip_eval_ctx_t *c, const char *text, size_t le
 int dwgsim_hip_eval_bam_begin(dwgsim_hip_eval_ctx_t *c)
 {
     if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
+    if (c->tr.begun && !c->tr.committed) {
+        c->err = "the truth is not committed";
+        return DWGSIM_HIP_ERR_STATE;
+    }
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
     c->begun = true;
     const int r = end_file(c);
@@ -763,7 +956,7 @@ int dwgsim_hip_eval_feed_bam(dwgsim_hip_eval_ctx_t *c, const void *buf, size_t l
 
 int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
 {
-    if (!c || c->finished || c->fmt != FMT_SAM) return DWGSIM_HIP_ERR_STATE;
+    if (!c || c->finished || c->fmt != FMT_SAM || (c->tr.begun && !c->tr.committed)) return DWGSIM_HIP_ERR_STATE;
     if (c->broken) return DWGSIM_HIP_ERR_FAILED;
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
     c->seen_header = c->begun = true;      // the first file's header is empty when feed comes first
@@ -805,6 +998,11 @@ int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *c, dwgsim_hip_eval_summary_t *
             CK(hipMemcpy(h.data(), c->d_hist.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             format_table(c, h);
         }
+        if (c->tr.committed) {
+            std::vector<unsigned long long> k(EVAL_TR_CTRS);
+            CK(hipMemcpy(k.data(), c->tr.d_ctrs.get(), k.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            c->tr.text = truth_text(k);
+        }
         char buf[128];
         snprintf(buf, sizeof buf, "\r%llu\n", (unsigned long long)c->n);
         c->stderr_text += buf;
@@ -845,6 +1043,10 @@ int dwgsim_hip_eval_incorrect_text(dwgsim_hip_eval_ctx_t *c, const char **txt, s
 int dwgsim_hip_eval_set_breakdown(dwgsim_hip_eval_ctx_t *c, const char *dims, int cap)
 {
     if (!c || c->finished || c->begun) return DWGSIM_HIP_ERR_STATE;
+    if (c->tr.begun && dims && *dims) {
+        c->err = "a breakdown and a truth in one context are not supported";
+        return DWGSIM_HIP_ERR_ARG;
+    }
     evt::Breakdown b;
     if (const char *why = evt::parse_breakdown(dims, cap, c->o.a, EVAL_BD_CTRS, EVAL_WIN, &b)) {
         c->err = why;
@@ -866,6 +1068,112 @@ int dwgsim_hip_eval_breakdown_text(dwgsim_hip_eval_ctx_t *c, const char **txt, s
 {
     if (!c || !c->finished || !txt || !len) return DWGSIM_HIP_ERR_STATE;
     *txt = c->bd_text.c_str(); *len = c->bd_text.size();
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_truth_header(dwgsim_hip_eval_ctx_t *c, const char *text, size_t len)
+{
+    if (const int r = truth_state(c)) return r;
+    if (len && !text) return DWGSIM_HIP_ERR_ARG;
+    auto &T = c->tr;
+    if (T.fed) return DWGSIM_HIP_ERR_STATE;       // (the records already loaded hold contig indices of the header before)
+    T.begun = true;
+    sq_names(text, len, T.names, T.off);
+    hash_names(T.names, T.off, T.hash);
+    return upload_names(c, T.names, T.off, T.hash, T.d_names, T.d_off, T.d_hash, &T.tg);
+}
+
+int dwgsim_hip_eval_truth_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
+{
+    if (const int r = truth_state(c)) return r;
+    if (len && !buf) return DWGSIM_HIP_ERR_ARG;
+    if (!c->tr.begun)
+        if (const int r = dwgsim_hip_eval_truth_header(c, "", 0)) return r;      // (no header: no contigs, so only unmapped lines can pass)
+    c->tr.fed = true;
+    while (len) {
+        Slot &F = c->s[0];
+        char *t = F.h_text.get<char>();
+        if (F.fill == F.h_text.cap()) {
+            size_t cut = F.fill;
+            while (cut > 0 && t[cut - 1] != '\n') --cut;
+            if (!cut) {
+                if (const int r = grow(c)) return r;
+                continue;
+            }
+            if (const int r = truth_chunk(c, cut)) return r;
+            memmove(t, t + cut, F.fill - cut);
+            F.fill -= cut;
+            continue;
+        }
+        const size_t k = len < F.h_text.cap() - F.fill ? len : F.h_text.cap() - F.fill;
+        memcpy(t + F.fill, buf, k);
+        F.fill += k; buf += k; len -= k;
+    }
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_truth_commit(dwgsim_hip_eval_ctx_t *c)
+{
+    if (const int r = truth_state(c)) return r;
+    if (!c->tr.begun)
+        if (const int r = dwgsim_hip_eval_truth_header(c, "", 0)) return r;
+    auto &T = c->tr;
+    // what is left, and a last line without its newline
+    if (c->s[0].fill) {
+        if (c->s[0].h_text.get<char>()[c->s[0].fill - 1] != '\n') {
+            if (c->s[0].fill == c->s[0].h_text.cap())
+                if (const int r = grow(c)) return r;
+            c->s[0].h_text.get<char>()[c->s[0].fill++] = '\n';
+        }
+        if (const int r = truth_chunk(c, c->s[0].fill)) return r;
+        c->s[0].fill = 0;
+    }
+    // at least twice as many slots as records, a power of two (the test hook may force another size, which must leave one slot empty).  A slot's
+    // number has 32 bits: beyond 2^31 records the factor of two gives way, and the table has 2^32 slots for at most 2^32 - 2 records
+    int lg = 1;
+    while (lg < 32 && (1ull << lg) < 2 * T.n_recs) ++lg;
+    if (T.force_log2 >= 0) lg = T.force_log2;
+    const uint64_t slots = 1ull << lg;
+    if (slots <= T.n_recs) return truth_fail(c, DWGSIM_HIP_ERR_ARG, "truth: the forced table has no room for the records and an empty slot");
+    if (T.d_slots.reserve(slots * 8, slots * 8) != hipSuccess || T.d_err.reserve(8, 8) != hipSuccess ||
+        T.d_ctrs.reserve(EVAL_TR_CTRS * 8, EVAL_TR_CTRS * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return truth_fail(c, DWGSIM_HIP_ERR_NOMEM, "truth: the index does not fit in device memory");
+    }
+    T.mask = (uint32_t)(slots - 1);
+    hipStream_t st = c->s[0].st.get();
+    CK(hipMemsetAsync(T.d_slots.get(), 0xff, slots * 8, st));
+    CK(hipMemsetAsync(T.d_err.get(), 0xff, 8, st));
+    CK(hipMemsetAsync(T.d_ctrs.get(), 0, EVAL_TR_CTRS * 8, st));
+    if (T.n_recs) launch_truth_index(st, T.d_slots.get<unsigned long long>(), T.mask, T.d_recs.get<ev::TruthRec>(), (uint32_t)T.n_recs, T.d_err.get<unsigned long long>());
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(st));
+    unsigned long long bad = 0;
+    CK(hipMemcpy(&bad, T.d_err.get(), 8, hipMemcpyDeviceToHost));
+    if (bad != ~0ull) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "truth: the truth holds read of record line %llu twice (its name and end are those of record line %llu)",
+                 (unsigned long long)(bad >> 32) + 1, (unsigned long long)(uint32_t)bad + 1);
+        return truth_fail(c, DWGSIM_HIP_ERR_FAILED, buf);
+    }
+    T.d_cnt.reset(); T.d_err.reset(); T.d_names.reset(); T.d_off.reset(); T.d_hash.reset();
+    T.tg = ev::Targets{};
+    T.committed = true;
+    return map_contigs(c);
+}
+
+int dwgsim_hip_eval_truth_text(dwgsim_hip_eval_ctx_t *c, const char **txt, size_t *len)
+{
+    if (!c || !c->finished || !txt || !len) return DWGSIM_HIP_ERR_STATE;
+    *txt = c->tr.text.c_str(); *len = c->tr.text.size();
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_eval_debug_truth_slots(dwgsim_hip_eval_ctx_t *c, int log2_slots)
+{
+    if (!c || c->finished || c->begun || c->tr.committed) return DWGSIM_HIP_ERR_STATE;
+    if (log2_slots < 1 || log2_slots > 32) return DWGSIM_HIP_ERR_ARG;
+    c->tr.force_log2 = log2_slots;
     return DWGSIM_HIP_OK;
 }
 

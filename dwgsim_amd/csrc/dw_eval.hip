@@ -18,6 +18,11 @@
 // the same per-record work, but a record is counted once per selected dimension, in its stratum of that dimension (EvalBdArgs lays the counters
 // out).  A block has 512 lanes and 32 768 16-bit counters, two to an LDS word (64 KiB, two blocks per CU); it merges them into the 64-bit global
 // counters before any of them can reach 2^16, that is every BD_FLUSH_ITERS turns of its record loop, and at its end.
+//
+// With a truth (dw_eval.hpp TRUTH) the truth SAM's text goes through the same newline kernels; k_truth_count, k_eval_scan and k_truth_write
+// turn every line into a 32-byte record and its CIGAR words, k_truth_insert / k_truth_check build and verify the index at commit, and the two
+// record kernels are replaced by k_eval_records_tr / k_eval_bam_records_tr: the plain body plus the join and the walk of the two CIGARs, with
+// 2 x 256 x 10 32-bit counters in LDS that are merged into 64-bit global ones every TR_FLUSH_ITERS turns.
 #include <hip/hip_runtime.h>
 #include "dw_eval.hpp"
 #include "dw_eval_launch.hpp"
@@ -140,6 +145,8 @@ struct BamFront {
 };
 
 // one lane per record, grid-stride; h: the block's LDS histogram, 5 x (EVAL_WIN + 1)
+// (The per-record part -- fatal atomicMin, n, histogram, spill, -p flag -- stands three times: here, in eval_records_bd_body and in
+// eval_records_tr_body.  A change to it is made in all three.)
 template <class Front> __device__ __forceinline__ void eval_records_body(const EvalRecArgs &A, uint32_t *h)
 {
     for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS) h[i] = 0;
@@ -221,6 +228,7 @@ __device__ __forceinline__ void bd_count(uint32_t *h, uint32_t row, uint32_t cls
 }
 
 // one lane per record, block-stride (every lane of a block makes the same number of turns); h: EVAL_BD_CTRS / 2 words
+// (the per-record part is eval_records_body's and eval_records_tr_body's: see the note there)
 template <class Front> __device__ __forceinline__ void eval_records_bd_body(const EvalRecArgs &A, const EvalBdArgs &B, uint32_t *h)
 {
     const uint32_t bins = B.win + 1, n_words = (B.n_rows * 5 * bins + 1) / 2;
@@ -288,6 +296,228 @@ __global__ __launch_bounds__(BD_THREADS) void k_eval_bam_records_bd(EvalRecArgs 
 {
     __shared__ uint32_t hb[EVAL_BD_CTRS / 2];
     eval_records_bd_body<BamFront>(A, B, hb);
+}
+
+// ---- the truth: load, index, and the truth form of the record kernels (dw_eval.hpp TRUTH) ----
+
+// line li of a chunk of truth text
+__device__ __forceinline__ const char *truth_line(const EvalTruthLoadArgs &L, uint32_t li, uint32_t *len)
+{
+    const uint32_t b = li ? L.ends[li - 1] + 1 : 0;
+    *len = L.ends[li] - b;
+    return (const char *)L.text + b;
+}
+
+// every line checked; cnt[li] = the pool words it needs
+__global__ __launch_bounds__(EV_THREADS) void k_truth_count(EvalTruthLoadArgs L)
+{
+    for (uint32_t li = blockIdx.x * EV_THREADS + threadIdx.x; li < L.n_lines; li += gridDim.x * EV_THREADS) {
+        uint32_t len;
+        const char *p = truth_line(L, li, &len);
+        ev::TruthLine t;
+        const int code = ev::truth_parse(p, len, L.tg, &t);
+        if (code) atomicMin(L.err, (unsigned long long)(((uint64_t)li << 8) | (uint32_t)code));
+        L.cnt[li] = (code || t.unmapped || t.one_m) ? 0 : t.n_ops;
+    }
+}
+
+// the records and their pool words (only after a chunk without a bad line)
+__global__ __launch_bounds__(EV_THREADS) void k_truth_write(EvalTruthLoadArgs L)
+{
+    for (uint32_t li = blockIdx.x * EV_THREADS + threadIdx.x; li < L.n_lines; li += gridDim.x * EV_THREADS) {
+        uint32_t len;
+        const char *p = truth_line(L, li, &len);
+        ev::TruthLine t;
+        if (ev::truth_parse(p, len, L.tg, &t)) continue;
+        L.recs[li] = ev::truth_pack(p, t, L.pool, L.pool_base + L.cnt[li]);
+    }
+}
+
+// Insertion with atomicMin alone: the smaller of the entry and the slot's stays, the larger goes on to the next slot, until a slot was empty.
+// Slots never become empty again, so every entry stays reachable from its home slot (the table has more slots than records)
+__global__ __launch_bounds__(EV_THREADS) void k_truth_insert(unsigned long long *slots, uint32_t mask, const ev::TruthRec *recs, uint32_t n)
+{
+    for (uint32_t i = blockIdx.x * EV_THREADS + threadIdx.x; i < n; i += gridDim.x * EV_THREADS) {
+        unsigned long long e = ev::slot_entry(recs[i].h1, i);
+        uint32_t s = ev::slot_home(recs[i].h1, mask);
+        for (uint64_t step = 0; step < 2 * ((uint64_t)mask + 1); ++step, s = (s + 1) & mask) {
+            const unsigned long long old = atomicMin(&slots[s], e);
+            if (old == ev::SLOT_EMPTY) break;
+            if (old > e) e = old;
+        }
+    }
+}
+
+// every record looks itself up and must be the first with its 128 bits: err = (record << 32) | the one found instead, of the first that is not
+__global__ __launch_bounds__(EV_THREADS) void k_truth_check(const unsigned long long *slots, uint32_t mask, const ev::TruthRec *recs, uint32_t n, unsigned long long *err)
+{
+    for (uint32_t i = blockIdx.x * EV_THREADS + threadIdx.x; i < n; i += gridDim.x * EV_THREADS) {
+        const int64_t f = ev::truth_find(slots, mask, recs, recs[i].h1, recs[i].h2);
+        if (f != (int64_t)i) atomicMin(err, (unsigned long long)(((uint64_t)i << 32) | (uint32_t)f));
+    }
+}
+
+// A compared record adds at most TR_LDS_MAX to an LDS counter (a longer one goes to the global counters directly), so a block adds less than
+// 2^32 to any of them in TR_FLUSH_ITERS turns of its record loop.  Reads of 25 000 bases stay in LDS.
+constexpr uint64_t TR_LDS_MAX = 65535;
+constexpr uint32_t TR_FLUSH_ITERS = (uint32_t)(0xFFFFFFFFull / (EV_THREADS * TR_LDS_MAX));
+static_assert(TR_FLUSH_ITERS >= 1 && (uint64_t)TR_FLUSH_ITERS * EV_THREADS * TR_LDS_MAX <= 0xFFFFFFFFull, "a 32-bit counter must not wrap between two merges");
+static_assert(TR_LDS_MAX >= 25000, "ordinary reads are counted in LDS");
+
+__device__ __forceinline__ void tr_merge(uint32_t *tc, unsigned long long *ctrs)
+{
+    for (uint32_t i = threadIdx.x; i < EVAL_TR_CTRS; i += EV_THREADS) {
+        const uint32_t v = tc[i];
+        if (!v) continue;
+        tc[i] = 0;
+        atomicAdd(&ctrs[i], (unsigned long long)v);
+    }
+}
+
+// the counts of one participating record, in stratum all and, for a compared record of an indel truth, in stratum indel
+__device__ __forceinline__ void tr_count(uint32_t *tc, unsigned long long *ctrs, uint32_t mapq, const ev::TruthCmp &c)
+{
+    const uint64_t v[EVAL_TR_COLS] = {c.outcome == ev::J_MISSING, c.outcome == ev::J_RANDOM, c.outcome == ev::J_UNUSABLE, c.outcome == ev::J_COMPARED,
+                                      (uint64_t)c.exact, c.bases, c.right, c.clipped, c.ibases, c.iright};
+    const bool lds = c.bases <= TR_LDS_MAX;     // (right, clipped, ibases, iright <= bases)
+    for (uint32_t s = 0; s < (c.indel ? 2u : 1u); ++s)
+        for (uint32_t k = 0; k < EVAL_TR_COLS; ++k) {
+            if (!v[k]) continue;
+            const uint32_t at = (s * 256 + mapq) * EVAL_TR_COLS + k;
+            if (lds) atomicAdd(&tc[at], (uint32_t)v[k]);
+            else atomicAdd(&ctrs[at], (unsigned long long)v[k]);
+        }
+}
+
+// the join of SPEC TRUTH for one participating record
+template <class Front> __device__ __forceinline__ void tr_join(const EvalRecArgs &A, const EvalTruthArgs &T, const ev::Rec &R, ev::TruthCmp *c)
+{
+    c->outcome = ev::J_MISSING; c->exact = 0; c->indel = false;
+    c->bases = c->right = c->clipped = c->ibases = c->iright = 0;
+    if (!ev::key_valid(R.flag)) return;
+    uint64_t h1, h2;
+    ev::key_hash(R.qname, (uint32_t)R.qlen, ev::key_end(R.flag), &h1, &h2);
+    const int64_t f = ev::truth_find(T.slots, T.mask, T.recs, h1, h2);
+    if (f < 0) return;
+    const int32_t t = R.bam ? R.tid : ev::target_find(A.tg, R.rname, R.rname_len);
+    ev::truth_compare(R, t >= 0 ? T.tmap[t] : -1, T.recs[f], T.pool, c);
+}
+
+// eval_records_body plus the join (its per-record part is a copy of that body's, as eval_records_bd_body's is: the plain kernels stay as they
+// are, so a change to that part is made in all three); block-stride, so that every lane of a block makes the same number of turns; tc: EVAL_TR_CTRS words
+template <class Front> __device__ __forceinline__ void eval_records_tr_body(const EvalRecArgs &A, const EvalTruthArgs &T, uint32_t *h, uint32_t *tc)
+{
+    for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS) h[i] = 0;
+    for (uint32_t i = threadIdx.x; i < EVAL_TR_CTRS; i += EV_THREADS) tc[i] = 0;
+    __syncthreads();
+
+    const uint32_t n_lines = A.res->n_lines;
+    const uint32_t n_rec = n_lines > A.has_ctx ? n_lines - A.has_ctx : 0;
+    uint32_t n_local = 0, turns = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * EV_THREADS; base < n_rec; base += (uint64_t)gridDim.x * EV_THREADS) {
+        const uint64_t r64 = base + threadIdx.x;
+        if (r64 < n_rec) {
+            const uint32_t r = (uint32_t)r64, li = r + A.has_ctx;
+            ev::Rec R;
+            ev::Out o = {ev::E_MALFORMED, 0, 0, -1, 0};
+            if (Front::rec(A, li, &R)) {
+                ev::Prev pv;
+                const bool have_prev = A.opt.m && li;
+                if (have_prev) pv = Front::prev(A, li);
+                o = ev::eval_rec(R, have_prev ? &pv : nullptr, A.opt, A.tg);
+            }
+            bool incorrect = false;
+            if (o.code) {
+                atomicMin((unsigned long long *)&A.res->err, (unsigned long long)(((uint64_t)r << 8) | (uint32_t)o.code));
+            } else if (!o.skipped) {
+                n_local += (uint32_t)o.n_inc;
+                if (o.cls >= 0) {
+                    incorrect = o.cls == ev::MI || o.cls == ev::UM;
+                    const int64_t bin = (int64_t)o.score - A.win_lo;
+                    if (bin >= 0 && bin < EVAL_WIN) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + (uint32_t)bin], 1u);
+                    else if (o.score == A.floor_score) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + EVAL_WIN], 1u);
+                    else {
+                        const uint32_t k = atomicAdd(&A.res->n_spill, 1u);
+                        A.spill[k] = ((uint64_t)(uint32_t)o.score << 32) | (uint32_t)o.cls;
+                    }
+                    if (!(R.flag & 4)) {
+                        ev::TruthCmp c;
+                        tr_join<Front>(A, T, R, &c);
+                        tr_count(tc, T.ctrs, R.mapq, c);
+                    }
+                }
+            }
+            if (A.flags) A.flags[r] = incorrect ? 1 : 0;
+        }
+        if (++turns == TR_FLUSH_ITERS) {
+            turns = 0;
+            __syncthreads();
+            tr_merge(tc, T.ctrs);
+            __syncthreads();
+        }
+    }
+    if (n_local) atomicAdd((unsigned long long *)&A.res->n, (unsigned long long)n_local);
+    __syncthreads();
+    for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS)
+        if (h[i]) atomicAdd((unsigned long long *)&A.hist[i], (unsigned long long)h[i]);
+    tr_merge(tc, T.ctrs);
+}
+
+__global__ __launch_bounds__(EV_THREADS) void k_eval_records_tr(EvalRecArgs A, EvalTruthArgs T)
+{
+    __shared__ uint32_t ht[(EVAL_WIN + 1) * 5];
+    __shared__ uint32_t tct[EVAL_TR_CTRS];
+    eval_records_tr_body<SamFront>(A, T, ht, tct);
+}
+
+__global__ __launch_bounds__(EV_THREADS) void k_eval_bam_records_tr(EvalRecArgs A, EvalTruthArgs T)
+{
+    __shared__ uint32_t ht[(EVAL_WIN + 1) * 5];
+    __shared__ uint32_t tct[EVAL_TR_CTRS];
+    eval_records_tr_body<BamFront>(A, T, ht, tct);
+}
+
+static uint32_t truth_grid(uint32_t n)
+{
+    const uint32_t g = (n + EV_THREADS - 1) / EV_THREADS;
+    return g < 1 ? 1 : g > 2048 ? 2048 : g;
+}
+
+void launch_eval_newlines(hipStream_t st, const uint8_t *text, uint64_t len, uint32_t *tile_count, EvalRes *res, uint32_t *ends)
+{
+    const uint32_t tiles = (uint32_t)((len + EV_TILE - 1) / EV_TILE);
+    if (!tiles) return;
+    hipLaunchKernelGGL(k_eval_count, dim3(tiles), dim3(EV_THREADS), 0, st, text, len, tile_count);
+    hipLaunchKernelGGL(k_eval_scan, dim3(1), dim3(EV_THREADS), 0, st, tile_count, tiles, res);
+    hipLaunchKernelGGL(k_eval_lines, dim3(tiles), dim3(EV_THREADS), 0, st, text, len, (const uint32_t *)tile_count, ends);
+}
+
+void launch_truth_load(hipStream_t st, const EvalTruthLoadArgs &L, EvalRes *scan_res)
+{
+    hipLaunchKernelGGL(k_truth_count, dim3(truth_grid(L.n_lines)), dim3(EV_THREADS), 0, st, L);
+    hipLaunchKernelGGL(k_eval_scan, dim3(1), dim3(EV_THREADS), 0, st, L.cnt, L.n_lines, scan_res);
+}
+
+void launch_truth_write(hipStream_t st, const EvalTruthLoadArgs &L)
+{
+    hipLaunchKernelGGL(k_truth_write, dim3(truth_grid(L.n_lines)), dim3(EV_THREADS), 0, st, L);
+}
+
+void launch_truth_index(hipStream_t st, unsigned long long *slots, uint32_t mask, const ev::TruthRec *recs, uint32_t n, unsigned long long *err)
+{
+    hipLaunchKernelGGL(k_truth_insert, dim3(truth_grid(n)), dim3(EV_THREADS), 0, st, slots, mask, recs, n);
+    hipLaunchKernelGGL(k_truth_check, dim3(truth_grid(n)), dim3(EV_THREADS), 0, st, (const unsigned long long *)slots, mask, recs, n, err);
+}
+
+void launch_eval_chunk_tr(hipStream_t st, const EvalRecArgs &A, const EvalTruthArgs &T, uint64_t len, uint32_t *tile_count, uint32_t grid_records)
+{
+    launch_eval_newlines(st, A.text, len, tile_count, A.res, A.ends);
+    hipLaunchKernelGGL(k_eval_records_tr, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A, T);
+}
+
+void launch_eval_bam_chunk_tr(hipStream_t st, const EvalRecArgs &A, const EvalTruthArgs &T, uint32_t grid_records)
+{
+    hipLaunchKernelGGL(k_eval_bam_records_tr, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A, T);
 }
 
 void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tile_count, uint32_t grid_records)

@@ -53,4 +53,40 @@ constexpr uint32_t EVAL_BD_THREADS = 512;
 void launch_eval_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint64_t len, uint32_t *tile_count, uint32_t grid_records);
 void launch_eval_bam_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint32_t grid_records);
 
+// The truth form (dw_eval.hpp TRUTH).  Load, per chunk of truth text behind the newline kernels: k_truth_count (every line checked, its pool
+// words counted), k_eval_scan over the counts, k_truth_write (records and pool words).  Commit: k_truth_insert, k_truth_check.  Afterwards the
+// table, the records and the pool are read-only, and k_eval_records_tr / k_eval_bam_records_tr join every participating record with them.
+// Counter (stratum * 256 + MAPQ) * EVAL_TR_COLS + column; stratum 0 all, 1 indel.
+enum { TC_MISSING = 0, TC_RANDOM, TC_UNUSABLE, TC_COMPARED, TC_EXACT, TC_BASES, TC_RIGHT, TC_CLIPPED, TC_IBASES, TC_IRIGHT, EVAL_TR_COLS };
+constexpr uint32_t EVAL_TR_CTRS = 2 * 256 * EVAL_TR_COLS;       // 32-bit LDS counters per block: 20 KiB
+
+struct EvalTruthLoadArgs {
+    const uint8_t *text;
+    const uint32_t *ends;           // the position of every newline of the chunk
+    uint32_t n_lines;               // (device-made, read back by the host)
+    uint32_t *cnt;                  // per line: its pool words; after the scan, where they start within the chunk's
+    ev::Targets tg;                 // the truth's own contigs
+    ev::TruthRec *recs;             // the chunk's first record
+    uint32_t *pool;
+    uint32_t pool_base;             // pool words of the chunks before
+    unsigned long long *err;        // (line << 8) | T_E_* of the first bad line, ~0 when none
+};
+
+struct EvalTruthArgs {
+    const unsigned long long *slots;
+    uint32_t mask;
+    const ev::TruthRec *recs;
+    const uint32_t *pool;
+    const int32_t *tmap;            // per target of the current file: the truth contig of the same name, or -1
+    unsigned long long *ctrs;       // EVAL_TR_CTRS
+};
+
+void launch_truth_load(hipStream_t st, const EvalTruthLoadArgs &L, EvalRes *scan_res);
+void launch_truth_write(hipStream_t st, const EvalTruthLoadArgs &L);
+void launch_truth_index(hipStream_t st, unsigned long long *slots, uint32_t mask, const ev::TruthRec *recs, uint32_t n, unsigned long long *err);
+void launch_eval_chunk_tr(hipStream_t st, const EvalRecArgs &A, const EvalTruthArgs &T, uint64_t len, uint32_t *tile_count, uint32_t grid_records);
+void launch_eval_bam_chunk_tr(hipStream_t st, const EvalRecArgs &A, const EvalTruthArgs &T, uint32_t grid_records);
+// the newline kernels alone (the truth load runs them before it knows how many records to make room for)
+void launch_eval_newlines(hipStream_t st, const uint8_t *text, uint64_t len, uint32_t *tile_count, EvalRes *res, uint32_t *ends);
+
 } // namespace dw

@@ -8,6 +8,8 @@
 //
 // Decoding: a 64-bit bit buffer, refilled eight bytes at a time away from the end of the input; one table of 2^11 entries per code set answers
 // every code of up to 11 bits in one look-up, and the few longer ones are walked bit by bit over the canonical counts.
+//
+// gzip_member() reads one member of a gzip file over it (dwgsim_eval-hip -T: dwgsim-hip's truth SAM is a chain of members without size fields).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -128,8 +130,9 @@ inline int huff_decode(Bits &b, const Huff &h)
 }
 
 // Inflates the raw deflate stream src[0, src_len) into dst[0, dst_cap): Z_OK and *dst_len, or a Z_E_* error (then *dst_len is what was
-// written before it).  Bytes of src after the final block are ignored.
-inline int inflate(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *dst_len)
+// written before it).  Bytes of src after the final block are ignored; *src_used says how many the stream took (the last one may be partly used),
+// so that a caller can find what follows it: a gzip member's CRC-32 and ISIZE, and the next member.
+inline int inflate_used(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *dst_len, size_t *src_used)
 {
     static const uint16_t LEN_BASE[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
     static const uint8_t LEN_EXTRA[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
@@ -237,7 +240,14 @@ inline int inflate(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_
         *dst_len = out;
     }
     *dst_len = out;
+    *src_used = (size_t)(b.p - src) - (size_t)(b.n >> 3);       // (whole bytes still in the bit buffer were not taken)
     return Z_OK;
+}
+
+inline int inflate(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *dst_len)
+{
+    size_t used;
+    return inflate_used(src, src_len, dst, dst_cap, dst_len, &used);
 }
 
 // CRC-32 (IEEE 802.3, the gzip one), slicing-by-8
@@ -266,6 +276,58 @@ inline uint32_t crc32(const uint8_t *p, size_t n, uint32_t crc = 0)
     }
     while (n--) c = (c >> 8) ^ T.t[0][(c ^ *p++) & 0xff];
     return ~c;
+}
+
+// One member of a gzip file (RFC 1952) at src[0, src_len): its deflate stream is data_off bytes in.  false and *why for a header that is not
+// gzip's, uses another method than deflate, or does not fit in the bytes.
+inline bool gzip_member_header(const uint8_t *src, size_t src_len, size_t *data_off, const char **why)
+{
+    *why = "the gzip member header is cut short";
+    if (src_len < 10) return false;
+    if (src[0] != 0x1f || src[1] != 0x8b) { *why = "not a gzip member"; return false; }
+    if (src[2] != 8 || (src[3] & 0xe0)) { *why = "unknown gzip method or flags"; return false; }
+    const uint8_t flg = src[3];
+    size_t p = 10;
+    if (flg & 4) {              // FEXTRA
+        if (src_len - p < 2) return false;
+        const size_t xlen = src[p] | (size_t)src[p + 1] << 8;
+        p += 2;
+        if (src_len - p < xlen) return false;
+        p += xlen;
+    }
+    for (int bit = 8; bit <= 16; bit <<= 1)         // FNAME, FCOMMENT: zero-terminated
+        if (flg & bit) {
+            while (p < src_len && src[p]) ++p;
+            if (p == src_len) return false;
+            ++p;
+        }
+    if (flg & 2) {              // FHCRC
+        if (src_len - p < 2) return false;
+        p += 2;
+    }
+    *data_off = p;
+    return true;
+}
+
+// Inflates the member at src into dst[0, dst_cap): Z_OK, *dst_len and *member_len (header, stream and the eight bytes behind it), after the
+// member's CRC-32 and ISIZE were checked; Z_E_ROOM asks for a larger dst; any other failure is < 0 with *why.
+inline int gzip_member(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *dst_len, size_t *member_len, const char **why)
+{
+    size_t off;
+    *dst_len = 0;
+    if (!gzip_member_header(src, src_len, &off, why)) return Z_E_TRUNCATED;
+    size_t used = 0;
+    const int r = inflate_used(src + off, src_len - off, dst, dst_cap, dst_len, &used);
+    *why = error_name(r);
+    if (r) return r;
+    if (src_len - off - used < 8) { *why = "the gzip member ends before its CRC-32 and ISIZE"; return Z_E_TRUNCATED; }
+    const uint8_t *t = src + off + used;
+    const uint32_t crc = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+    const uint32_t isize = t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+    if (isize != (uint32_t)*dst_len) { *why = "ISIZE differs from the inflated size"; return Z_E_SYMBOL; }
+    if (crc != crc32(dst, *dst_len)) { *why = "CRC-32 mismatch"; return Z_E_SYMBOL; }
+    *member_len = off + used + 8;
+    return Z_OK;
 }
 
 } // namespace zz

@@ -2,6 +2,8 @@
 // Input is BAM unless -S is given, as for the reference.  Without -S the first two bytes of every input are read before a device is opened:
 // when one of them is not gzip's 1f 8b the input is text, and the message that asks for -S is printed.
 // -B LIST and -K INT are this program's own (both letters are free in the reference's option string): the breakdown's sections follow the table.
+// -T FILE, also this program's own: the truth SAM of dwgsim-hip, plain or gzip, read completely before the first alignment file; the base-level
+// section (dw_eval.hpp TRUTH) follows the table.  A gzip truth is inflated member by member with dw_inflate.hpp on this one thread.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -10,6 +12,7 @@
 #include <string>
 #include <vector>
 #include "../../include/dwgsim_hip.h"
+#include "dw_inflate.hpp"
 
 #define PACKAGE_VERSION "0.1.17-hip"
 
@@ -45,6 +48,7 @@ static int print_usage(const dwgsim_hip_eval_opts_t *a)
     fprintf(f, "\t-P\tSTRING\ta read prefix that was prepended to each read name [%s]\n", a->P ? a->P : "not using");
     fprintf(f, "\t-B\tLIST\talso print the table of every stratum of these dimensions, comma separated: snps,errors,indels,end [%s]\n", "not using");
     fprintf(f, "\t-K\tINT\twith -B: snps and errors have the strata 0 ... INT-1 and INT+ (1 to 32; 0: the default) [%d]\n", 8);
+    fprintf(f, "\t-T\tFILE\tthe truth SAM of dwgsim-hip (plain or gzip; not with -B): also print how many bases were placed right [%s]\n", "not using");
     fprintf(f, "\t-h\t\tprint this help message\n");
     return 1;
 }
@@ -80,6 +84,67 @@ static int run_file(dwgsim_hip_eval_ctx_t *ctx, FILE *in)
     return DWGSIM_HIP_OK;
 }
 
+// the truth SAM: its '@' lines go to the truth header call, the rest is fed as it comes, then the index is built.  0, or 1 after a message
+static int load_truth(dwgsim_hip_eval_ctx_t *ctx, const char *path)
+{
+    FILE *in = fopen(path, "rb");
+    if (!in) {
+        fprintf(stderr, "dwgsim_eval-hip: -T %s: %s\n", path, strerror(errno));
+        return 1;
+    }
+    std::vector<uint8_t> z;
+    std::vector<uint8_t> buf(8u << 20);
+    size_t got;
+    while ((got = fread(buf.data(), 1, buf.size(), in)) > 0) z.insert(z.end(), buf.begin(), buf.begin() + (ptrdiff_t)got);
+    fclose(in);
+    std::string header;
+    bool in_header = true, at_line_start = true;
+    int r = DWGSIM_HIP_OK;
+    auto take = [&](const char *t, size_t n) {
+        size_t p = 0;
+        while (p < n && in_header) {
+            if (at_line_start && t[p] != '@') {
+                in_header = false;
+                r = dwgsim_hip_eval_truth_header(ctx, header.data(), header.size());
+                break;
+            }
+            const char *nl = (const char *)memchr(t + p, '\n', n - p);
+            const size_t e = nl ? (size_t)(nl - t) + 1 : n;
+            header.append(t + p, e - p);
+            at_line_start = nl != nullptr;
+            p = e;
+        }
+        if (!r && p < n) r = dwgsim_hip_eval_truth_feed(ctx, t + p, n - p);
+        return r == DWGSIM_HIP_OK;
+    };
+    if (z.size() >= 2 && z[0] == 0x1f && z[1] == 0x8b) {
+        size_t at = 0;
+        while (at < z.size()) {
+            size_t out_len = 0, member = 0;
+            const char *why = nullptr;
+            int k;
+            while ((k = dw::zz::gzip_member(z.data() + at, z.size() - at, buf.data(), buf.size(), &out_len, &member, &why)) == dw::zz::Z_E_ROOM &&
+                   buf.size() / 1100 <= z.size() - at)       // (deflate expands at most 1032 times)
+                buf.resize(buf.size() * 2);
+            if (k) {
+                fprintf(stderr, "dwgsim_eval-hip: -T %s: %s in the gzip member at byte %zu\n", path, why, at);
+                return 1;
+            }
+            if (!take((const char *)buf.data(), out_len)) break;
+            at += member;
+        }
+    } else {
+        take((const char *)z.data(), z.size());
+    }
+    if (!r && in_header) r = dwgsim_hip_eval_truth_header(ctx, header.data(), header.size());
+    if (!r) r = dwgsim_hip_eval_truth_commit(ctx);
+    if (r) {
+        fprintf(stderr, "dwgsim_eval-hip: -T %s: %s\n", path, dwgsim_hip_eval_last_error(ctx));
+        return 1;
+    }
+    return 0;
+}
+
 // one BAM file: `lead` (the bytes already read from it), then the rest, as they come
 static int run_bam_file(dwgsim_hip_eval_ctx_t *ctx, FILE *in, const std::string &lead)
 {
@@ -105,6 +170,7 @@ int main(int argc, char *argv[])
     dwgsim_hip_eval_opts_default(&o);
     int S = 0;
     std::string P;
+    const char *T = nullptr;      // -T: the truth SAM
     const char *B = nullptr;      // -B, -K: the breakdown (dwgsim_hip_eval_set_breakdown)
     int K = 0;
     bool have_K = false;
@@ -113,7 +179,7 @@ int main(int argc, char *argv[])
     const char *threads = getenv("DWGSIM_EVAL_THREADS");  // host threads that inflate BAM input
     if (threads) o.inflate_threads = atoi(threads);
     int c;
-    while ((c = getopt(argc, argv, "a:d:e:g:m:n:q:s:bchimpzSP:B:K:")) >= 0) {
+    while ((c = getopt(argc, argv, "a:d:e:g:m:n:q:s:bchimpzSP:B:K:T:")) >= 0) {
         switch (c) {
         case 'a': o.a = atoi(optarg); break;
         case 'b': o.b = 1; break;
@@ -132,6 +198,7 @@ int main(int argc, char *argv[])
         case 'i': o.i = 1; break;
         case 'P': P = optarg; o.P = P.c_str(); break;
         case 'B': B = optarg; break;
+        case 'T': T = optarg; break;
         case 'K': {
             char *end = nullptr;
             const long v = strtol(optarg, &end, 10);
@@ -148,6 +215,10 @@ int main(int argc, char *argv[])
     if (argc == optind) return print_usage(&o);
     if (have_K && !B) {
         fprintf(stderr, "dwgsim_eval-hip: -K has a meaning only with -B\n");
+        return 1;
+    }
+    if (T && B) {
+        fprintf(stderr, "dwgsim_eval-hip: -T and -B cannot be used together\n");
         return 1;
     }
     // BAM: every input is opened and its first two bytes are kept
@@ -185,6 +256,10 @@ int main(int argc, char *argv[])
     }
     if (B && dwgsim_hip_eval_set_breakdown(ctx, B, K) != DWGSIM_HIP_OK) {
         fprintf(stderr, "dwgsim_eval-hip: -B / -K: %s\n", dwgsim_hip_eval_last_error(ctx));
+        dwgsim_hip_eval_destroy(ctx);
+        return 1;
+    }
+    if (T && load_truth(ctx, T)) {
         dwgsim_hip_eval_destroy(ctx);
         return 1;
     }
@@ -232,6 +307,7 @@ int main(int argc, char *argv[])
         if (o.p && dwgsim_hip_eval_incorrect_text(ctx, &t, &n) == DWGSIM_HIP_OK) fwrite(t, 1, n, stdout);
         if (dwgsim_hip_eval_table_text(ctx, &t, &n) == DWGSIM_HIP_OK) fwrite(t, 1, n, stdout);
         if (B && dwgsim_hip_eval_breakdown_text(ctx, &t, &n) == DWGSIM_HIP_OK) fwrite(t, 1, n, stdout);
+        if (T && dwgsim_hip_eval_truth_text(ctx, &t, &n) == DWGSIM_HIP_OK) fwrite(t, 1, n, stdout);
         fflush(stdout);
     }
     fwrite(sm.stderr_text + skip, 1, sm.stderr_len - skip, stderr);

@@ -407,8 +407,10 @@ void dwgsim_hip_job_destroy(dwgsim_hip_job_t *job);
  * dwgsim_eval: score SAM or BAM alignments of simulated reads (reference src/dwgsim_eval.c; DESIGN.md "dwgsim_eval-hip").
  * A context evaluates one run: header(file 1), feed(records of file 1)..., header(file 2), feed..., finish, then the texts.  One device.
  * A BAM file is bam_begin, feed_bam(its raw bytes)... instead of header, feed...; SAM and BAM files may be mixed in one run.
+ * (ABI 3) A truth SAM, given before the first file (truth_header, truth_feed..., truth_commit), adds a base-level section: every aligned record
+ * is joined with its truth record on the device and the two CIGARs are walked side by side (truth_text; the rule: dw_eval.hpp TRUTH).
  * ==================================================================================================================================== */
-#define DWGSIM_HIP_EVAL_ABI_VERSION 2
+#define DWGSIM_HIP_EVAL_ABI_VERSION 3
 /* fatal record errors (dwgsim_hip_eval_summary_t.error_code): the first record of the run, in file order, that has one decides */
 #define DWGSIM_HIP_EVAL_E_MALFORMED       1   /* not a SAM record (fewer than 11 fields, FLAG / POS / MAPQ out of range, ...) */
 #define DWGSIM_HIP_EVAL_E_PREFIX          2   /* "could not match read name with given read name prefix (-P)" */
@@ -471,6 +473,26 @@ int dwgsim_hip_eval_set_breakdown(dwgsim_hip_eval_ctx_t *ctx, const char *dims, 
  * ("## snps=8+", "## errors=3", "## indels=0", "## indels=1+", "## end=1", "## end=2") and that stratum's table as in table_text -- in the order
  * snps, errors, indels, end, strata ascending, empty strata included (the one-row-of-zeros table) */
 int dwgsim_hip_eval_breakdown_text(dwgsim_hip_eval_ctx_t *ctx, const char **txt, size_t *len);
+/* Truth (ABI 3): the true alignment of every read end, as dwgsim-hip writes it (out.truth.sam).  All four calls below but truth_text are legal
+ * only after create and before the first header / bam_begin / feed: DWGSIM_HIP_ERR_STATE later, and a context whose truth is not committed
+ * refuses header / bam_begin / feed with DWGSIM_HIP_ERR_STATE; so does truth_header once truth_feed has been called.  A truth and a breakdown in one context: DWGSIM_HIP_ERR_ARG and a message.
+ * truth_header: the truth SAM's '@' lines; their @SQ SN: names are the truth's contigs (an aligned record has the truth's contig when its
+ *   RNAME -- through the targets of its own file -- is the same name).
+ * truth_feed: record text, split anywhere, any number of calls.  A key is (QNAME, end): end 0 when FLAG 0x1 is clear, else (FLAG >> 6) & 3.
+ *   DWGSIM_HIP_ERR_FAILED and "truth: record line N ..." (N counts record lines from 1) for a line with fewer than 11 fields, one that is no
+ *   truth record (QNAME, FLAG, POS, end 3 or a paired end 0), a mapped line at POS 0, with an RNAME outside the @SQ names, or with a CIGAR
+ *   that is no sequence of M, I and D runs with at least one query base; DWGSIM_HIP_ERR_NOMEM when the truth does not fit in device memory; DWGSIM_HIP_ERR_ARG for more
+ *   than 2^32 - 2 records.  After such an error the truth calls return DWGSIM_HIP_ERR_FAILED.
+ * truth_commit: builds the index and returns when it is complete and every record has found itself in it.  Two records with one key fail it:
+ *   DWGSIM_HIP_ERR_FAILED, "truth: the truth holds read of record line N twice (... record line M)".
+ * truth_text: after finish.  Empty without a truth or after a fatal record; else, for the strata all and indel (truth CIGARs with an I or a D),
+ *   "## truth all" / "## truth indel", a '#' line naming the columns, and one tab-separated row per MAPQ value that a record of the stratum
+ *   has, highest first, counts cumulative over MAPQ >= the row's: mapq missing random unusable compared exact bases right clipped ibases
+ *   iright.  A stratum without records has one row of zeros at MAPQ 0.  The main table, -p text and stderr are those of a run without a truth. */
+int dwgsim_hip_eval_truth_header(dwgsim_hip_eval_ctx_t *ctx, const char *text, size_t len);
+int dwgsim_hip_eval_truth_feed(dwgsim_hip_eval_ctx_t *ctx, const char *buf, size_t len);
+int dwgsim_hip_eval_truth_commit(dwgsim_hip_eval_ctx_t *ctx);
+int dwgsim_hip_eval_truth_text(dwgsim_hip_eval_ctx_t *ctx, const char **txt, size_t *len);
 const char *dwgsim_hip_eval_last_error(const dwgsim_hip_eval_ctx_t *ctx);
 void dwgsim_hip_eval_destroy(dwgsim_hip_eval_ctx_t *ctx);
 /* test hooks: the device time (ms, HIP events) of the chunks so far; and kernel-only throughput: `len` bytes of record lines (host memory)
@@ -483,6 +505,10 @@ int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *ctx, const void *t
  * BAM file on `threads` host threads, *ms = the best of `reps` passes, *out_bytes = the inflated size. */
 int dwgsim_hip_eval_debug_device_bam_chunk(dwgsim_hip_eval_ctx_t *ctx, const void *records, size_t len, int reps, double *ms);
 int dwgsim_hip_eval_debug_inflate(const void *bam, size_t len, int threads, int reps, double *ms, uint64_t *out_bytes);
+/* before truth_commit: the index gets 2^log2_slots slots instead of at least twice the records (more slots than records, or commit fails with
+ * DWGSIM_HIP_ERR_ARG): a nearly full table, whose probe chains are long and wrap around its end.  With a truth, the device_chunk hooks run the
+ * truth form of the record kernels. */
+int dwgsim_hip_eval_debug_truth_slots(dwgsim_hip_eval_ctx_t *ctx, int log2_slots);
 
 /* ====================================================================================================================================
  * TEST / ANALYSIS HOOKS -- everything below this line is NOT part of the drop-in surface.  A binding of the reference needs none of it; the

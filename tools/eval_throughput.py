@@ -9,8 +9,15 @@ With --bam the same records are also measured as a BAM file (level 6, 64 KiB BGZ
 With --breakdown every kernel and e2e figure is measured again in the same run with a breakdown set (dwgsim_hip_eval_set_breakdown): all four
 dimensions at the default cap (keys bd_*, and bd_*_ratio = breakdown / plain time) and, for the kernels, at cap 32 (keys bd32_*).
 --bam-threads LIST (default 1,4,8,16) chooses the inflate thread counts of bam_inflate and bam_e2e.
-Prints one JSON line.  Usage: python tools/eval_throughput.py [--mib 1024] [--reps 5] [--model-mib 16] [--a 3] [--bam] [--bam-threads 8] [--breakdown]"""
-import argparse, ctypes as C, json, os, random, sys, time
+With --truth the records are measured once more under names of their own (every copy of the block renamed, so that no key is asked for
+twice in a launch) against a truth SAM of --truth-copies sets of names (one record per name and end, one in eight with an insertion; the
+asked records lie spread over the whole truth), in the same run on the same records:
+  truth_load   header, feed and commit of that truth: records/s and GB/s of truth text (keys truth_*)
+  dn_kernel    the plain form over that device-resident text (keys dn_*)
+  tr_kernel    the truth form over it (keys tr_*, and tr_*_ratio = truth / plain time), SAM and, with --bam, BAM
+Prints one JSON line.  Usage: python tools/eval_throughput.py [--mib 1024] [--reps 5] [--model-mib 16] [--a 3] [--bam] [--bam-threads 8] [--breakdown]
+                                                              [--truth] [--truth-copies 100]"""
+import argparse, ctypes as C, io, json, os, random, re, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -28,6 +35,8 @@ def main():
     ap.add_argument("--bam", action="store_true")
     ap.add_argument("--breakdown", action="store_true")
     ap.add_argument("--bam-threads", default="1,4,8,16")
+    ap.add_argument("--truth", action="store_true")
+    ap.add_argument("--truth-copies", type=int, default=100)
     args = ap.parse_args()
     contigs = [("chr%d" % i, 200_000_000) for i in range(1, 23)]
     rng = random.Random(5)
@@ -54,6 +63,9 @@ def main():
             out[pre + "kernel_Mrec_s"] = n_recs / ms.value / 1e3
             if pre:
                 out[pre + "kernel_ratio"] = ms.value / out["kernel_ms"]
+
+    if args.truth:
+        truth_throughput(lib, args, head, block, k, out)
 
     pinned = lib.dwgsim_hip_host_alloc(n_bytes)
     if not pinned:
@@ -89,6 +101,85 @@ def main():
 
 # key prefix and EvalContext arguments of the plain form, of the breakdown at the default cap, and of the breakdown at cap 32
 FORMS = [("", {}), ("bd_", {"breakdown": "snps,errors,indels,end"}), ("bd32_", {"breakdown": "snps,errors,indels,end", "breakdown_cap": 32})]
+
+
+def renamed(block, c):
+    """the records of block under other names: copy c > 0 has #c behind every QNAME"""
+    return block if c == 0 else re.sub(rb"(?m)^([^\t\n]+)\t", rb"\1#%d\t" % c, block)
+
+
+def truth_for(head, block, copies):
+    """a truth SAM over the records of block: every (QNAME, end) once, under the names of the copies 0 ... copies - 1 (renamed), the copies
+    of one record next to each other, so that the records a run asks for lie spread over the whole truth"""
+    seen, lines = set(), []
+    for line in block.split(b"\n"):
+        f = line.split(b"\t")
+        if len(f) < 11:
+            continue
+        flag = int(f[1])
+        end = (flag >> 6) & 3 if flag & 1 else 0
+        if (f[0], end) in seen or (flag & 1 and end not in (1, 2)):
+            continue
+        seen.add((f[0], end))
+        rname = f[2] if f[2] != b"*" else b"chr1"
+        cigar = b"20M1I29M" if len(seen) % 8 == 0 else b"50M"
+        lines.append((f[0], b"\t%d\t%s\t%d\t255\t%s\t*\t0\t0\tACGT\tIIII\n" % (flag & 0xD1, rname, max(1, int(f[3])), cigar)))
+    suffix = [b""] + [b"#%d" % c for c in range(1, copies)]
+    return head + b"".join(q + x + rest for q, rest in lines for x in suffix), len(lines) * copies
+
+
+def truth_throughput(lib, args, head, block, k, out):
+    """Every record of the measured text has a name of its own (the block's records under k sets of names), so every look-up of a launch
+    goes to another slot and another record; the truth holds --truth-copies sets, the asked ones spread among them.  The plain form is
+    measured on the same text in the same run (keys dn_*: distinct names)."""
+    text = b"".join(renamed(block, c) for c in range(k))
+    n_recs = text.count(b"\n")
+    truth, n_truth = truth_for(head, block, max(args.truth_copies, k))
+    out.update({"truth_records": n_truth, "truth_bytes": len(truth), "truth_records_asked_for": n_truth // max(args.truth_copies, k) * k,
+                "dn_bytes": len(text), "dn_records": n_recs})
+    best = None
+    for _ in range(min(args.reps, 3)):
+        with api.EvalContext(a=args.a) as ctx:
+            t0 = time.perf_counter()
+            ctx.load_truth(io.BytesIO(truth), 64 << 20)
+            dt = time.perf_counter() - t0
+            best = dt if best is None else min(best, dt)
+    out["truth_load_s"] = best
+    out["truth_load_Mrec_s"] = n_truth / best / 1e6
+    out["truth_load_GBps"] = len(truth) / best / 1e9
+    times = {}
+    for pre, with_truth in (("dn_", False), ("tr_", True)):
+        with api.EvalContext(a=args.a) as ctx:
+            if with_truth:
+                ctx.load_truth(io.BytesIO(truth), 64 << 20)
+            ctx.header(head)
+            ms = C.c_double()
+            r = lib.dwgsim_hip_eval_debug_device_chunk(ctx.ctx, text, len(text), 1, C.byref(ms))      # warm-up
+            r = r or lib.dwgsim_hip_eval_debug_device_chunk(ctx.ctx, text, len(text), args.reps, C.byref(ms))
+            if r:
+                raise SystemExit("device chunk failed: %d" % r)
+            times[pre] = ms.value
+            out[pre + "kernel_ms"] = ms.value
+            out[pre + "kernel_Mrec_s"] = n_recs / ms.value / 1e3
+    out["tr_kernel_ratio"] = times["tr_"] / times["dn_"]
+    if args.bam:
+        import bam_io as B
+        payload, offs = B.bam_payload(head + text)
+        hdr, raw = payload[:offs[0]], payload[offs[0]:]
+        for pre, with_truth in (("dn_", False), ("tr_", True)):
+            with api.EvalContext(a=args.a) as ctx:
+                if with_truth:
+                    ctx.load_truth(io.BytesIO(truth), 64 << 20)
+                ctx.bam_begin()
+                ctx.feed_bam(B.bgzf(hdr, eof=False))
+                ms = C.c_double()
+                r = lib.dwgsim_hip_eval_debug_device_bam_chunk(ctx.ctx, raw, len(raw), 1, C.byref(ms))      # warm-up
+                r = r or lib.dwgsim_hip_eval_debug_device_bam_chunk(ctx.ctx, raw, len(raw), args.reps, C.byref(ms))
+                if r:
+                    raise SystemExit("device BAM chunk failed: %d" % r)
+                times[pre] = ms.value
+                out[pre + "bam_kernel_ms"] = ms.value
+        out["tr_bam_kernel_ratio"] = times["tr_"] / times["dn_"]
 
 
 def bam_throughput(lib, args, head, block, k, out):
