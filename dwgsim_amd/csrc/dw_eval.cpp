@@ -22,6 +22,12 @@
 // bam_begin uploads the map from the file's targets to the truth's contigs (map_contigs).  finish() makes the section from the 64-bit counters.
 // A container error (framing, inflate, CRC, ISIZE, magic, header, a file that ends inside something) first evaluates the whole records in
 // front of it: a fatal record there wins; otherwise the call returns DWGSIM_HIP_ERR_FAILED and last_error says what and where.
+//
+// The file in order.  The context's parts, each a struct: Slot and Pipeline (the chunks), NameTable (the targets of the current file; the
+// truth's contigs), BamStream, Outcome (what finish() reports), BreakdownRun, TruthRun.  Then: the kernels' arguments and launch(), the one
+// place that knows the run's form; process_oldest / hand_over / submit, the one way a chunk of either format goes to the device and comes
+// back; end_file; the name tables' upload; the BAM stream (whole_record, hop_records, bam_pump); convert_ctx; the truth's load; the texts;
+// begin_file, what header and bam_begin share; the C-ABI.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -66,63 +72,155 @@ struct Slot {
     size_t hop = 0;
 };
 
+// The chunk pipeline: the filling slot s[cur], and the submitted ones in submission order.
+struct Pipeline {
+    Slot s[2];
+    int cur = 0;
+    std::deque<int> pending;
+    Slot &filling() { return s[cur]; }
+};
+
+// A name table: contig names, names[off[t] .. off[t + 1]), with the open-addressing hash of ev::Targets over them (a repeated name: the first);
+// host copies (messages, map_contigs) and device copies (kernels).  tg is over the device copies, and empty until upload_names.
+struct NameTable {
+    std::string names;
+    std::vector<uint32_t> off = {0};
+    std::vector<int32_t> hash;
+    DevMem d_names, d_off, d_hash;      // char, u32, i32
+    ev::Targets tg = {};
+
+    int32_t n() const { return (int32_t)off.size() - 1; }
+    ev::Targets host() const { return {names.data(), off.data(), hash.data(), n(), (uint32_t)hash.size() - 1}; }
+
+    // from a finished names / off pair (the reference list of a BAM header)
+    void from_names(const std::string &nm, const std::vector<uint32_t> &o)
+    {
+        names = nm;
+        off = o;
+        uint32_t hs = 2;
+        while (hs < 2u * (uint32_t)n()) hs <<= 1;
+        hash.assign(hs, -1);
+        for (int32_t t = 0; t < n(); ++t) {
+            const uint32_t b = off[t], len = off[t + 1] - b;
+            uint32_t h = ev::fnv1a(names.data() + b, len) & (hs - 1);
+            while (hash[h] >= 0) {
+                const int32_t u = hash[h];
+                if (off[u + 1] - off[u] == len && !memcmp(names.data() + off[u], names.data() + b, len)) break;
+                h = (h + 1) & (hs - 1);
+            }
+            if (hash[h] < 0) hash[h] = t;
+        }
+    }
+
+    // from the SN: names of the @SQ lines of a header text
+    void from_sq(const char *text, size_t len)
+    {
+        std::string nm;
+        std::vector<uint32_t> o(1, 0);
+        for (size_t p = 0; p < len;) {
+            const char *nl = (const char *)memchr(text + p, '\n', len - p);
+            const size_t e = nl ? (size_t)(nl - text) : len;
+            if (e - p >= 3 && !memcmp(text + p, "@SQ", 3)) {
+                for (size_t f = p; f < e;) {
+                    const char *tab = (const char *)memchr(text + f, '\t', e - f);
+                    const size_t fe = tab ? (size_t)(tab - text) : e;
+                    if (f > p && fe - f >= 3 && !memcmp(text + f, "SN:", 3)) {
+                        nm.append(text + f + 3, fe - f - 3);
+                        o.push_back((uint32_t)nm.size());
+                        break;
+                    }
+                    f = fe + 1;
+                }
+            }
+            p = e + 1;
+        }
+        from_names(nm, o);
+    }
+
+    void drop_device()
+    {
+        d_names.reset(); d_off.reset(); d_hash.reset();
+        tg = ev::Targets{};
+    }
+};
+
+// The BGZF stream of the current BAM file, and what inflates it.
+struct BamStream {
+    int inflate_threads = DEFAULT_INFLATE_THREADS;
+    std::unique_ptr<bam::InflatePool> pool;     // (made at the first use)
+    std::vector<uint8_t> zbuf;          // compressed bytes not yet consumed: zbuf[zhead] is byte zpos of the file
+    size_t zhead = 0;
+    uint64_t zpos = 0;
+    bool in_header = false;             // the BAM header is not complete yet
+    bool bam_stop = false;              // a block_size that no record can have ended the stream
+    std::vector<uint8_t> hdr_bytes;     // inflated bytes while the header is incomplete
+    bam::Header bh;
+    std::vector<bam::InflateJob> jobs;
+
+    // the stream of a new file; the workers stay
+    void restart()
+    {
+        BamStream fresh;
+        fresh.inflate_threads = inflate_threads;
+        fresh.pool = std::move(pool);
+        fresh.in_header = true;
+        *this = std::move(fresh);
+    }
+};
+
+// The run's outcome: what finish() reports.  After the first fatal record (failed) nothing else is counted any more.
+struct Outcome {
+    bool failed = false;
+    int code = 0;
+    uint64_t err_rec = 0;
+    std::string err_line;
+    uint64_t n = 0, records = 0;
+    std::string incorrect, table, stderr_text;
+};
+
+// The breakdown: what is selected, its device counters, its part of the spill lists, its text.
+struct BreakdownRun {
+    evt::Breakdown b;
+    evt::BreakdownCounts spill;
+    DevMem d_hist;                      // unsigned long long
+    std::string text;
+};
+
+// The truth (dw_eval.hpp TRUTH): its contigs, its records, CIGAR pool and index on the device, the 64-bit counters, its text.
+struct TruthRun {
+    bool begun = false, fed = false, committed = false, bad = false;
+    NameTable contigs;                  // (their device copies are the load's own, as d_cnt and d_err are: freed by commit)
+    DevMem d_cnt, d_err;
+    DevMem d_recs, d_pool, d_slots, d_ctrs, d_tmap;     // TruthRec, u32, u64, u64, i32
+    uint64_t n_recs = 0, n_pool = 0;
+    uint32_t mask = 0;
+    int force_log2 = -1;
+    std::string text;
+};
+
 } // namespace
 
+// The fields outside the parts are the run's: options, state of the calls, the plain form's counters.  While fmt == FMT_SAM nothing of `bam`
+// means anything but its workers; `bd` is empty unless bd.b.on, and `tr` unless tr.begun.
 struct dwgsim_hip_eval_ctx {
     dwgsim_hip_eval_opts_t o;
     std::string P;
     int device = 0;
-    std::string err;
-    Slot s[2];
-    int cur = 0;
-    std::deque<int> pending;
-    // targets of the current file: host copies (messages) and device copies (kernels)
-    std::string names;
-    std::vector<uint32_t> off;
-    std::vector<int32_t> hash;
-    DevMem d_names, d_off, d_hash;      // char, u32, i32
-    ev::Targets tg = {};
+    std::string err;                    // last_error
+    bool begun = false;                 // a header, bam_begin or feed call has been made
+    bool finished = false, seen_header = false;
+    bool broken = false;                // a container error ended the run
+    int fmt = FMT_SAM;                  // the current file's format
+    int32_t floor_score = ev::MINAS;
+    double kernel_ms = 0;
     DevMem d_P, d_hist;                 // char, unsigned long long
     evt::Rows spill;
-    // the breakdown: what is selected, its device counters, its part of the spill lists, its text
-    evt::Breakdown bd;
-    evt::BreakdownCounts bdc;
-    DevMem d_bdhist;                    // unsigned long long
-    std::string bd_text;
-    bool begun = false;                 // a header, bam_begin or feed call has been made
-    uint64_t n = 0, records = 0;
-    bool failed = false, finished = false, seen_header = false;
-    int code = 0;
-    uint64_t err_rec = 0;
-    std::string err_line;
-    std::string incorrect, table, stderr_text;
-    double kernel_ms = 0;
-    int32_t floor_score = ev::MINAS;
-    // the current file's format, and the state of a BAM stream
-    int fmt = FMT_SAM;
-    int inflate_threads = DEFAULT_INFLATE_THREADS;
-    std::unique_ptr<bam::InflatePool> pool;
-    std::vector<uint8_t> zbuf;          // compressed bytes not yet consumed: zbuf[zhead] is byte zpos of the file
-    size_t zhead = 0;
-    uint64_t zpos = 0;
-    // the truth (dw_eval.hpp TRUTH): its contigs, its records, CIGAR pool and index on the device, the 64-bit counters, its text
-    struct Truth {
-        bool begun = false, fed = false, committed = false, bad = false;
-        std::string names;
-        std::vector<uint32_t> off;
-        std::vector<int32_t> hash;
-        DevMem d_names, d_off, d_hash, d_cnt, d_err;       // (the load's own: freed by commit)
-        ev::Targets tg = {};
-        DevMem d_recs, d_pool, d_slots, d_ctrs, d_tmap;     // TruthRec, u32, u64, u64, i32
-        uint64_t n_recs = 0, n_pool = 0;
-        uint32_t mask = 0;
-        int force_log2 = -1;
-        std::string text;
-    } tr;
-    bool in_header = false, bam_stop = false, broken = false;
-    std::vector<uint8_t> hdr_bytes;     // inflated bytes while the header is incomplete
-    bam::Header bh;
-    std::vector<bam::InflateJob> jobs;
+    Pipeline pipe;
+    NameTable targets;                  // of the current file
+    BamStream bam;
+    Outcome out;
+    BreakdownRun bd;
+    TruthRun tr;
 };
 
 namespace {
@@ -210,39 +308,23 @@ ev::Opts dev_opts(const dwgsim_hip_eval_ctx *c)
     return o;
 }
 
-uint32_t bam_records_grid(uint32_t n_rec)
-{
-    const uint32_t g = (n_rec + 255) / 256;      // one record per lane
-    return g < 1 ? 1 : g > 1024 ? 1024 : g;
-}
-
-uint32_t records_grid(size_t len)
-{
-    const size_t g = (len + 256 * 256 - 1) / (256 * 256);       // about 256 bytes of text per lane
-    return (uint32_t)(g < 1 ? 1 : g > 1024 ? 1024 : g);
-}
-
 EvalRecArgs rec_args(dwgsim_hip_eval_ctx *c, const uint8_t *text, uint32_t *ends, EvalRes *res, uint64_t *spill, uint8_t *flags, uint32_t has_ctx)
 {
     EvalRecArgs A;
     A.text = text; A.ends = ends; A.res = res; A.hist = c->d_hist.get<unsigned long long>(); A.spill = spill; A.flags = flags; A.has_ctx = has_ctx;
-    A.win_lo = WIN_LO; A.floor_score = c->floor_score; A.opt = dev_opts(c); A.tg = c->tg;
+    A.win_lo = WIN_LO; A.floor_score = c->floor_score; A.opt = dev_opts(c); A.tg = c->targets.tg;
     return A;
 }
 
 EvalBdArgs bd_args(dwgsim_hip_eval_ctx *c)
 {
-    const evt::Breakdown &b = c->bd;
+    const evt::Breakdown &b = c->bd.b;
     EvalBdArgs B;
-    B.hist = c->d_bdhist.get<unsigned long long>(); B.n_rows = (uint32_t)b.n_rows; B.win = b.win; B.win_lo = b.win_lo; B.cap = b.cap;
+    B.hist = c->bd.d_hist.get<unsigned long long>(); B.n_rows = (uint32_t)b.n_rows; B.win = b.win; B.win_lo = b.win_lo; B.cap = b.cap;
     B.row_snps = b.row[ev::D_SNPS]; B.row_errors = b.row[ev::D_ERRORS]; B.row_indels = b.row[ev::D_INDELS]; B.row_end = b.row[ev::D_END];
     return B;
 }
 
-// the breakdown form's blocks have twice the lanes
-uint32_t bd_grid(uint32_t plain_grid) { return (plain_grid + 1) / 2; }
-
-// the record kernels of a SAM chunk / a BAM chunk, in the form that the run uses
 EvalTruthArgs truth_args(dwgsim_hip_eval_ctx *c)
 {
     EvalTruthArgs T;
@@ -251,54 +333,51 @@ EvalTruthArgs truth_args(dwgsim_hip_eval_ctx *c)
     return T;
 }
 
-void launch_chunk(dwgsim_hip_eval_ctx *c, hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tiles)
+// the kernels of one chunk in the form that the run uses: `size` bytes of SAM lines, or `size` BAM records behind the context record
+void launch(dwgsim_hip_eval_ctx *c, hipStream_t st, const EvalRecArgs &A, int fmt, uint64_t size, uint32_t *tiles)
 {
-    if (c->bd.on) launch_eval_chunk_bd(st, A, bd_args(c), len, tiles, bd_grid(records_grid(len)));
-    else if (c->tr.committed) launch_eval_chunk_tr(st, A, truth_args(c), len, tiles, records_grid(len));
-    else launch_eval_chunk(st, A, len, tiles, records_grid(len));
-}
-
-void launch_bam_chunk(dwgsim_hip_eval_ctx *c, hipStream_t st, const EvalRecArgs &A, uint32_t n_rec)
-{
-    if (c->bd.on) launch_eval_bam_chunk_bd(st, A, bd_args(c), bd_grid(bam_records_grid(n_rec)));
-    else if (c->tr.committed) launch_eval_bam_chunk_tr(st, A, truth_args(c), bam_records_grid(n_rec));
-    else launch_eval_bam_chunk(st, A, bam_records_grid(n_rec));
+    const EvalBdArgs B = bd_args(c);
+    const EvalTruthArgs T = truth_args(c);
+    const EvalBdArgs *bd = c->bd.b.on ? &B : nullptr;
+    const EvalTruthArgs *tr = c->tr.committed ? &T : nullptr;
+    if (fmt == FMT_BAM) launch_eval_bam_chunk(st, A, bd, tr, (uint32_t)size);
+    else launch_eval_chunk(st, A, bd, tr, size, tiles);
 }
 
 // the results of the oldest submitted chunk
 int process_oldest(dwgsim_hip_eval_ctx *c)
 {
-    const int k = c->pending.front();
-    c->pending.pop_front();
-    Slot &S = c->s[k];
+    const int k = c->pipe.pending.front();
+    c->pipe.pending.pop_front();
+    Slot &S = c->pipe.s[k];
     CK(hipStreamSynchronize(S.st.get()));
     S.busy = false;
     float ms = 0;
     if (hipEventElapsedTime(&ms, S.e0.get(), S.e1.get()) == hipSuccess) c->kernel_ms += ms;
-    if (c->failed) return DWGSIM_HIP_OK;
+    if (c->out.failed) return DWGSIM_HIP_OK;
     const EvalRes r = *S.h_res.get<EvalRes>();
     const uint32_t n_rec = r.n_lines - S.has_ctx;
     if (r.err != ~0ull) {
         const uint64_t rec = r.err >> 8;
-        c->failed = true;
-        c->code = (int)(r.err & 0xff);
-        c->err_rec = c->records + rec;
+        c->out.failed = true;
+        c->out.code = (int)(r.err & 0xff);
+        c->out.err_rec = c->out.records + rec;
         if (S.fmt == FMT_BAM) {
-            c->err_line.clear();
-            if (c->code != ev::E_MALFORMED) bam::record_to_sam(S.h_text.get() + S.h_offs.get<uint32_t>()[rec + S.has_ctx], c->bh, c->err_line);
+            c->out.err_line.clear();
+            if (c->out.code != ev::E_MALFORMED) bam::record_to_sam(S.h_text.get() + S.h_offs.get<uint32_t>()[rec + S.has_ctx], c->bam.bh, c->out.err_line);
             return DWGSIM_HIP_OK;
         }
         const char *p = S.h_text.get<char>();
         for (uint64_t i = 0; i < rec + S.has_ctx; ++i) p = (const char *)memchr(p, '\n', S.h_text.get<char>() + S.len - p) + 1;
-        c->err_line.assign(p, (const char *)memchr(p, '\n', S.h_text.get<char>() + S.len - p) - p);
+        c->out.err_line.assign(p, (const char *)memchr(p, '\n', S.h_text.get<char>() + S.len - p) - p);
         return DWGSIM_HIP_OK;
     }
-    c->n += r.n;
-    c->records += n_rec;
+    c->out.n += r.n;
+    c->out.records += n_rec;
     if (r.n_spill) {
         std::vector<uint64_t> sp(r.n_spill);
         CK(hipMemcpy(sp.data(), S.d_spill.get<uint64_t>(), sp.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        if (c->bd.on) for (uint64_t w : sp) c->bdc.add_spill(c->bd, w, &c->spill);
+        if (c->bd.b.on) for (uint64_t w : sp) c->bd.spill.add_spill(c->bd.b, w, &c->spill);
         else for (uint64_t w : sp) c->spill[(int32_t)(uint32_t)(w >> 32)][(int)(w & 7)]++;
     }
     if (c->o.p && n_rec) {
@@ -307,15 +386,15 @@ int process_oldest(dwgsim_hip_eval_ctx *c)
         if (S.fmt == FMT_BAM) {
             for (uint32_t i = 0; i < n_rec; ++i)
                 if (fl[i]) {
-                    bam::record_to_sam(S.h_text.get() + S.h_offs.get<uint32_t>()[i + S.has_ctx], c->bh, c->incorrect);
-                    c->incorrect += '\n';
+                    bam::record_to_sam(S.h_text.get() + S.h_offs.get<uint32_t>()[i + S.has_ctx], c->bam.bh, c->out.incorrect);
+                    c->out.incorrect += '\n';
                 }
             return DWGSIM_HIP_OK;
         }
         const char *p = S.h_text.get<char>() + S.ctx_len, *end = S.h_text.get<char>() + S.len;
         for (uint32_t i = 0; i < n_rec; ++i) {
             const char *e = (const char *)memchr(p, '\n', end - p) + 1;
-            if (fl[i]) c->incorrect.append(p, e - p);
+            if (fl[i]) c->out.incorrect.append(p, e - p);
             p = e;
         }
     }
@@ -324,7 +403,7 @@ int process_oldest(dwgsim_hip_eval_ctx *c)
 
 int drain(dwgsim_hip_eval_ctx *c)
 {
-    while (!c->pending.empty()) {
+    while (!c->pipe.pending.empty()) {
         const int r = process_oldest(c);
         if (r) return r;
     }
@@ -335,11 +414,11 @@ int drain(dwgsim_hip_eval_ctx *c)
 // busy) and starts with the chunk's last record [lb, cut), the context record, and what follows the chunk.
 int hand_over(dwgsim_hip_eval_ctx *c, size_t cut, size_t lb)
 {
-    Slot &S = c->s[c->cur];
+    Slot &S = c->pipe.filling();
     S.busy = true;
-    c->pending.push_back(c->cur);
-    c->cur ^= 1;
-    Slot &T = c->s[c->cur];
+    c->pipe.pending.push_back(c->pipe.cur);
+    c->pipe.cur ^= 1;
+    Slot &T = c->pipe.filling();
     if (T.busy) {
         const int r = process_oldest(c);
         if (r) return r;
@@ -352,49 +431,37 @@ int hand_over(dwgsim_hip_eval_ctx *c, size_t cut, size_t lb)
     return DWGSIM_HIP_OK;
 }
 
-// submit the filling slot's text up to `cut` (just past a newline); the other slot continues with the context line and the rest
+// Submit the filling slot's chunk [0, cut) and continue in the other slot with the chunk's last record and what follows the chunk.
+// SAM: `cut` is just past a newline.  BAM: `cut` is the slot's hop, the end of its last whole record; the offsets go up with the text, the
+// device is told their number instead of counting newlines, and the new slot's offset list starts with its context record.
 int submit(dwgsim_hip_eval_ctx *c, size_t cut)
 {
-    Slot &S = c->s[c->cur];
+    Slot &S = c->pipe.filling();
+    const bool bam = S.fmt == FMT_BAM;
+    const uint32_t n = bam ? S.n_offs : 0;
+    hipStream_t st = S.st.get();
+    EvalRes *hres = S.h_res.get<EvalRes>(), *dres = S.d_res.get<EvalRes>();
     S.len = cut;
-    *S.h_res.get<EvalRes>() = EvalRes{~0ull, 0, 0, 0};
-    CK(hipEventRecord(S.e0.get(), S.st.get()));
-    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, S.st.get()));
-    CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st.get()));
-    const EvalRecArgs A = rec_args(c, S.d_text.get(), S.d_ends.get<uint32_t>(), S.d_res.get<EvalRes>(), S.d_spill.get<uint64_t>(), c->o.p ? S.d_flags.get() : nullptr, S.has_ctx);
-    launch_chunk(c, S.st.get(), A, cut, S.d_tiles.get<uint32_t>());
+    *hres = EvalRes{~0ull, 0, n, 0};
+    CK(hipEventRecord(S.e0.get(), st));
+    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, st));
+    if (bam) CK(hipMemcpyAsync(S.d_ends.get(), S.h_offs.get(), n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(dres, hres, sizeof(EvalRes), hipMemcpyHostToDevice, st));
+    const EvalRecArgs A = rec_args(c, S.d_text.get(), S.d_ends.get<uint32_t>(), dres, S.d_spill.get<uint64_t>(), c->o.p ? S.d_flags.get() : nullptr, S.has_ctx);
+    launch(c, st, A, S.fmt, bam ? n - S.has_ctx : cut, S.d_tiles.get<uint32_t>());
     CK(hipGetLastError());
-    CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st.get()));
-    CK(hipEventRecord(S.e1.get(), S.st.get()));
-    // the last line of the submitted chunk, then what follows it
-    size_t lb = cut - 1;
-    while (lb > 0 && S.h_text.get<char>()[lb - 1] != '\n') --lb;
-    return hand_over(c, cut, lb);
-}
-
-// the whole records of the filling slot (BAM): text and offsets up, one kernel, result back
-int submit_bam(dwgsim_hip_eval_ctx *c)
-{
-    Slot &S = c->s[c->cur];
-    const size_t cut = S.hop;
-    const uint32_t n = S.n_offs;
-    S.len = cut;
-    *S.h_res.get<EvalRes>() = EvalRes{~0ull, 0, n, 0};
-    CK(hipEventRecord(S.e0.get(), S.st.get()));
-    CK(hipMemcpyAsync(S.d_text.get(), S.h_text.get<char>(), cut, hipMemcpyHostToDevice, S.st.get()));
-    CK(hipMemcpyAsync(S.d_ends.get(), S.h_offs.get(), n * sizeof(uint32_t), hipMemcpyHostToDevice, S.st.get()));
-    CK(hipMemcpyAsync(S.d_res.get<EvalRes>(), S.h_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyHostToDevice, S.st.get()));
-    const EvalRecArgs A = rec_args(c, S.d_text.get(), S.d_ends.get<uint32_t>(), S.d_res.get<EvalRes>(), S.d_spill.get<uint64_t>(), c->o.p ? S.d_flags.get() : nullptr, S.has_ctx);
-    launch_bam_chunk(c, S.st.get(), A, n - S.has_ctx);
-    CK(hipGetLastError());
-    CK(hipMemcpyAsync(S.h_res.get<EvalRes>(), S.d_res.get<EvalRes>(), sizeof(EvalRes), hipMemcpyDeviceToHost, S.st.get()));
-    CK(hipEventRecord(S.e1.get(), S.st.get()));
-    const int r = hand_over(c, cut, S.h_offs.get<uint32_t>()[n - 1]);
-    if (r) return r;
-    Slot &T = c->s[c->cur];
-    T.h_offs.get<uint32_t>()[0] = 0;
-    T.n_offs = 1; T.hop = T.ctx_len;
-    S.n_offs = 0; S.hop = 0;
+    CK(hipMemcpyAsync(hres, dres, sizeof(EvalRes), hipMemcpyDeviceToHost, st));
+    CK(hipEventRecord(S.e1.get(), st));
+    // where the chunk's last record starts
+    size_t lb = bam ? S.h_offs.get<uint32_t>()[n - 1] : cut - 1;
+    while (!bam && lb > 0 && S.h_text.get<char>()[lb - 1] != '\n') --lb;
+    if (const int r = hand_over(c, cut, lb)) return r;
+    if (bam) {
+        Slot &T = c->pipe.filling();
+        T.h_offs.get<uint32_t>()[0] = 0;
+        T.n_offs = 1; T.hop = T.ctx_len;
+        S.n_offs = 0; S.hop = 0;
+    }
     return DWGSIM_HIP_OK;
 }
 
@@ -403,10 +470,10 @@ int grow(dwgsim_hip_eval_ctx *c)
 {
     int r = drain(c);
     if (r) return r;
-    Slot &F = c->s[c->cur];
+    Slot &F = c->pipe.filling();
     const size_t cap = F.h_text.cap() * 2;
     std::string keep(F.h_text.get<char>(), F.fill);
-    for (Slot &S : c->s) if ((r = slot_alloc(c, S, cap))) return r;
+    for (Slot &S : c->pipe.s) if ((r = slot_alloc(c, S, cap))) return r;
     memcpy(F.h_text.get<char>(), keep.data(), keep.size());
     if (F.fmt == FMT_BAM && F.has_ctx) F.h_offs.get<uint32_t>()[0] = 0;      // (grow is for a slot without a whole record behind its context)
     return DWGSIM_HIP_OK;
@@ -419,121 +486,74 @@ int end_file(dwgsim_hip_eval_ctx *c)
 {
     if (c->broken) return DWGSIM_HIP_ERR_FAILED;
     if (c->fmt == FMT_BAM) return end_bam_file(c);
-    Slot &F = c->s[c->cur];
+    Slot &F = c->pipe.filling();
     if (F.fill > F.ctx_len && F.h_text.get<char>()[F.fill - 1] != '\n') {
         if (F.fill == F.h_text.cap()) {
             const int r = grow(c);
             if (r) return r;
         }
-        Slot &G = c->s[c->cur];
+        Slot &G = c->pipe.filling();
         G.h_text.get<char>()[G.fill++] = '\n';
     }
-    Slot &H = c->s[c->cur];
-    if (H.fill > H.ctx_len && !c->failed) {
+    Slot &H = c->pipe.filling();
+    if (H.fill > H.ctx_len && !c->out.failed) {
         const int r = submit(c, H.fill);
         if (r) return r;
     }
     return drain(c);
 }
 
-// the SN: names of the @SQ lines of a header text: names[off[t] .. off[t + 1])
-void sq_names(const char *text, size_t len, std::string &names, std::vector<uint32_t> &off)
+// the device copies of a name table, and its ev::Targets over them
+int upload_names(dwgsim_hip_eval_ctx *c, NameTable &t)
 {
-    names.clear();
-    off.assign(1, 0);
-    for (size_t p = 0; p < len;) {
-        const char *nl = (const char *)memchr(text + p, '\n', len - p);
-        const size_t e = nl ? (size_t)(nl - text) : len;
-        if (e - p >= 3 && !memcmp(text + p, "@SQ", 3)) {
-            for (size_t f = p; f < e;) {
-                const char *tab = (const char *)memchr(text + f, '\t', e - f);
-                const size_t fe = tab ? (size_t)(tab - text) : e;
-                if (f > p && fe - f >= 3 && !memcmp(text + f, "SN:", 3)) {
-                    names.append(text + f + 3, fe - f - 3);
-                    off.push_back((uint32_t)names.size());
-                    break;
-                }
-                f = fe + 1;
-            }
-        }
-        p = e + 1;
-    }
-}
-
-// the open-addressing hash of ev::Targets over such names (a repeated name: the first)
-void hash_names(const std::string &names, const std::vector<uint32_t> &off, std::vector<int32_t> &hash)
-{
-    const int32_t nt = (int32_t)off.size() - 1;
-    uint32_t hs = 2;
-    while (hs < 2u * (uint32_t)nt) hs <<= 1;
-    hash.assign(hs, -1);
-    for (int32_t t = 0; t < nt; ++t) {
-        const uint32_t b = off[t], n = off[t + 1] - b;
-        uint32_t h = ev::fnv1a(names.data() + b, n) & (hs - 1);
-        while (hash[h] >= 0) {
-            const int32_t u = hash[h];
-            if (off[u + 1] - off[u] == n && !memcmp(names.data() + off[u], names.data() + b, n)) break;
-            h = (h + 1) & (hs - 1);
-        }
-        if (hash[h] < 0) hash[h] = t;
-    }
-}
-
-// device copies of names, offsets and hash, and the ev::Targets over them
-int upload_names(dwgsim_hip_eval_ctx *c, const std::string &names, const std::vector<uint32_t> &off, const std::vector<int32_t> &hash, DevMem &d_names,
-                 DevMem &d_off, DevMem &d_hash, ev::Targets *tg)
-{
-    if (const int r = upload(c, d_names, names.data(), names.size() + 1)) return r;
-    if (const int r = upload(c, d_off, off.data(), off.size() * sizeof(uint32_t))) return r;
-    if (const int r = upload(c, d_hash, hash.data(), hash.size() * sizeof(int32_t))) return r;
-    tg->names = d_names.get<char>(); tg->off = d_off.get<uint32_t>(); tg->hash = d_hash.get<int32_t>(); tg->n = (int32_t)off.size() - 1; tg->hmask = (uint32_t)hash.size() - 1;
+    if (const int r = upload(c, t.d_names, t.names.data(), t.names.size() + 1)) return r;
+    if (const int r = upload(c, t.d_off, t.off.data(), t.off.size() * sizeof(uint32_t))) return r;
+    if (const int r = upload(c, t.d_hash, t.hash.data(), t.hash.size() * sizeof(int32_t))) return r;
+    t.tg = {t.d_names.get<char>(), t.d_off.get<uint32_t>(), t.d_hash.get<int32_t>(), t.n(), (uint32_t)t.hash.size() - 1};
     return DWGSIM_HIP_OK;
 }
 
 // with a truth: for every target of the current file the truth contig of the same name, or -1
-int map_contigs(dwgsim_hip_eval_ctx *c)
+int map_contigs(dwgsim_hip_eval_ctx *c, const NameTable &file, const NameTable &truth)
 {
     if (!c->tr.committed) return DWGSIM_HIP_OK;
-    const ev::Targets T = {c->tr.names.data(), c->tr.off.data(), c->tr.hash.data(), (int32_t)c->tr.off.size() - 1, (uint32_t)c->tr.hash.size() - 1};
-    std::vector<int32_t> map(c->off.size(), -1);        // (one more than the targets: never empty)
-    for (size_t t = 0; t + 1 < c->off.size(); ++t) map[t] = ev::target_find(T, c->names.data() + c->off[t], c->off[t + 1] - c->off[t]);
+    const ev::Targets T = truth.host();
+    std::vector<int32_t> map(file.off.size(), -1);        // (one more than the targets: never empty)
+    for (int32_t t = 0; t < file.n(); ++t) map[t] = ev::target_find(T, file.names.data() + file.off[t], file.off[t + 1] - file.off[t]);
     return upload(c, c->tr.d_tmap, map.data(), map.size() * sizeof(int32_t));
 }
 
-// c->names / c->off (the @SQ names of a SAM header, or the reference list of a BAM file): the hash, and the device copies
-int build_targets(dwgsim_hip_eval_ctx *c)
+// c->targets (from the @SQ names of a SAM header, or the reference list of a BAM file) on the device, and mapped to the truth's contigs
+int upload_targets(dwgsim_hip_eval_ctx *c)
 {
-    hash_names(c->names, c->off, c->hash);
-    if (const int r = upload_names(c, c->names, c->off, c->hash, c->d_names, c->d_off, c->d_hash, &c->tg)) return r;
-    return map_contigs(c);
-}
-
-int upload_targets(dwgsim_hip_eval_ctx *c, const char *text, size_t len)
-{
-    sq_names(text, len, c->names, c->off);
-    return build_targets(c);
+    if (const int r = upload_names(c, c->targets)) return r;
+    return map_contigs(c, c->targets, c->tr.contigs);
 }
 
 // ---- BAM stream ----
 
+// The record at offset `at` of `fill` bytes of BAM records: its size, block_size field included, when all of it is there; 0 when it is not
+// there yet; -1 when its block_size is one that no record can have.
+int64_t whole_record(const uint8_t *t, size_t fill, size_t at)
+{
+    if (fill - at < 4) return 0;
+    const uint32_t bs = bam::le32(t + at);
+    if (bs < ev::BAM_FIXED || bs > ev::BAM_MAX_BLOCK) return -1;
+    return fill - at - 4 < bs ? 0 : 4 + (int64_t)bs;
+}
+
 // the whole records that the filling slot's new bytes complete; a block_size that no record can have ends the stream with that record
 void hop_records(dwgsim_hip_eval_ctx *c)
 {
-    Slot &F = c->s[c->cur];
-    const uint8_t *t = F.h_text.get();
+    Slot &F = c->pipe.filling();
     uint32_t *offs = F.h_offs.get<uint32_t>();
-    while (F.fill - F.hop >= 4) {
-        const uint32_t bs = bam::le32(t + F.hop);
-        if (bs < ev::BAM_FIXED || bs > ev::BAM_MAX_BLOCK) {
-            offs[F.n_offs++] = (uint32_t)F.hop;
-            F.hop += 4;
-            F.fill = F.hop;
-            c->bam_stop = true;
-            return;
-        }
-        if (F.fill - F.hop - 4 < bs) return;
+    int64_t k;
+    for (; (k = whole_record(F.h_text.get(), F.fill, F.hop)) > 0; F.hop += (size_t)k) offs[F.n_offs++] = (uint32_t)F.hop;
+    if (k < 0) {
         offs[F.n_offs++] = (uint32_t)F.hop;
-        F.hop += 4 + (size_t)bs;
+        F.hop += 4;
+        F.fill = F.hop;
+        c->bam.bam_stop = true;
     }
 }
 
@@ -541,9 +561,9 @@ void hop_records(dwgsim_hip_eval_ctx *c)
 int bam_room(dwgsim_hip_eval_ctx *c, size_t need)
 {
     for (;;) {
-        Slot &F = c->s[c->cur];
+        Slot &F = c->pipe.filling();
         if (F.h_text.cap() - F.fill >= need) return DWGSIM_HIP_OK;
-        const int r = F.n_offs > F.has_ctx ? submit_bam(c) : grow(c);
+        const int r = F.n_offs > F.has_ctx ? submit(c, F.hop) : grow(c);
         if (r) return r;
     }
 }
@@ -551,12 +571,12 @@ int bam_room(dwgsim_hip_eval_ctx *c, size_t need)
 // A container error at byte `at` of the compressed file.  The whole records in front of it are evaluated first: a fatal record wins.
 int container_error(dwgsim_hip_eval_ctx *c, const char *why, uint64_t at)
 {
-    Slot &F = c->s[c->cur];
+    Slot &F = c->pipe.filling();
     int r = DWGSIM_HIP_OK;
-    if (F.n_offs > F.has_ctx && !c->failed) r = submit_bam(c);
+    if (F.n_offs > F.has_ctx && !c->out.failed) r = submit(c, F.hop);
     if (!r) r = drain(c);
     if (r) return r;
-    if (c->failed) return DWGSIM_HIP_EVAL_STOPPED;
+    if (c->out.failed) return DWGSIM_HIP_EVAL_STOPPED;
     char buf[64];
     snprintf(buf, sizeof buf, " at byte %llu of the compressed file", (unsigned long long)at);
     c->err = std::string("BAM input: ") + why + buf;
@@ -567,19 +587,18 @@ int container_error(dwgsim_hip_eval_ctx *c, const char *why, uint64_t at)
 // the header is complete: targets, the -p header text, and the bytes behind it as the first record bytes
 int bam_header_done(dwgsim_hip_eval_ctx *c, size_t hlen)
 {
-    c->in_header = false;
-    if (!c->seen_header && c->o.p) c->incorrect = c->bh.text;
+    c->bam.in_header = false;
+    if (!c->seen_header && c->o.p) c->out.incorrect = c->bam.bh.text;
     c->seen_header = true;
-    c->names = c->bh.names;
-    c->off = c->bh.off;
-    int r = build_targets(c);
+    c->targets.from_names(c->bam.bh.names, c->bam.bh.off);
+    int r = upload_targets(c);
     if (r) return r;
-    const size_t rest = c->hdr_bytes.size() - hlen;
+    const size_t rest = c->bam.hdr_bytes.size() - hlen;
     if ((r = bam_room(c, rest))) return r;
-    Slot &F = c->s[c->cur];
-    if (rest) memcpy(F.h_text.get() + F.fill, c->hdr_bytes.data() + hlen, rest);
+    Slot &F = c->pipe.filling();
+    if (rest) memcpy(F.h_text.get() + F.fill, c->bam.hdr_bytes.data() + hlen, rest);
     F.fill += rest;
-    std::vector<uint8_t>().swap(c->hdr_bytes);
+    std::vector<uint8_t>().swap(c->bam.hdr_bytes);
     hop_records(c);
     return DWGSIM_HIP_OK;
 }
@@ -587,24 +606,24 @@ int bam_header_done(dwgsim_hip_eval_ctx *c, size_t hlen)
 // everything that the collected compressed bytes allow
 int bam_pump(dwgsim_hip_eval_ctx *c)
 {
-    if (!c->pool) c->pool.reset(new bam::InflatePool(c->inflate_threads));
-    while (!c->failed && !c->bam_stop) {
-        const uint8_t *z = c->zbuf.data() + c->zhead;
-        const size_t avail = c->zbuf.size() - c->zhead;
+    if (!c->bam.pool) c->bam.pool.reset(new bam::InflatePool(c->bam.inflate_threads));
+    while (!c->out.failed && !c->bam.bam_stop) {
+        const uint8_t *z = c->bam.zbuf.data() + c->bam.zhead;
+        const size_t avail = c->bam.zbuf.size() - c->bam.zhead;
         const char *why = nullptr;
         bam::BgzfBlock b;
-        if (c->in_header) {
+        if (c->bam.in_header) {
             const int k = bam::bgzf_block_at(z, avail, &b, &why);
             if (k == 0) break;
-            if (k < 0) return container_error(c, why, c->zpos);
-            const size_t at = c->hdr_bytes.size();
-            c->hdr_bytes.resize(at + b.isize);
-            bam::InflateJob j = {z + b.data_off, b.data_len, c->hdr_bytes.data() + at, b.isize, b.crc, nullptr};
-            bam::inflate_blocks(*c->pool, &j, 1);
-            if (j.error) return container_error(c, j.error, c->zpos);
-            c->zhead += b.size; c->zpos += b.size;
-            const int64_t hl = bam::parse_header(c->hdr_bytes.data(), c->hdr_bytes.size(), &c->bh, &why);
-            if (hl < 0) return container_error(c, why, c->zpos);
+            if (k < 0) return container_error(c, why, c->bam.zpos);
+            const size_t at = c->bam.hdr_bytes.size();
+            c->bam.hdr_bytes.resize(at + b.isize);
+            bam::InflateJob j = {z + b.data_off, b.data_len, c->bam.hdr_bytes.data() + at, b.isize, b.crc, nullptr};
+            bam::inflate_blocks(*c->bam.pool, &j, 1);
+            if (j.error) return container_error(c, j.error, c->bam.zpos);
+            c->bam.zhead += b.size; c->bam.zpos += b.size;
+            const int64_t hl = bam::parse_header(c->bam.hdr_bytes.data(), c->bam.hdr_bytes.size(), &c->bam.bh, &why);
+            if (hl < 0) return container_error(c, why, c->bam.zpos);
             if (hl > 0) {
                 const int r = bam_header_done(c, (size_t)hl);
                 if (r) return r;
@@ -612,70 +631,70 @@ int bam_pump(dwgsim_hip_eval_ctx *c)
             continue;
         }
         // the complete blocks that fit into the filling slot, each at the place that the ISIZE values in front of it give
-        Slot *F = &c->s[c->cur];
+        Slot *F = &c->pipe.filling();
         size_t room = F->h_text.cap() - F->fill, used = 0, zused = 0;
-        c->jobs.clear();
+        c->bam.jobs.clear();
         int k;
-        while ((k = bam::bgzf_block_at(z + zused, avail - zused, &b, &why)) == 1 && c->jobs.size() < MAX_BATCH) {
+        while ((k = bam::bgzf_block_at(z + zused, avail - zused, &b, &why)) == 1 && c->bam.jobs.size() < MAX_BATCH) {
             if (b.isize > room - used) {
-                if (!c->jobs.empty()) break;
+                if (!c->bam.jobs.empty()) break;
                 const int r = bam_room(c, b.isize);
                 if (r) return r;
-                F = &c->s[c->cur];
+                F = &c->pipe.filling();
                 room = F->h_text.cap() - F->fill;
             }
-            c->jobs.push_back({z + zused + b.data_off, b.data_len, F->h_text.get() + F->fill + used, b.isize, b.crc, nullptr});
+            c->bam.jobs.push_back({z + zused + b.data_off, b.data_len, F->h_text.get() + F->fill + used, b.isize, b.crc, nullptr});
             used += b.isize; zused += b.size;
         }
-        if (c->jobs.empty() && k == 0) break;
-        bam::inflate_blocks(*c->pool, c->jobs.data(), c->jobs.size());
+        if (c->bam.jobs.empty() && k == 0) break;
+        bam::inflate_blocks(*c->bam.pool, c->bam.jobs.data(), c->bam.jobs.size());
         // the blocks in front of the first bad one count
         size_t zgood = 0;
         const uint8_t *zb = z;
-        for (const bam::InflateJob &j : c->jobs) {
+        for (const bam::InflateJob &j : c->bam.jobs) {
             if (j.error) { why = j.error; k = -1; break; }
             F->fill += j.isize;
             bam::bgzf_block_at(zb, avail - zgood, &b, &why);
             zgood += b.size; zb += b.size;
         }
-        c->zhead += zgood; c->zpos += zgood;
+        c->bam.zhead += zgood; c->bam.zpos += zgood;
         hop_records(c);
-        if (c->bam_stop) break;
-        if (k < 0) return container_error(c, why, c->zpos);
+        if (c->bam.bam_stop) break;
+        if (k < 0) return container_error(c, why, c->bam.zpos);
     }
-    if (c->bam_stop && !c->failed) {
+    if (c->bam.bam_stop && !c->out.failed) {
         // the record that cannot be one is the last of the stream
-        int r = submit_bam(c);
+        int r = submit(c, c->pipe.filling().hop);
         if (!r) r = drain(c);
         if (r) return r;
     }
-    return c->failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
+    return c->out.failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
 }
 
 void bam_compact(dwgsim_hip_eval_ctx *c)
 {
-    c->zbuf.erase(c->zbuf.begin(), c->zbuf.begin() + (ptrdiff_t)c->zhead);
-    c->zhead = 0;
+    c->bam.zbuf.erase(c->bam.zbuf.begin(), c->bam.zbuf.begin() + (ptrdiff_t)c->bam.zhead);
+    c->bam.zhead = 0;
 }
 
 // the end of a BAM file: it must end at a block boundary, behind the header, and between two records
 int end_bam_file(dwgsim_hip_eval_ctx *c)
 {
-    Slot &F = c->s[c->cur];
-    if (!c->failed && !c->bam_stop) {
-        const char *why = c->zbuf.size() > c->zhead ? "the file ends inside a BGZF block" : c->in_header ? "the file ends inside the BAM header"
+    Slot &F = c->pipe.filling();
+    if (!c->out.failed && !c->bam.bam_stop) {
+        const char *why = c->bam.zbuf.size() > c->bam.zhead ? "the file ends inside a BGZF block" : c->bam.in_header ? "the file ends inside the BAM header"
                         : F.fill > F.hop ? "the file ends inside a record" : nullptr;
         if (why) {
             // (a fatal record in front of the end is the run's result, not an error of this call)
-            const int r = container_error(c, why, c->zpos + (c->zbuf.size() - c->zhead));
+            const int r = container_error(c, why, c->bam.zpos + (c->bam.zbuf.size() - c->bam.zhead));
             return r == DWGSIM_HIP_EVAL_STOPPED ? DWGSIM_HIP_OK : r;
         }
     }
-    if (F.n_offs > F.has_ctx && !c->failed) {
-        const int r = submit_bam(c);
+    if (F.n_offs > F.has_ctx && !c->out.failed) {
+        const int r = submit(c, F.hop);
         if (r) return r;
     }
-    c->zbuf.clear(); c->zhead = 0;
+    c->bam.zbuf.clear(); c->bam.zhead = 0;
     return drain(c);
 }
 
@@ -683,8 +702,8 @@ int end_bam_file(dwgsim_hip_eval_ctx *c)
 // of the other format with the same QNAME and FLAG.  A name that the other format cannot hold equals no name there: no context then.
 void convert_ctx(dwgsim_hip_eval_ctx *c, int fmt)
 {
-    Slot &F = c->s[c->cur];
-    if (F.has_ctx && F.fmt != fmt && !c->failed) {
+    Slot &F = c->pipe.filling();
+    if (F.has_ctx && F.fmt != fmt && !c->out.failed) {
         const ev::Prev pv = F.fmt == FMT_SAM ? ev::sam_prev(F.h_text.get<char>(), (uint32_t)F.ctx_len - 1) : ev::bam_prev(F.h_text.get());
         const std::string q(pv.qname, pv.qlen);
         std::string rec;
@@ -757,7 +776,7 @@ const char *truth_line_error(int code)
 // the whole lines h_text[0, cut) of slot 0: newline kernels, then count, scan and write, each sized by what the step before it produced
 int truth_chunk(dwgsim_hip_eval_ctx *c, size_t cut)
 {
-    Slot &S = c->s[0];
+    Slot &S = c->pipe.s[0];
     auto &T = c->tr;
     hipStream_t st = S.st.get();
     EvalRes *hres = S.h_res.get<EvalRes>(), *dres = S.d_res.get<EvalRes>();
@@ -777,7 +796,7 @@ int truth_chunk(dwgsim_hip_eval_ctx *c, size_t cut)
         return truth_fail(c, DWGSIM_HIP_ERR_NOMEM, "truth: the records do not fit in device memory");
     }
     EvalTruthLoadArgs L;
-    L.text = S.d_text.get(); L.ends = S.d_ends.get<uint32_t>(); L.n_lines = n; L.cnt = T.d_cnt.get<uint32_t>(); L.tg = T.tg;
+    L.text = S.d_text.get(); L.ends = S.d_ends.get<uint32_t>(); L.n_lines = n; L.cnt = T.d_cnt.get<uint32_t>(); L.tg = T.contigs.tg;
     L.recs = T.d_recs.get<ev::TruthRec>() + T.n_recs; L.pool = nullptr; L.pool_base = (uint32_t)T.n_pool; L.err = T.d_err.get<unsigned long long>();
     CK(hipMemsetAsync(T.d_err.get(), 0xff, 8, st));
     launch_truth_load(st, L, dres);
@@ -806,7 +825,7 @@ int truth_state(dwgsim_hip_eval_ctx *c)
 {
     if (!c || c->finished || c->begun || c->tr.committed) return DWGSIM_HIP_ERR_STATE;
     if (c->tr.bad) return DWGSIM_HIP_ERR_FAILED;
-    if (c->bd.on) {
+    if (c->bd.b.on) {
         c->err = "a breakdown and a truth in one context are not supported";
         return DWGSIM_HIP_ERR_ARG;
     }
@@ -844,16 +863,33 @@ void format_table(dwgsim_hip_eval_ctx *c, const std::vector<unsigned long long> 
 {
     evt::Rows rows = c->spill;
     evt::add_window(rows, h.data(), EVAL_WIN, WIN_LO, c->floor_score);
-    c->table = evt::table_text(rows, c->o.a, c->o.d);
+    c->out.table = evt::table_text(rows, c->o.a, c->o.d);
 }
 
 // the main table and the sections of a breakdown run
 void format_breakdown(dwgsim_hip_eval_ctx *c, const std::vector<unsigned long long> &counters)
 {
     evt::Rows rows = c->spill;
-    evt::add_main_window(c->bd, counters.data(), c->floor_score, &rows);
-    c->table = evt::table_text(rows, c->o.a, c->o.d);
-    c->bd_text = evt::breakdown_text(c->bd, c->bdc, counters.data(), c->floor_score, c->o.a, c->o.d);
+    evt::add_main_window(c->bd.b, counters.data(), c->floor_score, &rows);
+    c->out.table = evt::table_text(rows, c->o.a, c->o.d);
+    c->bd.text = evt::breakdown_text(c->bd.b, c->bd.spill, counters.data(), c->floor_score, c->o.a, c->o.d);
+}
+
+// A file of format `fmt` begins: the file before it ends (its last chunk is submitted and every result read), and the filling slot's context
+// record takes the new format.  Refused after finish() and while a truth is begun but not committed.
+int begin_file(dwgsim_hip_eval_ctx *c, int fmt)
+{
+    if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
+    if (c->tr.begun && !c->tr.committed) {
+        c->err = "the truth is not committed";
+        return DWGSIM_HIP_ERR_STATE;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
+    c->begun = true;
+    if (const int r = end_file(c)) return r;
+    c->fmt = fmt;
+    convert_ctx(c, fmt);
+    return DWGSIM_HIP_OK;
 }
 
 } // namespace
@@ -883,7 +919,7 @@ dwgsim_hip_eval_ctx_t *dwgsim_hip_eval_create(const dwgsim_hip_eval_opts_t *opts
     dwgsim_hip_eval_opts_default(&c->o);
     memcpy(&c->o, opts, opts->size);
     c->o.size = sizeof c->o;
-    if (c->o.inflate_threads) c->inflate_threads = c->o.inflate_threads > MAX_INFLATE_THREADS ? MAX_INFLATE_THREADS : c->o.inflate_threads;
+    if (c->o.inflate_threads) c->bam.inflate_threads = c->o.inflate_threads > MAX_INFLATE_THREADS ? MAX_INFLATE_THREADS : c->o.inflate_threads;
     if (opts->P) c->P = opts->P;
     c->o.P = opts->P ? c->P.c_str() : nullptr;
     c->device = device;
@@ -893,52 +929,32 @@ dwgsim_hip_eval_ctx_t *dwgsim_hip_eval_create(const dwgsim_hip_eval_opts_t *opts
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd || hipSetDevice(device) != hipSuccess) return fail(DWGSIM_HIP_ERR_DEVICE);
     const size_t cap = opts->chunk_bytes ? opts->chunk_bytes : DEFAULT_CHUNK;
-    for (Slot &S : c->s) {
+    for (Slot &S : c->pipe.s) {
         if (slot_alloc(c, S, cap)) return fail(DWGSIM_HIP_ERR_DEVICE);
         if (S.st.create() != hipSuccess || S.e0.create() != hipSuccess || S.e1.create() != hipSuccess) return fail(DWGSIM_HIP_ERR_DEVICE);
     }
     const size_t hb = 5 * (EVAL_WIN + 1) * sizeof(unsigned long long);
     if (c->d_hist.reserve(hb, hb) != hipSuccess || hipMemset(c->d_hist.get(), 0, hb) != hipSuccess) return fail(DWGSIM_HIP_ERR_DEVICE);
     if (upload(c, c->d_P, c->P.c_str(), c->P.size() + 1)) return fail(DWGSIM_HIP_ERR_DEVICE);
-    if (upload_targets(c, "", 0)) return fail(DWGSIM_HIP_ERR_DEVICE);
+    c->targets.from_sq("", 0);      // (no targets yet)
+    if (upload_targets(c)) return fail(DWGSIM_HIP_ERR_DEVICE);
     *err = DWGSIM_HIP_OK;
     return c;
 }
 
 int dwgsim_hip_eval_header(dwgsim_hip_eval_ctx_t *c, const char *text, size_t len)
 {
-    if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
-    if (c->tr.begun && !c->tr.committed) {
-        c->err = "the truth is not committed";
-        return DWGSIM_HIP_ERR_STATE;
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    c->begun = true;
-    int r = end_file(c);
-    if (r) return r;
-    c->fmt = FMT_SAM;
-    convert_ctx(c, FMT_SAM);
-    if (!c->seen_header && c->o.p) c->incorrect.assign(text, len);
+    if (const int r = begin_file(c, FMT_SAM)) return r;
+    if (!c->seen_header && c->o.p) c->out.incorrect.assign(text, len);
     c->seen_header = true;
-    return upload_targets(c, text, len);
+    c->targets.from_sq(text, len);
+    return upload_targets(c);
 }
 
 int dwgsim_hip_eval_bam_begin(dwgsim_hip_eval_ctx_t *c)
 {
-    if (!c || c->finished) return DWGSIM_HIP_ERR_STATE;
-    if (c->tr.begun && !c->tr.committed) {
-        c->err = "the truth is not committed";
-        return DWGSIM_HIP_ERR_STATE;
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    c->begun = true;
-    const int r = end_file(c);
-    if (r) return r;
-    c->fmt = FMT_BAM;
-    convert_ctx(c, FMT_BAM);
-    c->zbuf.clear(); c->zhead = 0; c->zpos = 0;
-    c->hdr_bytes.clear();
-    c->in_header = true; c->bam_stop = false;
+    if (const int r = begin_file(c, FMT_BAM)) return r;
+    c->bam.restart();
     return DWGSIM_HIP_OK;
 }
 
@@ -947,8 +963,8 @@ int dwgsim_hip_eval_feed_bam(dwgsim_hip_eval_ctx_t *c, const void *buf, size_t l
     if (!c || c->finished || c->fmt != FMT_BAM || (len && !buf)) return DWGSIM_HIP_ERR_STATE;
     if (c->broken) return DWGSIM_HIP_ERR_FAILED;
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    if (c->failed || c->bam_stop) return c->failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
-    c->zbuf.insert(c->zbuf.end(), (const uint8_t *)buf, (const uint8_t *)buf + len);
+    if (c->out.failed || c->bam.bam_stop) return c->out.failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
+    c->bam.zbuf.insert(c->bam.zbuf.end(), (const uint8_t *)buf, (const uint8_t *)buf + len);
     const int r = bam_pump(c);
     bam_compact(c);
     return r;
@@ -960,8 +976,8 @@ int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
     if (c->broken) return DWGSIM_HIP_ERR_FAILED;
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
     c->seen_header = c->begun = true;      // the first file's header is empty when feed comes first
-    while (len && !c->failed) {
-        Slot &F = c->s[c->cur];
+    while (len && !c->out.failed) {
+        Slot &F = c->pipe.filling();
         if (F.fill == F.h_text.cap()) {
             size_t cut = F.fill;
             while (cut > F.ctx_len && F.h_text.get<char>()[cut - 1] != '\n') --cut;
@@ -973,7 +989,7 @@ int dwgsim_hip_eval_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
         memcpy(F.h_text.get<char>() + F.fill, buf, k);
         F.fill += k; buf += k; len -= k;
     }
-    return c->failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
+    return c->out.failed ? DWGSIM_HIP_EVAL_STOPPED : DWGSIM_HIP_OK;
 }
 
 int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *c, dwgsim_hip_eval_summary_t *sm)
@@ -983,15 +999,15 @@ int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *c, dwgsim_hip_eval_summary_t *
     int r = end_file(c);
     if (r) return r;
     c->finished = true;
-    c->stderr_text = "Analyzing...\nCurrently on:\n0";
-    if (c->failed) {
-        c->stderr_text += fatal_text(c, c->code, c->err_line);
-        c->table.clear();
-        c->incorrect.clear();
+    c->out.stderr_text = "Analyzing...\nCurrently on:\n0";
+    if (c->out.failed) {
+        c->out.stderr_text += fatal_text(c, c->out.code, c->out.err_line);
+        c->out.table.clear();
+        c->out.incorrect.clear();
     } else {
-        if (c->bd.on) {
-            std::vector<unsigned long long> counters(c->bd.counters());
-            CK(hipMemcpy(counters.data(), c->d_bdhist.get(), counters.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (c->bd.b.on) {
+            std::vector<unsigned long long> counters(c->bd.b.counters());
+            CK(hipMemcpy(counters.data(), c->bd.d_hist.get(), counters.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             format_breakdown(c, counters);
         } else {
             std::vector<unsigned long long> h(5 * (EVAL_WIN + 1));
@@ -1004,39 +1020,39 @@ int dwgsim_hip_eval_finish(dwgsim_hip_eval_ctx_t *c, dwgsim_hip_eval_summary_t *
             c->tr.text = truth_text(k);
         }
         char buf[128];
-        snprintf(buf, sizeof buf, "\r%llu\n", (unsigned long long)c->n);
-        c->stderr_text += buf;
-        if (c->o.n > 0 && c->n != (uint64_t)c->o.n) {
-            snprintf(buf, sizeof buf, "(-n)=%d\tn=%llu\n", c->o.n, (unsigned long long)c->n);
-            c->stderr_text += buf;
-            c->stderr_text += error_block("run", nullptr, "Number of reads found differs from the number specified (-n)", false);
+        snprintf(buf, sizeof buf, "\r%llu\n", (unsigned long long)c->out.n);
+        c->out.stderr_text += buf;
+        if (c->o.n > 0 && c->out.n != (uint64_t)c->o.n) {
+            snprintf(buf, sizeof buf, "(-n)=%d\tn=%llu\n", c->o.n, (unsigned long long)c->out.n);
+            c->out.stderr_text += buf;
+            c->out.stderr_text += error_block("run", nullptr, "Number of reads found differs from the number specified (-n)", false);
         }
-        c->stderr_text += "Analysis complete.\n";
+        c->out.stderr_text += "Analysis complete.\n";
     }
     const uint32_t size = sm->size;
     memset(sm, 0, sizeof *sm);
     sm->size = size;
-    sm->status = c->failed ? 1 : 0;
-    sm->error_code = c->failed ? c->code : 0;
-    sm->error_record = c->failed ? c->err_rec : 0;
-    sm->n = c->n;
-    sm->records = c->records;
-    sm->stderr_text = c->stderr_text.c_str();
-    sm->stderr_len = c->stderr_text.size();
+    sm->status = c->out.failed ? 1 : 0;
+    sm->error_code = c->out.failed ? c->out.code : 0;
+    sm->error_record = c->out.failed ? c->out.err_rec : 0;
+    sm->n = c->out.n;
+    sm->records = c->out.records;
+    sm->stderr_text = c->out.stderr_text.c_str();
+    sm->stderr_len = c->out.stderr_text.size();
     return DWGSIM_HIP_OK;
 }
 
 int dwgsim_hip_eval_table_text(dwgsim_hip_eval_ctx_t *c, const char **txt, size_t *len)
 {
     if (!c || !c->finished || !txt || !len) return DWGSIM_HIP_ERR_STATE;
-    *txt = c->table.c_str(); *len = c->table.size();
+    *txt = c->out.table.c_str(); *len = c->out.table.size();
     return DWGSIM_HIP_OK;
 }
 
 int dwgsim_hip_eval_incorrect_text(dwgsim_hip_eval_ctx_t *c, const char **txt, size_t *len)
 {
     if (!c || !c->finished || !txt || !len) return DWGSIM_HIP_ERR_STATE;
-    *txt = c->incorrect.c_str(); *len = c->incorrect.size();
+    *txt = c->out.incorrect.c_str(); *len = c->out.incorrect.size();
     return DWGSIM_HIP_OK;
 }
 
@@ -1053,21 +1069,21 @@ int dwgsim_hip_eval_set_breakdown(dwgsim_hip_eval_ctx_t *c, const char *dims, in
         return DWGSIM_HIP_ERR_ARG;
     }
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
-    c->bd = evt::Breakdown();
-    c->d_bdhist.reset();
+    c->bd.b = evt::Breakdown();
+    c->bd.d_hist.reset();
     if (b.on) {
         const size_t bytes = b.counters() * sizeof(unsigned long long);
-        CK(c->d_bdhist.reserve(bytes, bytes));
-        CK(hipMemset(c->d_bdhist.get(), 0, bytes));
+        CK(c->bd.d_hist.reserve(bytes, bytes));
+        CK(hipMemset(c->bd.d_hist.get(), 0, bytes));
     }
-    c->bd = b;
+    c->bd.b = b;
     return DWGSIM_HIP_OK;
 }
 
 int dwgsim_hip_eval_breakdown_text(dwgsim_hip_eval_ctx_t *c, const char **txt, size_t *len)
 {
     if (!c || !c->finished || !txt || !len) return DWGSIM_HIP_ERR_STATE;
-    *txt = c->bd_text.c_str(); *len = c->bd_text.size();
+    *txt = c->bd.text.c_str(); *len = c->bd.text.size();
     return DWGSIM_HIP_OK;
 }
 
@@ -1078,9 +1094,8 @@ int dwgsim_hip_eval_truth_header(dwgsim_hip_eval_ctx_t *c, const char *text, siz
     auto &T = c->tr;
     if (T.fed) return DWGSIM_HIP_ERR_STATE;       // (the records already loaded hold contig indices of the header before)
     T.begun = true;
-    sq_names(text, len, T.names, T.off);
-    hash_names(T.names, T.off, T.hash);
-    return upload_names(c, T.names, T.off, T.hash, T.d_names, T.d_off, T.d_hash, &T.tg);
+    T.contigs.from_sq(text, len);
+    return upload_names(c, T.contigs);
 }
 
 int dwgsim_hip_eval_truth_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t len)
@@ -1091,7 +1106,7 @@ int dwgsim_hip_eval_truth_feed(dwgsim_hip_eval_ctx_t *c, const char *buf, size_t
         if (const int r = dwgsim_hip_eval_truth_header(c, "", 0)) return r;      // (no header: no contigs, so only unmapped lines can pass)
     c->tr.fed = true;
     while (len) {
-        Slot &F = c->s[0];
+        Slot &F = c->pipe.s[0];
         char *t = F.h_text.get<char>();
         if (F.fill == F.h_text.cap()) {
             size_t cut = F.fill;
@@ -1119,14 +1134,14 @@ int dwgsim_hip_eval_truth_commit(dwgsim_hip_eval_ctx_t *c)
         if (const int r = dwgsim_hip_eval_truth_header(c, "", 0)) return r;
     auto &T = c->tr;
     // what is left, and a last line without its newline
-    if (c->s[0].fill) {
-        if (c->s[0].h_text.get<char>()[c->s[0].fill - 1] != '\n') {
-            if (c->s[0].fill == c->s[0].h_text.cap())
+    if (c->pipe.s[0].fill) {
+        if (c->pipe.s[0].h_text.get<char>()[c->pipe.s[0].fill - 1] != '\n') {
+            if (c->pipe.s[0].fill == c->pipe.s[0].h_text.cap())
                 if (const int r = grow(c)) return r;
-            c->s[0].h_text.get<char>()[c->s[0].fill++] = '\n';
+            c->pipe.s[0].h_text.get<char>()[c->pipe.s[0].fill++] = '\n';
         }
-        if (const int r = truth_chunk(c, c->s[0].fill)) return r;
-        c->s[0].fill = 0;
+        if (const int r = truth_chunk(c, c->pipe.s[0].fill)) return r;
+        c->pipe.s[0].fill = 0;
     }
     // at least twice as many slots as records, a power of two (the test hook may force another size, which must leave one slot empty).  A slot's
     // number has 32 bits: beyond 2^31 records the factor of two gives way, and the table has 2^32 slots for at most 2^32 - 2 records
@@ -1141,7 +1156,7 @@ int dwgsim_hip_eval_truth_commit(dwgsim_hip_eval_ctx_t *c)
         return truth_fail(c, DWGSIM_HIP_ERR_NOMEM, "truth: the index does not fit in device memory");
     }
     T.mask = (uint32_t)(slots - 1);
-    hipStream_t st = c->s[0].st.get();
+    hipStream_t st = c->pipe.s[0].st.get();
     CK(hipMemsetAsync(T.d_slots.get(), 0xff, slots * 8, st));
     CK(hipMemsetAsync(T.d_err.get(), 0xff, 8, st));
     CK(hipMemsetAsync(T.d_ctrs.get(), 0, EVAL_TR_CTRS * 8, st));
@@ -1156,10 +1171,10 @@ int dwgsim_hip_eval_truth_commit(dwgsim_hip_eval_ctx_t *c)
                  (unsigned long long)(bad >> 32) + 1, (unsigned long long)(uint32_t)bad + 1);
         return truth_fail(c, DWGSIM_HIP_ERR_FAILED, buf);
     }
-    T.d_cnt.reset(); T.d_err.reset(); T.d_names.reset(); T.d_off.reset(); T.d_hash.reset();
-    T.tg = ev::Targets{};
+    T.d_cnt.reset(); T.d_err.reset();
+    T.contigs.drop_device();
     T.committed = true;
-    return map_contigs(c);
+    return map_contigs(c, c->targets, T.contigs);
 }
 
 int dwgsim_hip_eval_truth_text(dwgsim_hip_eval_ctx_t *c, const char **txt, size_t *len)
@@ -1183,7 +1198,7 @@ void dwgsim_hip_eval_destroy(dwgsim_hip_eval_ctx_t *c)
 {
     if (!c) return;
     hipSetDevice(c->device);
-    for (Slot &S : c->s) if (S.st) hipStreamSynchronize(S.st.get());      // (by name: the members' destructors only give handles and memory back)
+    for (Slot &S : c->pipe.s) if (S.st) hipStreamSynchronize(S.st.get());      // (by name: the members' destructors only give handles and memory back)
     delete c;
 }
 
@@ -1206,7 +1221,7 @@ int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *c, const void *tex
         c->err = "debug_device_chunk: out of device memory";
         return DWGSIM_HIP_ERR_NOMEM;
     }
-    hipStream_t st = c->s[0].st.get();
+    hipStream_t st = c->pipe.s[0].st.get();
     if (hipMemcpy(dev.get(), text, len, hipMemcpyHostToDevice) != hipSuccess) {
         c->err = "debug_device_chunk: upload failed";
         return DWGSIM_HIP_ERR_DEVICE;
@@ -1217,7 +1232,7 @@ int dwgsim_hip_eval_debug_device_chunk(dwgsim_hip_eval_ctx_t *c, const void *tex
     for (int i = 0; i < reps; ++i) {
         hipMemsetAsync(res.get(), 0xff, 8, st);
         hipMemsetAsync(res.get() + 8, 0, sizeof(EvalRes) - 8, st);
-        launch_chunk(c, st, A, len, tiles.get<uint32_t>());
+        launch(c, st, A, FMT_SAM, len, tiles.get<uint32_t>());
     }
     hipEventRecord(e1.get(), st);
     if (hipStreamSynchronize(st) != hipSuccess) { c->err = "debug_device_chunk: kernel failed"; rc = DWGSIM_HIP_ERR_DEVICE; }
@@ -1233,13 +1248,8 @@ int dwgsim_hip_eval_debug_device_bam_chunk(dwgsim_hip_eval_ctx_t *c, const void 
     if (hipSetDevice(c->device) != hipSuccess) return DWGSIM_HIP_ERR_DEVICE;
     // the offsets of the whole records, as hop_records finds them
     std::vector<uint32_t> offs;
-    const uint8_t *t = (const uint8_t *)records;
-    for (size_t q = 0; len - q >= 4;) {
-        const uint32_t bs = bam::le32(t + q);
-        if (bs < ev::BAM_FIXED || bs > ev::BAM_MAX_BLOCK || len - q - 4 < bs) break;
-        offs.push_back((uint32_t)q);
-        q += 4 + (size_t)bs;
-    }
+    int64_t k;
+    for (size_t q = 0; (k = whole_record((const uint8_t *)records, len, q)) > 0; q += (size_t)k) offs.push_back((uint32_t)q);
     if (offs.empty()) return DWGSIM_HIP_ERR_ARG;
     const size_t n = offs.size();
     DevMem dev, d_offs, res, spill;
@@ -1249,7 +1259,7 @@ int dwgsim_hip_eval_debug_device_bam_chunk(dwgsim_hip_eval_ctx_t *c, const void 
         c->err = "debug_device_bam_chunk: out of device memory";
         return DWGSIM_HIP_ERR_NOMEM;
     }
-    hipStream_t st = c->s[0].st.get();
+    hipStream_t st = c->pipe.s[0].st.get();
     const EvalRes init = {~0ull, 0, (uint32_t)n, 0};
     if (hipMemcpy(dev.get(), records, len, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_offs.get(), offs.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
@@ -1263,7 +1273,7 @@ int dwgsim_hip_eval_debug_device_bam_chunk(dwgsim_hip_eval_ctx_t *c, const void 
         // (the result words are set outside the timed span: a BAM chunk's count comes from the host)
         if (hipMemcpy(res.get(), &init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) { rc = DWGSIM_HIP_ERR_DEVICE; break; }
         hipEventRecord(e0.get(), st);
-        launch_bam_chunk(c, st, A, (uint32_t)n);
+        launch(c, st, A, FMT_BAM, n, nullptr);
         hipEventRecord(e1.get(), st);
         if (hipStreamSynchronize(st) != hipSuccess) { c->err = "debug_device_bam_chunk: kernel failed"; rc = DWGSIM_HIP_ERR_DEVICE; break; }
         float ms1 = 0;

@@ -5,24 +5,24 @@
 //   k_eval_count    newlines per 4 KiB tile
 //   k_eval_scan     exclusive scan of the tile counts (one block), and the number of lines
 //   k_eval_lines    the position of every newline, in order: line r = (ends[r-1], ends[r]]
-//   k_eval_records  one lane per record: parse, -m / -q / filters / class, first fatal error (atomicMin of record << 8 | code), n, and the
-//                   histogram: an LDS window of EVAL_WIN scores x 5 classes plus one bin for the floor score (the unmapped records of -a 1..3),
-//                   merged into the 64-bit global histogram once per block; a score outside both goes to the spill list, which the host adds.
-// The histogram is fused into k_eval_records: the per-record (class, score) words never go to memory.
-//
+//   k_eval_records  one lane per record: eval_records_loop behind the SAM front, in the run's form
 // A chunk of a BAM file is whole binary records instead, led by the same kind of context record, and comes with the offset of every record:
-//   k_eval_bam_records  the same body as k_eval_records behind another front (parse_bam_record instead of parse_sam_line); the three newline
-//                       kernels are not launched.
+//   k_eval_bam_records  the same loop behind the BAM front (parse_bam_record instead of parse_sam_line); the newline kernels are not launched.
 //
-// With a breakdown (dw_eval.hpp BREAKDOWN) the two record kernels are replaced by k_eval_records_bd / k_eval_bam_records_bd: the same fronts and
-// the same per-record work, but a record is counted once per selected dimension, in its stratum of that dimension (EvalBdArgs lays the counters
-// out).  A block has 512 lanes and 32 768 16-bit counters, two to an LDS word (64 KiB, two blocks per CU); it merges them into the 64-bit global
-// counters before any of them can reach 2^16, that is every BD_FLUSH_ITERS turns of its record loop, and at its end.
-//
-// With a truth (dw_eval.hpp TRUTH) the truth SAM's text goes through the same newline kernels; k_truth_count, k_eval_scan and k_truth_write
-// turn every line into a 32-byte record and its CIGAR words, k_truth_insert / k_truth_check build and verify the index at commit, and the two
-// record kernels are replaced by k_eval_records_tr / k_eval_bam_records_tr: the plain body plus the join and the walk of the two CIGARs, with
-// 2 x 256 x 10 32-bit counters in LDS that are merged into 64-bit global ones every TR_FLUSH_ITERS turns.
+// eval_records_loop is the per-record part, written once: parse, -m / -q / filters / class, the first fatal error (atomicMin of
+// record << 8 | code), n, the -p flag.  Where a record that has a class is counted is its form's business; a run has one form:
+//   Plain      (k_eval_records, k_eval_bam_records)  the histogram: an LDS window of EVAL_WIN scores x 5 classes plus one bin for the floor score
+//              (the unmapped records of -a 1..3), merged into the 64-bit global histogram once per block; a score outside both goes to the spill
+//              list, which the host adds.  The per-record (class, score) words never go to memory.
+//   Breakdown  (k_eval_records_bd, k_eval_bam_records_bd; dw_eval.hpp BREAKDOWN)  once per selected dimension, in the record's stratum of that
+//              dimension (EvalBdArgs lays the counters out).  A block has 512 lanes and 32 768 16-bit counters, two to an LDS word (64 KiB, two
+//              blocks per CU); it merges them into the 64-bit global counters before any of them can reach 2^16, that is every BD_FLUSH_ITERS
+//              turns of the record loop, and at its end.
+//   Truth      (k_eval_records_tr, k_eval_bam_records_tr; dw_eval.hpp TRUTH)  Plain's count plus the join with the truth and the walk of the two
+//              CIGARs, with 2 x 256 x 10 32-bit counters in LDS that are merged into 64-bit global ones every TR_FLUSH_ITERS turns.
+// The truth SAM's own text goes through the same newline kernels; k_truth_count, k_eval_scan and k_truth_write turn every line into a 32-byte
+// record and its CIGAR words, and k_truth_insert / k_truth_check build and verify the index at commit.
+// The launchers at the end choose the kernel of a chunk from its front and the run's form, and its grid from that kernel's block size.
 #include <hip/hip_runtime.h>
 #include "dw_eval.hpp"
 #include "dw_eval_launch.hpp"
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_lines(const uint8_t *text, 
 }
 
 // The two record fronts.  Record li of the chunk (the context record, when there is one, is record 0) becomes an ev::Rec, and the record in
-// front of it an ev::Prev; everything after that is the same for both formats (eval_records_body).
+// front of it an ev::Prev; everything after that is the same for both formats (eval_records_loop).
 struct SamFront {
     // line li = (ends[li-1], ends[li])
     static __device__ __forceinline__ bool rec(const EvalRecArgs &A, uint32_t li, ev::Rec *r)
@@ -144,101 +144,171 @@ struct BamFront {
     static __device__ __forceinline__ ev::Prev prev(const EvalRecArgs &A, uint32_t li) { return ev::bam_prev(A.text + A.ends[li - 1]); }
 };
 
-// one lane per record, grid-stride; h: the block's LDS histogram, 5 x (EVAL_WIN + 1)
-// (The per-record part -- fatal atomicMin, n, histogram, spill, -p flag -- stands three times: here, in eval_records_bd_body and in
-// eval_records_tr_body.  A change to it is made in all three.)
-template <class Front> __device__ __forceinline__ void eval_records_body(const EvalRecArgs &A, uint32_t *h)
+// ---- the three forms ----
+// A form says where a record that has a class is counted, and nothing else.  It has the lanes of its blocks (THREADS), its LDS counters
+// (zero(); merge(): the block's nonzero counters into the 64-bit global ones, and zero again -- the loop puts the barriers around both),
+// count() for one record, whether count() wants the record's strata (STRATA: eval_rec_any<true>), and PERIOD: the turns of the record loop
+// after which the counters are merged inside the loop because they could wrap otherwise; 0: only at the end.
+
+// the main table: the window and the floor score's bin in LDS, any other score to the spill list
+struct Plain {
+    static constexpr int THREADS = EV_THREADS;
+    static constexpr uint32_t PERIOD = 0;       // (a block counts far fewer than 2^32 records)
+    static constexpr bool STRATA = false;
+    uint32_t *h;                                // 5 x (EVAL_WIN + 1)
+
+    __device__ __forceinline__ void zero() const
+    {
+        for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += THREADS) h[i] = 0;
+    }
+    __device__ __forceinline__ void merge(const EvalRecArgs &A) const
+    {
+        for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += THREADS) {
+            const uint32_t v = h[i];
+            if (!v) continue;
+            h[i] = 0;
+            atomicAdd(&A.hist[i], (unsigned long long)v);
+        }
+    }
+    __device__ __forceinline__ void count(const EvalRecArgs &A, const ev::Rec &, const ev::Out &o, const ev::Strata &) const
+    {
+        const int64_t bin = (int64_t)o.score - A.win_lo;
+        if (bin >= 0 && bin < EVAL_WIN) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + (uint32_t)bin], 1u);
+        else if (o.score == A.floor_score) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + EVAL_WIN], 1u);
+        else {
+            const uint32_t k = atomicAdd(&A.res->n_spill, 1u);
+            A.spill[k] = ((uint64_t)(uint32_t)o.score << 32) | (uint32_t)o.cls;
+        }
+    }
+};
+
+// the breakdown: once per selected dimension, in the record's stratum of it; 16-bit counters, two to an LDS word
+constexpr int BD_THREADS = 512;
+constexpr uint32_t BD_FLUSH_ITERS = 65535u / BD_THREADS;        // a block counts fewer than 2^16 records between two merges
+static_assert(BD_FLUSH_ITERS >= 1 && BD_FLUSH_ITERS * BD_THREADS < 65536u, "a 16-bit counter must not wrap between two merges");
+
+struct Breakdown {
+    static constexpr int THREADS = BD_THREADS;
+    static constexpr uint32_t PERIOD = BD_FLUSH_ITERS;
+    static constexpr bool STRATA = true;
+    const EvalBdArgs &B;
+    uint32_t *h;                                // EVAL_BD_CTRS / 2 words
+    uint32_t bins, n_words;                     // bins per (row, class); the words that the selected dimensions' counters take
+
+    __device__ __forceinline__ Breakdown(const EvalBdArgs &b, uint32_t *lds) : B(b), h(lds), bins(b.win + 1), n_words((b.n_rows * 5 * (b.win + 1) + 1) / 2) {}
+    __device__ __forceinline__ void zero() const
+    {
+        for (uint32_t i = threadIdx.x; i < n_words; i += THREADS) h[i] = 0;
+    }
+    __device__ __forceinline__ void merge(const EvalRecArgs &) const
+    {
+        for (uint32_t i = threadIdx.x; i < n_words; i += THREADS) {
+            const uint32_t v = h[i];
+            if (!v) continue;
+            h[i] = 0;
+            if (v & 0xffffu) atomicAdd(&B.hist[2 * i], (unsigned long long)(v & 0xffffu));
+            if (v >> 16) atomicAdd(&B.hist[2 * i + 1], (unsigned long long)(v >> 16));
+        }
+    }
+    // one more record in counter (row * 5 + cls) * (win + 1) + bin
+    __device__ __forceinline__ void one(uint32_t row, uint32_t cls, uint32_t bin) const
+    {
+        const uint32_t k = (row * 5 + cls) * bins + bin;
+        if (k < EVAL_BD_CTRS) atomicAdd(&h[k >> 1], 1u << ((k & 1) * 16));
+    }
+    __device__ __forceinline__ void count(const EvalRecArgs &A, const ev::Rec &, const ev::Out &o, const ev::Strata &sv) const
+    {
+        const uint32_t s_snps = ev::capped(sv.snps, B.cap), s_errors = ev::capped(sv.errors, B.cap), s_indels = sv.indels ? 1 : 0, s_end = sv.end ? 1 : 0;
+        const int64_t d = (int64_t)o.score - B.win_lo;
+        if ((d >= 0 && d < (int64_t)B.win) || o.score == A.floor_score) {
+            const uint32_t bin = (d >= 0 && d < (int64_t)B.win) ? (uint32_t)d : B.win, cls = (uint32_t)o.cls;
+            if (B.row_snps >= 0) one((uint32_t)B.row_snps + s_snps, cls, bin);
+            if (B.row_errors >= 0) one((uint32_t)B.row_errors + s_errors, cls, bin);
+            if (B.row_indels >= 0) one((uint32_t)B.row_indels + s_indels, cls, bin);
+            if (B.row_end >= 0) one((uint32_t)B.row_end + s_end, cls, bin);
+        } else {
+            const uint32_t k = atomicAdd(&A.res->n_spill, 1u);
+            A.spill[k] = ev::bd_spill_pack(o.score, o.cls, s_snps, s_errors, s_indels, s_end);
+        }
+    }
+};
+
+// The truth: Plain's count, and for a mapped record the join of SPEC TRUTH and its counts.  A compared record adds at most TR_LDS_MAX to an LDS
+// counter (a longer one goes to the global counters directly), so a block adds less than 2^32 to any of them in TR_FLUSH_ITERS turns of its
+// record loop.  Reads of 25 000 bases stay in LDS.
+constexpr uint64_t TR_LDS_MAX = 65535;
+constexpr uint32_t TR_FLUSH_ITERS = (uint32_t)(0xFFFFFFFFull / (EV_THREADS * TR_LDS_MAX));
+static_assert(TR_FLUSH_ITERS >= 1 && (uint64_t)TR_FLUSH_ITERS * EV_THREADS * TR_LDS_MAX <= 0xFFFFFFFFull, "a 32-bit counter must not wrap between two merges");
+static_assert(TR_LDS_MAX >= 25000, "ordinary reads are counted in LDS");
+
+struct Truth {
+    static constexpr int THREADS = EV_THREADS;
+    static constexpr uint32_t PERIOD = TR_FLUSH_ITERS;
+    static constexpr bool STRATA = false;
+    const EvalTruthArgs &T;
+    Plain plain;
+    uint32_t *tc;                               // EVAL_TR_CTRS
+
+    __device__ __forceinline__ void zero() const
+    {
+        plain.zero();
+        for (uint32_t i = threadIdx.x; i < EVAL_TR_CTRS; i += THREADS) tc[i] = 0;
+    }
+    __device__ __forceinline__ void merge(const EvalRecArgs &A) const
+    {
+        plain.merge(A);
+        for (uint32_t i = threadIdx.x; i < EVAL_TR_CTRS; i += THREADS) {
+            const uint32_t v = tc[i];
+            if (!v) continue;
+            tc[i] = 0;
+            atomicAdd(&T.ctrs[i], (unsigned long long)v);
+        }
+    }
+    __device__ __forceinline__ void join(const EvalRecArgs &A, const ev::Rec &R, ev::TruthCmp *c) const
+    {
+        c->outcome = ev::J_MISSING; c->exact = 0; c->indel = false;
+        c->bases = c->right = c->clipped = c->ibases = c->iright = 0;
+        if (!ev::key_valid(R.flag)) return;
+        uint64_t h1, h2;
+        ev::key_hash(R.qname, (uint32_t)R.qlen, ev::key_end(R.flag), &h1, &h2);
+        const int64_t f = ev::truth_find(T.slots, T.mask, T.recs, h1, h2);
+        if (f < 0) return;
+        const int32_t t = R.bam ? R.tid : ev::target_find(A.tg, R.rname, R.rname_len);
+        ev::truth_compare(R, t >= 0 ? T.tmap[t] : -1, T.recs[f], T.pool, c);
+    }
+    // in stratum all and, for a compared record of an indel truth, in stratum indel
+    __device__ __forceinline__ void count(const EvalRecArgs &A, const ev::Rec &R, const ev::Out &o, const ev::Strata &sv) const
+    {
+        plain.count(A, R, o, sv);
+        if (R.flag & 4) return;
+        ev::TruthCmp c;
+        join(A, R, &c);
+        const uint64_t v[EVAL_TR_COLS] = {c.outcome == ev::J_MISSING, c.outcome == ev::J_RANDOM, c.outcome == ev::J_UNUSABLE, c.outcome == ev::J_COMPARED,
+                                          (uint64_t)c.exact, c.bases, c.right, c.clipped, c.ibases, c.iright};
+        const bool lds = c.bases <= TR_LDS_MAX;     // (right, clipped, ibases, iright <= bases)
+        for (uint32_t s = 0; s < (c.indel ? 2u : 1u); ++s)
+            for (uint32_t k = 0; k < EVAL_TR_COLS; ++k) {
+                if (!v[k]) continue;
+                const uint32_t at = (s * 256 + R.mapq) * EVAL_TR_COLS + k;
+                if (lds) atomicAdd(&tc[at], (uint32_t)v[k]);
+                else atomicAdd(&T.ctrs[at], (unsigned long long)v[k]);
+            }
+    }
+};
+
+// ---- the record loop ----
+// One lane per record.  Block-stride with a guard, so that every lane of a block makes the same number of turns and reaches the barriers of a
+// merge inside the loop.  (The form comes by value: by reference the breakdown kernels' frame grew from 80 to 96 bytes of scratch.)
+template <class Front, class Form> __device__ __forceinline__ void eval_records_loop(const EvalRecArgs &A, const Form F)
 {
-    for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS) h[i] = 0;
+    F.zero();
     __syncthreads();
 
     const uint32_t n_lines = A.res->n_lines;
     const uint32_t n_rec = n_lines > A.has_ctx ? n_lines - A.has_ctx : 0;
     uint32_t n_local = 0;
-    for (uint32_t r = blockIdx.x * EV_THREADS + threadIdx.x; r < n_rec; r += gridDim.x * EV_THREADS) {
-        const uint32_t li = r + A.has_ctx;
-        ev::Rec R;
-        ev::Out o = {ev::E_MALFORMED, 0, 0, -1, 0};
-        if (Front::rec(A, li, &R)) {
-            ev::Prev pv;
-            const bool have_prev = A.opt.m && li;
-            if (have_prev) pv = Front::prev(A, li);
-            o = ev::eval_rec(R, have_prev ? &pv : nullptr, A.opt, A.tg);
-        }
-        bool incorrect = false;
-        if (o.code) {
-            atomicMin((unsigned long long *)&A.res->err, (unsigned long long)(((uint64_t)r << 8) | (uint32_t)o.code));
-        } else if (!o.skipped) {
-            n_local += (uint32_t)o.n_inc;
-            if (o.cls >= 0) {
-                incorrect = o.cls == ev::MI || o.cls == ev::UM;
-                const int64_t bin = (int64_t)o.score - A.win_lo;
-                if (bin >= 0 && bin < EVAL_WIN) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + (uint32_t)bin], 1u);
-                else if (o.score == A.floor_score) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + EVAL_WIN], 1u);
-                else {
-                    const uint32_t k = atomicAdd(&A.res->n_spill, 1u);
-                    A.spill[k] = ((uint64_t)(uint32_t)o.score << 32) | (uint32_t)o.cls;
-                }
-            }
-        }
-        if (A.flags) A.flags[r] = incorrect ? 1 : 0;
-    }
-    if (n_local) atomicAdd((unsigned long long *)&A.res->n, (unsigned long long)n_local);
-    __syncthreads();
-    for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS)
-        if (h[i]) atomicAdd((unsigned long long *)&A.hist[i], (unsigned long long)h[i]);
-}
-
-__global__ __launch_bounds__(EV_THREADS) void k_eval_records(EvalRecArgs A)
-{
-    __shared__ uint32_t h[(EVAL_WIN + 1) * 5];
-    eval_records_body<SamFront>(A, h);
-}
-
-// a BAM chunk: A.ends holds the byte offset of every record of the chunk (host-made: dw_eval.cpp hops over the block_size chain), and
-// A.res->n_lines their number; no newline kernels run
-__global__ __launch_bounds__(EV_THREADS) void k_eval_bam_records(EvalRecArgs A)
-{
-    __shared__ uint32_t h[(EVAL_WIN + 1) * 5];
-    eval_records_body<BamFront>(A, h);
-}
-
-// ---- the breakdown form ----
-constexpr int BD_THREADS = (int)EVAL_BD_THREADS;
-constexpr uint32_t BD_FLUSH_ITERS = 65535u / BD_THREADS;        // a block counts fewer than 2^16 records between two merges
-static_assert(BD_FLUSH_ITERS >= 1 && BD_FLUSH_ITERS * BD_THREADS < 65536u, "a 16-bit counter must not wrap between two merges");
-
-// the block's nonzero counters into the global ones, and zero again (the caller puts barriers around it)
-__device__ __forceinline__ void bd_merge(uint32_t *h, uint32_t n_words, unsigned long long *hist)
-{
-    for (uint32_t i = threadIdx.x; i < n_words; i += BD_THREADS) {
-        const uint32_t v = h[i];
-        if (!v) continue;
-        h[i] = 0;
-        if (v & 0xffffu) atomicAdd(&hist[2 * i], (unsigned long long)(v & 0xffffu));
-        if (v >> 16) atomicAdd(&hist[2 * i + 1], (unsigned long long)(v >> 16));
-    }
-}
-
-// one more record in counter (row * 5 + cls) * (win + 1) + bin
-__device__ __forceinline__ void bd_count(uint32_t *h, uint32_t row, uint32_t cls, uint32_t bins, uint32_t bin)
-{
-    const uint32_t k = (row * 5 + cls) * bins + bin;
-    if (k < EVAL_BD_CTRS) atomicAdd(&h[k >> 1], 1u << ((k & 1) * 16));
-}
-
-// one lane per record, block-stride (every lane of a block makes the same number of turns); h: EVAL_BD_CTRS / 2 words
-// (the per-record part is eval_records_body's and eval_records_tr_body's: see the note there)
-template <class Front> __device__ __forceinline__ void eval_records_bd_body(const EvalRecArgs &A, const EvalBdArgs &B, uint32_t *h)
-{
-    const uint32_t bins = B.win + 1, n_words = (B.n_rows * 5 * bins + 1) / 2;
-    for (uint32_t i = threadIdx.x; i < n_words; i += BD_THREADS) h[i] = 0;
-    __syncthreads();
-
-    const uint32_t n_lines = A.res->n_lines;
-    const uint32_t n_rec = n_lines > A.has_ctx ? n_lines - A.has_ctx : 0;
-    uint32_t n_local = 0, turns = 0;
-    for (uint64_t base = (uint64_t)blockIdx.x * BD_THREADS; base < n_rec; base += (uint64_t)gridDim.x * BD_THREADS) {
+    [[maybe_unused]] uint32_t turns = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * Form::THREADS; base < n_rec; base += (uint64_t)gridDim.x * Form::THREADS) {
         const uint64_t r64 = base + threadIdx.x;
         if (r64 < n_rec) {
             const uint32_t r = (uint32_t)r64, li = r + A.has_ctx;
@@ -249,7 +319,7 @@ template <class Front> __device__ __forceinline__ void eval_records_bd_body(cons
                 ev::Prev pv;
                 const bool have_prev = A.opt.m && li;
                 if (have_prev) pv = Front::prev(A, li);
-                o = ev::eval_rec_bd(R, have_prev ? &pv : nullptr, A.opt, A.tg, &sv);
+                o = ev::eval_rec_any<Form::STRATA>(R, have_prev ? &pv : nullptr, A.opt, A.tg, &sv);
             }
             bool incorrect = false;
             if (o.code) {
@@ -258,47 +328,66 @@ template <class Front> __device__ __forceinline__ void eval_records_bd_body(cons
                 n_local += (uint32_t)o.n_inc;
                 if (o.cls >= 0) {
                     incorrect = o.cls == ev::MI || o.cls == ev::UM;
-                    const uint32_t s_snps = ev::capped(sv.snps, B.cap), s_errors = ev::capped(sv.errors, B.cap), s_indels = sv.indels ? 1 : 0, s_end = sv.end ? 1 : 0;
-                    const int64_t d = (int64_t)o.score - B.win_lo;
-                    if ((d >= 0 && d < (int64_t)B.win) || o.score == A.floor_score) {
-                        const uint32_t bin = (d >= 0 && d < (int64_t)B.win) ? (uint32_t)d : B.win, cls = (uint32_t)o.cls;
-                        if (B.row_snps >= 0) bd_count(h, (uint32_t)B.row_snps + s_snps, cls, bins, bin);
-                        if (B.row_errors >= 0) bd_count(h, (uint32_t)B.row_errors + s_errors, cls, bins, bin);
-                        if (B.row_indels >= 0) bd_count(h, (uint32_t)B.row_indels + s_indels, cls, bins, bin);
-                        if (B.row_end >= 0) bd_count(h, (uint32_t)B.row_end + s_end, cls, bins, bin);
-                    } else {
-                        const uint32_t k = atomicAdd(&A.res->n_spill, 1u);
-                        A.spill[k] = ev::bd_spill_pack(o.score, o.cls, s_snps, s_errors, s_indels, s_end);
-                    }
+                    F.count(A, R, o, sv);
                 }
             }
             if (A.flags) A.flags[r] = incorrect ? 1 : 0;
         }
-        if (++turns == BD_FLUSH_ITERS) {
-            turns = 0;
-            __syncthreads();
-            bd_merge(h, n_words, B.hist);
-            __syncthreads();
+        if constexpr (Form::PERIOD != 0) {
+            if (++turns == Form::PERIOD) {
+                turns = 0;
+                __syncthreads();
+                F.merge(A);
+                __syncthreads();
+            }
         }
     }
     if (n_local) atomicAdd((unsigned long long *)&A.res->n, (unsigned long long)n_local);
     __syncthreads();
-    bd_merge(h, n_words, B.hist);
+    F.merge(A);
+}
+
+__global__ __launch_bounds__(EV_THREADS) void k_eval_records(EvalRecArgs A)
+{
+    __shared__ uint32_t h[(EVAL_WIN + 1) * 5];
+    eval_records_loop<SamFront>(A, Plain{h});
+}
+
+// a BAM chunk: A.ends holds the byte offset of every record of the chunk (host-made: dw_eval.cpp hops over the block_size chain), and
+// A.res->n_lines their number; no newline kernels run
+__global__ __launch_bounds__(EV_THREADS) void k_eval_bam_records(EvalRecArgs A)
+{
+    __shared__ uint32_t h[(EVAL_WIN + 1) * 5];
+    eval_records_loop<BamFront>(A, Plain{h});
 }
 
 __global__ __launch_bounds__(BD_THREADS) void k_eval_records_bd(EvalRecArgs A, EvalBdArgs B)
 {
     __shared__ uint32_t hb[EVAL_BD_CTRS / 2];
-    eval_records_bd_body<SamFront>(A, B, hb);
+    eval_records_loop<SamFront>(A, Breakdown(B, hb));
 }
 
 __global__ __launch_bounds__(BD_THREADS) void k_eval_bam_records_bd(EvalRecArgs A, EvalBdArgs B)
 {
     __shared__ uint32_t hb[EVAL_BD_CTRS / 2];
-    eval_records_bd_body<BamFront>(A, B, hb);
+    eval_records_loop<BamFront>(A, Breakdown(B, hb));
 }
 
-// ---- the truth: load, index, and the truth form of the record kernels (dw_eval.hpp TRUTH) ----
+__global__ __launch_bounds__(EV_THREADS) void k_eval_records_tr(EvalRecArgs A, EvalTruthArgs T)
+{
+    __shared__ uint32_t ht[(EVAL_WIN + 1) * 5];
+    __shared__ uint32_t tct[EVAL_TR_CTRS];
+    eval_records_loop<SamFront>(A, Truth{T, Plain{ht}, tct});
+}
+
+__global__ __launch_bounds__(EV_THREADS) void k_eval_bam_records_tr(EvalRecArgs A, EvalTruthArgs T)
+{
+    __shared__ uint32_t ht[(EVAL_WIN + 1) * 5];
+    __shared__ uint32_t tct[EVAL_TR_CTRS];
+    eval_records_loop<BamFront>(A, Truth{T, Plain{ht}, tct});
+}
+
+// ---- the truth: load and index (dw_eval.hpp TRUTH) ----
 
 // line li of a chunk of truth text
 __device__ __forceinline__ const char *truth_line(const EvalTruthLoadArgs &L, uint32_t li, uint32_t *len)
@@ -357,125 +446,7 @@ __global__ __launch_bounds__(EV_THREADS) void k_truth_check(const unsigned long 
     }
 }
 
-// A compared record adds at most TR_LDS_MAX to an LDS counter (a longer one goes to the global counters directly), so a block adds less than
-// 2^32 to any of them in TR_FLUSH_ITERS turns of its record loop.  Reads of 25 000 bases stay in LDS.
-constexpr uint64_t TR_LDS_MAX = 65535;
-constexpr uint32_t TR_FLUSH_ITERS = (uint32_t)(0xFFFFFFFFull / (EV_THREADS * TR_LDS_MAX));
-static_assert(TR_FLUSH_ITERS >= 1 && (uint64_t)TR_FLUSH_ITERS * EV_THREADS * TR_LDS_MAX <= 0xFFFFFFFFull, "a 32-bit counter must not wrap between two merges");
-static_assert(TR_LDS_MAX >= 25000, "ordinary reads are counted in LDS");
-
-__device__ __forceinline__ void tr_merge(uint32_t *tc, unsigned long long *ctrs)
-{
-    for (uint32_t i = threadIdx.x; i < EVAL_TR_CTRS; i += EV_THREADS) {
-        const uint32_t v = tc[i];
-        if (!v) continue;
-        tc[i] = 0;
-        atomicAdd(&ctrs[i], (unsigned long long)v);
-    }
-}
-
-// the counts of one participating record, in stratum all and, for a compared record of an indel truth, in stratum indel
-__device__ __forceinline__ void tr_count(uint32_t *tc, unsigned long long *ctrs, uint32_t mapq, const ev::TruthCmp &c)
-{
-    const uint64_t v[EVAL_TR_COLS] = {c.outcome == ev::J_MISSING, c.outcome == ev::J_RANDOM, c.outcome == ev::J_UNUSABLE, c.outcome == ev::J_COMPARED,
-                                      (uint64_t)c.exact, c.bases, c.right, c.clipped, c.ibases, c.iright};
-    const bool lds = c.bases <= TR_LDS_MAX;     // (right, clipped, ibases, iright <= bases)
-    for (uint32_t s = 0; s < (c.indel ? 2u : 1u); ++s)
-        for (uint32_t k = 0; k < EVAL_TR_COLS; ++k) {
-            if (!v[k]) continue;
-            const uint32_t at = (s * 256 + mapq) * EVAL_TR_COLS + k;
-            if (lds) atomicAdd(&tc[at], (uint32_t)v[k]);
-            else atomicAdd(&ctrs[at], (unsigned long long)v[k]);
-        }
-}
-
-// the join of SPEC TRUTH for one participating record
-template <class Front> __device__ __forceinline__ void tr_join(const EvalRecArgs &A, const EvalTruthArgs &T, const ev::Rec &R, ev::TruthCmp *c)
-{
-    c->outcome = ev::J_MISSING; c->exact = 0; c->indel = false;
-    c->bases = c->right = c->clipped = c->ibases = c->iright = 0;
-    if (!ev::key_valid(R.flag)) return;
-    uint64_t h1, h2;
-    ev::key_hash(R.qname, (uint32_t)R.qlen, ev::key_end(R.flag), &h1, &h2);
-    const int64_t f = ev::truth_find(T.slots, T.mask, T.recs, h1, h2);
-    if (f < 0) return;
-    const int32_t t = R.bam ? R.tid : ev::target_find(A.tg, R.rname, R.rname_len);
-    ev::truth_compare(R, t >= 0 ? T.tmap[t] : -1, T.recs[f], T.pool, c);
-}
-
-// eval_records_body plus the join (its per-record part is a copy of that body's, as eval_records_bd_body's is: the plain kernels stay as they
-// are, so a change to that part is made in all three); block-stride, so that every lane of a block makes the same number of turns; tc: EVAL_TR_CTRS words
-template <class Front> __device__ __forceinline__ void eval_records_tr_body(const EvalRecArgs &A, const EvalTruthArgs &T, uint32_t *h, uint32_t *tc)
-{
-    for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS) h[i] = 0;
-    for (uint32_t i = threadIdx.x; i < EVAL_TR_CTRS; i += EV_THREADS) tc[i] = 0;
-    __syncthreads();
-
-    const uint32_t n_lines = A.res->n_lines;
-    const uint32_t n_rec = n_lines > A.has_ctx ? n_lines - A.has_ctx : 0;
-    uint32_t n_local = 0, turns = 0;
-    for (uint64_t base = (uint64_t)blockIdx.x * EV_THREADS; base < n_rec; base += (uint64_t)gridDim.x * EV_THREADS) {
-        const uint64_t r64 = base + threadIdx.x;
-        if (r64 < n_rec) {
-            const uint32_t r = (uint32_t)r64, li = r + A.has_ctx;
-            ev::Rec R;
-            ev::Out o = {ev::E_MALFORMED, 0, 0, -1, 0};
-            if (Front::rec(A, li, &R)) {
-                ev::Prev pv;
-                const bool have_prev = A.opt.m && li;
-                if (have_prev) pv = Front::prev(A, li);
-                o = ev::eval_rec(R, have_prev ? &pv : nullptr, A.opt, A.tg);
-            }
-            bool incorrect = false;
-            if (o.code) {
-                atomicMin((unsigned long long *)&A.res->err, (unsigned long long)(((uint64_t)r << 8) | (uint32_t)o.code));
-            } else if (!o.skipped) {
-                n_local += (uint32_t)o.n_inc;
-                if (o.cls >= 0) {
-                    incorrect = o.cls == ev::MI || o.cls == ev::UM;
-                    const int64_t bin = (int64_t)o.score - A.win_lo;
-                    if (bin >= 0 && bin < EVAL_WIN) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + (uint32_t)bin], 1u);
-                    else if (o.score == A.floor_score) atomicAdd(&h[o.cls * (EVAL_WIN + 1) + EVAL_WIN], 1u);
-                    else {
-                        const uint32_t k = atomicAdd(&A.res->n_spill, 1u);
-                        A.spill[k] = ((uint64_t)(uint32_t)o.score << 32) | (uint32_t)o.cls;
-                    }
-                    if (!(R.flag & 4)) {
-                        ev::TruthCmp c;
-                        tr_join<Front>(A, T, R, &c);
-                        tr_count(tc, T.ctrs, R.mapq, c);
-                    }
-                }
-            }
-            if (A.flags) A.flags[r] = incorrect ? 1 : 0;
-        }
-        if (++turns == TR_FLUSH_ITERS) {
-            turns = 0;
-            __syncthreads();
-            tr_merge(tc, T.ctrs);
-            __syncthreads();
-        }
-    }
-    if (n_local) atomicAdd((unsigned long long *)&A.res->n, (unsigned long long)n_local);
-    __syncthreads();
-    for (int i = threadIdx.x; i < 5 * (EVAL_WIN + 1); i += EV_THREADS)
-        if (h[i]) atomicAdd((unsigned long long *)&A.hist[i], (unsigned long long)h[i]);
-    tr_merge(tc, T.ctrs);
-}
-
-__global__ __launch_bounds__(EV_THREADS) void k_eval_records_tr(EvalRecArgs A, EvalTruthArgs T)
-{
-    __shared__ uint32_t ht[(EVAL_WIN + 1) * 5];
-    __shared__ uint32_t tct[EVAL_TR_CTRS];
-    eval_records_tr_body<SamFront>(A, T, ht, tct);
-}
-
-__global__ __launch_bounds__(EV_THREADS) void k_eval_bam_records_tr(EvalRecArgs A, EvalTruthArgs T)
-{
-    __shared__ uint32_t ht[(EVAL_WIN + 1) * 5];
-    __shared__ uint32_t tct[EVAL_TR_CTRS];
-    eval_records_tr_body<BamFront>(A, T, ht, tct);
-}
+// ---- launchers ----
 
 static uint32_t truth_grid(uint32_t n)
 {
@@ -509,47 +480,33 @@ void launch_truth_index(hipStream_t st, unsigned long long *slots, uint32_t mask
     hipLaunchKernelGGL(k_truth_check, dim3(truth_grid(n)), dim3(EV_THREADS), 0, st, (const unsigned long long *)slots, mask, recs, n, err);
 }
 
-void launch_eval_chunk_tr(hipStream_t st, const EvalRecArgs &A, const EvalTruthArgs &T, uint64_t len, uint32_t *tile_count, uint32_t grid_records)
+// The grid of a record kernel for `lanes` lanes of work: at most 1 024 blocks' worth of EV_THREADS lanes, in blocks of the form's size
+// (the breakdown form's blocks have twice the lanes, so it gets half the blocks)
+static uint32_t form_grid(uint64_t lanes, uint32_t threads)
+{
+    uint64_t g = (lanes + EV_THREADS - 1) / EV_THREADS;
+    g = g < 1 ? 1 : g > 1024 ? 1024 : g;
+    return (uint32_t)((g * EV_THREADS + threads - 1) / threads);
+}
+
+// the record kernel of a front in the run's form
+template <class K, class KB, class KT>
+static void launch_records(hipStream_t st, K plain, KB bd, KT tr, uint64_t lanes, const EvalRecArgs &A, const EvalBdArgs *B, const EvalTruthArgs *T)
+{
+    if (B) hipLaunchKernelGGL(bd, dim3(form_grid(lanes, Breakdown::THREADS)), dim3(Breakdown::THREADS), 0, st, A, *B);
+    else if (T) hipLaunchKernelGGL(tr, dim3(form_grid(lanes, Truth::THREADS)), dim3(Truth::THREADS), 0, st, A, *T);
+    else hipLaunchKernelGGL(plain, dim3(form_grid(lanes, Plain::THREADS)), dim3(Plain::THREADS), 0, st, A);
+}
+
+void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs *B, const EvalTruthArgs *T, uint64_t len, uint32_t *tile_count)
 {
     launch_eval_newlines(st, A.text, len, tile_count, A.res, A.ends);
-    hipLaunchKernelGGL(k_eval_records_tr, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A, T);
+    launch_records(st, k_eval_records, k_eval_records_bd, k_eval_records_tr, (len + 255) / 256, A, B, T);      // about 256 bytes of text per lane
 }
 
-void launch_eval_bam_chunk_tr(hipStream_t st, const EvalRecArgs &A, const EvalTruthArgs &T, uint32_t grid_records)
+void launch_eval_bam_chunk(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs *B, const EvalTruthArgs *T, uint32_t n_rec)
 {
-    hipLaunchKernelGGL(k_eval_bam_records_tr, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A, T);
-}
-
-void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tile_count, uint32_t grid_records)
-{
-    const uint32_t tiles = (uint32_t)((len + EV_TILE - 1) / EV_TILE);
-    if (tiles) {
-        hipLaunchKernelGGL(k_eval_count, dim3(tiles), dim3(EV_THREADS), 0, st, A.text, len, tile_count);
-        hipLaunchKernelGGL(k_eval_scan, dim3(1), dim3(EV_THREADS), 0, st, tile_count, tiles, A.res);
-        hipLaunchKernelGGL(k_eval_lines, dim3(tiles), dim3(EV_THREADS), 0, st, A.text, len, (const uint32_t *)tile_count, A.ends);
-    }
-    hipLaunchKernelGGL(k_eval_records, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A);
-}
-
-void launch_eval_bam_chunk(hipStream_t st, const EvalRecArgs &A, uint32_t grid_records)
-{
-    hipLaunchKernelGGL(k_eval_bam_records, dim3(grid_records ? grid_records : 1), dim3(EV_THREADS), 0, st, A);
-}
-
-void launch_eval_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint64_t len, uint32_t *tile_count, uint32_t grid_records)
-{
-    const uint32_t tiles = (uint32_t)((len + EV_TILE - 1) / EV_TILE);
-    if (tiles) {
-        hipLaunchKernelGGL(k_eval_count, dim3(tiles), dim3(EV_THREADS), 0, st, A.text, len, tile_count);
-        hipLaunchKernelGGL(k_eval_scan, dim3(1), dim3(EV_THREADS), 0, st, tile_count, tiles, A.res);
-        hipLaunchKernelGGL(k_eval_lines, dim3(tiles), dim3(EV_THREADS), 0, st, A.text, len, (const uint32_t *)tile_count, A.ends);
-    }
-    hipLaunchKernelGGL(k_eval_records_bd, dim3(grid_records ? grid_records : 1), dim3(BD_THREADS), 0, st, A, B);
-}
-
-void launch_eval_bam_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint32_t grid_records)
-{
-    hipLaunchKernelGGL(k_eval_bam_records_bd, dim3(grid_records ? grid_records : 1), dim3(BD_THREADS), 0, st, A, B);
+    launch_records(st, k_eval_bam_records, k_eval_bam_records_bd, k_eval_bam_records_tr, n_rec, A, B, T);      // one record per lane
 }
 
 } // namespace dw

@@ -46,13 +46,6 @@ struct EvalBdArgs {
     int32_t row_snps, row_errors, row_indels, row_end;      // the first row of each dimension, -1: not selected
 };
 
-void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, uint64_t len, uint32_t *tile_count, uint32_t grid_records);
-void launch_eval_bam_chunk(hipStream_t st, const EvalRecArgs &A, uint32_t grid_records);
-// the breakdown forms; their blocks have EVAL_BD_THREADS lanes
-constexpr uint32_t EVAL_BD_THREADS = 512;
-void launch_eval_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint64_t len, uint32_t *tile_count, uint32_t grid_records);
-void launch_eval_bam_chunk_bd(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs &B, uint32_t grid_records);
-
 // The truth form (dw_eval.hpp TRUTH).  Load, per chunk of truth text behind the newline kernels: k_truth_count (every line checked, its pool
 // words counted), k_eval_scan over the counts, k_truth_write (records and pool words).  Commit: k_truth_insert, k_truth_check.  Afterwards the
 // table, the records and the pool are read-only, and k_eval_records_tr / k_eval_bam_records_tr join every participating record with them.
@@ -84,9 +77,13 @@ struct EvalTruthArgs {
 void launch_truth_load(hipStream_t st, const EvalTruthLoadArgs &L, EvalRes *scan_res);
 void launch_truth_write(hipStream_t st, const EvalTruthLoadArgs &L);
 void launch_truth_index(hipStream_t st, unsigned long long *slots, uint32_t mask, const ev::TruthRec *recs, uint32_t n, unsigned long long *err);
-void launch_eval_chunk_tr(hipStream_t st, const EvalRecArgs &A, const EvalTruthArgs &T, uint64_t len, uint32_t *tile_count, uint32_t grid_records);
-void launch_eval_bam_chunk_tr(hipStream_t st, const EvalRecArgs &A, const EvalTruthArgs &T, uint32_t grid_records);
 // the newline kernels alone (the truth load runs them before it knows how many records to make room for)
 void launch_eval_newlines(hipStream_t st, const uint8_t *text, uint64_t len, uint32_t *tile_count, EvalRes *res, uint32_t *ends);
+
+// One chunk through the record loop.  SAM: `len` bytes of whole lines at A.text, the newline kernels first.  BAM: `n_rec` whole records (the
+// context record not counted) whose offsets are at A.ends.  The form: B for a breakdown, else T for a truth, else (both null) plain; the
+// kernel's grid follows from len / n_rec and the form's block size, which only dw_eval.hip knows.
+void launch_eval_chunk(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs *B, const EvalTruthArgs *T, uint64_t len, uint32_t *tile_count);
+void launch_eval_bam_chunk(hipStream_t st, const EvalRecArgs &A, const EvalBdArgs *B, const EvalTruthArgs *T, uint32_t n_rec);
 
 } // namespace dw
