@@ -49,6 +49,7 @@ MUT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.
 READS_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int)
 MSG_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
 HAP_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)      # (ABI 6) dwgsim_hip_job_haplotype_fn: the next piece of a haplotype's FASTA
+TVCF_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t)      # (ABI 10) dwgsim_hip_job_truth_vcf_fn: the truth-VCF records of the next contig
 READS_AT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int)      # (ABI 5) pieces with their offset, from several threads
 
 
@@ -94,6 +95,7 @@ EXPORTS = [
     "dwgsim_hip_debug_sim_instances",
     "dwgsim_hip_set_truth_sam", "dwgsim_hip_truth_sam_header", "dwgsim_hip_job_set_truth_sam",
     "dwgsim_hip_set_truth_md", "dwgsim_hip_job_set_truth_md", "dwgsim_hip_job_debug_option", "dwgsim_hip_job_debug_get",
+    "dwgsim_hip_set_truth_depth", "dwgsim_hip_truth_depth_fetch", "dwgsim_hip_mutlist_truth_vcf_text", "dwgsim_hip_truth_vcf_header", "dwgsim_hip_job_set_truth_vcf_sink",
 ]
 
 _lib = None
@@ -193,6 +195,13 @@ def load(path: str | None = None):
     lib.dwgsim_hip_job_set_truth_md.argtypes = [C.c_void_p, C.c_int]
     lib.dwgsim_hip_job_debug_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.dwgsim_hip_job_debug_get.argtypes = [C.c_void_p, C.c_char_p, P(C.c_int64)]
+    lib.dwgsim_hip_set_truth_depth.argtypes = [C.c_void_p, C.c_int]
+    lib.dwgsim_hip_truth_depth_fetch.restype = C.c_int64
+    lib.dwgsim_hip_truth_depth_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+    lib.dwgsim_hip_mutlist_truth_vcf_text.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, P(C.c_void_p), P(C.c_size_t)]
+    lib.dwgsim_hip_truth_vcf_header.restype = C.c_int64
+    lib.dwgsim_hip_truth_vcf_header.argtypes = [P(C.c_char_p), P(C.c_int64), C.c_int, C.c_char_p, C.c_size_t]
+    lib.dwgsim_hip_job_set_truth_vcf_sink.argtypes = [C.c_void_p, TVCF_CB, C.c_void_p]
     if hasattr(lib, "dwgsim_hip_eval_create"):
         _bind_eval(lib)
     if path is None:
@@ -333,6 +342,8 @@ class JobResult:
     haplotypes: dict = field(default_factory=dict)   # haplotypes=True: {0: bytes, 1: bytes}, the two mutated haplotypes as FASTA
     sim_forms: set = field(default_factory=set)      # debug_get("sim_form") after every simulate call of the job (run_job): the k_simulate forms it ran
     truth_sam: bytes = b""                           # truth_sam=True: the records of the truth SAM (no header: truth_sam_header)
+    truth_vcf: bytes = b""                           # truth_vcf=True: the records of the truth VCF (no header: truth_vcf_header)
+    truth_depth: dict = field(default_factory=dict)  # truth_vcf=True (run_job): contig name -> numpy uint64 array [cells, 2], the counters the records were made from
     truth_reruns: int = 0                            # batches that ran a second time because their tagged truth SAM (truth_md=True) needed more room than planned (run_job)
 
 
@@ -528,6 +539,41 @@ class Context:
         """(ABI 9) On top of set_truth_sam: every mapped record of the truth SAM also carries NM:i: and MD:Z:.  While the truth SAM is off it does nothing."""
         self._chk(self.lib.dwgsim_hip_set_truth_md(self.h, 1 if on else 0))
 
+    def set_truth_depth(self, on: bool = True):
+        """(ABI 10) Every simulate call adds to the counters of the true read depth of its group's mutated cells (Illumina reads only), with or without the truth SAM."""
+        self._chk(self.lib.dwgsim_hip_set_truth_depth(self.h, 1 if on else 0))
+
+    def truth_depth(self, cid: int):
+        """The counters of contig cid, everything simulated for it on this context since its walk: a numpy uint64 array [cells, 2] (haplotype 1, haplotype 2), one row per
+        cell of the contig's slice of the list of mutated cells, in list order.  Waits for the batches that are enqueued."""
+        import numpy as np
+        n = self.lib.dwgsim_hip_truth_depth_fetch(self.h, cid, None, 0)
+        self._chk(n)
+        out = np.zeros((n, 2), dtype=np.uint64)
+        if n:
+            self._chk(self.lib.dwgsim_hip_truth_depth_fetch(self.h, cid, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def truth_vcf_via_list(self, cid: int, counts):
+        """The truth-VCF records of every contig of cid's group, from counts = one [cells, 2] array per contig (truth_depth, or sums of several contexts'): [bytes]"""
+        import numpy as np
+        n = C.c_int()
+        L = self.lib.dwgsim_hip_mutations_take(self.h, cid, C.byref(n))
+        if not L:
+            raise DwgsimError(self.lib.dwgsim_hip_last_error(self.h).decode(errors="replace"))
+        try:
+            out = []
+            for k in range(n.value):
+                a = np.ascontiguousarray(counts[k], dtype=np.uint64)
+                v, vl = C.c_void_p(), C.c_size_t()
+                rc = self.lib.dwgsim_hip_mutlist_truth_vcf_text(L, k, a.ctypes.data_as(C.c_void_p), len(a), C.byref(v), C.byref(vl))
+                if rc < 0:
+                    raise DwgsimError(f"dwgsim_hip_mutlist_truth_vcf_text: error {rc}")
+                out.append(C.string_at(v, vl.value) if vl.value else b"")
+            return out
+        finally:
+            self.lib.dwgsim_hip_mutlist_free(L)
+
     def fetch_gz(self, slot: int, stream: int, nbytes: int) -> bytes:
         """The .gz form of a finished stream (GPU gzip), through a page-locked bounce buffer."""
         if not nbytes:
@@ -577,6 +623,20 @@ def truth_sam_header(contigs, lib=None) -> bytes:
         raise DwgsimError(f"dwgsim_hip_truth_sam_header: error {size}")
     buf = C.create_string_buffer(size + 1)
     lib.dwgsim_hip_truth_sam_header(names, lens, n, buf, size)
+    return buf.raw[:size]
+
+
+def truth_vcf_header(contigs, lib=None) -> bytes:
+    """(ABI 10) The header of a truth VCF for the contig table `contigs` ((name, sequence or length) pairs, FASTA order)."""
+    lib = lib or load()
+    n = len(contigs)
+    names = (C.c_char_p * n)(*[nm.encode() for nm, _ in contigs])
+    lens = (C.c_int64 * n)(*[a if isinstance(a, int) else len(a) for _, a in contigs])
+    size = lib.dwgsim_hip_truth_vcf_header(names, lens, n, None, 0)
+    if size < 0:
+        raise DwgsimError(f"dwgsim_hip_truth_vcf_header: error {size}")
+    buf = C.create_string_buffer(size + 1)
+    lib.dwgsim_hip_truth_vcf_header(names, lens, n, buf, size)
     return buf.raw[:size]
 
 
@@ -636,7 +696,7 @@ def split_ranges(ranges, batch_pairs):
 
 
 def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22, fetch: bool = True, lib=None, debug_options=None, group_bp: int = 0, check_list_form: bool = False,
-            haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False, truth_md: bool = False) -> JobResult:
+            haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False, truth_md: bool = False, truth_vcf: bool = False) -> JobResult:
     """dwgsim_core (dwgsim.c:419-1121) over the C-ABI: header pass, then schedule -> mutate -> mutations text -> simulate in
     read-index batches.  group_bp = 0: contig after contig, as the reference walks them.  group_bp > 0: consecutive contigs are resident
     together in groups of up to group_bp bases (dwgsim_hip_add_contigs): one walk per group, batches that run across contig boundaries."""
@@ -648,6 +708,7 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
     txt = bytearray()
     haps = {0: bytearray(), 1: bytearray()}
     sam = bytearray()
+    tvcf = bytearray()
     if want_mut:
         vcf += b"##fileformat=VCFv4.1\n"
         for name, arr in contigs:
@@ -662,6 +723,8 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
             ctx.set_truth_sam(True)
         if truth_md:
             ctx.set_truth_md(True)
+        if truth_vcf:
+            ctx.set_truth_depth(True)
         if getattr(params, "_mut_input", None):
             ctx.set_mutation_input(params._mut_input[0], params._mut_input[1], contigs)
         have_regions = bool(getattr(params, "_regions", None))
@@ -707,6 +770,11 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
                         sam += ctx.fetch(0, STREAM_SAM, b.sam_bytes)
                 rand_ii += b.n_random
                 n_sim += b.n_pairs
+            if truth_vcf:
+                counts = [ctx.truth_depth(h0 + k) for k in range(len(grp))]
+                for k, ent in enumerate(grp):
+                    res.truth_depth[ent[1]] = counts[k]
+                tvcf += b"".join(ctx.truth_vcf_via_list(h0, counts))
             ctx.drop_contig(h0)
         res.flow_cap_mult = ctx.debug_get("flow_cap_mult")
         res.truth_reruns = ctx.debug_get("truth_reruns")
@@ -718,12 +786,13 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
     if haplotypes:
         res.haplotypes = {k: bytes(v) for k, v in haps.items()}
     res.truth_sam = bytes(sam)
+    res.truth_vcf = bytes(tvcf)
     return res
 
 
 def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True, batch_pairs: int = 0, group_bp: int = 0, min_share: int = 0,
                 lib=None, keep_output: bool = True, offset_sink: bool = False, haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False,
-                truth_md: bool = False, debug_options=None) -> JobResult:
+                truth_md: bool = False, debug_options=None, truth_vcf: bool = False) -> JobResult:
     """The same job through the JOB level of the C-ABI (dwgsim_hip_job_*): the library schedules, groups, shards over `devices`
     (default: all) and delivers in file order; the sink below only collects.  Streams are returned as text (gzip members are
     decompressed here)."""
@@ -769,7 +838,15 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
         hap_pieces.append((hap, C.string_at(data, n) if n else b""))
         return 0
 
+    tvcf_pieces, tvcf_threads = [], set()
+
+    def on_tvcf(user, name, v, vl):
+        tvcf_threads.add(threading.get_ident())
+        tvcf_pieces.append((name.decode(), C.string_at(v, vl) if vl else b""))
+        return 0
+
     hap_cb = HAP_CB(on_hap)
+    tvcf_cb = TVCF_CB(on_tvcf)
     sink = JobSink(None, MUT_CB(on_mut), READS_CB(on_reads), MSG_CB(lambda u, m: None), READS_AT_CB(on_reads_at) if offset_sink else READS_AT_CB())
     opt = JobOptions(1 if gzip_on_gpu else 0, 1, batch_pairs, group_bp, min_share)
     err = C.c_int(0)
@@ -791,6 +868,8 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
             chk(lib.dwgsim_hip_job_set_truth_sam(job, 1))
         if truth_md:
             chk(lib.dwgsim_hip_job_set_truth_md(job, 1))
+        if truth_vcf:
+            chk(lib.dwgsim_hip_job_set_truth_vcf_sink(job, tvcf_cb, None))
         for k, v in (debug_options or {}).items():
             chk(lib.dwgsim_hip_job_debug_option(job, k.encode(), v))
         if getattr(params, "_regions", None):
@@ -830,6 +909,9 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
             else:
                 res.streams[s_] += piece
     res.truth_sam = bytes(sam)
+    res.truth_vcf = b"".join(p for _, p in tvcf_pieces)
+    res.truth_vcf_contigs = [nm for nm, _ in tvcf_pieces]
+    res.truth_vcf_threads = len(tvcf_threads)
     res.mutations_txt, res.mutations_vcf = bytes(txt), bytes(vcf)
     res.streams = {k: bytes(v) for k, v in res.streams.items()}
     res.delivered_text_bytes = {k: v for k, v in order["text_n"].items() if k != STREAM_SAM or truth_sam}

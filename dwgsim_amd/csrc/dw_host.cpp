@@ -67,6 +67,7 @@ struct GroupMem {
     DevMem d_refview, d_refsumm, d_refsumm2, d_dirty;
     DevEvent ev_walk, ev_walk0;      // end / start of the walk chain on the walk stream
     DevMem d_hap_text[2], d_hap_rec, d_hap_pool;      // dwgsim_hip_haplotype_fasta (empty until it is called): each haplotype's FASTA text; the records and header lines of the text made last
+    DevMem d_depth_pos, d_depth_cnt;      // dwgsim_hip_set_truth_depth (empty until a batch runs with it): the group's listed cells (int32, ascending) and two u64 counters per cell (dw_kernels.hpp DepthArgs)
     HostMem h_wc;                    // page-locked mirror (a WalkCounters) of the walk's counters (the context's d_wcounters) at the end of THIS group's walk: several groups' walks can be in flight
 };
 
@@ -106,6 +107,8 @@ struct Group {
     uint32_t n_patch = 0, n_patch_ev = 0;       // file-driven mutations: patched cells / indel events
     // the mutated cells of the finished walk, fetched once for mutations_text
     bool list_valid = false; std::vector<int32_t> pos; std::vector<uint32_t> cells; HostIns ins[2];
+    // the true read depth: the listed cells of the finished walk as mem.d_depth_pos holds them (host copy: a contig's slice), the counters zeroed behind them (depth_prepare)
+    bool depth_valid = false; std::vector<int32_t> depth_pos;
     // the FASTA text of each finished haplotype (mem.d_hap_text), made on request: its width and size, and per contig where the record lies and its bases
     struct HapText { bool valid = false; int width = 0; uint64_t bytes = 0; std::vector<uint64_t> off, len; std::vector<int64_t> bases; } hap_text[2];
 };
@@ -123,6 +126,7 @@ struct Slot {                       // one of the two batches a context can have
     DevEvent ev_k0, ev_k1, ev_end, ev_done, ev_fetched;
     DevEvent ev_t0, ev_t1;          // around the truth step (made by dwgsim_hip_set_truth_sam: a context that never switches it on has none)
     bool pending = false, empty = true, fetch_in_flight = false;
+    bool truth_timed = false;       // the batch in flight recorded ev_t0 / ev_t1 (it ran the truth step, or its depth counters alone)
     int group = -1;                 // the group the batch in flight reads
     uint64_t n_pairs = 0, out_bytes[N_STREAMS] = {0, 0, 0, 0}, gz_bytes[N_STREAMS] = {0, 0, 0, 0};
     DevMem gz_out[N_STREAMS], gz_status, segs;        // GPU gzip: the members of each stream, look-back words; the range table of the launch
@@ -200,6 +204,7 @@ struct dwgsim_hip_ctx {
     bool gzip_on = false; DevMem d_crc_table, d_crc_shift;      // dwgsim_hip_set_gzip (u32; d_crc_shift is uploaded last)
     bool truth_on = false;                 // dwgsim_hip_set_truth_sam: every batch also leaves stream DWGSIM_HIP_STREAM_SAM
     bool truth_md = false;                 // dwgsim_hip_set_truth_md: ... with NM:i: and MD:Z: on every mapped record (nothing while truth_on is off)
+    bool depth_on = false;                 // dwgsim_hip_set_truth_depth: every batch adds to its group's counters of the true read depth (with or without the truth SAM)
     DevMem t_nl[2], t_rec[2], t_ends, t_len, t_blk;      // ... its working set (dw_truth.hpp TruthArgs): newline counts and record starts of the source streams, the read ends, the line lengths per end and per block
     HostMem h_stage;                       // pinned staging for fetch
     DevStream hap_stream;                  // dwgsim_hip_haplotype_fetch: copies of its own (made at the first call), not behind the batches' copy-outs
@@ -1299,7 +1304,7 @@ int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
     HIPC(c, hipSetDevice(c->device));
     g.walk_reset = g.mutated;      // walked before: the cells start again from the resident packed reference
     for (int h = 0; h < 2; ++h) g.n_ins[h] = g.n_ins_bases[h] = 0;
-    g.mutated = true; g.n_cand = 0; g.list_valid = false;
+    g.mutated = true; g.n_cand = 0; g.list_valid = false; g.depth_valid = false;
     for (int h = 0; h < 2; ++h) g.hap_text[h].valid = false;
     g.walk_attempt = 0;
     if (g.total == 0) return DWGSIM_HIP_OK;
@@ -1408,9 +1413,14 @@ void ins_text(const HostIns &t, int32_t pos, std::string &tmp)
     for (uint32_t q = 0; q < t.len[k]; ++q) tmp.push_back("ACGTN"[t.bases[t.off[k] + q] & 3]);
 }
 // mut_print (mut.c:781-893) for one contig: name, first cell s0 and length l in the group's coordinates
-void format_mutations(const ListView &g, const std::string &name, int64_t s0, int64_t l, std::string &txt_s, std::string &vcf_s)
+// With tvcf_s the records of the truth VCF are made beside those of the VCF: the same line with FORMAT and one sample column behind it, GT:AD:DP from
+// depth = the counters of this contig's slice of the list, two per cell (the rule: dw_truth.hpp k_truth_depth).  GT is the phase pl says; AD is ref,alt -- alt
+// the ends of the haplotype(s) that carry the record's allele, ref those of the other haplotype where its cell is unmutated (else 0; none when pl = 3) --
+// and DP both counters.  A deletion's record takes the counters of the first deleted cell of the run.
+void format_mutations(const ListView &g, const std::string &name, int64_t s0, int64_t l, std::string &txt_s, std::string &vcf_s, const uint64_t *depth = nullptr, std::string *tvcf_s = nullptr)
 {
     txt_s.clear(); vcf_s.clear();
+    if (tvcf_s) tvcf_s->clear();
     // this contig's slice of the list, positions inside the contig
     const size_t e0 = (size_t)(std::lower_bound(g.pos, g.pos + g.n, (int32_t)s0) - g.pos);
     const size_t e1 = (size_t)(std::lower_bound(g.pos, g.pos + g.n, (int32_t)(s0 + l)) - g.pos);
@@ -1424,7 +1434,18 @@ void format_mutations(const ListView &g, const std::string &name, int64_t s0, in
     auto cell = [&](size_t e, int h) -> uint8_t { return (uint8_t)(h ? g.cells[e] >> 8 : g.cells[e]); };
     auto refc = [&](size_t e) -> uint8_t { return (uint8_t)(g.cells[e] >> 16); };          // nst_nt4_table code of the reference base
     auto prevc = [&](size_t e) -> uint8_t { return (uint8_t)(g.cells[e] >> 24); };         // ... of the base in front of it
-    auto vcf_head = [&](long long at) { vcf.str(name.data(), name.size()); vcf.ch('\t'); vcf.num(at); vcf.lit("\t.\t"); };
+    size_t rec_at = 0;      // where the VCF record being made starts
+    auto vcf_head = [&](long long at) { rec_at = vcf_s.size(); vcf.str(name.data(), name.size()); vcf.ch('\t'); vcf.num(at); vcf.lit("\t.\t"); };
+    auto sample = [&](size_t e, int pl) {      // the finished record of cell e once more, with its sample column
+        if (!tvcf_s) return;
+        TextOut t{*tvcf_s};
+        t.str(vcf_s.data() + rec_at, vcf_s.size() - rec_at - 1);
+        const uint64_t n1 = depth ? depth[2 * (e - e0)] : 0, n2 = depth ? depth[2 * (e - e0) + 1] : 0;      // (no counters: nothing was simulated)
+        const uint64_t alt = pl == 3 ? n1 + n2 : pl == 1 ? n1 : n2;
+        const uint64_t ref = pl == 3 ? 0 : (cell(e, pl == 1 ? 1 : 0) & TMASK) == T_NONE ? (pl == 1 ? n2 : n1) : 0;
+        t.lit("\tGT:AD:DP\t"); t.lit(pl == 3 ? "1|1" : pl == 1 ? "1|0" : "0|1");
+        t.ch(':'); t.num((long long)ref); t.ch(','); t.num((long long)alt); t.ch(':'); t.num((long long)(n1 + n2)); t.ch('\n');
+    };
     for (size_t e = e0; e < e1; ++e) {
         const int64_t i = g.pos[e] - s0;
         const uint8_t r0 = refc(e), c1 = cell(e, 0), c2 = cell(e, 1);
@@ -1438,10 +1459,12 @@ void format_mutations(const ListView &g, const std::string &name, int64_t s0, in
             if (hom) {
                 txt.ch(B5[r0]); txt.ch('\t'); txt.ch(B5[c1 & 0xf]); txt.lit("\t3\n");
                 vcf_head((long long)i + 1); vcf.ch(B5[r0]); vcf.ch('\t'); vcf.ch(B5[c1 & 0xf]); vcf.lit("\t100\tPASS\tAF=1.0;pl=3;mt=SUBSTITUTE\n");
+                sample(e, 3);
             } else {
                 const int hap = t1 == T_SUB ? 1 : 2;
                 txt.ch(B5[r0]); txt.ch('\t'); txt.ch("XACMGRSVTWYHKDBN"[1 << (c1 & 3) | 1 << (c2 & 3)]); txt.ch('\t'); txt.ch((char)('0' + hap)); txt.ch('\n');
                 vcf_head((long long)i + 1); vcf.ch(B5[r0]); vcf.ch('\t'); vcf.ch(B5[(hap == 1 ? c1 : c2) & 0xf]); vcf.lit("\t100\tPASS\tAF=0.5;pl="); vcf.ch((char)('0' + hap)); vcf.lit(";mt=SUBSTITUTE\n");
+                sample(e, hap);
             }
         } else if (hom ? t1 == T_DEL : (t1 == T_DEL || t2 == T_DEL)) {
             const int pl = hom ? 3 : (t1 == T_DEL ? 1 : 2);
@@ -1464,6 +1487,7 @@ void format_mutations(const ListView &g, const std::string &name, int64_t s0, in
                 }
                 if (i > 0) { vcf.ch('\t'); vcf.ch(B5[prevc(e)]); } else vcf.lit("\t.");
                 vcf.lit("\t100\tPASS\tAF="); vcf.lit(hom ? "1.0" : "0.5"); vcf.lit(";pl="); vcf.ch((char)('0' + pl)); vcf.lit(";mt=DELETE\n");
+                sample(e, pl);
             }
         } else {
             const int pl = hom ? 3 : (t1 == T_INS ? 1 : 2);
@@ -1471,8 +1495,33 @@ void format_mutations(const ListView &g, const std::string &name, int64_t s0, in
             txt.lit("-\t"); txt.str(tmp.data(), tmp.size()); txt.ch('\t'); txt.ch((char)('0' + pl)); txt.ch('\n');
             vcf_head((long long)i + 1); vcf.ch(B5[r0]); vcf.ch('\t'); vcf.ch(B5[r0]); vcf.str(tmp.data(), tmp.size());
             vcf.lit("\t100\tPASS\tAF="); vcf.lit(hom ? "1.0" : "0.5"); vcf.lit(";pl="); vcf.ch((char)('0' + pl)); vcf.lit(";mt=INSERT\n");
+            sample(e, pl);
         }
     }
+}
+
+// The positions of a walked group's mutated cells (group coordinates, ascending) into the context's l_pos, on the walk stream: *n_out of them, known here
+// (the call waits for the count), the positions themselves enqueued behind it
+int collect_listed_positions(dwgsim_hip_ctx_t *c, Group &g, uint32_t *n_out)
+{
+    *n_out = 0;
+    if (g.total <= 0 || g.n_cand == 0) return DWGSIM_HIP_OK;
+    hipStream_t st = c->walk_stream.get();
+    const uint32_t nblk = (uint32_t)((g.total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
+    if (ensure(c, c->scratch_mask, (size_t)nblk * SCAN_THREADS * sizeof(uint16_t))) return DWGSIM_HIP_ERR_DEVICE;
+    if (ensure(c, c->scratch_cnt, (size_t)nblk * sizeof(uint32_t))) return DWGSIM_HIP_ERR_DEVICE;
+    uint16_t *d_mask = c->scratch_mask.get<uint16_t>(); uint32_t *d_cnt = c->scratch_cnt.get<uint32_t>();
+    launch_collect_mask(st, g.mem.d_cells[0].get(), g.mem.d_cells[1].get(), g.total, d_mask, d_cnt);
+    launch_scan_excl(st, d_cnt, nblk, &c->d_wcounters.get<WalkCounters>()->n_listed);
+    HIPC(c, wc_fetch(c, g.mem, WC_LISTED, st));
+    HIPC(c, hipStreamSynchronize(st));
+    const uint32_t n = (uint32_t)g.mem.h_wc.get<WalkCounters>()->n_listed;
+    if (n) {
+        if (ensure(c, c->l_pos, sizeof(int32_t) * (size_t)n)) return DWGSIM_HIP_ERR_DEVICE;
+        launch_compact(st, d_mask, d_cnt, c->l_pos.get<int32_t>(), g.total, n);
+    }
+    *n_out = n;
+    return DWGSIM_HIP_OK;
 }
 
 // the mutated cells of a walked group (positions in group coordinates, cells + reference codes) and its insertion tables, fetched once
@@ -1483,18 +1532,10 @@ int fetch_mutated_list(dwgsim_hip_ctx_t *c, Group &g)
     for (int h = 0; h < 2; ++h) g.ins[h] = HostIns();
     hipStream_t st = c->walk_stream.get();
     if (g.total > 0 && g.n_cand > 0) {
-        const uint32_t nblk = (uint32_t)((g.total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
-        if (ensure(c, c->scratch_mask, (size_t)nblk * SCAN_THREADS * sizeof(uint16_t))) return DWGSIM_HIP_ERR_DEVICE;
-        if (ensure(c, c->scratch_cnt, (size_t)nblk * sizeof(uint32_t))) return DWGSIM_HIP_ERR_DEVICE;
-        uint16_t *d_mask = c->scratch_mask.get<uint16_t>(); uint32_t *d_cnt = c->scratch_cnt.get<uint32_t>();
-        launch_collect_mask(st, g.mem.d_cells[0].get(), g.mem.d_cells[1].get(), g.total, d_mask, d_cnt);
-        launch_scan_excl(st, d_cnt, nblk, &c->d_wcounters.get<WalkCounters>()->n_listed);
-        HIPC(c, wc_fetch(c, g.mem, WC_LISTED, st));
-        HIPC(c, hipStreamSynchronize(st));
-        const uint32_t n = (uint32_t)g.mem.h_wc.get<WalkCounters>()->n_listed;
+        uint32_t n = 0;
+        if (const int rc = collect_listed_positions(c, g, &n)) return rc;
         if (n) {
-            if (ensure(c, c->l_pos, sizeof(int32_t) * (size_t)n) || ensure(c, c->l_cells, sizeof(uint32_t) * (size_t)n)) return DWGSIM_HIP_ERR_DEVICE;
-            launch_compact(st, d_mask, d_cnt, c->l_pos.get<int32_t>(), g.total, n);
+            if (ensure(c, c->l_cells, sizeof(uint32_t) * (size_t)n)) return DWGSIM_HIP_ERR_DEVICE;
             launch_gather(st, c->l_pos.get<int32_t>(), n, g.mem.d_ref.get(), g.mem.d_cells[0].get(), g.mem.d_cells[1].get(), c->l_cells.get<uint32_t>());
             g.pos.resize(n); g.cells.resize(n);
             HIPC(c, hipMemcpyAsync(g.pos.data(), c->l_pos.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -1507,6 +1548,27 @@ int fetch_mutated_list(dwgsim_hip_ctx_t *c, Group &g)
         HIPC(c, hipStreamSynchronize(st));
     }
     g.list_valid = true;
+    return DWGSIM_HIP_OK;
+}
+
+// The true read depth (dwgsim_hip_set_truth_depth): the group's own copy of its listed positions and the zeroed counters behind them, made before the group's
+// first batch with the feature on.  The call returns when both are in place (the batches run on another stream).
+int depth_prepare(dwgsim_hip_ctx_t *c, Group &g)
+{
+    if (g.depth_valid) return DWGSIM_HIP_OK;
+    uint32_t n = 0;
+    if (const int rc = collect_listed_positions(c, g, &n)) return rc;
+    g.depth_pos.assign(n, 0);
+    if (n) {
+        hipStream_t st = c->walk_stream.get();
+        HIPC(c, reserve(c, g.mem.d_depth_pos, sizeof(int32_t) * (size_t)n, sizeof(int32_t) * ((size_t)n + n / 8 + 1024)));
+        HIPC(c, reserve(c, g.mem.d_depth_cnt, 2 * sizeof(uint64_t) * (size_t)n, 2 * sizeof(uint64_t) * ((size_t)n + n / 8 + 1024)));
+        HIPC(c, hipMemcpyAsync(g.mem.d_depth_pos.get(), c->l_pos.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIPC(c, hipMemsetAsync(g.mem.d_depth_cnt.get(), 0, 2 * sizeof(uint64_t) * (size_t)n, st));
+        HIPC(c, hipMemcpyAsync(g.depth_pos.data(), c->l_pos.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPC(c, hipStreamSynchronize(st));
+    }
+    g.depth_valid = true;
     return DWGSIM_HIP_OK;
 }
 } // namespace
@@ -1536,7 +1598,7 @@ struct dwgsim_hip_mutlist {
     std::vector<int32_t> pos; std::vector<uint32_t> cells; HostIns ins[2];
     struct M { std::string name; int64_t l; int32_t start; };
     std::vector<M> m;
-    std::string txt, vcf;
+    std::string txt, vcf, tvcf;
 };
 
 dwgsim_hip_mutlist_t *dwgsim_hip_mutations_take(dwgsim_hip_ctx_t *c, int contig, int *n_contigs)
@@ -1567,6 +1629,20 @@ int dwgsim_hip_mutlist_text(dwgsim_hip_mutlist_t *L, int k, const char **txt, si
     if (txt_len) *txt_len = L->txt.size();
     if (vcf) *vcf = L->vcf.data();
     if (vcf_len) *vcf_len = L->vcf.size();
+    return DWGSIM_HIP_OK;
+}
+
+// ... and the records of the truth VCF (DESIGN.md "6f") of contig k from the counters the caller passes: the contig's slice of the list, two per cell, as
+// dwgsim_hip_truth_depth_fetch gives them -- or the sum of what several contexts gave
+int dwgsim_hip_mutlist_truth_vcf_text(dwgsim_hip_mutlist_t *L, int k, const uint64_t *counts, size_t n_cells, const char **vcf, size_t *vcf_len)
+{
+    if (!L || k < 0 || k >= (int)L->m.size() || (!counts && n_cells)) return DWGSIM_HIP_ERR_ARG;
+    const auto &m = L->m[(size_t)k];
+    const int32_t *p0 = L->pos.data(), *p1 = p0 + L->pos.size();
+    if (counts && (size_t)(std::lower_bound(p0, p1, (int32_t)(m.start + m.l)) - std::lower_bound(p0, p1, m.start)) != n_cells) return DWGSIM_HIP_ERR_ARG;      // (not this contig's counters)
+    format_mutations(ListView{L->pos.data(), L->cells.data(), L->pos.size(), L->ins}, m.name, m.start, m.l, L->txt, L->vcf, counts, &L->tvcf);
+    if (vcf) *vcf = L->tvcf.data();
+    if (vcf_len) *vcf_len = L->tvcf.size();
     return DWGSIM_HIP_OK;
 }
 
@@ -1976,6 +2052,7 @@ static SimPlan sim_plan(const dwgsim_hip_ctx_t *c, const Launch &L, const SimRun
     P.cap[2] = P.cap[0] + P.cap[1];
     if (!L.a.p.has_bwa) P.cap[0] = P.cap[1] = 0;
     if (!L.a.p.has_bfast) P.cap[2] = 0;
+    if (c->depth_on && !c->truth_on) { size_t ends = 0; for (int j = 0; j < 2; ++j) if (p.length[j] > 0) ends += n_pairs; P.t_ends = sizeof(TruthEnd) * ends; }      // the true read depth alone: the read ends, nothing else of the truth step
     if (c->truth_on) {
         // The truth SAM (dw_truth.hpp), sized here so that no length crosses to the host.  A line of a read end of s bases is at most
         //   QNAME (the FASTQ name without '@': below fixed_max + 120, the bound the FASTQ buffers are sized with) + FLAG (3) + RNAME (fixed_max) + POS (10) + MAPQ (2)
@@ -2040,7 +2117,8 @@ static int sim_reserve(dwgsim_hip_ctx_t *c, int slot, const SimPlan &P)
     if (sl.fetch_in_flight) { HIPC(c, hipStreamWaitEvent(c->stream.get(), sl.ev_fetched.get(), 0)); bool grows = false; for (int t = 0; t < N_STREAMS; ++t) if (P.cap[t] + 64 > out[t].cap() && (t < 3 || P.cap[t])) grows = true; if (grows) HIPC(c, hipEventSynchronize(sl.ev_fetched.get())); sl.fetch_in_flight = false; }
     for (int t = 0; t < 3; ++t) if (ensure(c, out[t], P.cap[t] + 64)) return DWGSIM_HIP_ERR_DEVICE;
     if (P.cap[3] && (ensure(c, out[3], P.cap[3] + 64) || ensure(c, c->t_nl[0], P.t_nl[0]) || ensure(c, c->t_nl[1], P.t_nl[1]) || ensure(c, c->t_rec[0], P.t_rec[0]) || ensure(c, c->t_rec[1], P.t_rec[1]) ||
-                     ensure(c, c->t_ends, P.t_ends) || ensure(c, c->t_len, P.t_len) || ensure(c, c->t_blk, P.t_blk))) return DWGSIM_HIP_ERR_DEVICE;
+                     ensure(c, c->t_len, P.t_len) || ensure(c, c->t_blk, P.t_blk))) return DWGSIM_HIP_ERR_DEVICE;
+    if (ensure(c, c->t_ends, P.t_ends)) return DWGSIM_HIP_ERR_DEVICE;
     if (ensure(c, c->block_rand, P.block_rand) || ensure(c, c->status_all, P.status) ||
         ensure(c, c->split_state, P.split_state) || ensure(c, c->split_hand, P.split_hand) || ensure(c, c->split_agg, P.split_agg) || ensure(c, c->split_pre, P.split_pre) || ensure(c, c->split_chunk, P.split_chunk) ||
         ensure(c, c->meta, P.meta) || ensure(c, c->fail_summ, P.fail_summ) || ensure(c, c->flow_scratch, P.flow_scratch) || ensure(c, c->flow_free, P.flow_free) || ensure(c, sl.segs, P.segs)) return DWGSIM_HIP_ERR_DEVICE;
@@ -2071,7 +2149,7 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
     Slot &sl = c->slot[slot]; SimArgs &a = L.a; const SimForm &f = L.f; uint64_t *cnt = sl.counters.dev();
     const uint64_t n_pairs = L.n_pairs, rand_base = run.rand_base; const uint32_t nblk = L.nblk;
     for (int t = 0; t < N_STREAMS; ++t) sl.out_bytes[t] = sl.gz_bytes[t] = 0;
-    sl.n_pairs = n_pairs; sl.empty = n_pairs == 0;
+    sl.n_pairs = n_pairs; sl.empty = n_pairs == 0; sl.truth_timed = false;
     if (n_pairs == 0) { if (ch.set_rand || ch.set_carry) launch_chain_set(c->stream.get(), ch.words, rand_base, ch.set_rand, ch.carry, ch.set_carry); return DWGSIM_HIP_OK; }
     uint32_t opens = 0; for (const SimSeg &s : L.segs) opens |= s.contig_start;      // (ranges that begin their contig)
     memcpy(sl.h_segs.get(), L.segs.data(), P.segs);
@@ -2092,14 +2170,18 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
     HIPC(c, hipEventRecord(sl.ev_k1.get(), c->stream.get()));
     sl.cap_mult = c->flow_cap_mult;
     if (!run.again) launch_failrule(c->stream.get(), a.meta, n_pairs, opens, c->fail_summ.get<uint64_t>(), cnt, c->d_chain.get<uint64_t>());
-    if (P.cap[3]) {
+    // the true read depth: counted by the first run of a batch alone (a second run replays the same ends)
+    const bool depth = c->depth_on && !run.again && L.g->depth_valid && !L.g->depth_pos.empty();
+    if (P.cap[3] || depth) {
         // The truth step (dw_truth.hpp): this batch's alignments as SAM text, replayed from what the launch left.  It reads meta, which belongs to the CONTEXT, not
         // to the slot -- the next batch's k_simulate overwrites it -- and the slot's FASTQ text and counters: all of it is safe because the step runs on the
         // stream of the launches, behind this batch's kernels and in front of the next batch's (and of the gzip kernels below, which take the SAM as a fourth stream).
         TruthArgs t; memset(&t, 0, sizeof t);
+        sl.truth_timed = true;
         HIPC(c, hipEventRecord(sl.ev_t0.get(), c->stream.get()));
         t.lpp = f.lpp; t.bfast = a.p.has_bwa ? 0 : 1; t.prefix_len = c->read_prefix.empty() ? 0 : (int32_t)c->read_prefix.size() + 1; t.qname_max = P.t_qname_max;
-        for (int q = 0; q < (t.bfast ? 1 : f.lpp); ++q) {
+        DepthArgs dp; dp.pos = L.g->mem.d_depth_pos.get<int32_t>(); dp.n = (uint32_t)L.g->depth_pos.size(); dp.cnt = L.g->mem.d_depth_cnt.get<unsigned long long>();
+        for (int q = 0; P.cap[3] && q < (t.bfast ? 1 : f.lpp); ++q) {
             const int st = t.bfast ? 2 : q;
             t.src[q] = a.out[st]; t.src_bytes[q] = &cnt[text_len_counter(st)]; t.src_cap[q] = P.cap[st];
             t.nl_count[q] = c->t_nl[q].get<uint32_t>(); t.rec[q] = c->t_rec[q].get<uint32_t>(); t.n_rec[q] = t.bfast ? n_pairs * (uint64_t)f.lpp : n_pairs;
@@ -2107,7 +2189,8 @@ static int sim_launch(dwgsim_hip_ctx_t *c, int slot, Launch &L, const SimPlan &P
         t.ends = c->t_ends.get<TruthEnd>(); t.line_len = c->t_len.get<uint32_t>(); t.blk = c->t_blk.get<uint32_t>();
         t.out = c->out[slot][3].get<uint8_t>(); t.cap = P.cap[3]; t.total = &cnt[text_len_counter(3)];
         t.md = c->truth_md ? 1 : 0; t.ref = L.g->mem.d_ref.get(); t.fit = &cnt[TRUTH_FIT_COUNTER];
-        launch_truth(c->stream.get(), a, t);
+        if (P.cap[3]) launch_truth(c->stream.get(), a, t, depth ? &dp : nullptr);
+        else launch_truth_depth(c->stream.get(), a, t, dp);
         HIPC(c, hipEventRecord(sl.ev_t1.get(), c->stream.get()));
     }
     if (c->gzip_on) {      // the .gz form of every stream, enqueued behind the text (lengths are read on the device: gz_src_len_counter)
@@ -2140,6 +2223,7 @@ static int sim_enqueue(dwgsim_hip_ctx_t *c, const dwgsim_hip_range_t *r, int n, 
     const SimPlan P = sim_plan(c, L, run);
     if (P.too_many) { c->err = "too many pairs in one call"; return DWGSIM_HIP_ERR_ARG; }
     if (L.n_pairs) { if (const int rc = sim_reserve(c, slot, P)) return rc; }
+    if (L.n_pairs && c->depth_on && !run.again) { if (const int rc = depth_prepare(c, *L.g)) return rc; }
     // ---- nothing below fails for want of memory ----
     return sim_launch(c, slot, L, P, sim_chain(c, c->slot[slot], r, n, run), run);
 }
@@ -2222,7 +2306,7 @@ int dwgsim_hip_wait(dwgsim_hip_ctx_t *c, int slot, dwgsim_hip_batch_t *out)
     if (out) {
         out->n_pairs = sl.n_pairs; out->n_random = h[RANDOM_COUNTER]; out->n_retries = h[RETRY_COUNTER];
         for (int t = 0; t < 3; ++t) { out->bytes[t] = sl.out_bytes[t]; out->gz_bytes[t] = sl.gz_bytes[t]; out->dev_ptr[t] = c->out[slot][t].get(); }
-        if (sl.out_bytes[3]) { float ms = 0; HIPC(c, hipEventElapsedTime(&ms, sl.ev_t0.get(), sl.ev_t1.get())); c->dbg.truth_us = 1e3 * ms; }
+        if (sl.truth_timed) { float ms = 0; HIPC(c, hipEventElapsedTime(&ms, sl.ev_t0.get(), sl.ev_t1.get())); c->dbg.truth_us = 1e3 * ms; }
         out->sam_bytes = sl.out_bytes[3]; out->sam_gz_bytes = sl.gz_bytes[3]; out->sam_dev_ptr = sl.out_bytes[3] ? c->out[slot][3].get() : nullptr;
         for (int t = 0; t < 4; ++t) out->fail_seg[t] = h[fail_seg_counter(t)];
         out->fail_carry = h[CARRY_COUNTER];
@@ -2348,6 +2432,61 @@ int dwgsim_hip_set_truth_md(dwgsim_hip_ctx_t *c, int on)
     if (on && c->prm.data_type != 0) { c->err = "dwgsim-hip: no truth SAM, and so no NM / MD tags, for SOLiD and Ion Torrent reads (-c 1, -c 2)\n"; return DWGSIM_HIP_ERR_UNSUP; }
     c->truth_md = on != 0;
     return DWGSIM_HIP_OK;
+}
+
+// The true read depth of every listed mutated cell (DESIGN.md "6f"; the rule: dw_truth.hpp k_truth_depth).  Switched on, every batch adds to the counters of its
+// group, with or without the truth SAM; switched off nothing of it is launched or allocated.
+int dwgsim_hip_set_truth_depth(dwgsim_hip_ctx_t *c, int on)
+{
+    if (!c) return DWGSIM_HIP_ERR_ARG;
+    for (const Slot &sl : c->slot) if (sl.pending) { c->err = "set_truth_depth: a batch is in flight (wait for every slot first)"; return DWGSIM_HIP_ERR_STATE; }
+    if (on && c->prm.data_type != 0) {
+        c->err = c->prm.data_type == 1 ? "dwgsim-hip: no true read depth for SOLiD reads (-c 1): it is counted from the alignments of the truth SAM, which colour space does not have\n"
+                                       : "dwgsim-hip: no true read depth for Ion Torrent reads (-c 2): it is counted from the alignments of the truth SAM, which the flow model's own indels rule out\n";
+        return DWGSIM_HIP_ERR_UNSUP;
+    }
+    if (on) { HIPC(c, hipSetDevice(c->device)); for (Slot &sl : c->slot) { HIPC(c, sl.ev_t0.create()); HIPC(c, sl.ev_t1.create()); } }
+    c->depth_on = on != 0;
+    return DWGSIM_HIP_OK;
+}
+// The counters of one contig: its slice of the group's list, in list order, two per cell (haplotype 1, haplotype 2) -- everything this context has simulated
+// for it since its walk.  Waits for the batches the context has enqueued.  Returns the cells of the slice; at most cap_cells of them are written.
+int64_t dwgsim_hip_truth_depth_fetch(dwgsim_hip_ctx_t *c, int contig, uint64_t *counts, size_t cap_cells)
+{
+    int km = 0;
+    Group *gp = c ? get_group(c, contig, &km) : nullptr;
+    if (!gp) return DWGSIM_HIP_ERR_ARG;
+    if (!c->depth_on) { c->err = "truth_depth_fetch: the true read depth is switched off (dwgsim_hip_set_truth_depth)"; return DWGSIM_HIP_ERR_ARG; }
+    if (!counts && cap_cells) { c->err = "bad truth_depth_fetch arguments"; return DWGSIM_HIP_ERR_ARG; }
+    Group &g = *gp;
+    if (!g.mutated || g.walk_pending) { c->err = "mutate_contig must run first"; return DWGSIM_HIP_ERR_STATE; }
+    HIPC(c, hipSetDevice(c->device));
+    if (const int rc = depth_prepare(c, g)) return rc;      // (no batch yet: zeroes)
+    const Member &m = g.m[(size_t)km];
+    const auto b = g.depth_pos.begin(), e = g.depth_pos.end();
+    const size_t e0 = (size_t)(std::lower_bound(b, e, m.start) - b), e1 = (size_t)(std::lower_bound(b, e, (int32_t)(m.start + m.l)) - b);
+    const size_t n = e1 - e0, take = n < cap_cells ? n : cap_cells;
+    if (take) HIPC(c, hipMemcpyAsync(counts, g.mem.d_depth_cnt.get<uint64_t>() + 2 * e0, 2 * sizeof(uint64_t) * take, hipMemcpyDeviceToHost, c->stream.get()));      // (behind the batches)
+    HIPC(c, hipStreamSynchronize(c->stream.get()));
+    return (int64_t)n;
+}
+
+// The header of a truth VCF: that of mutations.vcf with the three FORMAT lines in front of #CHROM and the sample column behind it.  Host text, one function for
+// every caller, with the calling rules of dwgsim_hip_truth_sam_header.
+int64_t dwgsim_hip_truth_vcf_header(const char *const *names, const int64_t *lens, int n, char *buf, size_t cap)
+{
+    if (n < 0 || (n > 0 && (!names || !lens)) || (!buf && cap)) return DWGSIM_HIP_ERR_ARG;
+    std::string h = "##fileformat=VCFv4.1\n";
+    for (int k = 0; k < n; ++k) { if (!names[k]) return DWGSIM_HIP_ERR_ARG; h += "##contig=<ID="; h += names[k]; h += ",length=" + std::to_string((int)lens[k]) + ">\n"; }
+    h += "##INFO=<ID=AF,Number=A,Type=Float,Description=\"Allele Frequency\">\n"
+         "##INFO=<ID=pl,Number=1,Type=Integer,Description=\"Phasing: 1 - HET contig 1, #2 - HET contig #2, 3 - HOM both contigs\">\n"
+         "##INFO=<ID=mt,Number=1,Type=String,Description=\"Variant Type: SUBSTITUTE/INSERT/DELETE\">\n"
+         "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype, phased: haplotype 1 | haplotype 2\">\n"
+         "##FORMAT=<ID=AD,Number=.,Type=Integer,Description=\"Simulated read ends that hold the site, by the haplotype they were read from: ref,alt\">\n"
+         "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Simulated read ends that hold the site, both haplotypes\">\n"
+         "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tdwgsim\n";
+    if (buf) memcpy(buf, h.data(), h.size() < cap ? h.size() : cap);
+    return (int64_t)h.size();
 }
 
 // The header of a truth SAM: host text, the same bytes for every caller.  One @SQ per contig of the table, in its order.  Returns the bytes the header has

@@ -117,6 +117,9 @@ struct GroupJob {
     bool totalled = false;                                        // its total has been recorded (advance_rand_base)
     int batches_done = 0;
     int joined = 0; uint64_t fail_acc[4] = {0, 0, 0, 0};          // abort rule: batches 0 .. joined-1 are simulated and their summaries joined, in order
+    // the truth VCF (dwgsim_hip_job_set_truth_vcf_sink): per contig the counters of the true read depth, summed over the devices that have handed theirs in
+    // behind their last batch of the group (depth_in of them so far)
+    std::vector<std::vector<uint64_t>> depth; int depth_in = 0;
 };
 
 // The pairs of a group's contigs, in file order, cut into read-index ranges: a multiple of nd near-equal batches of at most batch_pairs pairs, so
@@ -172,6 +175,7 @@ struct dwgsim_hip_job {
         dwgsim_hip_job_haplotype_fn hap_fn = nullptr; void *hap_user = nullptr; int hap_width = 60;      // dwgsim_hip_job_set_haplotype_sink
         bool truth_sam = false;       // dwgsim_hip_job_set_truth_sam: every batch also delivers stream DWGSIM_HIP_STREAM_SAM
         bool truth_md = false;        // dwgsim_hip_job_set_truth_md: ... its mapped records with NM:i: and MD:Z:
+        dwgsim_hip_job_truth_vcf_fn tvcf_fn = nullptr; void *tvcf_user = nullptr;      // dwgsim_hip_job_set_truth_vcf_sink
     } cfg;
 
     // CALLER: touched only by the thread that calls the job_ functions (the ABI allows one at a time).  The workers see the staging through
@@ -330,6 +334,11 @@ struct Worker {
     std::vector<std::unique_ptr<HostMem>> hap_bufs; std::vector<HostMem *> hap_free;
     struct HapState { bool active = false; int h = -1, hap = 0; uint64_t off = 0, bytes[2] = {0, 0}; } hs;      // the group whose texts are on their way out
 
+    // (device 0) the truth VCF: a second list of the group's mutated cells goes to a thread of its own, which waits until every device that simulates batches
+    // of the group has handed its counters in (hand_depth_in, behind its last batch), then makes the records from their sum and hands them to the sink
+    struct TvcfTask { MutList list; std::shared_ptr<GroupJob> g; };
+    std::thread tvcf_thread; std::mutex tm; std::condition_variable tcv; std::deque<TvcfTask> tq; bool tvcf_quit = false;
+
     bool ok() const { return !j->failed.load(); }
     void fail_ctx() { job_fail(j, std::string("dwgsim-hip: ") + dwgsim_hip_last_error(x)); }
     bool mine(const GroupJob &g, int b) const { return b % g.nd == j->cfg.vrank(d); }
@@ -359,6 +368,67 @@ struct Worker {
         { std::lock_guard<std::mutex> lk(mm); mut_quit = true; }
         mcv.notify_all();
         mut_thread.join();
+    }
+
+    // devices of this job that simulate batches of the group, and so hand counters in
+    int depth_devices(const GroupJob &g) const
+    {
+        int n = 0;
+        for (int dd = 0; dd < j->cfg.ND; ++dd) { bool any = false; for (int b = 0; b < (int)g.batch.size(); ++b) if (b % g.nd == j->cfg.vrank(dd)) any = true; n += any ? 1 : 0; }
+        return n;
+    }
+    void tvcf_loop()      // groups and contigs in order
+    {
+        for (;;) {
+            TvcfTask t;
+            {
+                std::unique_lock<std::mutex> lk(tm);
+                tcv.wait(lk, [&]() { return tvcf_quit || !tq.empty(); });
+                if (tq.empty()) return;
+                t = std::move(tq.front()); tq.pop_front();
+            }
+            std::vector<std::vector<uint64_t>> sum;
+            {
+                std::unique_lock<std::mutex> lk(j->m);
+                const int want = depth_devices(*t.g);
+                j->cv.wait(lk, [&]() { return j->failed.load() || t.g->depth_in >= want; });
+                sum.swap(t.g->depth);
+            }
+            for (size_t k = 0; k < t.g->names.size() && ok(); ++k) {
+                const char *v; size_t vl;
+                const bool have = k < sum.size() && !sum[k].empty();      // (no device simulated anything of the group: every depth is 0)
+                if (dwgsim_hip_mutlist_truth_vcf_text(t.list.get(), (int)k, have ? sum[k].data() : nullptr, have ? sum[k].size() / 2 : 0, &v, &vl) < 0) { job_fail(j, "dwgsim-hip: the truth VCF could not be made"); break; }
+                if (j->cfg.tvcf_fn(j->cfg.tvcf_user, t.g->names[k].c_str(), v, vl) != 0) { job_fail(j, "dwgsim-hip: the sink refused the truth VCF"); break; }
+            }
+        }
+    }
+    void tvcf_stop()
+    {
+        if (!tvcf_thread.joinable()) return;
+        { std::lock_guard<std::mutex> lk(tm); tvcf_quit = true; }
+        tcv.notify_all();
+        tvcf_thread.join();
+    }
+    // this device's last batch of the group is done: its counters of the true read depth, contig by contig, are added to the group's
+    bool hand_depth_in(GroupJob &g, int h)
+    {
+        const size_t n = g.names.size();
+        std::vector<std::vector<uint64_t>> mine(n);
+        for (size_t k = 0; k < n; ++k) {
+            const int64_t cells = dwgsim_hip_truth_depth_fetch(x, h + (int)k, nullptr, 0);
+            if (cells < 0) { fail_ctx(); return false; }
+            mine[k].assign(2 * (size_t)cells, 0);
+            if (cells && dwgsim_hip_truth_depth_fetch(x, h + (int)k, mine[k].data(), (size_t)cells) != cells) { fail_ctx(); return false; }
+        }
+        std::lock_guard<std::mutex> lk(j->m);
+        if (g.depth.empty()) g.depth.swap(mine);
+        else for (size_t k = 0; k < n; ++k) {
+            if (g.depth[k].size() != mine[k].size()) { if (!j->failed.exchange(true)) j->sh.err = "dwgsim-hip: two devices list different mutated cells for one contig"; j->cv.notify_all(); return false; }
+            for (size_t q = 0; q < mine[k].size(); ++q) g.depth[k][q] += mine[k][q];
+        }
+        ++g.depth_in;
+        j->cv.notify_all();
+        return true;
     }
 
     void hap_loop()      // the pieces in the order the worker made them: each haplotype's file in order
@@ -511,6 +581,7 @@ struct Worker {
             if (j->cfg.sink.reads_at) { B.sized = true; assign_offsets(j); j->cv.notify_all(); }      // this batch's offsets, and those of any batch behind it that was only waiting for its sizes
         }
         if (pb.b < 2 * j->cfg.VD) trace(j, "dev %d group %d: batch %d kernels done, copy issued (%.1f MB)", d, pb.g->id, pb.b, j->cfg.has_sink() ? (n[0] + n[1] + n[2] + n[3]) / 1e6 : 0.0);
+        if (pb.last_of_group && j->cfg.tvcf_fn && !hand_depth_in(*pb.g, pb.h)) return false;      // (every batch of the group on this device is done: they run in order on one stream)
         if (pb.last_of_group && !flush_haplotypes(pb.h)) return false;
         if (pb.last_of_group && dwgsim_hip_drop_contig(x, pb.h) < 0) { fail_ctx(); return false; }      // (the kernels of the group's last batch are done: nothing reads it any more)
         return true;
@@ -564,6 +635,7 @@ struct Worker {
         pin_thread_to_device_node(j->cfg.devices[(size_t)d]);
         if (j->cfg.vrank(d) == 0 && j->cfg.want_mut && j->cfg.sink.mutations) mut_thread = std::thread([this]() { mut_loop(); });
         if (j->cfg.vrank(d) == 0 && j->cfg.hap_fn) hap_thread = std::thread([this]() { hap_loop(); });
+        if (j->cfg.vrank(d) == 0 && j->cfg.tvcf_fn) tvcf_thread = std::thread([this]() { tvcf_loop(); });
         bool fine = true;
         for (;;) {
             std::shared_ptr<GroupJob> g;
@@ -589,6 +661,7 @@ struct Worker {
         if (ahead.g && !ahead.walked) (void)dwgsim_hip_mutate_wait(x, ahead.h);
         mut_stop();
         hap_stop();
+        tvcf_stop();
     }
 
     // ---- one group: process() and its steps ----
@@ -626,6 +699,13 @@ struct Worker {
     // (device 0) the group's list of mutated cells goes to the text thread (a few MB; the device part takes well under a millisecond)
     bool hand_mutations_on(const Resident &cur)
     {
+        if (tvcf_thread.joinable()) {      // the truth VCF takes a list of its own: its thread makes the text when the group's last batch is done, long after the mutation text
+            int n = 0;
+            MutList L(dwgsim_hip_mutations_take(x, cur.h, &n));
+            if (!L) { fail_ctx(); return false; }
+            { std::lock_guard<std::mutex> lk(tm); tq.push_back(TvcfTask{std::move(L), cur.g}); }
+            tcv.notify_all();
+        }
         if (!mut_thread.joinable()) return true;
         int n = 0;
         MutList L(dwgsim_hip_mutations_take(x, cur.h, &n));
@@ -828,6 +908,7 @@ int start_threads(dwgsim_hip_job *j)
         if (c.mutin_type >= 0 &&            // dwgsim.c:494-497
             dwgsim_hip_set_mutation_input(x, c.mutin_type, c.mutin_path.c_str(), nm.data(), c.tab_lens.data(), (int)nm.size()) < 0) { job_fail(j, dwgsim_hip_last_error(x)); return DWGSIM_HIP_ERR_ARG; }
         if (c.gzip && c.want_reads && c.has_sink() && dwgsim_hip_set_gzip(x, 1) < 0) { job_fail(j, dwgsim_hip_last_error(x)); return DWGSIM_HIP_ERR_DEVICE; }
+        if (c.tvcf_fn) { const int rc = dwgsim_hip_set_truth_depth(x, 1); if (rc < 0) { job_fail(j, dwgsim_hip_last_error(x)); return rc; } }
         if (c.truth_sam && c.want_reads) { int rc = dwgsim_hip_set_truth_sam(x, 1); if (rc >= 0 && c.truth_md) rc = dwgsim_hip_set_truth_md(x, 1); if (rc < 0) { job_fail(j, dwgsim_hip_last_error(x)); return rc; } }      // (-M 2: no reads, no SAM)
     }
     for (int d = 0; d < c.ND; ++d) j->me.workers.emplace_back([j, d]() { Worker w{j, d, j->cfg.ctx[(size_t)d].get()}; w.run(); });
@@ -974,6 +1055,15 @@ int dwgsim_hip_job_set_haplotype_sink(dwgsim_hip_job_t *j, dwgsim_hip_job_haplot
     if (!j || width < 0) return arg_error(j, DWGSIM_HIP_ERR_ARG, "job: the haplotype line width must not be negative");
     if (j->me.started) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: the haplotype sink must be set before the first contig");
     j->cfg.hap_fn = fn; j->cfg.hap_user = user; j->cfg.hap_width = width;
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_job_set_truth_vcf_sink(dwgsim_hip_job_t *j, dwgsim_hip_job_truth_vcf_fn fn, void *user)
+{
+    if (!j) return DWGSIM_HIP_ERR_ARG;
+    if (j->me.started) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: the truth VCF sink must be set before prepare / the first contig");
+    if (fn && j->cfg.prm.data_type != 0) return arg_error(j, DWGSIM_HIP_ERR_UNSUP, "dwgsim-hip: the truth VCF is made for Illumina reads only (-c 0)\n");
+    j->cfg.tvcf_fn = fn; j->cfg.tvcf_user = user;
     return DWGSIM_HIP_OK;
 }
 

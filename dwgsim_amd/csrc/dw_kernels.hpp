@@ -297,5 +297,9 @@ struct TruthArgs {
     uint64_t *fit;                       // ... and the length the gzip kernel takes for the SAM (a device word of its own): the total where the text fits cap, else 0 -- the grid of
                                          // k_gzip covers cap, and a chunk reads up to the length it is given
 };
+// ---- the true read depth (dw_truth.hpp k_truth_depth; dwgsim_hip_set_truth_depth) ----
+// The group's listed mutated cells (group coordinates, ascending: what fetch_mutated_list collects) and two counters per cell: cnt[2 e + h] = read ends of
+// haplotype h + 1 that hold listed cell e.  Owned by the group; the counters run from the group's walk to its drop.
+struct DepthArgs { const int32_t *pos; uint32_t n; unsigned long long *cnt; };
 
 } // namespace dw

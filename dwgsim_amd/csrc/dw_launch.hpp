@@ -29,7 +29,8 @@ void launch_hap_len(hipStream_t st, HapDev h, SegTab seg, int64_t l, uint32_t *b
 void launch_hap_write(hipStream_t st, HapDev h, SegTab seg, int64_t l, const uint32_t *block_base, const HapRec *rec, uint32_t n_rec, const uint8_t *pool, uint32_t width, uint8_t *text);      // ... and, from their scan and the records the host placed, the text
 void launch_place(hipStream_t st, const SimArgs &a);
 bool launch_simulate(hipStream_t st, const SimArgs &a, const SimForm &f);      // false: the form has no instance
-void launch_truth(hipStream_t st, const SimArgs &a, const TruthArgs &t);      // the truth step behind the k_simulate launch with arguments a (dw_truth.hpp)
+void launch_truth(hipStream_t st, const SimArgs &a, const TruthArgs &t, const DepthArgs *depth);      // the truth step behind the k_simulate launch with arguments a (dw_truth.hpp); depth: with the counters of the true read depth (nullptr: without)
+void launch_truth_depth(hipStream_t st, const SimArgs &a, const TruthArgs &t, const DepthArgs &depth);      // ... those counters alone, without the truth SAM
 int sim_instances(int64_t *out, int cap);     // test hook: the k_simulate instances that exist, packed like "sim_form"; returns their number, fills at most cap
 void launch_calibrate(hipStream_t st, const CalibArgs &a);
 void launch_failrule(hipStream_t st, const uint32_t *meta, uint64_t n_pairs, uint32_t opens_contig, uint64_t *summ, uint64_t *counters, uint64_t *chain);

@@ -9,6 +9,8 @@
 //   k_truth_len, k_truth_len2                               one lane per read end: the replay and the travel walk; then, with the mate's record in reach, the bytes of its line
 //   k_scan_excl                                            over the blocks' bytes: with the scan k_truth_len2 makes inside each block, where each line starts
 //   k_truth_write                                           one lane per read end: the line, its CIGAR from a second walk over the cells (no CIGAR is ever stored)
+// With dwgsim_hip_set_truth_depth (DESIGN.md "6f") k_truth_depth runs behind k_truth_len: the read ends it left, joined with the group's list of mutated cells
+// into two counters per cell (the rule: at the kernel).  Without the truth SAM the step is k_truth_len<false, false> and k_truth_depth alone (launch_truth_depth).
 // With dwgsim_hip_set_truth_md the three kernels run as their <true> instances (the <false> ones are the step as it was, to the instruction): the length pass also
 // takes NM and the characters of MD (truth_tags), the sums are taken in 64 bits (k_truth_scan), the write pass spells MD out with a second truth_tags walk.
 //
@@ -232,6 +234,8 @@ struct TruthLane {
     uint32_t rs, qn; bool rec_ok; const uint8_t *text;      // the record's start in `text`, the length of its QNAME, and whether the index and the text agree
 };
 // The grid is that of the k_simulate launch (a.n_blocks blocks of a.sim_threads lanes, the range table laid out for them): lane = read end.
+// REC = false (the depth without the truth SAM): no record index exists and none is looked at -- rec_ok says yes, the text fields stay empty.
+template <bool REC = true>
 DW_DEV TruthLane truth_lane(const SimArgs &a, const TruthArgs &t)
 {
     TruthLane L;
@@ -244,6 +248,7 @@ DW_DEV TruthLane truth_lane(const SimArgs &a, const TruthArgs &t)
     L.e = L.pair * (uint64_t)lpp + (uint64_t)L.j;
     L.rs = 0; L.qn = 0; L.rec_ok = false; L.text = nullptr;
     if (!L.valid) return L;
+    if constexpr (!REC) { L.rec_ok = true; return L; }
     // BWA: end j is record `pair` of stream j, its name ends "/1" or "/2"; BFAST alone: record e of the one interleaved stream, no suffix
     const int q = t.bfast ? 0 : L.j;
     const uint64_t r = t.bfast ? L.e : L.pair;
@@ -273,10 +278,12 @@ DW_DEV int32_t truth_tlen(const TruthEnd &me, const TruthEnd &mate, int j)
 
 // The length pass.  Reads meta, which belongs to the context and is overwritten by the next batch's k_simulate: the step runs on the stream of the
 // launches, behind this batch's and in front of the next one's.
-template <bool MD>
+// <false, false>: the same replay where there is no FASTQ record to look at (the depth without the truth SAM: launch_truth_depth)
+template <bool MD, bool REC = true>
 __global__ void __launch_bounds__(SIM_THREADS) k_truth_len(SimArgs a, TruthArgs t)
 {
-    const TruthLane L = truth_lane(a, t);
+    static_assert(REC || !MD, "the tags are read off the FASTQ record");
+    const TruthLane L = truth_lane<REC>(a, t);
     if (!L.valid) return;
     const SegCtx sc = seg_ctx(a, L.sg);
     const uint32_t m = a.meta[L.pair];
@@ -434,8 +441,48 @@ __global__ void __launch_bounds__(SIM_THREADS) k_truth_write(SimArgs a, TruthArg
     o.flush();
 }
 
+// ---- the true read depth of every listed mutated cell (dwgsim_hip_set_truth_depth; DESIGN.md "6f") ----
+// THE RULE.  Per listed cell p of the group (DepthArgs::pos: every cell that is mutated on either haplotype, ascending) there are two 64-bit counters, n[1] and
+// n[2].  A mapped read end of haplotype h whose alignment is the cells lo .. hi with `tail` inserted bases behind hi's own (TruthEnd, as k_truth_len left it)
+// adds 1 to n[h] of every listed cell p with lo <= p <= hi -- except that where haplotype h carries an insertion at p and p == hi the end counts only if
+// `tail` is the insertion's full length: it then holds the cell's own base AND every inserted base, anything less does not show the variant.
+// What follows from the replay law above needs no case of its own: lo and hi are never deleted cells and a CIGAR never starts or ends with D, so a deleted cell
+// inside lo .. hi is a deletion the read spans completely (the first cell of a deleted run stands for the run in the VCF record); a `lead` never counts (the
+// cell it belongs to lies left of lo and its own base is not in the read); random ends (TRUTH_F_RAND) and ends without a line (TRUTH_F_BAD) count nowhere.
+// Sequencing errors are not looked at: this is the depth by ORIGIN of the read, not by the base it shows.
+// One lane per read end on the grid of the launch, behind k_truth_len.  Most ends hold no listed cell at all (at the default rate one 150-base end in seven
+// does), so the search is what every lane pays: a lower bound without a branch, the same number of steps in every lane (it depends on the list's length
+// alone), then the walk over the few cells in reach -- the only divergent part -- with one 64-bit atomicAdd each.  Integer adds commute: the counters do
+// not depend on the order of lanes, blocks, batches or devices.
+DW_DEV uint32_t depth_lower_bound(const int32_t *pos, uint32_t n, int32_t key)      // the first e with pos[e] >= key (n: none)
+{
+    uint32_t base = 0, len = n;
+    while (len > 1u) { const uint32_t half = len >> 1; base += pos[base + half - 1u] < key ? half : 0u; len -= half; }
+    return base + (len == 1u && pos[base] < key ? 1u : 0u);
+}
+__global__ void __launch_bounds__(SIM_THREADS) k_truth_depth(SimArgs a, TruthArgs t, DepthArgs d)
+{
+    const TruthLane L = truth_lane<false>(a, t);
+    if (!L.valid || d.n == 0u) return;
+    const TruthEnd E = t.ends[L.e];
+    if (E.flags & (TRUTH_F_RAND | TRUTH_F_BAD)) return;
+    const SegCtx sc = seg_ctx(a, L.sg);
+    const int hap = (E.flags & TRUTH_F_HAP2) ? 1 : 0;
+    const int32_t glo = (int32_t)sc.start + E.lo, ghi = (int32_t)sc.start + E.hi;      // the list holds group coordinates
+    for (uint32_t e = depth_lower_bound(d.pos, d.n, glo); e < d.n; ++e) {
+        const int32_t p = d.pos[e];
+        if (p > ghi) break;
+        if (p == ghi) {      // (E.hi lies inside the contig: h.cells is the contig's)
+            const HapDev h = sel_hap(a, sc, hap);
+            if ((h.cells[E.hi] & TMASK) == T_INS && E.tail != truth_ins_len(h, E.hi)) break;
+        }
+        atomicAdd(&d.cnt[2u * e + (uint32_t)hap], 1ull);
+    }
+}
+
 // The step, enqueued behind the k_simulate launch whose arguments `a` are (and the k_split_scan / look-backs that leave the text lengths in its counters)
-void launch_truth(hipStream_t st, const SimArgs &a, const TruthArgs &t)
+// depth: the counters of the true read depth are taken behind the length pass (nullptr: not)
+void launch_truth(hipStream_t st, const SimArgs &a, const TruthArgs &t, const DepthArgs *depth)
 {
     const int n_src = t.bfast ? 1 : t.lpp;
     for (int q = 0; q < n_src; ++q) {
@@ -447,15 +494,23 @@ void launch_truth(hipStream_t st, const SimArgs &a, const TruthArgs &t)
     }
     if (t.md) {
         hipLaunchKernelGGL(k_truth_len<true>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+        if (depth) hipLaunchKernelGGL(k_truth_depth, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t, *depth);
         hipLaunchKernelGGL(k_truth_len2<true>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
         hipLaunchKernelGGL(k_truth_scan, dim3(1), dim3(1024), 0, st, t.blk, a.n_blocks, t.total, t.cap, t.fit);
         hipLaunchKernelGGL(k_truth_write<true>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
         return;
     }
     hipLaunchKernelGGL(k_truth_len<false>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+    if (depth) hipLaunchKernelGGL(k_truth_depth, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t, *depth);
     hipLaunchKernelGGL(k_truth_len2<false>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
     launch_scan_excl(st, t.blk, a.n_blocks, t.total);
     hipLaunchKernelGGL(k_truth_write<false>, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+}
+// The depth without the truth SAM: the replay and the counters, nothing else -- no record index, no lengths, no scan, no text (t: lpp and ends alone)
+void launch_truth_depth(hipStream_t st, const SimArgs &a, const TruthArgs &t, const DepthArgs &depth)
+{
+    hipLaunchKernelGGL((k_truth_len<false, false>), dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t);
+    hipLaunchKernelGGL(k_truth_depth, dim3(a.n_blocks), dim3(a.sim_threads), 0, st, a, t, depth);
 }
 
 } // namespace dw

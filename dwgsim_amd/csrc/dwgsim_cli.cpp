@@ -27,6 +27,9 @@
 //     DWGSIM_HIP_HAPLOTYPES_WIDTH  bases per line of those files (default 60; 0: the whole sequence on one line)
 //     DWGSIM_HIP_TRUTH_SAM   anything but empty or "0": also write <prefix>.truth.sam.gz, the true alignment of every read end (Illumina reads):
 //                          the header, then the job's stream 3, in the gzip mode of the FASTQ files.  -M 2 writes none
+//     DWGSIM_HIP_TRUTH_VCF   anything but empty or "0": also write <prefix>.truth.vcf, the records of mutations.vcf with GT:AD:DP in one sample column: the
+//                          phased genotype and the true read depth of every simulated variant, counted on the GPU from the reads the job made (Illumina
+//                          reads).  Independent of -M and of DWGSIM_HIP_TRUTH_SAM
 //     DWGSIM_HIP_TRUTH_MD    anything but empty or "0", together with DWGSIM_HIP_TRUTH_SAM: every mapped record of that file also carries NM:i: and MD:Z:
 //                          (samtools calmd's convention; SEQ with its errors against the reference).  Without DWGSIM_HIP_TRUTH_SAM it does nothing
 //     DWGSIM_HIP_DEBUG     "key=value,...": test / analysis only -- dwgsim_hip_job_debug_option for each pair, and a line "[dwgsim-hip-debug] truth_reruns=<n>" on stderr at the end
@@ -453,6 +456,12 @@ struct FileSink {
         if (s->fp_vcf && fwrite(vcf, 1, vl, s->fp_vcf) != vl) return 1;
         return 0;
     }
+    FILE *fp_tvcf = nullptr;      // DWGSIM_HIP_TRUTH_VCF: <prefix>.truth.vcf
+    static int truth_vcf(void *u, const char *, const char *vcf, size_t vl)      // (dwgsim_hip_job_set_truth_vcf_sink: one thread, contigs in order)
+    {
+        FileSink *s = (FileSink *)u;
+        return s->fp_tvcf && fwrite(vcf, 1, vl, s->fp_tvcf) == vl ? 0 : 1;
+    }
     FILE *fp_hap[2] = {nullptr, nullptr};      // DWGSIM_HIP_HAPLOTYPES: <prefix>.hap1.fa / .hap2.fa
     static int haplotype(void *u, int hap, const void *data, size_t len)      // (dwgsim_hip_job_set_haplotype_sink: one thread, each file's pieces in order)
     {
@@ -674,6 +683,17 @@ int main(int argc, char **argv)
         fs.fp_hap[0] = fopen((p + ".hap1.fa").c_str(), "wb"); fs.fp_hap[1] = fopen((p + ".hap2.fa").c_str(), "wb");
         if (!fs.fp_hap[0] || !fs.fp_hap[1]) { fprintf(stderr, "dwgsim-hip: fail to open the haplotype files for '%s'\n", out_prefix); return give_up(1); }
     }
+    // the truth VCF: the header (one exported function), then the job's records
+    const char *tvcf_env = getenv("DWGSIM_HIP_TRUTH_VCF");
+    const bool want_tvcf = tvcf_env && tvcf_env[0] && strcmp(tvcf_env, "0");
+    if (want_tvcf) {
+        std::vector<const char *> nm; for (auto &s : tab_names) nm.push_back(s.c_str());
+        const int64_t hn = dwgsim_hip_truth_vcf_header(nm.data(), tab_lens.data(), (int)nm.size(), nullptr, 0);
+        std::vector<char> hdr((size_t)(hn > 0 ? hn : 0));
+        if (hn > 0) (void)dwgsim_hip_truth_vcf_header(nm.data(), tab_lens.data(), (int)nm.size(), hdr.data(), hdr.size());
+        fs.fp_tvcf = fopen((p + ".truth.vcf").c_str(), "w");
+        if (!fs.fp_tvcf || hn <= 0 || fwrite(hdr.data(), 1, hdr.size(), fs.fp_tvcf) != hdr.size()) { fprintf(stderr, "dwgsim-hip: fail to write the truth VCF for '%s'\n", out_prefix); if (fs.fp_tvcf) (void)unlink((p + ".truth.vcf").c_str()); return give_up(1); }
+    }
     std::unique_ptr<DeflatePool> pool;
     if (!gpu_gzip && want_reads) { pool = std::make_unique<DeflatePool>(nthreads, gz_level); fs.pool = pool.get(); }
     // the truth SAM: the header (one exported function: the same bytes as every other caller's) as the first piece, then the job's stream 3, in the job's gzip mode
@@ -697,7 +717,7 @@ int main(int argc, char **argv)
     }
 
     dwgsim_hip_job_t *job = job_made.get();
-    if (!job) { fprintf(stderr, "dwgsim-hip: cannot set the job up (error %d)\n", job_err); if (want_hap) { (void)unlink((p + ".hap1.fa").c_str()); (void)unlink((p + ".hap2.fa").c_str()); } return 1; }
+    if (!job) { fprintf(stderr, "dwgsim-hip: cannot set the job up (error %d)\n", job_err); if (want_hap) { (void)unlink((p + ".hap1.fa").c_str()); (void)unlink((p + ".hap2.fa").c_str()); } if (want_tvcf) (void)unlink((p + ".truth.vcf").c_str()); return 1; }
     int rc = 0;
     auto job_error = [&]() { const char *e = dwgsim_hip_job_last_error(job); if (rc == 0) fprintf(stderr, "%s%s", e, (e[0] && e[strlen(e) - 1] != '\n') ? "\n" : ""); rc = 1; };
     {
@@ -707,6 +727,7 @@ int main(int argc, char **argv)
         if (rc == 0 && muts_type >= 0 && dwgsim_hip_job_set_mutation_input(job, muts_type, muts_fn.c_str()) < 0) job_error();   // dwgsim.c:494-497
         if (rc == 0 && want_hap && dwgsim_hip_job_set_haplotype_sink(job, FileSink::haplotype, &fs, hap_width) < 0) job_error();
         if (rc == 0 && want_sam && dwgsim_hip_job_set_truth_sam(job, 1) < 0) job_error();
+        if (rc == 0 && want_tvcf && dwgsim_hip_job_set_truth_vcf_sink(job, FileSink::truth_vcf, &fs) < 0) job_error();
         if (rc == 0 && want_md && dwgsim_hip_job_set_truth_md(job, 1) < 0) job_error();
         if (const char *e = getenv("DWGSIM_HIP_DEBUG")) {
             for (std::string rest = e; rc == 0 && !rest.empty();) {
@@ -763,6 +784,10 @@ int main(int argc, char **argv)
     for (int h = 0; h < 2; ++h) if (fs.fp_hap[h]) {      // (a failed job leaves no partial haplotype file)
         if (fclose(fs.fp_hap[h]) != 0 && rc == 0) { fprintf(stderr, "dwgsim-hip: writing the haplotype files failed\n"); rc = 1; }
         if (rc != 0) (void)unlink((p + (h ? ".hap2.fa" : ".hap1.fa")).c_str());
+    }
+    if (fs.fp_tvcf) {      // (a failed job leaves no partial truth VCF)
+        if (fclose(fs.fp_tvcf) != 0 && rc == 0) { fprintf(stderr, "dwgsim-hip: writing the truth VCF failed\n"); rc = 1; }
+        if (rc != 0) (void)unlink((p + ".truth.vcf").c_str());
     }
     for (int s = 0; s < 4; ++s) close_gz(fs.fgz[s], gz_level, fs.written[s].load());
     if (want_sam && rc != 0) (void)unlink((p + ".truth.sam.gz").c_str());      // (a failed job leaves no partial truth SAM)

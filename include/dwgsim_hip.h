@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define DWGSIM_HIP_ABI_VERSION 9
+#define DWGSIM_HIP_ABI_VERSION 10
 
 /* error codes (negative) */
 #define DWGSIM_HIP_OK            0
@@ -308,6 +308,28 @@ int dwgsim_hip_set_truth_md(dwgsim_hip_ctx_t *ctx, int on);
  * order, skipped ones included), one @PG.  Needs no context.  Returns the header's size; at most cap bytes of it are written to buf (NULL with cap 0: the
  * size alone). */
 int64_t dwgsim_hip_truth_sam_header(const char *const *names, const int64_t *lens, int n, char *buf, size_t cap);
+/* (ABI 10) The true read depth of every simulated variant, the counters behind <prefix>.truth.vcf (DESIGN.md "6f").  Switched on, every simulate call adds to
+ * two 64-bit counters per listed mutated cell of its group, on the device, from the replayed alignments of the reads it made -- with or without the truth SAM,
+ * whose every output byte stays as it is.  The rule (stated once, next to the kernel: dw_truth.hpp k_truth_depth): a mapped read end of haplotype h aligned to
+ * the cells lo .. hi adds 1 to counter h of every listed cell in lo .. hi; where haplotype h has an insertion at hi the end counts there only if it holds all
+ * inserted bases.  Deleted cells inside lo .. hi count (the read spans the deletion); random reads count nowhere; sequencing errors are not looked at (depth by
+ * origin, not by observed base).  A batch counts once, also when dwgsim_hip_wait runs it a second time.  Illumina reads only: DWGSIM_HIP_ERR_UNSUP for -c 1 /
+ * -c 2; DWGSIM_HIP_ERR_STATE while a batch is in flight.  Off (the default): nothing is launched or allocated, every byte is as before. */
+int dwgsim_hip_set_truth_depth(dwgsim_hip_ctx_t *ctx, int on);
+/* ... the counters of one contig: its slice of the group's list of mutated cells (the cells dwgsim_hip_mutations_text walks, reference codes outside ACGT
+ * included), in list order, two per cell: haplotype 1, haplotype 2.  They hold everything this context has simulated for the contig since its walk; the call
+ * waits for the batches the context has enqueued.  Returns the cells of the slice; at most cap_cells of them (2 cap_cells words) are written to counts (NULL
+ * with cap_cells 0: the size alone).  DWGSIM_HIP_ERR_ARG while the feature is off. */
+int64_t dwgsim_hip_truth_depth_fetch(dwgsim_hip_ctx_t *ctx, int contig, uint64_t *counts, size_t cap_cells);
+/* ... the records of the truth VCF for contig k of a list taken with dwgsim_hip_mutations_take: the lines dwgsim_hip_mutlist_text gives as vcf, each with
+ * "GT:AD:DP" and one sample column behind it.  counts: the contig's n_cells cells as dwgsim_hip_truth_depth_fetch gave them -- or the sum of what several
+ * contexts gave (DWGSIM_HIP_ERR_ARG when n_cells is not the contig's slice); NULL: every counter 0.  GT 1|0, 0|1, 1|1 for pl = 1, 2, 3; AD ref,alt: alt the ends of the haplotype(s)
+ * that carry the record's allele, ref those of the other haplotype where its cell is unmutated, else 0; DP both counters.  A deletion's record takes the
+ * counters of the first deleted cell of its run.  No context, no device.  The text is valid until the next call for the list. */
+int dwgsim_hip_mutlist_truth_vcf_text(dwgsim_hip_mutlist_t *list, int k, const uint64_t *counts, size_t n_cells, const char **vcf, size_t *vcf_len);
+/* ... and the header in front of them: that of mutations.vcf with three ##FORMAT lines (GT, AD, DP) in front of #CHROM and "FORMAT" and the sample name
+ * "dwgsim" behind INFO.  Called like dwgsim_hip_truth_sam_header. */
+int64_t dwgsim_hip_truth_vcf_header(const char *const *names, const int64_t *lens, int n, char *buf, size_t cap);
 
 /* Copy one finished stream of a slot to host memory.  A page-locked destination (hipHostMalloc / hipHostRegister) takes one direct
  * hipMemcpyAsync at link speed; pageable memory goes through double-buffered pinned staging inside. */
@@ -383,6 +405,13 @@ int dwgsim_hip_job_set_truth_sam(dwgsim_hip_job_t *job, int on);
 /* (ABI 9) ... with NM:i: and MD:Z: on its mapped records (dwgsim_hip_set_truth_md).  Before dwgsim_hip_job_prepare / the first contig, like the call above; without
  * it, it does nothing. */
 int dwgsim_hip_job_set_truth_md(dwgsim_hip_job_t *job, int on);
+/* (ABI 10) The truth VCF (dwgsim_hip_set_truth_depth) through the job.  Every device counts the batches it simulates; when the last batch of a group has been
+ * simulated the job fetches the counters of every device that took part, adds them up on the host and calls fn with the records of each of the group's contigs
+ * (dwgsim_hip_mutlist_truth_vcf_text; no header: dwgsim_hip_truth_vcf_header), contigs in FASTA order, from ONE thread of the job.  A contig dwgsim_core passes
+ * over has none.  Independent of -M (with -M 2 no read is made and every depth is 0).  A non-zero return fails the job.  To be called before
+ * dwgsim_hip_job_prepare / the first contig: DWGSIM_HIP_ERR_STATE later; DWGSIM_HIP_ERR_UNSUP for -c 1 / -c 2; fn == NULL: off. */
+typedef int (*dwgsim_hip_job_truth_vcf_fn)(void *user, const char *contig, const char *vcf, size_t vcf_len);
+int dwgsim_hip_job_set_truth_vcf_sink(dwgsim_hip_job_t *job, dwgsim_hip_job_truth_vcf_fn fn, void *user);
 /* optional: parse the files above and start the device threads now (errors of -x / -m / -b / -v surface here instead of at the first contig) */
 int dwgsim_hip_job_prepare(dwgsim_hip_job_t *job, uint64_t *total_len);
 /* The body of the contig loop (dwgsim.c:519-625 and everything below it) for the next contig of the FASTA.  Returns the pairs scheduled for

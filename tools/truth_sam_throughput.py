@@ -7,8 +7,11 @@ One batch of --pairs pairs (default 2^18) of the chr20-sized contig of bench.py'
   plain_*       the same batch with the feature off: its k_simulate and kernel times (nothing of the step runs)
 --md: the same with dwgsim_hip_set_truth_md on top (NM:i: and MD:Z: on every mapped record); the line then also holds "md": true and "truth_reruns" (second
 runs for want of room: 0 on this workload).
+--depth: the counters of the true read depth (dwgsim_hip_set_truth_depth; DESIGN.md "6f") on top.  The line then also holds "depth": three rounds that alternate the
+truth step without the counters ("truth_us") and with them ("truth_depth_us": k_truth_depth behind k_truth_len, between the same two events), then the counters
+without the truth SAM ("depth_alone_us": k_truth_len<false, false> and k_truth_depth, nothing else), the listed cells and the sum of all counters.
 Each is the best of --reps batches (the first one allocates: not counted).  Prints one JSON line.
-Usage: python tools/truth_sam_throughput.py [--reps 5] [--pairs 262144] [--md]"""
+Usage: python tools/truth_sam_throughput.py [--reps 5] [--pairs 262144] [--md] [--depth]"""
 import argparse, json, os, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,13 +21,13 @@ from dwgsim_amd import api, synth  # noqa: E402
 FLAGS = "-z 13 -1 150 -2 150 -C 30 -o 1"      # bench.py's
 
 
-def batches(ctx, h, pairs, reps):
+def batches(ctx, h, pairs, reps, timed=False):
     best = {}
     last = None
     for r in range(reps + 1):
         b = ctx.simulate(h, r * pairs, pairs, 0, 0)
         if r:
-            for k, v in (("simulate_us", 1e3 * b.sim_kernel_ms), ("kernels_us", 1e3 * b.kernel_ms), ("truth_us", ctx.debug_get("truth_us") if b.sam_bytes else 0)):
+            for k, v in (("simulate_us", 1e3 * b.sim_kernel_ms), ("kernels_us", 1e3 * b.kernel_ms), ("truth_us", ctx.debug_get("truth_us") if b.sam_bytes or timed else 0)):
                 best[k] = v if k not in best else min(best[k], v)
         last = b
     return best, last
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=1 << 18)
     ap.add_argument("--md", action="store_true", help="with NM:i: and MD:Z: (dwgsim_hip_set_truth_md)")
+    ap.add_argument("--depth", action="store_true", help="also: the truth step with and without the counters of the true read depth, and the counters alone (dwgsim_hip_set_truth_depth)")
     args = ap.parse_args()
     lib = api.load()
     if lib.dwgsim_hip_device_count() < 1:
@@ -63,6 +67,19 @@ def main():
         out["truth_over_simulate"] = on["truth_us"] / max(on["simulate_us"], 1)
         if args.md:
             out["truth_reruns"] = ctx.debug_get("truth_reruns")
+        if args.depth:
+            rounds = []
+            for _ in range(3):
+                ctx.set_truth_depth(False)
+                off, _b = batches(ctx, h, args.pairs, args.reps)
+                ctx.set_truth_depth(True)
+                with_d, _b = batches(ctx, h, args.pairs, args.reps)
+                rounds.append({"truth_us": off["truth_us"], "truth_depth_us": with_d["truth_us"], "simulate_us": with_d["simulate_us"]})
+            ctx.set_truth_sam(False)
+            alone, b = batches(ctx, h, args.pairs, args.reps, timed=True)
+            counts = ctx.truth_depth(h)
+            out["depth"] = {"rounds": rounds, "depth_alone_us": alone["truth_us"], "alone_simulate_us": alone["simulate_us"], "alone_sam_bytes": int(b.sam_bytes),
+                            "listed_cells": int(len(counts)), "counter_sum": int(counts.sum())}
         ctx.drop_contig(h)
     print(json.dumps(out))
 
