@@ -49,6 +49,16 @@ MUT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.
 READS_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int)
 MSG_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
 HAP_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)      # (ABI 6) dwgsim_hip_job_haplotype_fn: the next piece of a haplotype's FASTA
+CHAIN_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t)      # (ABI 11) dwgsim_hip_job_chain_fn: the next piece of the chain file (hap, direction)
+CHAIN_TO_REF, CHAIN_FROM_REF = 0, 1      # DWGSIM_HIP_CHAIN_TO_REF / _FROM_REF
+CHAIN_DIRECTIONS = {CHAIN_TO_REF: "to_ref", CHAIN_FROM_REF: "from_ref"}
+
+
+class ChainBlock(C.Structure):
+    """dwgsim_hip_chain_block_t"""
+    _fields_ = [("size", C.c_int64), ("d_ref", C.c_int64), ("d_hap", C.c_int64)]
+
+
 TVCF_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t)      # (ABI 10) dwgsim_hip_job_truth_vcf_fn: the truth-VCF records of the next contig
 READS_AT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int)      # (ABI 5) pieces with their offset, from several threads
 
@@ -95,6 +105,7 @@ EXPORTS = [
     "dwgsim_hip_debug_sim_instances",
     "dwgsim_hip_set_truth_sam", "dwgsim_hip_truth_sam_header", "dwgsim_hip_job_set_truth_sam",
     "dwgsim_hip_set_truth_md", "dwgsim_hip_job_set_truth_md", "dwgsim_hip_job_debug_option", "dwgsim_hip_job_debug_get",
+    "dwgsim_hip_haplotype_chain", "dwgsim_hip_chain_blocks", "dwgsim_hip_chain_format", "dwgsim_hip_job_set_chain_sink",
     "dwgsim_hip_set_truth_depth", "dwgsim_hip_truth_depth_fetch", "dwgsim_hip_mutlist_truth_vcf_text", "dwgsim_hip_truth_vcf_header", "dwgsim_hip_job_set_truth_vcf_sink",
 ]
 
@@ -186,6 +197,11 @@ def load(path: str | None = None):
     lib.dwgsim_hip_haplotype_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_uint64), P(C.c_uint64), P(C.c_int64)]
     lib.dwgsim_hip_haplotype_fetch.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
     lib.dwgsim_hip_job_set_haplotype_sink.argtypes = [C.c_void_p, HAP_CB, C.c_void_p, C.c_int]
+    lib.dwgsim_hip_haplotype_chain.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_uint64)]
+    lib.dwgsim_hip_chain_blocks.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_uint64), P(C.c_int64), P(ChainBlock), C.c_uint64]
+    lib.dwgsim_hip_chain_format.restype = C.c_int64
+    lib.dwgsim_hip_chain_format.argtypes = [C.c_char_p, C.c_int64, C.c_int64, P(ChainBlock), C.c_uint64, C.c_int, C.c_uint64, C.c_char_p, C.c_size_t]
+    lib.dwgsim_hip_job_set_chain_sink.argtypes = [C.c_void_p, CHAIN_CB, C.c_void_p]
     lib.dwgsim_hip_debug_sim_instances.argtypes = [P(C.c_int64), C.c_int]
     lib.dwgsim_hip_set_truth_sam.argtypes = [C.c_void_p, C.c_int]
     lib.dwgsim_hip_truth_sam_header.restype = C.c_int64
@@ -340,6 +356,7 @@ class JobResult:
     walk_ms: float = 0.0
     flow_cap_mult: int = 1                           # Ion Torrent: by how much the read capacity had grown at the end of the job (run_job)
     haplotypes: dict = field(default_factory=dict)   # haplotypes=True: {0: bytes, 1: bytes}, the two mutated haplotypes as FASTA
+    chain: dict = field(default_factory=dict)        # chain=True: {(hap, "to_ref" | "from_ref"): bytes}, the four chain files
     sim_forms: set = field(default_factory=set)      # debug_get("sim_form") after every simulate call of the job (run_job): the k_simulate forms it ran
     truth_sam: bytes = b""                           # truth_sam=True: the records of the truth SAM (no header: truth_sam_header)
     truth_vcf: bytes = b""                           # truth_vcf=True: the records of the truth VCF (no header: truth_vcf_header)
@@ -487,6 +504,16 @@ class Context:
         self._chk(self.lib.dwgsim_hip_haplotype_fetch(self.h, hap, 0, buf, n.value))
         return buf.raw[:n.value]
 
+    def haplotype_chain(self, cid: int, hap: int):
+        """(ABI 11) (ref_start, [(size, d_ref, d_hap), ...]): the ungapped blocks of haplotype `hap` (0 or 1) of contig cid against the reference, built for the
+        whole group cid belongs to.  The last block's d_ref / d_hap are the deleted cells / inserted bases behind it.  No block: the haplotype has no chain."""
+        self._chk(self.lib.dwgsim_hip_haplotype_chain(self.h, cid, hap, None))
+        n, r0 = C.c_uint64(0), C.c_int64(0)
+        self._chk(self.lib.dwgsim_hip_chain_blocks(self.h, cid, hap, C.byref(n), C.byref(r0), None, 0))
+        blk = (ChainBlock * max(n.value, 1))()
+        self._chk(self.lib.dwgsim_hip_chain_blocks(self.h, cid, hap, None, None, blk, n.value))
+        return r0.value, [(blk[k].size, blk[k].d_ref, blk[k].d_hap) for k in range(n.value)]
+
     def haplotype_layout(self, cid: int, hap: int):
         """(offset, bytes, bases): where the contig's record lies in its group's text (after haplotype_fasta), and the haplotype's length"""
         off, n, b = C.c_uint64(0), C.c_uint64(0), C.c_int64(0)
@@ -612,6 +639,20 @@ class Context:
         return buf.raw[:nbytes]
 
 
+def chain_format(name: str, l: int, ref_start: int, blocks, direction, chain_id: int, lib=None) -> bytes:
+    """(ABI 11) The chain of one contig as text (dwgsim_hip_chain_format): blocks as Context.haplotype_chain returns them, direction "to_ref" / "from_ref" (or 0 / 1)."""
+    lib = lib or load()
+    d = {"to_ref": CHAIN_TO_REF, "from_ref": CHAIN_FROM_REF}.get(direction, direction)
+    n = len(blocks)
+    blk = (ChainBlock * max(n, 1))(*[ChainBlock(*b) for b in blocks])
+    size = lib.dwgsim_hip_chain_format(name.encode(), l, ref_start, blk, n, d, chain_id, None, 0)
+    if size < 0:
+        raise DwgsimError(f"dwgsim_hip_chain_format: error {size}")
+    buf = C.create_string_buffer(size + 1)
+    lib.dwgsim_hip_chain_format(name.encode(), l, ref_start, blk, n, d, chain_id, buf, size)
+    return buf.raw[:size]
+
+
 def truth_sam_header(contigs, lib=None) -> bytes:
     """The header of a truth SAM for the contig table `contigs` ((name, sequence or length) pairs, FASTA order)."""
     lib = lib or load()
@@ -696,7 +737,7 @@ def split_ranges(ranges, batch_pairs):
 
 
 def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22, fetch: bool = True, lib=None, debug_options=None, group_bp: int = 0, check_list_form: bool = False,
-            haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False, truth_md: bool = False, truth_vcf: bool = False) -> JobResult:
+            haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False, truth_md: bool = False, truth_vcf: bool = False, chain: bool = False) -> JobResult:
     """dwgsim_core (dwgsim.c:419-1121) over the C-ABI: header pass, then schedule -> mutate -> mutations text -> simulate in
     read-index batches.  group_bp = 0: contig after contig, as the reference walks them.  group_bp > 0: consecutive contigs are resident
     together in groups of up to group_bp bases (dwgsim_hip_add_contigs): one walk per group, batches that run across contig boundaries."""
@@ -707,6 +748,8 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
     vcf = bytearray()
     txt = bytearray()
     haps = {0: bytearray(), 1: bytearray()}
+    chains = {(hap, d): bytearray() for hap in (0, 1) for d in CHAIN_DIRECTIONS.values()}
+    chain_id = {0: 1, 1: 1}
     sam = bytearray()
     tvcf = bytearray()
     if want_mut:
@@ -755,6 +798,14 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
             if haplotypes:
                 for hap in (0, 1):
                     haps[hap] += ctx.haplotype_fasta(h0, hap, hap_width)
+            if chain:
+                for hap in (0, 1):
+                    for k, ent in enumerate(grp):
+                        r0, blocks = ctx.haplotype_chain(h0 + k, hap)
+                        if blocks:
+                            for d in CHAIN_DIRECTIONS.values():
+                                chains[(hap, d)] += chain_format(ent[1], len(ent[2]), r0, blocks, d, chain_id[hap], lib)
+                            chain_id[hap] += 1
             ranges = [(h0 + k, 0, ent[3]) for k, ent in enumerate(grp) if want_reads and ent[3] > 0]
             for batch in split_ranges(ranges, batch_pairs):
                 b = ctx.simulate_ranges(batch, rand_ii, 0)
@@ -785,6 +836,8 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
     res.streams = {k: bytes(v) for k, v in res.streams.items()}
     if haplotypes:
         res.haplotypes = {k: bytes(v) for k, v in haps.items()}
+    if chain:
+        res.chain = {k: bytes(v) for k, v in chains.items()}
     res.truth_sam = bytes(sam)
     res.truth_vcf = bytes(tvcf)
     return res
@@ -792,7 +845,7 @@ def run_job(params: Params, contigs, device: int = 0, batch_pairs: int = 1 << 22
 
 def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True, batch_pairs: int = 0, group_bp: int = 0, min_share: int = 0,
                 lib=None, keep_output: bool = True, offset_sink: bool = False, haplotypes: bool = False, hap_width: int = 60, truth_sam: bool = False,
-                truth_md: bool = False, debug_options=None, truth_vcf: bool = False) -> JobResult:
+                truth_md: bool = False, debug_options=None, truth_vcf: bool = False, chain: bool = False) -> JobResult:
     """The same job through the JOB level of the C-ABI (dwgsim_hip_job_*): the library schedules, groups, shards over `devices`
     (default: all) and delivers in file order; the sink below only collects.  Streams are returned as text (gzip members are
     decompressed here)."""
@@ -845,7 +898,15 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
         tvcf_pieces.append((name.decode(), C.string_at(v, vl) if vl else b""))
         return 0
 
+    chain_pieces, chain_threads = [], set()      # (hap, direction, bytes) in the order of the calls
+
+    def on_chain(user, hap, direction, data, n):
+        chain_threads.add(threading.get_ident())
+        chain_pieces.append((hap, direction, C.string_at(data, n) if n else b""))
+        return 0
+
     hap_cb = HAP_CB(on_hap)
+    chain_cb = CHAIN_CB(on_chain)
     tvcf_cb = TVCF_CB(on_tvcf)
     sink = JobSink(None, MUT_CB(on_mut), READS_CB(on_reads), MSG_CB(lambda u, m: None), READS_AT_CB(on_reads_at) if offset_sink else READS_AT_CB())
     opt = JobOptions(1 if gzip_on_gpu else 0, 1, batch_pairs, group_bp, min_share)
@@ -864,6 +925,8 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
         chk(lib.dwgsim_hip_job_set_contig_table(job, names, lens, n))
         if haplotypes:
             chk(lib.dwgsim_hip_job_set_haplotype_sink(job, hap_cb, None, hap_width))
+        if chain:
+            chk(lib.dwgsim_hip_job_set_chain_sink(job, chain_cb, None))
         if truth_sam:
             chk(lib.dwgsim_hip_job_set_truth_sam(job, 1))
         if truth_md:
@@ -918,6 +981,9 @@ def run_job_api(params: Params, contigs, devices=None, gzip_on_gpu: bool = True,
     if haplotypes:
         res.haplotypes = {h: b"".join(p for q, p in hap_pieces if q == h) for h in (0, 1)}
         res.haplotype_pieces = [(q, len(p)) for q, p in hap_pieces]
+    if chain:
+        res.chain = {(h, name): b"".join(p for q, d_, p in chain_pieces if q == h and d_ == d) for h in (0, 1) for d, name in CHAIN_DIRECTIONS.items()}
+        res.chain_threads = len(chain_threads)
     return res
 
 

@@ -67,6 +67,7 @@ struct GroupMem {
     DevMem d_refview, d_refsumm, d_refsumm2, d_dirty;
     DevEvent ev_walk, ev_walk0;      // end / start of the walk chain on the walk stream
     DevMem d_hap_text[2], d_hap_rec, d_hap_pool;      // dwgsim_hip_haplotype_fasta (empty until it is called): each haplotype's FASTA text; the records and header lines of the text made last
+    DevMem d_hap_chain[2];           // dwgsim_hip_haplotype_chain (empty until it is called): each haplotype's block ends (ChainEnt), sized from the count the device made
     DevMem d_depth_pos, d_depth_cnt;      // dwgsim_hip_set_truth_depth (empty until a batch runs with it): the group's listed cells (int32, ascending) and two u64 counters per cell (dw_kernels.hpp DepthArgs)
     HostMem h_wc;                    // page-locked mirror (a WalkCounters) of the walk's counters (the context's d_wcounters) at the end of THIS group's walk: several groups' walks can be in flight
 };
@@ -111,6 +112,8 @@ struct Group {
     bool depth_valid = false; std::vector<int32_t> depth_pos;
     // the FASTA text of each finished haplotype (mem.d_hap_text), made on request: its width and size, and per contig where the record lies and its bases
     struct HapText { bool valid = false; int width = 0; uint64_t bytes = 0; std::vector<uint64_t> off, len; std::vector<int64_t> bases; } hap_text[2];
+    // the ungapped blocks of each finished haplotype against the reference (mem.d_hap_chain, paired by the host), made on request: contig k's are blocks[first[k] .. first[k + 1])
+    struct HapChain { bool valid = false; std::vector<uint64_t> first; std::vector<int64_t> ref_start; std::vector<dwgsim_hip_chain_block_t> blocks; } hap_chain[2];
 };
 
 struct HandleRef { int group = -1, k = 0; };
@@ -167,7 +170,7 @@ struct dwgsim_hip_ctx {
         uint64_t place_open = 0; double walk_us = 0, count_us = 0;      // "place_open", "walk_us", "count_us": read back
         int64_t sim_form = 0;                  // dwgsim_hip_debug_get("sim_form"): the k_simulate form of the last launch
         int64_t walk_form = 0;                 // dwgsim_hip_debug_get("walk_form"): what the last walk enqueued was made of
-        double hap_len_us = 0, hap_write_us = 0, hap_copy_us = 0, truth_us = 0, truth_copy_us = 0; bool hap_yardstick = false;      // "hap_len_us" / "hap_write_us" / "hap_copy_us", "hap_yardstick" (dwgsim_hip_debug_get / _option)
+        double hap_len_us = 0, hap_write_us = 0, hap_copy_us = 0, truth_us = 0, truth_copy_us = 0; bool hap_yardstick = false; double chain_count_us = 0, chain_write_us = 0; int64_t chain_blocks = 0;      // "chain_count_us" / "chain_write_us" / "chain_blocks"; "hap_len_us" / "hap_write_us" / "hap_copy_us", "hap_yardstick" (dwgsim_hip_debug_get / _option)
     } dbg;
     int device = 0;
     DevStream stream;            // simulate: kernels of the batches
@@ -209,7 +212,8 @@ struct dwgsim_hip_ctx {
     HostMem h_stage;                       // pinned staging for fetch
     DevStream hap_stream;                  // dwgsim_hip_haplotype_fetch: copies of its own (made at the first call), not behind the batches' copy-outs
     DevEvent hap_ev[6];                    // dwgsim_hip_haplotype_fasta: the ends of its passes (dbg.hap_*_us)
-    int hap_cur[2] = {-1, -1};             // ... and the group whose text the last call for that haplotype built or found
+    DevEvent chain_ev[4];                  // dwgsim_hip_haplotype_chain: around its passes (dbg.chain_*_us), made at its first call
+    int hap_cur[2] = {-1, -1};           // ... and the group whose text the last call for that haplotype built or found
     std::string txt, vcf;
 };
 
@@ -1305,7 +1309,7 @@ int dwgsim_hip_mutate_async(dwgsim_hip_ctx_t *c, int contig)
     g.walk_reset = g.mutated;      // walked before: the cells start again from the resident packed reference
     for (int h = 0; h < 2; ++h) g.n_ins[h] = g.n_ins_bases[h] = 0;
     g.mutated = true; g.n_cand = 0; g.list_valid = false; g.depth_valid = false;
-    for (int h = 0; h < 2; ++h) g.hap_text[h].valid = false;
+    for (int h = 0; h < 2; ++h) g.hap_text[h].valid = g.hap_chain[h].valid = false;
     g.walk_attempt = 0;
     if (g.total == 0) return DWGSIM_HIP_OK;
     if (c->has_mutin) {
@@ -1774,6 +1778,126 @@ int dwgsim_hip_haplotype_fetch(dwgsim_hip_ctx_t *c, int hap, uint64_t offset, vo
         done += cur; cur = next; b ^= 1;
     }
     return DWGSIM_HIP_OK;
+}
+
+// ---- the map between a finished haplotype and the reference (dw_walk.hip k_hapchain_count / k_hapchain_write) ----
+// On the walk stream, behind the group's walk: block ends per block of cells, their scan, the entries -- into a buffer sized from the scan's total, which the
+// device made -- and their copy to the host, which pairs them: the entries of a contig are its blocks' first and last cells in turn.
+int dwgsim_hip_haplotype_chain(dwgsim_hip_ctx_t *c, int contig, int hap, uint64_t *blocks)
+{
+    Group *gp = get_group(c, contig);
+    if (!gp) return DWGSIM_HIP_ERR_ARG;
+    Group &g = *gp;
+    if (hap < 0 || hap > 1) { c->err = "haplotype_chain: hap must be 0 or 1"; return DWGSIM_HIP_ERR_ARG; }
+    if (!g.mutated || g.walk_pending) { c->err = "mutate_contig must run first"; return DWGSIM_HIP_ERR_STATE; }
+    Group::HapChain &T = g.hap_chain[hap];
+    if (!T.valid) {
+        HIPC(c, hipSetDevice(c->device));
+        GroupMem &M = g.mem;
+        hipStream_t st = c->walk_stream.get();
+        const size_t n = g.m.size();
+        const uint32_t nblk = (uint32_t)((g.total + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK);
+        if (ensure(c, c->scratch_cnt, ((size_t)nblk + 1) * sizeof(uint32_t))) return DWGSIM_HIP_ERR_DEVICE;
+        uint32_t *d_cnt = c->scratch_cnt.get<uint32_t>();
+        HapDev hd[2]; fill_haps(g, hd);
+        const SegTab seg = seg_tab(g);
+        std::vector<uint32_t> pre((size_t)nblk + 1, 0);      // entries in front of every block, and (the last one) of the group: at most two per cell, below 2^32
+        std::vector<ChainEnt> ent;
+        for (DevEvent &e : c->chain_ev) HIPC(c, e.create());
+        c->dbg.chain_count_us = c->dbg.chain_write_us = 0;
+        if (nblk) {
+            HIPC(c, hipMemsetAsync(d_cnt + nblk, 0, sizeof(uint32_t), st));
+            HIPC(c, hipEventRecord(c->chain_ev[0].get(), st));
+            launch_hapchain_count(st, hd[hap], seg, g.total, d_cnt);
+            launch_scan_excl(st, d_cnt, nblk + 1, nullptr);
+            HIPC(c, hipEventRecord(c->chain_ev[1].get(), st));
+            HIPC(c, hipMemcpyAsync(pre.data(), d_cnt, ((size_t)nblk + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPC(c, hipStreamSynchronize(st));
+            const uint32_t total = pre[nblk];
+            ent.resize(total);
+            if (total) {
+                if (ensure(c, M.d_hap_chain[hap], sizeof(ChainEnt) * (size_t)total)) return DWGSIM_HIP_ERR_DEVICE;
+                HIPC(c, hipEventRecord(c->chain_ev[2].get(), st));
+                launch_hapchain_write(st, hd[hap], seg, g.total, d_cnt, M.d_hap_chain[hap].get<ChainEnt>(), total);
+                HIPC(c, hipEventRecord(c->chain_ev[3].get(), st));
+                HIPC(c, hipGetLastError());
+                HIPC(c, hipMemcpyAsync(ent.data(), M.d_hap_chain[hap].get(), sizeof(ChainEnt) * (size_t)total, hipMemcpyDeviceToHost, st));
+                HIPC(c, hipStreamSynchronize(st));
+            }
+            float ms = 0;      // (analysis: dwgsim_hip_debug_get "chain_count_us" / "chain_write_us", of the chain built last)
+            c->dbg.chain_count_us = hipEventElapsedTime(&ms, c->chain_ev[0].get(), c->chain_ev[1].get()) == hipSuccess ? 1e3 * ms : 0;
+            c->dbg.chain_write_us = total && hipEventElapsedTime(&ms, c->chain_ev[2].get(), c->chain_ev[3].get()) == hipSuccess ? 1e3 * ms : 0;
+            (void)hipGetLastError();
+        }
+        T.first.assign(n + 1, 0); T.ref_start.assign(n, 0); T.blocks.clear(); T.blocks.reserve(ent.size() / 2);
+        for (size_t k = 0; k < n; ++k) {
+            const Member &m = g.m[k];
+            const size_t b0 = (size_t)(m.start / SCAN_POS_PER_BLOCK), b1 = m.l > 0 ? (size_t)((m.start + m.l + SCAN_POS_PER_BLOCK - 1) / SCAN_POS_PER_BLOCK) : b0;
+            const size_t e0 = pre[b0], e1 = pre[b1];
+            T.first[k] = T.blocks.size();
+            bool fine = (e1 - e0) % 2 == 0;
+            for (size_t q = e0; fine && q < e1; q += 2) {
+                const ChainEnt &s = ent[q], &e = ent[q + 1];
+                fine = s.info == 0 && (e.info & CHAIN_END) && s.pos <= e.pos && (int64_t)e.pos < m.l && (q == e0 || ent[q - 1].pos < s.pos);
+                if (!fine) break;
+                if (q == e0) T.ref_start[k] = s.pos; else T.blocks.back().d_ref = (int64_t)s.pos - (int64_t)ent[q - 1].pos - 1;
+                T.blocks.push_back(dwgsim_hip_chain_block_t{(int64_t)e.pos - (int64_t)s.pos + 1, m.l - (int64_t)e.pos - 1, (int64_t)(e.info & ~CHAIN_END)});
+            }
+            if (!fine) { c->err = "haplotype_chain: the block ends of contig '" + m.name + "' do not pair up"; return DWGSIM_HIP_ERR_DEVICE; }
+        }
+        T.first[n] = T.blocks.size();
+        T.valid = true;
+    }
+    c->dbg.chain_blocks = (int64_t)T.blocks.size();
+    if (blocks) *blocks = T.blocks.size();
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_chain_blocks(dwgsim_hip_ctx_t *c, int contig, int hap, uint64_t *n, int64_t *ref_start, dwgsim_hip_chain_block_t *blocks, uint64_t cap)
+{
+    int km = 0;
+    Group *gp = get_group(c, contig, &km);
+    if (!gp) return DWGSIM_HIP_ERR_ARG;
+    if (hap < 0 || hap > 1 || (!blocks && cap)) { c->err = "chain_blocks: hap must be 0 or 1, and a capacity needs an array"; return DWGSIM_HIP_ERR_ARG; }
+    const Group::HapChain &T = gp->hap_chain[hap];
+    if (!T.valid) { c->err = "chain_blocks: dwgsim_hip_haplotype_chain must run first"; return DWGSIM_HIP_ERR_STATE; }
+    const uint64_t f = T.first[(size_t)km], cnt = T.first[(size_t)km + 1] - f;
+    if (n) *n = cnt;
+    if (ref_start) *ref_start = T.ref_start[(size_t)km];
+    if (cnt && cap) memcpy(blocks, T.blocks.data() + f, sizeof(dwgsim_hip_chain_block_t) * (size_t)(cnt < cap ? cnt : cap));
+    return DWGSIM_HIP_OK;
+}
+
+// The one formatter of a chain: the command line, the job and Python write these bytes
+int64_t dwgsim_hip_chain_format(const char *name, int64_t l, int64_t ref_start, const dwgsim_hip_chain_block_t *blocks, uint64_t n, int direction, uint64_t id, char *buf, size_t cap)
+{
+    if (!name || !blocks || n == 0 || (direction != DWGSIM_HIP_CHAIN_TO_REF && direction != DWGSIM_HIP_CHAIN_FROM_REF) || ref_start < 0) return DWGSIM_HIP_ERR_ARG;
+    int64_t score = 0, ref = ref_start, hap = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        const dwgsim_hip_chain_block_t &b = blocks[k];
+        if (b.size <= 0 || b.d_ref < 0 || b.d_hap < 0 || (k + 1 < n && b.d_ref == 0 && b.d_hap == 0)) return DWGSIM_HIP_ERR_ARG;
+        score += b.size; ref += b.size + b.d_ref; hap += b.size + b.d_hap;
+    }
+    if (ref != l) return DWGSIM_HIP_ERR_ARG;
+    const dwgsim_hip_chain_block_t &z = blocks[n - 1];
+    const bool from_ref = direction == DWGSIM_HIP_CHAIN_FROM_REF;
+    std::string t = "chain " + std::to_string(score);
+    for (int side = 0; side < 2; ++side) {
+        const bool is_ref = (side == 0) == from_ref;
+        t += ' '; t += name; t += ' ';
+        if (is_ref) t += std::to_string(l) + " + " + std::to_string(ref_start) + " " + std::to_string(l - z.d_ref);
+        else t += std::to_string(hap) + " + 0 " + std::to_string(hap - z.d_hap);
+    }
+    t += ' '; t += std::to_string(id); t += '\n';
+    char num[80];
+    for (uint64_t k = 0; k + 1 < n; ++k) {
+        const dwgsim_hip_chain_block_t &b = blocks[k];
+        const int w = snprintf(num, sizeof num, "%lld\t%lld\t%lld\n", (long long)b.size, (long long)(from_ref ? b.d_ref : b.d_hap), (long long)(from_ref ? b.d_hap : b.d_ref));
+        t.append(num, (size_t)w);
+    }
+    t += std::to_string(z.size); t += "\n\n";
+    if (buf && cap >= t.size()) memcpy(buf, t.data(), t.size());
+    return (int64_t)t.size();
 }
 
 // ---- read simulation ----
@@ -2654,6 +2778,9 @@ int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *c, const char *key, int64_t *value)
     else if (!strcmp(key, "hap_len_us")) *value = (int64_t)c->dbg.hap_len_us;     // the haplotype text built last: HIP-event time of its length pass + scan,
     else if (!strcmp(key, "hap_write_us")) *value = (int64_t)c->dbg.hap_write_us; // ... of its header and write kernels,
     else if (!strcmp(key, "hap_copy_us")) *value = (int64_t)c->dbg.hap_copy_us;   // ... and ("hap_yardstick") of a device-to-device copy of its size
+    else if (!strcmp(key, "chain_count_us")) *value = (int64_t)c->dbg.chain_count_us;      // the haplotype chain built last (dwgsim_hip_haplotype_chain): HIP-event time of its count pass + scan,
+    else if (!strcmp(key, "chain_write_us")) *value = (int64_t)c->dbg.chain_write_us;      // ... of its write pass,
+    else if (!strcmp(key, "chain_blocks")) *value = c->dbg.chain_blocks;                   // ... and the blocks it found
     else if (!strcmp(key, "truth_us")) *value = (int64_t)c->dbg.truth_us;         // HIP-event time (microseconds) of the truth step of the batch waited for last (dwgsim_hip_set_truth_sam)
     else if (!strcmp(key, "truth_reruns")) *value = c->dbg.truth_reruns;         // batches of this context that ran a second time because their tagged truth SAM needed room (dwgsim_hip_set_truth_md)
     else if (!strcmp(key, "truth_copy_us")) *value = (int64_t)c->dbg.truth_copy_us;      // ... and of the copy the option "truth_yardstick" made

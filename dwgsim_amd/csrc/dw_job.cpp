@@ -176,6 +176,7 @@ struct dwgsim_hip_job {
         bool truth_sam = false;       // dwgsim_hip_job_set_truth_sam: every batch also delivers stream DWGSIM_HIP_STREAM_SAM
         bool truth_md = false;        // dwgsim_hip_job_set_truth_md: ... its mapped records with NM:i: and MD:Z:
         dwgsim_hip_job_truth_vcf_fn tvcf_fn = nullptr; void *tvcf_user = nullptr;      // dwgsim_hip_job_set_truth_vcf_sink
+        dwgsim_hip_job_chain_fn chain_fn = nullptr; void *chain_user = nullptr;        // dwgsim_hip_job_set_chain_sink
     } cfg;
 
     // CALLER: touched only by the thread that calls the job_ functions (the ABI allows one at a time).  The workers see the staging through
@@ -669,7 +670,7 @@ struct Worker {
     {
         if (!takes_part(*g)) return pass_by(*g);      // a small group is not worth a copy on every device
         Resident cur;
-        return adopt_or_prepare(g, cur) && hand_mutations_on(cur) && hand_haplotypes_on(cur) && exchange_counts(cur) && run_batches(cur);
+        return adopt_or_prepare(g, cur) && hand_mutations_on(cur) && hand_haplotypes_on(cur) && hand_chains_on(cur) && exchange_counts(cur) && run_batches(cur);
     }
 
     bool pass_by(GroupJob &g)
@@ -726,6 +727,40 @@ struct Worker {
         hs.active = true;
         trace(j, "dev %d group %d: haplotype text made (%.1f MB)", d, cur.g->id, (hs.bytes[0] + hs.bytes[1]) / 1e6);
         return pump_haplotypes(false);
+    }
+
+    // (device 0) the chains of both haplotypes: two passes over the cells on the device, a few bytes per block to the host, the text made here and handed to the
+    // sink by this thread -- a file's pieces in file order, a few megabytes for a whole genome
+    uint64_t chain_next_id[2] = {1, 1};      // the id of a haplotype's next chain (its two directions carry the same ids)
+    bool hand_chains_on(const Resident &cur)
+    {
+        if (j->cfg.vrank(d) != 0 || !j->cfg.chain_fn) return true;
+        const GroupJob &g = *cur.g;
+        std::vector<dwgsim_hip_chain_block_t> blk;
+        std::string text[2];      // DWGSIM_HIP_CHAIN_TO_REF, _FROM_REF
+        for (int hap = 0; hap < 2; ++hap) {
+            if (dwgsim_hip_haplotype_chain(x, cur.h, hap, nullptr) < 0) { fail_ctx(); return false; }
+            text[0].clear(); text[1].clear();
+            for (size_t k = 0; k < g.names.size(); ++k) {
+                uint64_t n = 0; int64_t ref_start = 0;
+                if (dwgsim_hip_chain_blocks(x, cur.h + (int)k, hap, &n, nullptr, nullptr, 0) < 0) { fail_ctx(); return false; }
+                if (n == 0) continue;      // (every cell deleted: no chain)
+                blk.resize((size_t)n);
+                if (dwgsim_hip_chain_blocks(x, cur.h + (int)k, hap, nullptr, &ref_start, blk.data(), n) < 0) { fail_ctx(); return false; }
+                for (int dir = 0; dir < 2; ++dir) {
+                    const int64_t need = dwgsim_hip_chain_format(g.names[k].c_str(), g.lens[k], ref_start, blk.data(), n, dir, chain_next_id[hap], nullptr, 0);
+                    if (need < 0) { job_fail(j, "dwgsim-hip: the blocks of contig '" + g.names[k] + "' make no chain"); return false; }
+                    const size_t at = text[dir].size();
+                    text[dir].resize(at + (size_t)need);
+                    (void)dwgsim_hip_chain_format(g.names[k].c_str(), g.lens[k], ref_start, blk.data(), n, dir, chain_next_id[hap], &text[dir][at], (size_t)need);
+                }
+                ++chain_next_id[hap];
+            }
+            for (int dir = 0; dir < 2; ++dir)
+                if (!text[dir].empty() && j->cfg.chain_fn(j->cfg.chain_user, hap, dir, text[dir].data(), text[dir].size()) != 0) { job_fail(j, "dwgsim-hip: the sink refused the chain text"); return false; }
+        }
+        trace(j, "dev %d group %d: chains made", d, g.id);
+        return true;
     }
 
     // several devices: my batches' random reads are counted and published; then every device's counts, and the group's base, are waited for
@@ -1047,6 +1082,14 @@ int dwgsim_hip_job_set_mutation_input(dwgsim_hip_job_t *j, int type, const char 
 {
     if (!j || !path || type < 0 || type > 2 || j->me.started) return arg_error(j, DWGSIM_HIP_ERR_ARG, "job: the mutation input must be set before the first contig");
     j->cfg.mutin_type = type; j->cfg.mutin_path = path;
+    return DWGSIM_HIP_OK;
+}
+
+int dwgsim_hip_job_set_chain_sink(dwgsim_hip_job_t *j, dwgsim_hip_job_chain_fn fn, void *user)
+{
+    if (!j) return DWGSIM_HIP_ERR_ARG;
+    if (j->me.started) return arg_error(j, DWGSIM_HIP_ERR_STATE, "job: the chain sink must be set before the first contig");
+    j->cfg.chain_fn = fn; j->cfg.chain_user = user;
     return DWGSIM_HIP_OK;
 }
 

@@ -90,7 +90,11 @@ struct ContigDev {             // a group of contigs in its coordinate space (a 
 // One record of a haplotype FASTA (dw_walk.hip k_hap_headers / k_hap_write), one per contig of the group: where it lies in the group's text, its header
 // line ('>' + name + '\n') in the header pool, the emitted bases of the group in front of the contig's first block (k_hap_len, scanned) and its own
 struct HapRec { uint64_t rec_off; uint32_t hdr_off, hdr_len, base0, n_bases; uint32_t pad_; };
-constexpr int HAP_WINDOW = 8192;         // k_hap_write: characters a block stages in LDS at a time (a block of 4096 cells emits more only where insertions make it)
+// One end of an ungapped block of a haplotype against the reference (dw_walk.hip k_hapchain_write): the aligned cell, counted from its contig's first cell, and
+// for the block's last cell CHAIN_END | the inserted bases behind it (below 2^31: a group's cells and inserted bases stay below 2^32 together); a block's first cell: 0
+struct ChainEnt { uint32_t pos, info; };
+constexpr uint32_t CHAIN_END = 0x80000000u;
+constexpr int HAP_WINDOW = 8192;        // k_hap_write: characters a block stages in LDS at a time (a block of 4096 cells emits more only where insertions make it)
 
 // An element count that is either known on the host or still being produced on the device: kernels are launched for `host`
 // elements (an exact count, or the capacity the buffers were sized for) and work on min(*dev, host).

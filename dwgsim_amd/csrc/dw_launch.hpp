@@ -27,6 +27,8 @@ void launch_collect_mask(hipStream_t st, const uint8_t *h0, const uint8_t *h1, i
 void launch_gather(hipStream_t st, const int32_t *pos, uint32_t n, const uint8_t *ref, const uint8_t *h0, const uint8_t *h1, uint32_t *cells);
 void launch_hap_len(hipStream_t st, HapDev h, SegTab seg, int64_t l, uint32_t *block_count);      // the haplotype FASTA: emitted bases per block of SCAN_POS_PER_BLOCK cells ...
 void launch_hap_write(hipStream_t st, HapDev h, SegTab seg, int64_t l, const uint32_t *block_base, const HapRec *rec, uint32_t n_rec, const uint8_t *pool, uint32_t width, uint8_t *text);      // ... and, from their scan and the records the host placed, the text
+void launch_hapchain_count(hipStream_t st, HapDev h, SegTab seg, int64_t l, uint32_t *block_count);      // the haplotype chain: block ends per block of SCAN_POS_PER_BLOCK cells ...
+void launch_hapchain_write(hipStream_t st, HapDev h, SegTab seg, int64_t l, const uint32_t *block_base, ChainEnt *out, uint32_t cap);      // ... and, from their scan, the `cap` entries themselves
 void launch_place(hipStream_t st, const SimArgs &a);
 bool launch_simulate(hipStream_t st, const SimArgs &a, const SimForm &f);      // false: the form has no instance
 void launch_truth(hipStream_t st, const SimArgs &a, const TruthArgs &t, const DepthArgs *depth);      // the truth step behind the k_simulate launch with arguments a (dw_truth.hpp); depth: with the counters of the true read depth (nullptr: without)

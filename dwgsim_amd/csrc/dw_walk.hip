@@ -861,8 +861,84 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_hap_write(HapDev h, SegTab seg
 }
 
 // ------------------------------------------------------------------------------------------------
+// The map between a finished haplotype and the reference, as the ends of its ungapped blocks (the host pairs them into a UCSC chain; DESIGN.md
+// "6g").  A cell is ALIGNED unless it is a DELETE cell; ins(i) = the inserted bases behind an aligned cell (hap_ins_entry: an INSERT cell with a table
+// entry of n > 0 bases; every other cell 0).  An aligned cell i of the contig [start, end)
+//     STARTS a block when i = start,   or cell i-1 is a DELETE cell, or ins(i-1) > 0;
+//     ENDS   a block when i = end - 1, or cell i+1 is a DELETE cell, or ins(i) > 0.
+// Starts and ends alternate in coordinate order (a one-cell block gives both, the start first), so the entries of a contig, in order, ARE its blocks:
+// nothing follows a deletion run, whatever its length, and nothing depends on where a cell lies in a thread, a block or the group.  The geometry is
+// k_hap_len's -- a block takes SCAN_POS_PER_BLOCK cells and lies inside one contig, a thread sixteen cells in one load -- plus the byte in front of the
+// sixteen and the byte behind them where the contig has one; the padding between contigs is never looked at as a neighbour.  k_hapchain_count: entries
+// per block; k_scan_excl over the blocks; k_hapchain_write: the entries (ChainEnt), placed by the scan.  Both only read the cells and the insertion tables.
+// ------------------------------------------------------------------------------------------------
+DW_DEV uint32_t hapchain_ins(const HapDev &h, int64_t g, uint32_t cell)
+{
+    if ((cell & TMASK) != T_INS) return 0;
+    const uint32_t idx = hap_ins_entry(h, g);
+    return idx < h.n_ins ? h.ins_len[idx] : 0u;
+}
+// The entries of the nv cells v at group coordinate g of the contig [start, end): emit(position in the contig, ChainEnt::info) for each, in order; returns their number.
+template <class Emit>
+DW_DEV uint32_t hapchain_entries(const HapDev &h, int64_t g, const uint4 &v, int nv, int64_t start, int64_t end, Emit emit)
+{
+    const bool first = g == start, last = g + nv == end;
+    const uint32_t pb = first ? 0u : (uint32_t)h.cells[g - 1], nb = last ? 0u : (uint32_t)h.cells[g + nv];      // (neither first nor last: nv = 16)
+    // the thread most cells belong to: no INSERT or DELETE cell among its sixteen or next to them, no contig end
+    if (!first && !last && (((v.x | v.y | v.z | v.w) | pb | nb) & 0x10101010u) == 0) return 0;
+    uint32_t n = 0;
+    bool gap = first || (pb & TMASK) == T_DEL || hapchain_ins(h, g - 1, pb) > 0;      // the cell in front is not aligned to the one before it
+    for (int q = 0; q < nv; ++q) {
+        const uint32_t c = hap_cell(v, q);
+        if ((c & TMASK) == T_DEL) { gap = true; continue; }
+        const uint32_t ins = hapchain_ins(h, g + q, c);
+        const bool more = q + 1 < nv || !last;                             // the contig has a cell behind this one
+        const uint32_t nx = q + 1 < nv ? hap_cell(v, q + 1) : nb;
+        if (gap) { emit((uint32_t)(g + q - start), 0u); ++n; }
+        if (ins > 0 || !more || (nx & TMASK) == T_DEL) { emit((uint32_t)(g + q - start), CHAIN_END | ins); ++n; }
+        gap = ins > 0;
+    }
+    return n;
+}
+__global__ void __launch_bounds__(SCAN_THREADS) k_hapchain_count(HapDev h, SegTab seg, uint32_t *__restrict__ block_count)
+{
+    __shared__ uint32_t sm[17];
+    const int64_t g0 = (int64_t)blockIdx.x * SCAN_POS_PER_BLOCK, g = g0 + (int64_t)threadIdx.x * SCAN_POS_PER_THREAD;
+    const uint32_t sk = seg_of(seg, g0);
+    const int64_t start = (int64_t)seg.start[sk], end = start + seg.len[sk];      // (g >= end: the padding behind the contig)
+    uint32_t cnt = 0;
+    if (g < end) { const uint4 v = *reinterpret_cast<const uint4 *>(h.cells + g); cnt = hapchain_entries(h, g, v, end - g < 16 ? (int)(end - g) : 16, start, end, [](uint32_t, uint32_t) {}); }
+    uint32_t total;
+    (void)block_excl_scan(cnt, sm, &total);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+// block_base: the scanned counts; cap: the entries `out` has room for (the scan's total: nothing is written past it)
+__global__ void __launch_bounds__(SCAN_THREADS) k_hapchain_write(HapDev h, SegTab seg, const uint32_t *__restrict__ block_base, ChainEnt *__restrict__ out, uint32_t cap)
+{
+    __shared__ uint32_t sm[17];
+    const int64_t g0 = (int64_t)blockIdx.x * SCAN_POS_PER_BLOCK, g = g0 + (int64_t)threadIdx.x * SCAN_POS_PER_THREAD;
+    const uint32_t sk = seg_of(seg, g0);
+    const int64_t start = (int64_t)seg.start[sk], end = start + seg.len[sk];
+    uint4 v = make_uint4(0, 0, 0, 0); int nv = 0; uint32_t cnt = 0;
+    if (g < end) { v = *reinterpret_cast<const uint4 *>(h.cells + g); nv = end - g < 16 ? (int)(end - g) : 16; cnt = hapchain_entries(h, g, v, nv, start, end, [](uint32_t, uint32_t) {}); }
+    uint32_t total;
+    const uint32_t off = block_excl_scan(cnt, sm, &total);
+    if (cnt == 0) return;
+    uint32_t at = block_base[blockIdx.x] + off;
+    (void)hapchain_entries(h, g, v, nv, start, end, [&](uint32_t pos, uint32_t info) { if (at < cap) out[at] = ChainEnt{pos, info}; ++at; });
+}
+
+// ------------------------------------------------------------------------------------------------
 // host-side launchers (declared in dw_launch.hpp)
 // ------------------------------------------------------------------------------------------------
+void launch_hapchain_count(hipStream_t st, HapDev h, SegTab seg, int64_t l, uint32_t *block_count)
+{
+    if (l > 0) hipLaunchKernelGGL(k_hapchain_count, dim3(cdiv((uint64_t)l, SCAN_POS_PER_BLOCK)), dim3(SCAN_THREADS), 0, st, h, seg, block_count);
+}
+void launch_hapchain_write(hipStream_t st, HapDev h, SegTab seg, int64_t l, const uint32_t *block_base, ChainEnt *out, uint32_t cap)
+{
+    if (l > 0 && cap > 0) hipLaunchKernelGGL(k_hapchain_write, dim3(cdiv((uint64_t)l, SCAN_POS_PER_BLOCK)), dim3(SCAN_THREADS), 0, st, h, seg, block_base, out, cap);
+}
 void launch_hap_len(hipStream_t st, HapDev h, SegTab seg, int64_t l, uint32_t *block_count)
 {
     if (l > 0) hipLaunchKernelGGL(k_hap_len, dim3(cdiv((uint64_t)l, SCAN_POS_PER_BLOCK)), dim3(SCAN_THREADS), 0, st, h, seg, block_count);

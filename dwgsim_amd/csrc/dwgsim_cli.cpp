@@ -25,6 +25,10 @@
 //     DWGSIM_HIP_HAPLOTYPES  anything but empty or "0": also write the two mutated haplotypes the reads are drawn from, <prefix>.hap1.fa and <prefix>.hap2.fa
 //                          (plain text, assembled on the GPU; a record per simulated contig, the contig's plain name; removed again if the job fails)
 //     DWGSIM_HIP_HAPLOTYPES_WIDTH  bases per line of those files (default 60; 0: the whole sequence on one line)
+//     DWGSIM_HIP_CHAIN       anything but empty or "0": also write the maps between those haplotypes and the reference as UCSC chain files,
+//                          <prefix>.hap1.to_ref.chain, .hap1.from_ref.chain, .hap2.to_ref.chain, .hap2.from_ref.chain -- to_ref lifts coordinates on <prefix>.hapN.fa
+//                          to the reference, from_ref the other way; a chain per simulated contig, the contig's plain name on both sides; removed again if the job
+//                          fails.  Independent of DWGSIM_HIP_HAPLOTYPES and of -M
 //     DWGSIM_HIP_TRUTH_SAM   anything but empty or "0": also write <prefix>.truth.sam.gz, the true alignment of every read end (Illumina reads):
 //                          the header, then the job's stream 3, in the gzip mode of the FASTQ files.  -M 2 writes none
 //     DWGSIM_HIP_TRUTH_VCF   anything but empty or "0": also write <prefix>.truth.vcf, the records of mutations.vcf with GT:AD:DP in one sample column: the
@@ -468,6 +472,13 @@ struct FileSink {
         FileSink *s = (FileSink *)u;
         return s->fp_hap[hap] && fwrite(data, 1, len, s->fp_hap[hap]) == len ? 0 : 1;
     }
+    FILE *fp_chain[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      // DWGSIM_HIP_CHAIN: <prefix>.hap1 / .hap2 x .to_ref.chain / .from_ref.chain
+    static int chain(void *u, int hap, int direction, const void *data, size_t len)      // (dwgsim_hip_job_set_chain_sink: one thread, each file's pieces in order)
+    {
+        FileSink *s = (FileSink *)u;
+        FILE *f = s->fp_chain[hap][direction];
+        return f && fwrite(data, 1, len, f) == len ? 0 : 1;
+    }
     std::atomic<uint64_t> written[4] = {{0}, {0}, {0}, {0}};      // bytes that went to file `stream` through reads_at
     uint64_t base_off[4] = {0, 0, 0, 0};      // ... behind what main wrote into the file first (the truth SAM's header)
     // pieces with their place (dwgsim_hip_job_sink_t::reads_at): several threads per file, pwrite
@@ -683,6 +694,15 @@ int main(int argc, char **argv)
         fs.fp_hap[0] = fopen((p + ".hap1.fa").c_str(), "wb"); fs.fp_hap[1] = fopen((p + ".hap2.fa").c_str(), "wb");
         if (!fs.fp_hap[0] || !fs.fp_hap[1]) { fprintf(stderr, "dwgsim-hip: fail to open the haplotype files for '%s'\n", out_prefix); return give_up(1); }
     }
+    const char *chain_env = getenv("DWGSIM_HIP_CHAIN");
+    const bool want_chain = chain_env && chain_env[0] && strcmp(chain_env, "0");
+    auto chain_path = [&](int hap, int dir) { return p + (hap ? ".hap2" : ".hap1") + (dir == DWGSIM_HIP_CHAIN_TO_REF ? ".to_ref.chain" : ".from_ref.chain"); };
+    auto unlink_chains = [&]() { for (int h = 0; h < 2; ++h) for (int dir = 0; dir < 2; ++dir) (void)unlink(chain_path(h, dir).c_str()); };
+    if (want_chain) {
+        bool ok = true;
+        for (int h = 0; h < 2; ++h) for (int dir = 0; dir < 2; ++dir) ok = (fs.fp_chain[h][dir] = fopen(chain_path(h, dir).c_str(), "wb")) != nullptr && ok;
+        if (!ok) { fprintf(stderr, "dwgsim-hip: fail to open the chain files for '%s'\n", out_prefix); return give_up(1); }
+    }
     // the truth VCF: the header (one exported function), then the job's records
     const char *tvcf_env = getenv("DWGSIM_HIP_TRUTH_VCF");
     const bool want_tvcf = tvcf_env && tvcf_env[0] && strcmp(tvcf_env, "0");
@@ -717,7 +737,7 @@ int main(int argc, char **argv)
     }
 
     dwgsim_hip_job_t *job = job_made.get();
-    if (!job) { fprintf(stderr, "dwgsim-hip: cannot set the job up (error %d)\n", job_err); if (want_hap) { (void)unlink((p + ".hap1.fa").c_str()); (void)unlink((p + ".hap2.fa").c_str()); } if (want_tvcf) (void)unlink((p + ".truth.vcf").c_str()); return 1; }
+    if (!job) { fprintf(stderr, "dwgsim-hip: cannot set the job up (error %d)\n", job_err); if (want_hap) { (void)unlink((p + ".hap1.fa").c_str()); (void)unlink((p + ".hap2.fa").c_str()); } if (want_tvcf) (void)unlink((p + ".truth.vcf").c_str()); if (want_chain) unlink_chains(); return 1; }
     int rc = 0;
     auto job_error = [&]() { const char *e = dwgsim_hip_job_last_error(job); if (rc == 0) fprintf(stderr, "%s%s", e, (e[0] && e[strlen(e) - 1] != '\n') ? "\n" : ""); rc = 1; };
     {
@@ -726,6 +746,7 @@ int main(int argc, char **argv)
         if (rc == 0 && !regions_fn.empty() && dwgsim_hip_job_set_regions(job, regions_fn.c_str()) < 0) job_error();             // dwgsim.c:499-506
         if (rc == 0 && muts_type >= 0 && dwgsim_hip_job_set_mutation_input(job, muts_type, muts_fn.c_str()) < 0) job_error();   // dwgsim.c:494-497
         if (rc == 0 && want_hap && dwgsim_hip_job_set_haplotype_sink(job, FileSink::haplotype, &fs, hap_width) < 0) job_error();
+        if (rc == 0 && want_chain && dwgsim_hip_job_set_chain_sink(job, FileSink::chain, &fs) < 0) job_error();
         if (rc == 0 && want_sam && dwgsim_hip_job_set_truth_sam(job, 1) < 0) job_error();
         if (rc == 0 && want_tvcf && dwgsim_hip_job_set_truth_vcf_sink(job, FileSink::truth_vcf, &fs) < 0) job_error();
         if (rc == 0 && want_md && dwgsim_hip_job_set_truth_md(job, 1) < 0) job_error();
@@ -785,6 +806,10 @@ int main(int argc, char **argv)
         if (fclose(fs.fp_hap[h]) != 0 && rc == 0) { fprintf(stderr, "dwgsim-hip: writing the haplotype files failed\n"); rc = 1; }
         if (rc != 0) (void)unlink((p + (h ? ".hap2.fa" : ".hap1.fa")).c_str());
     }
+    for (int h = 0; h < 2; ++h) for (int dir = 0; dir < 2; ++dir) if (fs.fp_chain[h][dir]) {      // (a failed job leaves no partial chain file)
+        if (fclose(fs.fp_chain[h][dir]) != 0 && rc == 0) { fprintf(stderr, "dwgsim-hip: writing the chain files failed\n"); rc = 1; }
+    }
+    if (want_chain && rc != 0) unlink_chains();
     if (fs.fp_tvcf) {      // (a failed job leaves no partial truth VCF)
         if (fclose(fs.fp_tvcf) != 0 && rc == 0) { fprintf(stderr, "dwgsim-hip: writing the truth VCF failed\n"); rc = 1; }
         if (rc != 0) (void)unlink((p + ".truth.vcf").c_str());

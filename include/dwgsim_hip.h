@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define DWGSIM_HIP_ABI_VERSION 10
+#define DWGSIM_HIP_ABI_VERSION 11
 
 /* error codes (negative) */
 #define DWGSIM_HIP_OK            0
@@ -217,6 +217,34 @@ void dwgsim_hip_mutlist_free(dwgsim_hip_mutlist_t *list);
 int dwgsim_hip_haplotype_fasta(dwgsim_hip_ctx_t *ctx, int contig, int hap, int width, uint64_t *bytes);
 int dwgsim_hip_haplotype_layout(dwgsim_hip_ctx_t *ctx, int contig, int hap, uint64_t *offset, uint64_t *bytes, int64_t *bases);
 int dwgsim_hip_haplotype_fetch(dwgsim_hip_ctx_t *ctx, int hap, uint64_t offset, void *host_dst, size_t n);
+
+/* (ABI 11) The map between a haplotype (dwgsim_hip_haplotype_fasta) and the reference, as a UCSC chain (no counterpart in the reference; DESIGN.md "6g").
+ * A cell of the haplotype is ALIGNED unless it is deleted: its own base stands opposite the reference base of the cell; the n > 0 bases inserted behind a
+ * cell stand opposite nothing.  An ungapped BLOCK is a maximal run of consecutive aligned cells s .. e in which no cell but e has inserted bases behind it.
+ * Block k of a contig of l cells is {size = e - s + 1, d_ref, d_hap}: d_ref the deleted cells and d_hap the inserted bases between it and block k + 1 -- for
+ * the LAST block what lies behind it, the deleted cells up to the contig's end and the bases inserted behind e, which are not part of the chain.  So
+ * ref_start + the sum of size + d_ref is l, and the sum of size + d_hap is the haplotype's length.
+ * haplotype_chain finds the blocks of haplotype `hap` (0 or 1) of the whole GROUP `contig` belongs to (two passes over its cells on the device; the block ends
+ * come to the host, which pairs them); *blocks (optional) = their number in the group.  They are kept per group and haplotype until the group is dropped or
+ * walked again: a second call finds them there.  DWGSIM_HIP_ERR_STATE before the group's walk has finished, DWGSIM_HIP_ERR_ARG for another hap.
+ * chain_blocks (after haplotype_chain for that group and hap: DWGSIM_HIP_ERR_STATE else): the blocks of one contig.  *n = their number (0: every cell of the
+ * haplotype is deleted -- it has no chain), *ref_start = the first aligned cell; the first min(*n, cap) blocks are copied to `blocks` (NULL with cap 0: ask
+ * for the number).  Any of n, ref_start may be NULL. */
+typedef struct dwgsim_hip_chain_block { int64_t size, d_ref, d_hap; } dwgsim_hip_chain_block_t;
+int dwgsim_hip_haplotype_chain(dwgsim_hip_ctx_t *ctx, int contig, int hap, uint64_t *blocks);
+int dwgsim_hip_chain_blocks(dwgsim_hip_ctx_t *ctx, int contig, int hap, uint64_t *n, int64_t *ref_start, dwgsim_hip_chain_block_t *blocks, uint64_t cap);
+/* The chain of one contig as text, from the blocks above (n > 0).  direction DWGSIM_HIP_CHAIN_FROM_REF: target the reference, query the haplotype --
+ *     chain <score> <name> <l> + <ref_start> <ref_end> <name> <hap_len> + 0 <hap_end> <id>\n
+ *     <size>\t<d_ref>\t<d_hap>\n      a line per block but the last
+ *     <size>\n\n                       the last block, and the empty line that ends a chain
+ * score = the sum of the sizes; hap_end = hap_len - the last block's d_hap; ref_end = l - the last block's d_ref.  DWGSIM_HIP_CHAIN_TO_REF (what liftOver wants
+ * for coordinates on the haplotype FASTA): the same chain with target and query exchanged -- the two groups of name, size, strand, start, end swapped and every
+ * block line <size>\t<d_hap>\t<d_ref>.  Needs no context.  Returns the size of the text (no terminating 0) and writes it when buf has room for it (cap >= the
+ * size); a negative DWGSIM_HIP_ERR_ARG for n = 0, a NULL name or blocks, another direction, or blocks that do not add up to l. */
+#define DWGSIM_HIP_CHAIN_TO_REF 0
+#define DWGSIM_HIP_CHAIN_FROM_REF 1
+int64_t dwgsim_hip_chain_format(const char *name, int64_t l, int64_t ref_start, const dwgsim_hip_chain_block_t *blocks, uint64_t n, int direction, uint64_t id,
+                                char *buf, size_t cap);
 
 /* Number of random reads among pairs [first_ii, first_ii + n_pairs) of the contig (for sharding:
  * rand_ii is a running count over all earlier pairs, dwgsim.c:1042,1096). */
@@ -412,6 +440,14 @@ int dwgsim_hip_job_set_truth_md(dwgsim_hip_job_t *job, int on);
  * dwgsim_hip_job_prepare / the first contig: DWGSIM_HIP_ERR_STATE later; DWGSIM_HIP_ERR_UNSUP for -c 1 / -c 2; fn == NULL: off. */
 typedef int (*dwgsim_hip_job_truth_vcf_fn)(void *user, const char *contig, const char *vcf, size_t vcf_len);
 int dwgsim_hip_job_set_truth_vcf_sink(dwgsim_hip_job_t *job, dwgsim_hip_job_truth_vcf_fn fn, void *user);
+/* (ABI 11) The chain files (dwgsim_hip_haplotype_chain) through the job.  Right behind a group's walk the first device finds the blocks of both haplotypes,
+ * and fn gets, for haplotype 0 and then 1, for direction DWGSIM_HIP_CHAIN_TO_REF and then _FROM_REF, the chains of the group's contigs in FASTA order
+ * (dwgsim_hip_chain_format) as one piece of the file (hap, direction): the pieces of a file arrive in file order, from ONE thread of the job.  The ids of a
+ * file run 1, 2, ... across the groups.  A contig dwgsim_core passes over has no chain, and neither has a haplotype of a contig without an aligned cell.
+ * Independent of -M and of the haplotype sink.  A non-zero return fails the job.  To be called before dwgsim_hip_job_prepare / the first contig:
+ * DWGSIM_HIP_ERR_STATE later; fn == NULL: off. */
+typedef int (*dwgsim_hip_job_chain_fn)(void *user, int hap, int direction, const void *data, size_t len);
+int dwgsim_hip_job_set_chain_sink(dwgsim_hip_job_t *job, dwgsim_hip_job_chain_fn fn, void *user);
 /* optional: parse the files above and start the device threads now (errors of -x / -m / -b / -v surface here instead of at the first contig) */
 int dwgsim_hip_job_prepare(dwgsim_hip_job_t *job, uint64_t *total_len);
 /* The body of the contig loop (dwgsim.c:519-625 and everything below it) for the next contig of the FASTA.  Returns the pairs scheduled for
@@ -567,7 +603,8 @@ int dwgsim_hip_debug_option(dwgsim_hip_ctx_t *ctx, const char *key, int64_t valu
  * last (dwgsim_hip_haplotype_fasta); "hap_copy_us": with the option "hap_yardstick" = 1, of a device-to-device copy of that text's size behind it;
  * "truth_us": HIP-event time (microseconds) of the truth step of the batch waited for last (dwgsim_hip_set_truth_sam); "truth_copy_us": of the device-to-device copy
  * of n bytes of slot 0's truth SAM that the option "truth_yardstick" = n makes at once; "truth_reruns": batches of the context that ran a second time because
- * their tagged truth SAM needed more room than planned */
+ * their tagged truth SAM needed more room than planned; "chain_count_us" / "chain_write_us": HIP-event time (microseconds) of the count pass + scan / of the
+ * write pass of the chain built last (dwgsim_hip_haplotype_chain), "chain_blocks": the blocks of the group it built or found */
 int dwgsim_hip_debug_get(dwgsim_hip_ctx_t *ctx, const char *key, int64_t *value);
 /* (ABI 9) the two calls above through a job: the option goes to every context of the job (before dwgsim_hip_job_prepare / the first contig: DWGSIM_HIP_ERR_STATE
  * later); the value is the sum over the job's contexts (before the first contig or after dwgsim_hip_job_finish).  dwgsim-hip: DWGSIM_HIP_DEBUG="key=value,..."
